@@ -16,6 +16,11 @@ One timed "step" advances EVERY trainer of the reference once over those rows:
                       32 sums] -> Adam + clamp on device; the cache is built once per trainer call, outside the step)
 value = rows of all ranks * steps / max-over-ranks wall time (weak scaling: rows per GPU fixed).
 
+A plain run sets up, warms up, times --steps steps and prints the headline line; --dump-outputs DIR then also
+writes what the last timed step computed (loss sums, weights, gradient, physics parameters, stage sums) as
+DIR/<name>.npy.  Everything below ("extra legs", the other precisions, the blocking all-reduce comparison of
+N > 1) runs only with --full.
+
 Arithmetic (--precision, default f32x6 = the library default): fp32 in, fp32 out, fp32 accumulation;
 the matrix products run on the 16-bit matrix cores with split operands: two fp16 parts per operand
 (exact power-of-two scales bring them into fp16's range: constants in the forward passes, per row in
@@ -25,9 +30,9 @@ tensors as close to a float64 autograd as torch's own fp32 autograd).  The train
 fp16 fragments themselves (4 B per element, as fp32 did): the weight-gradient kernels read ready operands.
 The exact-fp32 kernels (v_mfma_f32_*_f32), the opt-in bf16-mixed ones and the f32x6g6 variant
 (gradients from three bf16 parts, six products: round 2's first default) are measured beside it
-unless --only.
+with --full, unless --only.
 
-Extra legs reported in the same JSON line (rank 0):
+Extra legs reported in the same JSON line (rank 0; --full only):
    mc_dropout   : get_MC_samples-equivalent launch (1 eval + T stochastic passes, on-chip reduce)
    roofline     : the chain (forward + loss kernel, backward kernel) timed with events on the launch
                   stream, together and each alone; algorithmic FLOP per row = 4*M - 32 H (forward
@@ -98,7 +103,25 @@ def parse():
     ap.add_argument("--precision", default="f32x6", choices=sorted(PRECISIONS), help="arithmetic of the headline measurement")
     ap.add_argument("--only", action="store_true", help="skip the extra legs in the other precisions")
     ap.add_argument("--no-bf16", action="store_true", help="skip the extra bf16/fp32-mixed leg")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: roofline and per-phase times, MC-dropout, the other precisions, "
+                         "the BASELINE config legs, the CPU baseline (the --no-* / --only options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(d, arrays):
+    """Write {name: host array} as d/<name>.npy (float32 or float64 as computed)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def _cpu_model_name():
@@ -467,8 +490,9 @@ def main():
 
     loss_buf = torch.empty(4, dtype=torch.float64, device=dev)
 
-    def measure(precision, warmup, steps):
-        """Timed steps, per-phase kernel times (events on the launch stream) and the MC-dropout launch in one precision."""
+    def measure(precision, warmup, steps, extras=True, snapshot=False):
+        """Timed steps, per-phase kernel times (events on the launch stream) and the MC-dropout launch in one precision.
+        extras=False: the timed steps alone.  snapshot: r["outputs"] = host copies of what the last timed step computed."""
         model.dnn.set_precision(precision)
         dtype, chain_kernel, fwd_kernel, pf, pb, pw, peak1 = PRECISIONS[precision]
         model.dnn.train()
@@ -482,6 +506,12 @@ def main():
         elapsed = max_over_ranks(time.perf_counter() - t0)
         r = {"precision": precision, "dtype": dtype, "elapsed": elapsed, "ms_per_step": elapsed / steps * 1e3,
              "train_samples_per_s": n_global * steps / elapsed, "final_loss": float((loss[0] + 0.01 * loss[1]).item() / n_global)}
+        if snapshot:
+            host = lambda t: t.detach().cpu().numpy().copy()
+            r["outputs"] = {"train_loss_sums": host(loss), "params": host(flat), "grads": host(model.dnn._flat_grad),
+                            "lambdas": host(model._lambdas()), "lambda_stage_loss": host(loss_l), "stage_sums": host(model._sums)}
+        if not extras:
+            return r
         work = model._workspace(rows)
         drop = model.dnn.dropout_struct(7, model.row_offset)
 
@@ -547,7 +577,9 @@ def main():
         stage_cache[flags] = torch.empty(6 * rows, dtype=torch.float32, device=dev)
         _lib.check(lib.pinn_residuals_prepare(_ptr(xd), _ptr(u_eval), _ptr(yd), ctypes.byref(aff), _ptr(model._lambdas()), flags, rows,
                                               _ptr(stage_cache[flags]), _stream()), "residuals_prepare")
-    head = measure(args.precision, args.warmup, args.steps)
+    head = measure(args.precision, args.warmup, args.steps, extras=args.full, snapshot=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head.pop("outputs"))
     out = {
         "metric": "pinn_train_samples_per_s", "value": head["train_samples_per_s"], "unit": "samples/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -557,86 +589,87 @@ def main():
                                % rows,
                    "rows_per_gpu": rows, "global_rows": n_global, "parallelism": "dp%d" % world, "precision": args.precision,
                    "final_loss": head["final_loss"]},
-        "roofline": head["roofline"],
     }
-    if "mc_dropout" in head:
-        out["mc_dropout"] = head["mc_dropout"]
-    # HBM bytes per launch of the chain kernel: NOT measured by this run -- read from the newest committed rocprofv3 PMC
-    # summary (FETCH_SIZE and WRITE_SIZE collected in separate --pmc passes at this workload size by
-    # tools/collect_profiles.sh); null when the row count or the kernel differs
-    import glob
-    cand = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", "pmc_summary_x6.json" if args.precision.startswith("f32x6") else "pmc_summary_v2.json")))
-    pmc = cand[-1] if cand else ""
-    if rows == 1_000_000 and pmc:
-        try:
-            # one entry per kernel of the chain ("train_fwd_x3_kernel<256> + train_bwd_kernel<X6,256>": two launches per step)
-            keys = [part.strip().split("<")[0] + "<" + ("pinn::x6::" + part.split("<")[1].split(",")[0] + "," if "bwd" in part else "")
-                    for part in head["roofline"]["kernel"].split("+")]
-            table = json.load(open(pmc))
-            ks = [[v for n, v in table.items() if key in n][0] for key in keys]
-            # gfx950 correction of the guide's HBM section: FETCH_SIZE counts 16-B/lane streaming reads at half their bytes
-            out["roofline"]["traffic"] = sum((2.0 * k["FETCH_SIZE_KB"] + k["WRITE_SIZE_KB"]) * 1024.0 for k in ks)
-            out["roofline"]["traffic_source"] = os.path.relpath(pmc, ROOT) + " (a committed profile, not this run): (2 x FETCH_SIZE + WRITE_SIZE) " \
-                "KB x 1024, per launch, N=1e6 (separate --pmc passes; the factor 2 is the guide's gfx950 correction for 16-B/lane reads and an " \
-                "upper bound here: the layer-0 activation re-reads are dword loads); by design 3.84 KB/row of stash written, 3.84 KB/row of d " \
-                "pre-activations written, the stash read back once -- see roofline_hbm_design -- not the 36 B/row the algorithm needs"
-        except Exception:
-            pass
-
-    # ------------------------------------------------------------------ extra legs: the same measurement in the other precisions
-    if not args.only:
-        extras = [("exact_fp32", "fp32")] + ([] if args.no_bf16 else [("bf16_mixed", "bf16")]) + [("f32x6_g6", "f32x6g6")]
-        for name, prec in extras:
-            if prec == args.precision:
-                continue
-            e = measure(prec, max(1, args.warmup), args.steps)
-            o = {"dtype": e["dtype"], "train_samples_per_s": e["train_samples_per_s"], "ms_per_step": e["ms_per_step"],
-                 "chain_ms": e["roofline"]["ms"], "chain_frac_of_peak": e["roofline"]["frac"], "peak_TFLOPs": e["roofline"]["peak"],
-                 "wgrad_ms": e["roofline"]["wgrad"]["ms"]}
-            if "mc_dropout" in e:
-                o["mc_fwd_passes_per_s"] = e["mc_dropout"]["value"]
-                o["mc_seconds"] = e["mc_dropout"]["seconds"]
-            out[name] = o
-        model.dnn.set_precision(args.precision)
-
-    if world > 1:
-        # the same step with ONE blocking all-reduce of the whole bucket instead of the overlapped two-part one
-        model.overlap_allreduce = False
-        for _ in range(max(1, args.warmup)):
-            one_step()
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            one_step()
-        barrier()
-        out["ms_per_step_blocking_allreduce"] = max_over_ranks(time.perf_counter() - t0) / args.steps * 1e3
-        model.overlap_allreduce = True
     out["config"]["backend"] = dist.get_backend() if world > 1 else "none (single process)"
     out["config"]["world_size"] = world
     out["config"]["rows_per_rank"] = [rows] * world
-    # the HBM roof next to the MFMA one: DESIGN bytes of a step (not the 36 B/row the algorithm needs) -- the activation
-    # stash (3.84 KB/row) and the d pre-activations (3.84 KB/row) written by the chain, the stash read back by it and both
-    # read by the weight-gradient kernels -- over the same times; which roof binds is the larger fraction
-    r = out["roofline"]
-    chain_bytes, wgrad_bytes = (36 + 3 * 3840 + 3 * 256 + 2 * 8) * rows, (2 * 3840 + 32 + 8) * rows      # (+ v2 and du, dz across the kernel seam)
-    out["roofline_hbm_design"] = {
-        "bound": "hbm", "unit": "GB/s", "peak": 8000.0,
-        "chain": {"bytes": chain_bytes, "achieved": chain_bytes / (r["ms"] * 1e-3) / 1e9, "frac": chain_bytes / (r["ms"] * 1e-3) / 1e9 / 8000.0},
-        "wgrad": {"bytes": wgrad_bytes, "achieved": wgrad_bytes / (r["wgrad"]["ms"] * 1e-3) / 1e9,
-                  "frac": wgrad_bytes / (r["wgrad"]["ms"] * 1e-3) / 1e9 / 8000.0},
-        "step": {"bytes": chain_bytes + wgrad_bytes, "achieved": (chain_bytes + wgrad_bytes) / (out["ms_per_step"] * 1e-3) / 1e9,
-                 "frac": (chain_bytes + wgrad_bytes) / (out["ms_per_step"] * 1e-3) / 1e9 / 8000.0},
-        "note": "design bytes: stash written once (h and d pre as packed fp16 fragments, 3.84 KB/row each + heads), h read back by the chain, "
-                "both read once by the weight-gradient kernels; algorithmic bytes are 36 B/row (roofline.hbm_algorithmic_GBps).  A pure "
-                "LDS-DMA streaming read sustains 6.3 TB/s on this part (profiles/r03/hbm_read_probe.txt): the practical roof for wgrad"}
-    if rank == 0 and world == 1 and not args.no_configs:
+    if args.full:
+        out["roofline"] = head["roofline"]
+        if "mc_dropout" in head:
+            out["mc_dropout"] = head["mc_dropout"]
+        # HBM bytes per launch of the chain kernel: NOT measured by this run -- read from the newest committed rocprofv3 PMC
+        # summary (FETCH_SIZE and WRITE_SIZE collected in separate --pmc passes at this workload size by
+        # tools/collect_profiles.sh); null when the row count or the kernel differs
+        import glob
+        cand = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*", "pmc_summary_x6.json" if args.precision.startswith("f32x6") else "pmc_summary_v2.json")))
+        pmc = cand[-1] if cand else ""
+        if rows == 1_000_000 and pmc:
+            try:
+                # one entry per kernel of the chain ("train_fwd_x3_kernel<256> + train_bwd_kernel<X6,256>": two launches per step)
+                keys = [part.strip().split("<")[0] + "<" + ("pinn::x6::" + part.split("<")[1].split(",")[0] + "," if "bwd" in part else "")
+                        for part in head["roofline"]["kernel"].split("+")]
+                table = json.load(open(pmc))
+                ks = [[v for n, v in table.items() if key in n][0] for key in keys]
+                # gfx950 correction: FETCH_SIZE counts 16-B/lane streaming reads at half their bytes
+                out["roofline"]["traffic"] = sum((2.0 * k["FETCH_SIZE_KB"] + k["WRITE_SIZE_KB"]) * 1024.0 for k in ks)
+                out["roofline"]["traffic_source"] = os.path.relpath(pmc, ROOT) + " (a committed profile, not this run): (2 x FETCH_SIZE + WRITE_SIZE) " \
+                    "KB x 1024, per launch, N=1e6 (separate --pmc passes; the factor 2 is the gfx950 correction for 16-B/lane reads and an " \
+                    "upper bound here: the layer-0 activation re-reads are dword loads); by design 3.84 KB/row of stash written, 3.84 KB/row of d " \
+                    "pre-activations written, the stash read back once -- see roofline_hbm_design -- not the 36 B/row the algorithm needs"
+            except Exception:
+                pass
+
+        # ------------------------------------------------------------------ extra legs: the same measurement in the other precisions
+        if not args.only:
+            extras = [("exact_fp32", "fp32")] + ([] if args.no_bf16 else [("bf16_mixed", "bf16")]) + [("f32x6_g6", "f32x6g6")]
+            for name, prec in extras:
+                if prec == args.precision:
+                    continue
+                e = measure(prec, max(1, args.warmup), args.steps)
+                o = {"dtype": e["dtype"], "train_samples_per_s": e["train_samples_per_s"], "ms_per_step": e["ms_per_step"],
+                     "chain_ms": e["roofline"]["ms"], "chain_frac_of_peak": e["roofline"]["frac"], "peak_TFLOPs": e["roofline"]["peak"],
+                     "wgrad_ms": e["roofline"]["wgrad"]["ms"]}
+                if "mc_dropout" in e:
+                    o["mc_fwd_passes_per_s"] = e["mc_dropout"]["value"]
+                    o["mc_seconds"] = e["mc_dropout"]["seconds"]
+                out[name] = o
+            model.dnn.set_precision(args.precision)
+
+        if world > 1:
+            # the same step with ONE blocking all-reduce of the whole bucket instead of the overlapped two-part one
+            model.overlap_allreduce = False
+            for _ in range(max(1, args.warmup)):
+                one_step()
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                one_step()
+            barrier()
+            out["ms_per_step_blocking_allreduce"] = max_over_ranks(time.perf_counter() - t0) / args.steps * 1e3
+            model.overlap_allreduce = True
+        # the HBM roof next to the MFMA one: DESIGN bytes of a step (not the 36 B/row the algorithm needs) -- the activation
+        # stash (3.84 KB/row) and the d pre-activations (3.84 KB/row) written by the chain, the stash read back by it and both
+        # read by the weight-gradient kernels -- over the same times; which roof binds is the larger fraction
+        r = out["roofline"]
+        chain_bytes, wgrad_bytes = (36 + 3 * 3840 + 3 * 256 + 2 * 8) * rows, (2 * 3840 + 32 + 8) * rows      # (+ v2 and du, dz across the kernel seam)
+        out["roofline_hbm_design"] = {
+            "bound": "hbm", "unit": "GB/s", "peak": 8000.0,
+            "chain": {"bytes": chain_bytes, "achieved": chain_bytes / (r["ms"] * 1e-3) / 1e9, "frac": chain_bytes / (r["ms"] * 1e-3) / 1e9 / 8000.0},
+            "wgrad": {"bytes": wgrad_bytes, "achieved": wgrad_bytes / (r["wgrad"]["ms"] * 1e-3) / 1e9,
+                      "frac": wgrad_bytes / (r["wgrad"]["ms"] * 1e-3) / 1e9 / 8000.0},
+            "step": {"bytes": chain_bytes + wgrad_bytes, "achieved": (chain_bytes + wgrad_bytes) / (out["ms_per_step"] * 1e-3) / 1e9,
+                     "frac": (chain_bytes + wgrad_bytes) / (out["ms_per_step"] * 1e-3) / 1e9 / 8000.0},
+            "note": "design bytes: stash written once (h and d pre as packed fp16 fragments, 3.84 KB/row each + heads), h read back by the chain, "
+                    "both read once by the weight-gradient kernels; algorithmic bytes are 36 B/row (roofline.hbm_algorithmic_GBps).  A pure "
+                    "LDS-DMA streaming read sustains 6.3 TB/s on this part (profiles/r03/hbm_read_probe.txt): the practical roof for wgrad"}
+    if args.full and rank == 0 and world == 1 and not args.no_configs:
         del stage_cache
         model._work.clear()
         torch.cuda.empty_cache()
         out["configs"] = {"4_step": leg_config4_step(dev), "5": leg_config5(dev), "residuals": leg_residuals(dev),
                           "1": leg_config1(not args.no_cpu)}
     if rank == 0:
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.cpu_rows, 0 if args.no_cpu_full else rows, args.mc_passes)
         print(json.dumps(out))
     if world > 1:

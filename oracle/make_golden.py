@@ -23,8 +23,12 @@ import importlib.util
 import os
 import sys
 
-import numpy as np
-import torch
+# MKL's COMPATIBLE reproducibility branch: the recorded CPU float32 products do not depend on which vector code path
+# MKL picks on the generating host (tests/conftest.py pins the same branch for the bit-exact replays)
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,8 +1,13 @@
 import os
 import sys
 
-import numpy as np
-import pytest
+# The golden vectors were recorded with MKL's COMPATIBLE reproducibility branch (oracle/make_golden.py) and the oracle tests
+# replay them bit for bit on CPU torch: pin the same branch before the first MKL call, so that the float32 products do not
+# depend on the vector code path MKL picks on the host CPU (its AVX-512 path on Intel and its path on AMD round differently).
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "oracle")):
