@@ -287,6 +287,50 @@ int pinn_mlp_train_step(const pinn_net_t* net, float* d_params, const float* d_x
                         double* d_loss, void* d_work, size_t work_bytes, float* d_m, float* d_v, float lr, int step,
                         void* stream);
 
+/* ---- any layers list: exact-fp32 layer-by-layer kernels (pinn_general.hip) -----------------------------------------
+ * The entry points above run [8, H x k, 1] with one width H.  These run the reference's DNN(p, logvar, layers) (01:389-438) for
+ * any layers = [8, h_1, ..., h_k, 1]: 1 <= k <= 8 hidden layers of widths 1 <= h_i <= 2048 (unequal widths allowed), the last
+ * one h_k >= 4; the variance head is h_k -> h_k // 2 -> h_k // 4 -> 1 (floor division, 01:412-419).  n_in = 8 (the physics
+ * residuals read 8 fixed columns) and n_out = 1; anything else is PINN_E_ARCH.
+ * Flat layout: the reference's tensors in state_dict order, each torch [out, in] row-major and starting on a 16-byte boundary:
+ *   W_0 [h_1, 8] b_0  W_1 [h_2, h_1] b_1 ...  W_p [1, h_k] b_p  Wv_0 [h_k/2, h_k] bv_0  Wv_1 [h_k/4, h_k/2] bv_1  Wv_2 [1, h_k/4] bv_2
+ * (for equal widths this is pinn_param_count's layout).
+ * Dropout modules: l = 0 .. k-1 after hidden layer l, l = k after Wv_0.  Philox: the same stream as every other kernel, keyed
+ * (seed, stream + pass, global row, module, feature), 16-bit threshold round(65536 p); PINN_DROP_BITS: bit f & 31 of word
+ * word_l + f / 32 of a row, word_l = sum_{j<l} ceil(w_j / 32) over w = (h_1, ..., h_k, h_k / 2), words per row = the total.
+ * d_step_counter must be NULL (these nets run launch by launch).
+ * Arithmetic: exact fp32 (v_mfma_f32_16x16x4_f32, a k-ordered fmaf chain); no range limit, no packed copies in the net.  Widths
+ * are padded to 32 inside the workspace only.  Deterministic: no floating-point atomics; a row's forward / MC result does not
+ * depend on the rows around it; two identical calls are bitwise equal.  The workspace (16-byte aligned) holds padded weight
+ * copies and one bounded chunk of activations: pinn_gnet_workspace_bytes(net, n_rows, n_passes) is enough for forward and
+ * train_grads on n_rows rows and, with n_passes > 0, for MC-dropout with n_passes passes. */
+typedef struct pinn_gnet {
+  int n_in;         /* 8 */
+  int n_hidden;     /* k */
+  int width[8];     /* h_1 .. h_k (entries past k ignored) */
+  int n_out;        /* 1 */
+  int reserved;     /* 0 */
+} pinn_gnet_t;
+
+long long pinn_gnet_param_count(const pinn_gnet_t* net);             /* floats in the flat buffer; < 0: PINN_E_ARCH / PINN_E_ARG */
+size_t pinn_gnet_workspace_bytes(const pinn_gnet_t* net, long long n_rows, int n_passes);   /* 0 for an unsupported net */
+/* as pinn_mlp_forward */
+int pinn_gnet_forward(const pinn_gnet_t* net, const float* d_params, const float* d_x, long long n_rows, const pinn_dropout_t* drop,
+                      float* d_u, float* d_logvar, void* d_work, size_t work_bytes, void* stream);
+/* as pinn_mc_dropout: 1 eval pass + n_passes stochastic passes (PHILOX stream `stream + t`, BITS pass t), processed as virtual rows
+ * (pass, row); per row the moments of pinn_mc_dropout in pass order */
+int pinn_gnet_mc_dropout(const pinn_gnet_t* net, const float* d_params, const float* d_x, long long n_rows, const pinn_dropout_t* drop,
+                         int n_passes, float* d_pred_mean, float* d_a_u, float* d_e_u, void* d_work, size_t work_bytes, void* stream);
+/* as pinn_mlp_train_grads: d_grads [pinn_gnet_param_count] already divided by n_global, d_loss double[4] raw sums
+ * (nll, |logvar|, (y-u)^2, sum dL/du) */
+int pinn_gnet_train_grads(const pinn_gnet_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
+                          long long n_global, const pinn_dropout_t* drop, float* d_grads, double* d_loss, void* d_work,
+                          size_t work_bytes, void* stream);
+/* pinn_gnet_train_grads + pinn_adam_step (lr, 1-based step by value), like pinn_mlp_train_step */
+int pinn_gnet_train_step(const pinn_gnet_t* net, float* d_params, const float* d_x, const float* d_y, long long n_rows,
+                         long long n_global, const pinn_dropout_t* drop, float* d_grads, double* d_loss, void* d_work,
+                         size_t work_bytes, float* d_m, float* d_v, float lr, int step, void* stream);
+
 /* ---- results assembly: create_comprehensive_results_array_v2 (01:1877-2010) -----------------------------------
  * Fills d_out = float64 [n_rows, 22] row-major (the `comprehensive_results` layout scripts 02-05 read):
  *   0-7 inputs and 8 target, de-normalised like sklearn's inverse_transform on float32 (aff->x_*, aff->y_*; 01:1916-1917);

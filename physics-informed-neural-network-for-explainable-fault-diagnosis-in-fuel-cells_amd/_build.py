@@ -37,6 +37,7 @@ SOURCES = [
     ("pinn_x6_wgrad.hip", []),
     ("pinn_wide.hip", []),
     ("pinn_optim.hip", []),
+    ("pinn_general.hip", []),
 ]
 HEADERS = ["pinn_mlp_core.h", "pinn_bf16_core.h", "pinn_x6_core.h", "pinn_wgrad_args.h", os.path.join("..", "..", "include", "pinn_hip.h")]
 

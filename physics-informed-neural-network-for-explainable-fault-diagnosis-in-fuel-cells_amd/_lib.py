@@ -45,6 +45,17 @@ class Net(ctypes.Structure):
         super().__init__(n_in, hidden, n_hidden, precision, d_packed)
 
 
+class GNet(ctypes.Structure):
+    """pinn_gnet_t: any layers list [8, h_1, ..., h_k, 1] (pinn_general.hip)."""
+    _fields_ = [("n_in", c_int), ("n_hidden", c_int), ("width", c_int * 8), ("n_out", c_int), ("reserved", c_int)]
+
+    def __init__(self, layers):
+        layers = [int(v) for v in layers]
+        hid = layers[1:-1]
+        w = (c_int * 8)(*(hid[:8] + [0] * (8 - min(len(hid), 8))))
+        super().__init__(layers[0], len(hid), w, layers[-1], 0)
+
+
 class Dropout(ctypes.Structure):
     _fields_ = [("mode", c_int), ("p", c_float * 9), ("seed", ctypes.c_ulonglong), ("stream", c_uint),
                 ("row_offset", c_ll), ("d_bits", c_void_p), ("d_step_counter", c_void_p)]
@@ -94,6 +105,16 @@ _SIGS = {
     "pinn_residuals_cached": (c_int, [c_void_p, ctypes.POINTER(Affine), c_void_p, c_uint, c_ll, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_net_f_t": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Affine), c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
                              c_void_p]),
+    "pinn_gnet_param_count": (c_ll, [ctypes.POINTER(GNet)]),
+    "pinn_gnet_workspace_bytes": (c_size_t, [ctypes.POINTER(GNet), c_ll, c_int]),
+    "pinn_gnet_forward": (c_int, [ctypes.POINTER(GNet), c_void_p, c_void_p, c_ll, ctypes.POINTER(Dropout), c_void_p, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
+    "pinn_gnet_mc_dropout": (c_int, [ctypes.POINTER(GNet), c_void_p, c_void_p, c_ll, ctypes.POINTER(Dropout), c_int, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gnet_train_grads": (c_int, [ctypes.POINTER(GNet), c_void_p, c_void_p, c_void_p, c_ll, c_ll, ctypes.POINTER(Dropout),
+                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gnet_train_step": (c_int, [ctypes.POINTER(GNet), c_void_p, c_void_p, c_void_p, c_ll, c_ll, ctypes.POINTER(Dropout),
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_float, c_int, c_void_p]),
     "pinn_results_assemble": (c_int, [c_void_p, c_void_p, ctypes.POINTER(Affine), ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p]),
 }

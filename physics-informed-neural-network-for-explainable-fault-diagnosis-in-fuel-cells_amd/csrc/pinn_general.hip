@@ -1,0 +1,960 @@
+// pinn_general.hip -- any layers list [8, h_1, ..., h_k, 1] (01:389-438) on exact-fp32 layer-by-layer kernels for gfx950.
+//
+// The fused chain (pinn_mlp.hip / pinn_train.hip, H in {128, 256}) and the wide kernels (pinn_wide.hip, H in {512, 1024, 2048})
+// need one width for every hidden layer.  This family takes unequal widths 1 <= h_i <= 2048: every layer is one launch of a
+// tiled GEMM on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain: exact fp32) with the layer's elementwise work fused into its
+// epilogue, and activations go through HBM in caller-provided workspace, one bounded row chunk at a time.
+//
+//   gemm_kernel<kFwd>   act_out^T[f][r] = tanh(b[f] + sum_k W[f][k] act_in[r][k]), then dropout (Philox or injected bits)
+//   gemm_kernel<kBwd>   dpre_in[r][i] = (sum_o W[o][i] dpre_out[r][o] (+ w_p[i] du[r])) * scale * keep * (1 - a^2)
+//   gemm_kernel<kWgrad> slab[s][o][i] = sum_{r in slice s} dpre_out[r][o] act_in[r][i]; column i = n_in is the bias (a ones column)
+//   heads_kernel        predict dot, variance-head dot, softplus / log, per-row dL/du, dL/dz, loss partials, d pre_v2
+//   vec_grad_kernel     the two 1-row tensors (predict, last variance layer) of the gradient, per slice
+//   reduce / finalize   fixed-order slab sums -> the flat gradient (state_dict layout); loss sums in fp64
+//   mc_moments_kernel   MC-dropout: (pass, row) pairs are virtual rows; per row, in pass order, the Welford moments of pinn_mc_dropout
+//
+// Widths are padded to 32 inside the workspace only (zero weights, zero activations); the flat parameter buffer holds exactly the
+// reference's tensors.  Determinism: no floating-point atomics; every output element's K order is fixed by the layer alone (the
+// same 32-wide K slabs in the same order for every tile), so a row's forward / MC result does not depend on its tile or chunk.
+#include "pinn_mlp_core.h"
+
+namespace pinn {
+namespace gen {
+
+constexpr int kMaxHidden = 8;
+constexpr int kMaxMat = kMaxHidden + 4;      // hidden layers, predict, variance head 0, 1, 2
+constexpr int kMaxWidth = 2048;
+constexpr int kLd = 36;                      // LDS row stride (floats) of a 64 x 32 operand tile
+constexpr int kBK = 32;
+constexpr size_t kTrainBudget = 512ull << 20;   // activation bytes per training chunk
+constexpr size_t kInferBudget = 256ull << 20;   // activation bytes per inference chunk
+constexpr long long kMaxChunkRows = 131072;
+constexpr long long kMaxVirtualRows = 1ll << 20;
+constexpr size_t kSlabBudget = 256ull << 20;
+
+enum { kFwd = 0, kBwd = 1, kWgrad = 2 };
+
+__host__ __device__ inline long long rup(long long v, long long m) { return (v + m - 1) / m * m; }
+
+// ---------------------------------------------------------------------------------------
+// shape, flat layout and workspace layout (host)
+// ---------------------------------------------------------------------------------------
+struct Shape {
+  int k;                       // hidden layers
+  int w[kMaxHidden];           // hidden widths
+  int hk, hv1, hv2;            // last hidden width, h_k // 2, h_k // 4
+  int n_mat;                   // k + 4
+  int out[kMaxMat], in[kMaxMat];
+  long long woff[kMaxMat], boff[kMaxMat], total;     // flat buffer (floats)
+  long long reg[kMaxMat], gtotal;                    // gradient regions [out][in + 1] (bias = column in), 16-B aligned
+  long long pf[kMaxMat], pt[kMaxMat], pack_total;    // packed copies: forward [mp][kp], transposed [kp][mp]; -1 = none
+  int mp[kMaxMat], kp[kMaxMat];
+  int word_off[kMaxHidden + 1], words;               // keep-word offset of dropout module l, words per row
+  int max_wp;
+  int mat_pred() const { return k; }
+  int mat_v0() const { return k + 1; }
+  int mat_v1() const { return k + 2; }
+  int mat_v2() const { return k + 3; }
+  bool is_gemm(int t) const { return t < k || t == k + 1 || t == k + 2; }
+};
+
+static int make_shape(const pinn_gnet_t* net, Shape* s) {
+  if (!net) return PINN_E_ARG;
+  if (net->n_in != 8 || net->n_out != 1) return PINN_E_ARCH;
+  if (net->n_hidden < 1 || net->n_hidden > kMaxHidden) return PINN_E_ARCH;
+  for (int l = 0; l < net->n_hidden; ++l)
+    if (net->width[l] < 1 || net->width[l] > kMaxWidth) return PINN_E_ARCH;
+  if (net->width[net->n_hidden - 1] < 4) return PINN_E_ARCH;
+  s->k = net->n_hidden;
+  for (int l = 0; l < kMaxHidden; ++l) s->w[l] = l < s->k ? net->width[l] : 0;
+  s->hk = s->w[s->k - 1]; s->hv1 = s->hk / 2; s->hv2 = s->hk / 4;
+  s->n_mat = s->k + 4;
+  for (int t = 0; t < s->k; ++t) { s->out[t] = s->w[t]; s->in[t] = t == 0 ? 8 : s->w[t - 1]; }
+  s->out[s->k] = 1;          s->in[s->k] = s->hk;
+  s->out[s->k + 1] = s->hv1; s->in[s->k + 1] = s->hk;
+  s->out[s->k + 2] = s->hv2; s->in[s->k + 2] = s->hv1;
+  s->out[s->k + 3] = 1;      s->in[s->k + 3] = s->hv2;
+  long long off = 0, g = 0, p = 0;
+  s->max_wp = 0;
+  for (int t = 0; t < s->n_mat; ++t) {
+    s->woff[t] = off; off += rup((long long)s->out[t] * s->in[t], 4);
+    s->boff[t] = off; off += rup(s->out[t], 4);
+    s->reg[t] = g; g += rup((long long)s->out[t] * (s->in[t] + 1), 4);
+    s->mp[t] = (int)rup(s->out[t], 32); s->kp[t] = (int)rup(s->in[t], 32);
+    s->pf[t] = s->pt[t] = -1;
+    if (s->is_gemm(t)) {
+      s->pf[t] = p; p += (long long)s->mp[t] * s->kp[t];
+      if (t != 0) { s->pt[t] = p; p += (long long)s->mp[t] * s->kp[t]; }
+      if (s->mp[t] > s->max_wp) s->max_wp = s->mp[t];
+    }
+  }
+  s->total = off; s->gtotal = g; s->pack_total = p;
+  int wo = 0;
+  for (int l = 0; l <= s->k; ++l) { s->word_off[l] = wo; wo += ((l < s->k ? s->w[l] : s->hv1) + 31) / 32; }
+  s->words = wo;
+  return PINN_OK;
+}
+
+// output activation buffer of GEMM matrix t (width mp[t]); index into Layout::act
+static int act_index(const Shape& s, int t) { return t < s.k ? t : (t == s.mat_v0() ? s.k : s.k + 1); }
+
+struct Layout {
+  long long rows;              // rows (virtual rows) per chunk
+  int slices; long long slice_rows;
+  size_t pack, act[kMaxHidden + 2], keep, dpre[2], du, dz, slabs, acc, loss, ubuf, lvbuf, state, end;
+};
+
+static size_t take(size_t& at, size_t bytes) { const size_t o = at; at = (at + bytes + 255) / 256 * 256; return o; }
+
+static long long n_chunks(long long n, long long r) { return (n + r - 1) / r; }
+
+// training: every activation of a chunk is kept for the backward pass
+static Layout train_layout(const Shape& s, long long n_rows) {
+  Layout L{};
+  long long per_row = s.words + 2LL * s.max_wp + 2;
+  for (int t = 0; t < s.n_mat; ++t) if (s.is_gemm(t)) per_row += s.mp[t];
+  long long cap = (long long)(kTrainBudget / (4 * (size_t)per_row)) / 64 * 64;
+  cap = cap < 64 ? 64 : (cap > kMaxChunkRows ? kMaxChunkRows : cap);
+  L.rows = rup(n_rows < 1 ? 1 : n_rows, 64);
+  if (L.rows > cap) L.rows = cap;
+  // weight-gradient slices: enough tiles to fill the chip, at most kSlabBudget of partial slabs, >= 128 rows each
+  long long tiles = 1;
+  for (int t = 0; t < s.n_mat; ++t)
+    if (s.is_gemm(t)) {
+      const long long tt = rup(s.out[t], 64) / 64 * (rup(s.in[t] + 1, 64) / 64);
+      if (tt > tiles) tiles = tt;
+    }
+  long long sl = (2048 + tiles - 1) / tiles;
+  const long long by_rows = L.rows / 128 > 1 ? L.rows / 128 : 1;
+  const long long by_mem = (long long)(kSlabBudget / (4 * (size_t)s.gtotal)) > 1 ? (long long)(kSlabBudget / (4 * (size_t)s.gtotal)) : 1;
+  if (sl > by_rows) sl = by_rows;
+  if (sl > by_mem) sl = by_mem;
+  if (sl < 1) sl = 1;
+  L.slice_rows = rup((L.rows + sl - 1) / sl, kBK);
+  L.slices = (int)((L.rows + L.slice_rows - 1) / L.slice_rows);
+  size_t at = 0;
+  L.pack = take(at, 4 * (size_t)s.pack_total);
+  for (int t = 0; t < s.n_mat; ++t) if (s.is_gemm(t)) L.act[act_index(s, t)] = take(at, 4 * (size_t)L.rows * s.mp[t]);
+  L.keep = take(at, 4 * (size_t)L.rows * s.words);
+  L.dpre[0] = take(at, 4 * (size_t)L.rows * s.max_wp);
+  L.dpre[1] = take(at, 4 * (size_t)L.rows * s.max_wp);
+  L.du = take(at, 4 * (size_t)L.rows);
+  L.dz = take(at, 4 * (size_t)L.rows);
+  L.slabs = take(at, 4 * (size_t)L.slices * s.gtotal);
+  L.acc = take(at, 4 * (size_t)s.gtotal);
+  L.loss = take(at, 8 * 8 * (size_t)(n_chunks(n_rows, L.rows) * (L.rows / 16)));
+  L.end = at;
+  return L;
+}
+
+// forward / MC-dropout: two ping-pong activation buffers (+ one for the variance head's second layer) per chunk of virtual rows (pass, row)
+static Layout infer_layout(const Shape& s, long long n_rows, int n_passes) {
+  Layout L{};
+  const long long per_row = 3LL * s.max_wp + 2;
+  long long cap = (long long)(kInferBudget / (4 * (size_t)per_row)) / 64 * 64;
+  cap = cap < 64 ? 64 : (cap > kMaxVirtualRows ? kMaxVirtualRows : cap);
+  const long long v = (n_rows < 1 ? 1 : n_rows) * (n_passes > 0 ? (long long)n_passes + 1 : 1);
+  L.rows = rup(v, 64);
+  if (L.rows > cap) L.rows = cap;
+  size_t at = 0;
+  L.pack = take(at, 4 * (size_t)s.pack_total);
+  L.act[0] = take(at, 4 * (size_t)L.rows * s.max_wp);
+  L.act[1] = take(at, 4 * (size_t)L.rows * s.max_wp);
+  L.act[2] = take(at, 4 * (size_t)L.rows * s.max_wp);
+  L.ubuf = take(at, 4 * (size_t)L.rows);
+  L.lvbuf = take(at, 4 * (size_t)L.rows);
+  L.state = take(at, 4 * 4 * (size_t)(n_passes > 0 ? n_rows : 0));
+  L.end = at;
+  return L;
+}
+
+// ---------------------------------------------------------------------------------------
+// dropout (device copy; same Philox stream and 16-bit threshold as every other kernel)
+// ---------------------------------------------------------------------------------------
+struct Drop {
+  int mode;
+  unsigned thr[kMaxDrop];
+  float scale[kMaxDrop];
+  unsigned seed_lo, seed_hi, stream;
+  long long row_offset;
+  const unsigned* bits;
+  int words;
+};
+
+static int convert(const Shape& s, const pinn_dropout_t* in, Drop* d) {
+  d->mode = PINN_DROP_NONE; d->seed_lo = d->seed_hi = d->stream = 0; d->row_offset = 0; d->bits = nullptr; d->words = s.words;
+  for (int l = 0; l < kMaxDrop; ++l) { d->thr[l] = 0; d->scale[l] = 1.0f; }
+  if (!in) return PINN_OK;
+  if (in->mode < PINN_DROP_NONE || in->mode > PINN_DROP_BITS) return PINN_E_ARG;
+  if (in->d_step_counter) return PINN_E_ARG;        // general nets run launch by launch (no captured replay)
+  d->mode = in->mode;
+  d->row_offset = in->row_offset;
+  if (in->mode == PINN_DROP_NONE) return PINN_OK;
+  for (int l = 0; l <= s.k; ++l) {
+    const float p = in->p[l];
+    if (!(p >= 0.0f && p < 1.0f)) return PINN_E_ARG;
+    double t = floor((double)p * 65536.0 + 0.5);
+    if (p > 0.0f && t < 1.0) t = 1.0;
+    d->thr[l] = (unsigned)(t < 0 ? 0 : (t > 65536.0 ? 65536.0 : t));
+    d->scale[l] = 1.0f / (float)(1.0 - (double)p);
+  }
+  d->seed_lo = (unsigned)(in->seed & 0xFFFFFFFFull);
+  d->seed_hi = (unsigned)(in->seed >> 32);
+  d->stream = in->stream;
+  if (in->mode == PINN_DROP_BITS) {
+    if (!in->d_bits) return PINN_E_ARG;
+    d->bits = in->d_bits;
+  }
+  return PINN_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// weight packing: zero-padded forward [mp][kp] and transposed [kp][mp] copies of the GEMM matrices
+// ---------------------------------------------------------------------------------------
+struct PackJob { long long src, dst; int out, in, mp, kp, transposed; };
+struct PackArgs { const float* params; float* pack; PackJob job[2 * kMaxMat]; int n_jobs; };
+
+__global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
+  const PackJob j = a.job[blockIdx.y];
+  const long long n = (long long)j.mp * j.kp;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+    int o, i;
+    if (j.transposed) { i = (int)(e / j.mp); o = (int)(e - (long long)i * j.mp); }
+    else { o = (int)(e / j.kp); i = (int)(e - (long long)o * j.kp); }
+    a.pack[j.dst + e] = (o < j.out && i < j.in) ? a.params[j.src + (long long)o * j.in + i] : 0.0f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// the layer GEMM: 64 x 64 output tile per 256-thread workgroup, 32 x 32 per wave (2 x 2 MFMA blocks), K slabs of 32.
+// FWD / BWD: M = features (A: packed weights, K-contiguous), N = rows (B: activations [row][k], K-contiguous).
+// WGRAD:     M = output features (A: d pre-activations [row][o]), N = input features (B: activations [row][i]), K = rows.
+// ---------------------------------------------------------------------------------------
+struct GemmArgs {
+  const float* A; long long lda; long long a_mv, a_kv;
+  const float* B; long long ldb; long long b_mv, b_kv;
+  long long M, K;                // output feature extent (stores: m < M), contraction length (FWD / BWD)
+  float* out; long long ldo;
+  long long n_valid;             // valid rows of the chunk
+  // FWD
+  const float* bias; int bias_n; int module;   // dropout module of the output (-1: tanh only)
+  int map_rows;                  // B rows are input rows: chunk row n -> row0 + n (MC: virtual row -> row % n_rows)
+  int mc;
+  long long row0, n_rows;
+  Drop drop;
+  unsigned* keep; int keep_off;  // keep words [row][drop.words] (training), module word offset
+  // BWD
+  const float* stash; long long ld_stash; int stash_module;
+  const float* wp; const float* du; int wp_n;
+  const unsigned* keep_in;
+  // WGRAD
+  long long slice_rows; float* slab; long long slab_stride; long long reg; int out_real, in_real;
+};
+
+// one 64 x 32 operand tile: K-contiguous source (row m, 4 consecutive k per float4)
+__device__ __forceinline__ void load_kc(f32x4 (&r)[2], const float* __restrict__ p, long long ld, long long m0, long long k0,
+                                        long long mv, long long kv, int tid) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const long long m = m0 + (tid >> 3) + 32 * q, k = k0 + (tid & 7) * 4;
+    r[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (m < mv && k < kv) r[q] = *reinterpret_cast<const f32x4*>(p + m * ld + k);
+  }
+}
+__device__ __forceinline__ void store_kc(float* s, const f32x4 (&r)[2], int tid) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q) *reinterpret_cast<f32x4*>(s + ((tid >> 3) + 32 * q) * kLd + (tid & 7) * 4) = r[q];
+}
+// MN-contiguous source: element (m, k) at p[k * ld + m], 4 consecutive m per float4
+__device__ __forceinline__ void load_mc(f32x4 (&r)[2], const float* __restrict__ p, long long ld, long long m0, long long k0,
+                                        long long mv, long long kv, int tid, int ones_col) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const long long k = k0 + (tid >> 4) + 16 * q, m = m0 + (tid & 15) * 4;
+    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (k < kv && m < mv) v = *reinterpret_cast<const f32x4*>(p + k * ld + m);
+    if (ones_col >= 0) {          // columns >= the layer's real input width: the bias column (1 on valid rows), then zeros
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (m + e >= ones_col) v[e] = (m + e == ones_col && k < kv) ? 1.0f : 0.0f;
+    }
+    r[q] = v;
+  }
+}
+__device__ __forceinline__ void store_mc(float* s, const f32x4 (&r)[2], int tid) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int k = (tid >> 4) + 16 * q, m = (tid & 15) * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s[(m + e) * kLd + k] = r[q][e];
+  }
+}
+
+// row context of chunk row n in FWD: input row (for x and the Philox / bit-mask keys) and pass (-1: MC eval pass, dropout off)
+__device__ __forceinline__ void row_ctx(const GemmArgs& a, long long n, long long& lrow, int& pass) {
+  if (a.mc) {
+    const long long v = a.row0 + n;
+    const long long q = v / a.n_rows;
+    lrow = v - q * a.n_rows;
+    pass = (int)q - 1;
+  } else {
+    lrow = a.row0 + n;
+    pass = 0;
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
+  __shared__ __attribute__((aligned(16))) float As[64 * kLd];
+  __shared__ __attribute__((aligned(16))) float Bs[64 * kLd];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, li = lane & 15;
+  const int wm = wave & 1, wn = wave >> 1;
+  const long long m0 = (long long)blockIdx.y * 64, n0 = (long long)blockIdx.x * 64;
+  long long kbeg = 0, kend = a.K;
+  if (MODE == kWgrad) {
+    kbeg = (long long)blockIdx.z * a.slice_rows;
+    kend = kbeg + a.slice_rows;
+    if (kend > a.K) kend = a.K;
+  }
+
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (MODE == kFwd) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long long m = m0 + 32 * wm + 16 * i + 4 * kq + r;
+          acc[i][j][r] = m < a.bias_n ? a.bias[m] : 0.0f;
+        }
+      }
+      if (MODE == kBwd && a.wp) {
+        const long long n = n0 + 32 * wn + 16 * j + li;
+        const float du = a.du[n];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long long m = m0 + 32 * wm + 16 * i + 4 * kq + r;
+          acc[i][j][r] = (m < a.wp_n ? a.wp[m] : 0.0f) * du;
+        }
+      }
+    }
+
+  // B rows of the FWD input layer are input rows (x), possibly virtual (MC)
+  auto load_b = [&](f32x4 (&r)[2], long long k0) {
+    if (MODE == kWgrad) {
+      load_mc(r, a.B, a.ldb, n0, k0, a.b_mv, a.b_kv, tid, a.in_real);
+    } else if (MODE == kFwd && a.map_rows) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const long long n = n0 + (tid >> 3) + 32 * q, k = k0 + (tid & 7) * 4;
+        long long lrow; int pass;
+        row_ctx(a, n, lrow, pass);
+        r[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (n < a.n_valid && k < a.b_kv) r[q] = *reinterpret_cast<const f32x4*>(a.B + lrow * a.ldb + k);
+      }
+    } else {
+      load_kc(r, a.B, a.ldb, n0, k0, a.b_mv, a.b_kv, tid);
+    }
+  };
+  auto load_a = [&](f32x4 (&r)[2], long long k0) {
+    if (MODE == kWgrad) load_mc(r, a.A, a.lda, m0, k0, a.a_mv, a.a_kv, tid, -1);
+    else load_kc(r, a.A, a.lda, m0, k0, a.a_mv, a.a_kv, tid);
+  };
+
+  f32x4 ra[2], rb[2];
+  if (kbeg < kend) { load_a(ra, kbeg); load_b(rb, kbeg); }
+  for (long long k = kbeg; k < kend; k += kBK) {
+    __syncthreads();
+    if (MODE == kWgrad) { store_mc(As, ra, tid); store_mc(Bs, rb, tid); }
+    else { store_kc(As, ra, tid); store_kc(Bs, rb, tid); }
+    __syncthreads();
+    if (k + kBK < kend) { load_a(ra, k + kBK); load_b(rb, k + kBK); }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      f32x4 fa[2], fb[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) fa[i] = *reinterpret_cast<const f32x4*>(As + (32 * wm + 16 * i + li) * kLd + 16 * h + 4 * kq);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const f32x4*>(Bs + (32 * wn + 16 * j + li) * kLd + 16 * h + 4 * kq);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][r], fb[j][r], acc[i][j], 0, 0, 0);
+    }
+  }
+
+  // acc[i][j][r] = C[m = m0 + 32 wm + 16 i + 4 kq + r][n = n0 + 32 wn + 16 j + li]
+  const long long mw = m0 + 32 * wm;          // first feature of this wave's 32-feature group
+  if (MODE == kWgrad) {
+    float* dst = a.slab + (long long)blockIdx.z * a.slab_stride + a.reg;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long long o = mw + 16 * i + 4 * kq + r, c = n0 + 32 * wn + 16 * j + li;
+          if (o < a.out_real && c <= a.in_real) dst[o * (a.in_real + 1) + c] = acc[i][j][r];
+        }
+    return;
+  }
+  const int P = (int)(mw >> 5);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const long long n = n0 + 32 * wn + 16 * j + li;
+    if (MODE == kFwd) {
+      long long lrow; int pass;
+      row_ctx(a, n, lrow, pass);
+      const bool on = a.module >= 0 && a.drop.mode != PINN_DROP_NONE && pass >= 0;
+      const unsigned thr = a.module >= 0 ? a.drop.thr[a.module] : 0u;
+      const float scale = on ? a.drop.scale[a.module] : 1.0f;
+      unsigned mine = 0;
+      if (on && a.drop.mode == PINN_DROP_PHILOX) {
+        const unsigned long long g = (unsigned long long)(a.drop.row_offset + lrow);
+        unsigned o[4];
+        philox4x32_10((unsigned)g, (unsigned)(g >> 32), ((unsigned)a.module << 16) | ((unsigned)P << 2) | (unsigned)kq,
+                      a.drop.stream + (unsigned)pass, a.drop.seed_lo, a.drop.seed_hi, o);
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int idx = 4 * b + r;
+            const unsigned draw = (o[idx >> 1] >> (16 * (idx & 1))) & 0xFFFFu;
+            mine |= (draw >= thr ? 1u : 0u) << (16 * b + 4 * kq + r);
+          }
+      }
+      mine |= __shfl_xor(mine, 16, 64);
+      mine |= __shfl_xor(mine, 32, 64);
+      unsigned word = 0xFFFFFFFFu;
+      if (on && a.drop.mode == PINN_DROP_PHILOX) word = mine;
+      if (on && a.drop.mode == PINN_DROP_BITS && n < a.n_valid)
+        word = a.drop.bits[((long long)pass * a.n_rows + lrow) * a.drop.words + a.keep_off + P];
+      if (mw < a.M) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          f32x4 v;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float t = tanh_f32(acc[i][j][r]);
+            v[r] = ((word >> (16 * i + 4 * kq + r)) & 1u) ? t * scale : 0.0f;
+          }
+          *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = v;
+        }
+        if (a.keep && a.module >= 0 && kq == 0) a.keep[n * a.drop.words + a.keep_off + P] = word;
+      }
+    } else {      // kBwd
+      if (mw < a.M) {
+        const bool on = a.drop.mode != PINN_DROP_NONE && a.stash_module >= 0;
+        const float scale = on ? a.drop.scale[a.stash_module] : 1.0f, inv_scale = 1.0f / scale;
+        const unsigned word = a.stash_module >= 0 ? a.keep_in[n * a.drop.words + a.keep_off + P] : 0xFFFFFFFFu;
+        const bool valid = n < a.n_valid;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const f32x4 h = *reinterpret_cast<const f32x4*>(a.stash + n * a.ld_stash + mw + 16 * i + 4 * kq);
+          f32x4 v;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float t = h[r] * inv_scale;
+            const float g = acc[i][j][r] * (scale * (1.0f - t * t));
+            v[r] = (valid && ((word >> (16 * i + 4 * kq + r)) & 1u)) ? g : 0.0f;
+          }
+          *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = v;
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// heads: 16 lanes per row.  u = w_p . h_k + b_p;  z = w_v2 . v2 + b_v2;  logvar = log(softplus(z) + 1e-6)
+// ---------------------------------------------------------------------------------------
+enum { kHeadFwd = 0, kHeadMC = 1, kHeadTrain = 2 };
+struct HeadArgs {
+  const float* h; long long ldh; int hk;          // last hidden activation [row][ldh]
+  const float* v2; long long ldv; int hv2;        // variance head's second activation [row][ldv]
+  const float* wp; const float* bp; const float* wv2; const float* bv2;
+  long long n_valid, row0;
+  float* u; float* lv;                            // FWD: outputs at row0 + r; MC: chunk buffers at r
+  const float* y; long long n_global;             // TRAIN
+  float* du; float* dz; float* dpre_v2; long long ld_dpre; int wd; double* loss_part;
+};
+
+__device__ __forceinline__ float sum16(float s) {
+  s += __shfl_xor(s, 8, 64);
+  s += __shfl_xor(s, 4, 64);
+  s += __shfl_xor(s, 2, 64);
+  s += __shfl_xor(s, 1, 64);
+  return s;
+}
+
+template <int HM>
+__global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
+  __shared__ double red[16][5];
+  const int tid = threadIdx.x, g = tid & 15, rr = tid >> 4;
+  const long long r = (long long)blockIdx.x * 16 + rr;      // chunk row (every one is allocated)
+  const float* hrow = a.h + r * a.ldh;
+  const float* vrow = a.v2 + r * a.ldv;
+  float su = 0.f, sz = 0.f;
+  for (int f = g; f < a.hk; f += 16) su = fmaf(a.wp[f], hrow[f], su);
+  for (int f = g; f < a.hv2; f += 16) sz = fmaf(a.wv2[f], vrow[f], sz);
+  const float u = sum16(su) + a.bp[0];
+  const float z = sum16(sz) + a.bv2[0];
+  const bool valid = r < a.n_valid;
+  if (HM == kHeadFwd || HM == kHeadMC) {
+    if (valid && g == 0) {
+      const long long o = HM == kHeadFwd ? a.row0 + r : r;
+      a.u[o] = u;
+      a.lv[o] = logf(softplus_f32(z) + 1e-6f);
+    }
+    return;
+  }
+  // aleatoric_loss (01:916-927) and its gradient, arithmetic of pinn_train.hip
+  const float inv_n = (float)(1.0 / (double)a.n_global);
+  float du = 0.f, dz = 0.f;
+  double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  {
+    const float yv = a.y[valid ? a.row0 + r : a.row0];
+    const float sp = softplus_f32(z);
+    const float var = sp + 1e-6f;
+    const float s = logf(var);
+    const float prec = expf(-s);
+    const float e = yv - u;
+    if (valid) {
+      du = -(prec * e) * inv_n;
+      const float sgn = (s > 0.f) ? 1.f : ((s < 0.f) ? -1.f : 0.f);
+      const float ds = (-0.5f * prec * e * e + 0.5f + 0.01f * sgn) * inv_n;
+      const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
+      dz = ds * sig / var;
+      t[0] = (double)(0.5f * prec * e * e + 0.5f * s);
+      t[1] = (double)fabsf(s);
+      t[2] = (double)(e * e);
+      t[3] = (double)du;
+      t[4] = (double)dz;
+    }
+  }
+  if (g == 0) {
+    a.du[r] = du;
+    a.dz[r] = dz;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) red[rr][q] = t[q];
+  }
+  // d pre_v2 = w_v2[f] * dz * (1 - v2^2) (zero in the padding and on invalid rows)
+  float* drow = a.dpre_v2 + r * a.ld_dpre;
+  for (int f = g; f < a.wd; f += 16) {
+    const float v = vrow[f];
+    drow[f] = f < a.hv2 ? a.wv2[f] * dz * (1.0f - v * v) : 0.0f;
+  }
+  __syncthreads();
+  if (tid < 5) {
+    double s = 0.0;
+    for (int q = 0; q < 16; ++q) s += red[q][tid];
+    a.loss_part[((a.row0 / 16) + blockIdx.x) * 8 + tid] = s;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// the two one-row tensors of the gradient, per slice: predict (du x h_k, bias = sum du), last variance layer (dz x v2, sum dz)
+// ---------------------------------------------------------------------------------------
+struct VecArgs {
+  const float* h; long long ldh; int hk;
+  const float* v2; long long ldv; int hv2;
+  const float* du; const float* dz;
+  long long K, slice_rows;
+  float* slab; long long slab_stride, reg_p, reg_v2;
+};
+__global__ __launch_bounds__(256) void vec_grad_kernel(VecArgs a) {
+  const int c = blockIdx.y * 256 + threadIdx.x;
+  const long long r0 = (long long)blockIdx.x * a.slice_rows;
+  long long r1 = r0 + a.slice_rows;
+  if (r1 > a.K) r1 = a.K;
+  float* dst = a.slab + (long long)blockIdx.x * a.slab_stride;
+  if (c <= a.hk) {
+    float s = 0.f;
+    for (long long r = r0; r < r1; ++r) s = fmaf(a.du[r], c < a.hk ? a.h[r * a.ldh + c] : 1.0f, s);
+    dst[a.reg_p + c] = s;
+  } else if (c - (a.hk + 1) <= a.hv2) {
+    const int j = c - (a.hk + 1);
+    float s = 0.f;
+    for (long long r = r0; r < r1; ++r) s = fmaf(a.dz[r], j < a.hv2 ? a.v2[r * a.ldv + j] : 1.0f, s);
+    dst[a.reg_v2 + j] = s;
+  }
+}
+
+// acc (+)= sum_s slab[s], slices in order, fp64 within the chunk
+__global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ slabs, int slices, long long total, float* __restrict__ acc,
+                                                     int first) {
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    double s = 0.0;
+    for (int q = 0; q < slices; ++q) s += (double)slabs[(long long)q * total + e];
+    acc[e] = first ? (float)s : acc[e] + (float)s;
+  }
+}
+
+// padded gradient regions -> flat gradient (state_dict layout, zero padding); block 0 also sums the loss partials in order
+struct FinArgs {
+  const float* acc; float* grads; long long total;
+  int n_mat; long long woff[kMaxMat], boff[kMaxMat], reg[kMaxMat]; int out[kMaxMat], in[kMaxMat];
+  const double* loss_part; long long n_parts; double* loss;
+};
+__global__ __launch_bounds__(256) void finalize_kernel(FinArgs a) {
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < a.total; e += (long long)gridDim.x * 256) {
+    float v = 0.0f;
+    for (int t = 0; t < a.n_mat; ++t) {
+      const long long nw = (long long)a.out[t] * a.in[t];
+      if (e >= a.woff[t] && e < a.woff[t] + nw) {
+        const long long q = e - a.woff[t], o = q / a.in[t], i = q - o * a.in[t];
+        v = a.acc[a.reg[t] + o * (a.in[t] + 1) + i];
+      } else if (e >= a.boff[t] && e < a.boff[t] + a.out[t]) {
+        const long long o = e - a.boff[t];
+        v = a.acc[a.reg[t] + o * (a.in[t] + 1) + a.in[t]];
+      }
+    }
+    a.grads[e] = v;
+  }
+  if (blockIdx.x == 0) {
+    __shared__ double red[256];
+    for (int q = 0; q < 4; ++q) {
+      double s = 0.0;
+      for (long long b = threadIdx.x; b < a.n_parts; b += 256) s += a.loss_part[b * 8 + q];
+      red[threadIdx.x] = s;
+      __syncthreads();
+      for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) a.loss[q] = red[0];
+      __syncthreads();
+    }
+  }
+}
+
+// MC-dropout moments: virtual row v = (pass + 1) * n_rows + row, pass -1 = eval.  Per row, passes in order (pinn_mc_dropout's
+// arithmetic): state [4][n_rows] = u_eval, Welford mean and m2 of u - u_eval, sum of logvar
+__global__ __launch_bounds__(256) void mc_moments_kernel(const float* __restrict__ ub, const float* __restrict__ lvb, long long v0,
+                                                         long long nv, long long n_rows, float* __restrict__ st) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rows) return;
+  long long q = v0 > r ? (v0 - r + n_rows - 1) / n_rows : 0;
+  if (q * n_rows + r >= v0 + nv) return;
+  float ue = st[r], mean = st[n_rows + r], m2 = st[2 * n_rows + r], sl = st[3 * n_rows + r];
+  for (; q * n_rows + r < v0 + nv; ++q) {
+    const long long c = q * n_rows + r - v0;
+    if (q == 0) { ue = ub[c]; mean = 0.f; m2 = 0.f; sl = 0.f; continue; }
+    welford_update(mean, m2, ub[c] - ue, 1.0f / (float)q);
+    sl += lvb[c];
+  }
+  st[r] = ue; st[n_rows + r] = mean; st[2 * n_rows + r] = m2; st[3 * n_rows + r] = sl;
+}
+__global__ __launch_bounds__(256) void mc_final_kernel(const float* __restrict__ st, long long n_rows, int n_passes, float* o0, float* o1,
+                                                       float* o2) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rows) return;
+  const float inv_t = 1.0f / (float)n_passes;
+  o0[r] = st[r];
+  o1[r] = expf(0.5f * (st[3 * n_rows + r] * inv_t));
+  o2[r] = sqrtf(st[2 * n_rows + r] * inv_t);
+}
+
+// ---------------------------------------------------------------------------------------
+// host orchestration
+// ---------------------------------------------------------------------------------------
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static int last_error() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? PINN_OK : (int)e; }
+
+static int launch_pack(const Shape& s, const float* params, float* pack, hipStream_t st) {
+  PackArgs pa{};
+  pa.params = params; pa.pack = pack;
+  int nj = 0;
+  long long mx = 0;
+  for (int t = 0; t < s.n_mat; ++t) {
+    if (!s.is_gemm(t)) continue;
+    pa.job[nj++] = PackJob{s.woff[t], s.pf[t], s.out[t], s.in[t], s.mp[t], s.kp[t], 0};
+    if (s.pt[t] >= 0) pa.job[nj++] = PackJob{s.woff[t], s.pt[t], s.out[t], s.in[t], s.mp[t], s.kp[t], 1};
+    const long long n = (long long)s.mp[t] * s.kp[t];
+    if (n > mx) mx = n;
+  }
+  pa.n_jobs = nj;
+  long long gx = (mx + 255) / 256;
+  if (gx > 1024) gx = 1024;
+  hipLaunchKernelGGL(pack_kernel, dim3((unsigned)gx, nj), dim3(256), 0, st, pa);
+  return last_error();
+}
+
+
+// every GEMM layer of the forward pass for one chunk of (virtual) rows
+struct ChunkIO {
+  const float* in[kMaxMat]; long long ld_in[kMaxMat];
+  float* out[kMaxMat]; long long ld_out[kMaxMat];
+  unsigned* keep;          // training: keep words written here
+};
+
+static void forward_layers(const Shape& s, const float* params, const float* pack, const Drop& d, const ChunkIO& io, long long row0,
+                           long long nv, long long rows, long long n_rows, bool mc, hipStream_t st) {
+  for (int step = 0; step < s.k + 2; ++step) {
+    const int t = step < s.k ? step : (step == s.k ? s.mat_v0() : s.mat_v1());
+    GemmArgs g{};
+    g.A = pack + s.pf[t]; g.lda = s.kp[t]; g.a_mv = s.mp[t]; g.a_kv = s.kp[t];
+    g.B = io.in[t]; g.ldb = io.ld_in[t]; g.b_mv = rows; g.b_kv = t == 0 ? 8 : s.kp[t];
+    g.M = s.mp[t]; g.K = s.kp[t];
+    g.out = io.out[t]; g.ldo = io.ld_out[t];
+    g.n_valid = nv;
+    g.bias = params + s.boff[t]; g.bias_n = s.out[t];
+    g.module = t < s.k ? t : (t == s.mat_v0() ? s.k : -1);
+    g.map_rows = t == 0;
+    g.mc = mc ? 1 : 0;
+    g.row0 = row0; g.n_rows = n_rows;
+    g.drop = d;
+    g.keep = io.keep;
+    g.keep_off = g.module >= 0 ? s.word_off[g.module] : 0;
+    g.stash_module = -1;
+    const dim3 grid((unsigned)(rows / 64), (unsigned)((s.mp[t] + 63) / 64));
+    hipLaunchKernelGGL(gemm_kernel<kFwd>, grid, dim3(256), 0, st, g);
+  }
+}
+
+static HeadArgs head_args(const Shape& s, const float* params, const float* h, long long ldh, const float* v2, long long ldv,
+                          long long nv, long long row0) {
+  HeadArgs h2{};
+  h2.h = h; h2.ldh = ldh; h2.hk = s.hk;
+  h2.v2 = v2; h2.ldv = ldv; h2.hv2 = s.hv2;
+  h2.wp = params + s.woff[s.mat_pred()]; h2.bp = params + s.boff[s.mat_pred()];
+  h2.wv2 = params + s.woff[s.mat_v2()]; h2.bv2 = params + s.boff[s.mat_v2()];
+  h2.n_valid = nv; h2.row0 = row0;
+  return h2;
+}
+
+// forward (n_passes == 0) or MC-dropout (1 eval pass + n_passes stochastic passes as virtual rows)
+static int run_infer(const Shape& s, const float* d_params, const float* d_x, long long n_rows, const Drop& d, int n_passes,
+                     float* o0, float* o1, float* o2, void* d_work, size_t work_bytes, hipStream_t st) {
+  const bool mc = n_passes > 0;
+  const Layout L = infer_layout(s, n_rows, n_passes);
+  if (!d_work || !al16(d_work)) return PINN_E_ARG;
+  if (work_bytes < L.end) return PINN_E_WORKSPACE;
+  char* base = (char*)d_work;
+  const float* pack = (const float*)(base + L.pack);
+  int rc = launch_pack(s, d_params, (float*)(base + L.pack), st);
+  if (rc) return rc;
+  float* buf[3] = {(float*)(base + L.act[0]), (float*)(base + L.act[1]), (float*)(base + L.act[2])};
+  ChunkIO io{};
+  for (int t = 0; t < s.k; ++t) {       // hidden layer t writes buf[t & 1]; v0 the other one; v1 buf[2]
+    io.in[t] = t == 0 ? d_x : buf[(t - 1) & 1];
+    io.ld_in[t] = t == 0 ? 8 : s.max_wp;
+    io.out[t] = buf[t & 1]; io.ld_out[t] = s.max_wp;
+  }
+  const int c = (s.k - 1) & 1;
+  io.in[s.mat_v0()] = buf[c]; io.ld_in[s.mat_v0()] = s.max_wp; io.out[s.mat_v0()] = buf[c ^ 1]; io.ld_out[s.mat_v0()] = s.max_wp;
+  io.in[s.mat_v1()] = buf[c ^ 1]; io.ld_in[s.mat_v1()] = s.max_wp; io.out[s.mat_v1()] = buf[2]; io.ld_out[s.mat_v1()] = s.max_wp;
+  io.keep = nullptr;
+  float* ub = (float*)(base + L.ubuf);
+  float* lvb = (float*)(base + L.lvbuf);
+  float* state = (float*)(base + L.state);
+  const long long total = mc ? n_rows * ((long long)n_passes + 1) : n_rows;
+  for (long long v0 = 0; v0 < total; v0 += L.rows) {
+    const long long nv = total - v0 < L.rows ? total - v0 : L.rows;
+    forward_layers(s, d_params, pack, d, io, v0, nv, L.rows, n_rows, mc, st);
+    HeadArgs h = head_args(s, d_params, buf[c], s.max_wp, buf[2], s.max_wp, nv, v0);
+    if (mc) {
+      h.u = ub; h.lv = lvb;
+      hipLaunchKernelGGL(heads_kernel<kHeadMC>, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, h);
+      hipLaunchKernelGGL(mc_moments_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, ub, lvb, v0, nv, n_rows, state);
+    } else {
+      h.u = o0; h.lv = o1;
+      hipLaunchKernelGGL(heads_kernel<kHeadFwd>, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, h);
+    }
+    rc = last_error();
+    if (rc) return rc;
+  }
+  if (mc) hipLaunchKernelGGL(mc_final_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, state, n_rows, n_passes, o0, o1, o2);
+  return last_error();
+}
+
+static void wgrad(const Shape& s, int t, const Layout& L, const float* dpre, long long ld_dpre, const float* x_in, long long ld_in,
+                  long long nv, float* slabs, hipStream_t st) {
+  GemmArgs g{};
+  g.A = dpre; g.lda = ld_dpre; g.a_mv = s.mp[t]; g.a_kv = nv;
+  g.B = x_in; g.ldb = ld_in; g.b_mv = ld_in; g.b_kv = nv;
+  g.K = L.rows;
+  g.n_valid = nv;
+  g.slice_rows = L.slice_rows; g.slab = slabs; g.slab_stride = s.gtotal; g.reg = s.reg[t];
+  g.out_real = s.out[t]; g.in_real = s.in[t];
+  g.module = -1; g.stash_module = -1;
+  const dim3 grid((unsigned)((s.in[t] + 1 + 63) / 64), (unsigned)((s.out[t] + 63) / 64), (unsigned)L.slices);
+  hipLaunchKernelGGL(gemm_kernel<kWgrad>, grid, dim3(256), 0, st, g);
+}
+
+// d pre-activation of the layer feeding matrix t: (W_t^T dpre_t (+ w_p du)) * tanh' * mask
+static void bwd(const Shape& s, int t, const Layout& L, const float* pack, const Drop& d, const float* dpre, float* dpre_in,
+                const float* stash, long long ld_stash, int module, const unsigned* keep, const float* wp, const float* du, long long nv,
+                hipStream_t st) {
+  GemmArgs g{};
+  g.A = pack + s.pt[t]; g.lda = s.mp[t]; g.a_mv = s.kp[t]; g.a_kv = s.mp[t];
+  g.B = dpre; g.ldb = s.max_wp; g.b_mv = L.rows; g.b_kv = s.mp[t];
+  g.M = s.kp[t]; g.K = s.mp[t];
+  g.out = dpre_in; g.ldo = s.max_wp;
+  g.n_valid = nv;
+  g.drop = d;
+  g.module = -1;
+  g.stash = stash; g.ld_stash = ld_stash; g.stash_module = module;
+  g.keep_in = keep; g.keep_off = s.word_off[module];
+  g.wp = wp; g.du = du; g.wp_n = wp ? s.hk : 0;
+  const dim3 grid((unsigned)(L.rows / 64), (unsigned)((s.kp[t] + 63) / 64));
+  hipLaunchKernelGGL(gemm_kernel<kBwd>, grid, dim3(256), 0, st, g);
+}
+
+static int run_train(const Shape& s, const float* d_params, const float* d_x, const float* d_y, long long n_rows, long long n_global,
+                     const Drop& d, float* d_grads, double* d_loss, void* d_work, size_t work_bytes, hipStream_t st) {
+  const Layout L = train_layout(s, n_rows);
+  if (!d_work || !al16(d_work)) return PINN_E_ARG;
+  if (work_bytes < L.end) return PINN_E_WORKSPACE;
+  char* base = (char*)d_work;
+  const float* pack = (const float*)(base + L.pack);
+  int rc = launch_pack(s, d_params, (float*)(base + L.pack), st);
+  if (rc) return rc;
+  float* act[kMaxMat];
+  for (int t = 0; t < s.n_mat; ++t) act[t] = s.is_gemm(t) ? (float*)(base + L.act[act_index(s, t)]) : nullptr;
+  unsigned* keep = (unsigned*)(base + L.keep);
+  float* dp[2] = {(float*)(base + L.dpre[0]), (float*)(base + L.dpre[1])};
+  float* du = (float*)(base + L.du);
+  float* dz = (float*)(base + L.dz);
+  float* slabs = (float*)(base + L.slabs);
+  float* acc = (float*)(base + L.acc);
+  double* loss_part = (double*)(base + L.loss);
+  ChunkIO io{};
+  for (int t = 0; t < s.n_mat; ++t) {
+    if (!s.is_gemm(t)) continue;
+    const int src = t == 0 ? -1 : (t < s.k ? t - 1 : (t == s.mat_v0() ? s.k - 1 : s.mat_v0()));
+    io.out[t] = act[t]; io.ld_out[t] = s.mp[t];
+    io.in[t] = src < 0 ? nullptr : act[src]; io.ld_in[t] = src < 0 ? 8 : s.mp[src];
+  }
+  io.keep = keep;
+  const int v0m = s.mat_v0(), v1m = s.mat_v1();
+  const long long nch = n_chunks(n_rows, L.rows);
+  for (long long ch = 0; ch < nch; ++ch) {
+    const long long row0 = ch * L.rows;
+    const long long nv = n_rows - row0 < L.rows ? n_rows - row0 : L.rows;
+    const float* x = d_x + row0 * 8;
+    io.in[0] = d_x;
+    forward_layers(s, d_params, pack, d, io, row0, nv, L.rows, n_rows, false, st);
+    HeadArgs h = head_args(s, d_params, act[s.k - 1], s.mp[s.k - 1], act[v1m], s.mp[v1m], nv, row0);
+    h.y = d_y; h.n_global = n_global; h.du = du; h.dz = dz; h.dpre_v2 = dp[0]; h.ld_dpre = s.max_wp; h.wd = s.mp[v1m];
+    h.loss_part = loss_part;
+    hipLaunchKernelGGL(heads_kernel<kHeadTrain>, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, h);
+    // variance head layer 1, then layer 0 (+ the predict head), then the hidden layers top-down
+    wgrad(s, v1m, L, dp[0], s.max_wp, act[v0m], s.mp[v0m], nv, slabs, st);
+    bwd(s, v1m, L, pack, d, dp[0], dp[1], act[v0m], s.mp[v0m], s.k, keep, nullptr, nullptr, nv, st);
+    wgrad(s, v0m, L, dp[1], s.max_wp, act[s.k - 1], s.mp[s.k - 1], nv, slabs, st);
+    {
+      VecArgs va{};
+      va.h = act[s.k - 1]; va.ldh = s.mp[s.k - 1]; va.hk = s.hk;
+      va.v2 = act[v1m]; va.ldv = s.mp[v1m]; va.hv2 = s.hv2;
+      va.du = du; va.dz = dz; va.K = L.rows; va.slice_rows = L.slice_rows;
+      va.slab = slabs; va.slab_stride = s.gtotal; va.reg_p = s.reg[s.mat_pred()]; va.reg_v2 = s.reg[s.mat_v2()];
+      const int cols = s.hk + 1 + s.hv2 + 1;
+      hipLaunchKernelGGL(vec_grad_kernel, dim3((unsigned)L.slices, (unsigned)((cols + 255) / 256)), dim3(256), 0, st, va);
+    }
+    bwd(s, v0m, L, pack, d, dp[1], dp[0], act[s.k - 1], s.mp[s.k - 1], s.k - 1, keep, d_params + s.woff[s.mat_pred()], du, nv, st);
+    int cur = 0;
+    for (int l = s.k - 1; l >= 0; --l) {
+      if (l == 0) wgrad(s, 0, L, dp[cur], s.max_wp, x, 8, nv, slabs, st);
+      else wgrad(s, l, L, dp[cur], s.max_wp, act[l - 1], s.mp[l - 1], nv, slabs, st);
+      if (l > 0) {
+        bwd(s, l, L, pack, d, dp[cur], dp[cur ^ 1], act[l - 1], s.mp[l - 1], l - 1, keep, nullptr, nullptr, nv, st);
+        cur ^= 1;
+      }
+    }
+    long long gx = (s.gtotal + 255) / 256;
+    if (gx > 4096) gx = 4096;
+    hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)gx), dim3(256), 0, st, (const float*)slabs, L.slices, s.gtotal, acc, ch == 0 ? 1 : 0);
+    rc = last_error();
+    if (rc) return rc;
+  }
+  FinArgs f{};
+  f.acc = acc; f.grads = d_grads; f.total = s.total; f.n_mat = s.n_mat;
+  for (int t = 0; t < s.n_mat; ++t) { f.woff[t] = s.woff[t]; f.boff[t] = s.boff[t]; f.reg[t] = s.reg[t]; f.out[t] = s.out[t]; f.in[t] = s.in[t]; }
+  f.loss_part = loss_part; f.n_parts = nch * (L.rows / 16); f.loss = d_loss;
+  long long gx = (s.total + 255) / 256;
+  if (gx > 4096) gx = 4096;
+  hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)gx), dim3(256), 0, st, f);
+  return last_error();
+}
+
+}  // namespace gen
+}  // namespace pinn
+
+using namespace pinn::gen;
+
+extern "C" long long pinn_gnet_param_count(const pinn_gnet_t* net) {
+  Shape s;
+  const int rc = make_shape(net, &s);
+  return rc ? rc : s.total;
+}
+
+extern "C" size_t pinn_gnet_workspace_bytes(const pinn_gnet_t* net, long long n_rows, int n_passes) {
+  Shape s;
+  if (make_shape(net, &s) || n_rows < 0 || n_passes < 0) return 0;
+  const size_t a = train_layout(s, n_rows).end, b = infer_layout(s, n_rows, n_passes).end;
+  return a > b ? a : b;
+}
+
+extern "C" int pinn_gnet_forward(const pinn_gnet_t* net, const float* d_params, const float* d_x, long long n_rows, const pinn_dropout_t* drop,
+                                 float* d_u, float* d_logvar, void* d_work, size_t work_bytes, void* stream) {
+  Shape s;
+  int rc = make_shape(net, &s);
+  if (rc) return rc;
+  if (n_rows < 0 || !d_params || !al16(d_params)) return PINN_E_ARG;
+  if (n_rows == 0) return PINN_OK;
+  if (!d_x || !al16(d_x) || !d_u || !d_logvar) return PINN_E_ARG;
+  Drop d;
+  rc = convert(s, drop, &d);
+  if (rc) return rc;
+  (void)hipGetLastError();
+  return run_infer(s, d_params, d_x, n_rows, d, 0, d_u, d_logvar, nullptr, d_work, work_bytes, (hipStream_t)stream);
+}
+
+extern "C" int pinn_gnet_mc_dropout(const pinn_gnet_t* net, const float* d_params, const float* d_x, long long n_rows, const pinn_dropout_t* drop,
+                                    int n_passes, float* d_pred_mean, float* d_a_u, float* d_e_u, void* d_work, size_t work_bytes,
+                                    void* stream) {
+  Shape s;
+  int rc = make_shape(net, &s);
+  if (rc) return rc;
+  if (n_rows < 0 || !d_params || !al16(d_params) || n_passes < 1 || !drop) return PINN_E_ARG;
+  if (n_rows == 0) return PINN_OK;
+  if (!d_x || !al16(d_x) || !d_pred_mean || !d_a_u || !d_e_u) return PINN_E_ARG;
+  if (drop->mode == PINN_DROP_NONE) return PINN_E_ARG;
+  Drop d;
+  rc = convert(s, drop, &d);
+  if (rc) return rc;
+  (void)hipGetLastError();
+  return run_infer(s, d_params, d_x, n_rows, d, n_passes, d_pred_mean, d_a_u, d_e_u, d_work, work_bytes, (hipStream_t)stream);
+}
+
+extern "C" int pinn_gnet_train_grads(const pinn_gnet_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
+                                     long long n_global, const pinn_dropout_t* drop, float* d_grads, double* d_loss, void* d_work,
+                                     size_t work_bytes, void* stream) {
+  Shape s;
+  int rc = make_shape(net, &s);
+  if (rc) return rc;
+  if (n_rows < 0 || n_global < 1 || n_global < n_rows || !d_params || !al16(d_params) || !d_grads || !al16(d_grads) || !d_loss)
+    return PINN_E_ARG;
+  if (n_rows == 0) return PINN_OK;
+  if (!d_x || !al16(d_x) || !d_y) return PINN_E_ARG;
+  Drop d;
+  rc = convert(s, drop, &d);
+  if (rc) return rc;
+  (void)hipGetLastError();
+  return run_train(s, d_params, d_x, d_y, n_rows, n_global, d, d_grads, d_loss, d_work, work_bytes, (hipStream_t)stream);
+}
+
+extern "C" int pinn_gnet_train_step(const pinn_gnet_t* net, float* d_params, const float* d_x, const float* d_y, long long n_rows,
+                                    long long n_global, const pinn_dropout_t* drop, float* d_grads, double* d_loss, void* d_work,
+                                    size_t work_bytes, float* d_m, float* d_v, float lr, int step, void* stream) {
+  if (!d_m || !d_v || step < 1) return PINN_E_ARG;
+  int rc = pinn_gnet_train_grads(net, d_params, d_x, d_y, n_rows, n_global, drop, d_grads, d_loss, d_work, work_bytes, stream);
+  if (rc) return rc;
+  const long long n = pinn_gnet_param_count(net);
+  return pinn_adam_step(d_params, d_grads, d_m, d_v, n, lr, step, stream);
+}

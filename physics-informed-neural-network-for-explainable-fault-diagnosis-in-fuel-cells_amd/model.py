@@ -14,8 +14,10 @@ Extensions (keyword-only, all optional): `precision` ("f32x6", default: fp32-acc
 matrix cores, same parity tolerances as "fp32"; "fp32": exact fp32 MFMA; "bf16" = bf16 MFMA inputs with fp32
 accumulation, rtol ~2e-2 -- see DNN.set_precision), `seed` (Philox dropout seed), `row_offset` /
 `n_global` (this process holds rows [row_offset, row_offset+N) of an n_global-row series:
-data-parallel training with one all-reduce(SUM) of the flat gradient per step), and
-`train_dnn(..., batch_size=)` for minibatches.
+data-parallel training with one all-reduce(SUM) of the flat gradient per step),
+`train_dnn(..., batch_size=)` for minibatches, and `kernels` ("auto", default: the shapes `layout.check_arch` accepts on the
+fused / wide kernels; "general": ANY layers list `layout.check_general` accepts -- unequal widths, widths 1..2048 -- on the
+exact-fp32 layer-by-layer kernels of csrc/pinn_general.hip, precision "fp32" only).
 """
 import ctypes
 import math
@@ -56,20 +58,40 @@ class DNN(torch.nn.Module):
     """01:389-438.  Same module tree / state_dict keys as the reference; the 14 weight and
     bias tensors are views into ONE flat float32 device buffer that the kernels read."""
 
-    def __init__(self, p, logvar, layers, seed=0, precision="f32x6"):
+    def __init__(self, p, logvar, layers, seed=0, precision=None, kernels="auto"):
+        """kernels="auto": the shapes layout.check_arch accepts, precision None = "f32x6".  kernels="general": any list
+        layout.check_general accepts (exact-fp32 layer-by-layer kernels, csrc/pinn_general.hip); precision None or "fp32"."""
         super().__init__()
         self.depth = len(layers) - 1
         self.p = p
         self.logvar = logvar
         self.activation = torch.nn.Tanh
-        self.n_in, self.hidden, self.n_hidden = layout.check_arch(layers)
+        if kernels not in ("auto", "general"):
+            raise ValueError("kernels must be 'auto' or 'general'")
+        self.kernels = kernels
         dev = _device()
         self._lib = _lib.load()
-        self._net = _lib.Net(self.n_in, self.hidden, self.n_hidden)
-        offs, total = layout.param_offsets(self.n_in, self.hidden, self.n_hidden)
-        assert self._lib.pinn_param_count(ctypes.byref(self._net)) == total
         self._packed = None
-        self.set_precision(precision)
+        self._gwork = None
+        if kernels == "general":
+            self.widths = layout.check_general(layers)
+            if precision not in (None, "fp32"):
+                raise ValueError("kernels='general' runs exact fp32 only (precision None or 'fp32', got %r)" % (precision,))
+            self.n_in, self.hidden, self.n_hidden = int(layers[0]), None, len(self.widths)
+            self._net = None
+            self._gnet = _lib.GNet(layers)
+            offs, total = layout.general_offsets(layers)
+            assert self._lib.pinn_gnet_param_count(ctypes.byref(self._gnet)) == total
+            self.precision = "fp32"
+        else:
+            self.n_in, self.hidden, self.n_hidden = layout.check_arch(layers)
+            self.widths = [self.hidden] * self.n_hidden
+            self._gnet = None
+            self._net = _lib.Net(self.n_in, self.hidden, self.n_hidden)
+            offs, total = layout.param_offsets(self.n_in, self.hidden, self.n_hidden)
+            assert self._lib.pinn_param_count(ctypes.byref(self._net)) == total
+            self.set_precision("f32x6" if precision is None else precision)
+        self.layer_sizes = [self.n_in] + list(self.widths) + [1]
         self._offsets = offs
         self._flat = torch.zeros(total, dtype=torch.float32, device=dev)
         self._flat_grad_full = torch.zeros(total + _dp.LOSS_TAIL, dtype=torch.float32, device=dev)
@@ -112,7 +134,12 @@ class DNN(torch.nn.Module):
         math on the 16-bit matrix cores from split operands (two fp16 parts, three products, fp32 accumulation; gradients
         under exact power-of-two scales) -- same parity tolerances as "fp32", 2-3x faster.  "f32x6g6": as "f32x6" with the
         gradients from three bf16 parts / six products (24-bit operands, fp32's exponent range per element; ~20 % slower).
-        "bf16": bf16 MFMA inputs, fp32 accumulate / activations / loss / master weights; rtol ~2e-2."""
+        "bf16": bf16 MFMA inputs, fp32 accumulate / activations / loss / master weights; rtol ~2e-2.
+        kernels="general" nets: "fp32" only."""
+        if self.kernels == "general":
+            if precision != "fp32":
+                raise ValueError("kernels='general' runs exact fp32 only (got %r)" % (precision,))
+            return
         codes = {"fp32": _lib.PREC_FP32, "bf16": _lib.PREC_BF16, "f32x6": _lib.PREC_F32X6, "f32x6g6": _lib.PREC_F32X6_G6}
         if precision not in codes:
             raise ValueError("precision must be 'fp32', 'f32x6', 'f32x6g6' or 'bf16'")
@@ -129,7 +156,10 @@ class DNN(torch.nn.Module):
     def check_range(self):
         """Raise PinnRangeError when the last launches met a weight (or, in training, a gradient) outside the domain of the
         split-operand precisions -- |w| >= 1023.5 in a hidden or variance-head matrix, which the fp32 reference (01:389-438)
-        computes without trouble.  Synchronises the stream: called where the host waits anyway (log lines, results)."""
+        computes without trouble.  Synchronises the stream: called where the host waits anyway (log lines, results).
+        A no-op on kernels="general" nets (exact fp32: no range limit)."""
+        if self.kernels == "general":
+            return
         rc = self._lib.pinn_net_range_status(ctypes.byref(self._net), _stream())
         if rc == _lib.E_RANGE:
             raise _lib.PinnRangeError(
@@ -168,6 +198,16 @@ class DNN(torch.nn.Module):
             d.d_bits = self._mask_bits[self._mask_pass].data_ptr()
         return d
 
+    def general_workspace(self, n_rows, n_passes=0):
+        """Workspace of the general kernels for n_rows rows (and n_passes MC passes); cached, grown on demand."""
+        nb = self._lib.pinn_gnet_workspace_bytes(ctypes.byref(self._gnet), int(n_rows), int(n_passes))
+        if nb == 0:
+            raise _lib.PinnError("pinn_gnet_workspace_bytes rejected the network")
+        if self._gwork is None or self._gwork.numel() < nb:
+            self._gwork = None
+            self._gwork = torch.empty(nb, dtype=torch.uint8, device=self._flat.device)
+        return self._gwork
+
     def inject_masks(self, bits):
         """Replay recorded keep-masks (tests only). bits: int32 [n_passes, N, words] or None."""
         self._mask_bits = None if bits is None else bits.to(self._flat.device).contiguous()
@@ -185,9 +225,16 @@ class DNN(torch.nn.Module):
             drop = self.dropout_struct(0x80000000 + self._fwd_counter, row_offset)
             if self._mask_bits is not None:
                 self._mask_pass += 1
-        rc = self._lib.pinn_mlp_forward(ctypes.byref(self._net), _ptr(self.flat_params()), _ptr(x), n,
-                                        ctypes.byref(drop) if drop is not None else None, _ptr(u), _ptr(lv), _stream())
-        _lib.check(rc, "pinn_mlp_forward")
+        if self.kernels == "general":
+            work = self.general_workspace(n)
+            rc = self._lib.pinn_gnet_forward(ctypes.byref(self._gnet), _ptr(self.flat_params()), _ptr(x), n,
+                                             ctypes.byref(drop) if drop is not None else None, _ptr(u), _ptr(lv), _ptr(work),
+                                             work.numel(), _stream())
+            _lib.check(rc, "pinn_gnet_forward")
+        else:
+            rc = self._lib.pinn_mlp_forward(ctypes.byref(self._net), _ptr(self.flat_params()), _ptr(x), n,
+                                            ctypes.byref(drop) if drop is not None else None, _ptr(u), _ptr(lv), _stream())
+            _lib.check(rc, "pinn_mlp_forward")
         if not self.logvar:
             lv = torch.zeros_like(u)
         return u, lv
@@ -197,7 +244,10 @@ class PhysicsInformedNN():
     """01:441-1410."""
 
     def __init__(self, X, u, layers, x_scal, u_scal, p, logvar, *, seed=0, row_offset=0, n_global=None, process_group=None,
-                 precision="f32x6"):
+                 precision=None, kernels="auto"):
+        """kernels="general" runs any layers list layout.check_general accepts on the exact-fp32 layer-by-layer kernels
+        (precision None or "fp32"); such nets train launch by launch (use_graph is ignored) and, data-parallel, with one
+        blocking all-reduce of the whole gradient per step (no two-part overlap)."""
         dev = _device()
         self._lib = _lib.load()
         self.x = X[:, 0:].clone().detach().float().to(dev).contiguous().requires_grad_(True)
@@ -213,7 +263,7 @@ class PhysicsInformedNN():
         self._lambda = torch.tensor(LAMBDA_INIT, dtype=torch.float32, device=dev)
         for i, name in enumerate(LAMBDA_NAMES):
             setattr(self, name, torch.nn.Parameter(self._lambda[i:i + 1]))
-        self.dnn = DNN(p, logvar, layers, seed=seed, precision=precision)
+        self.dnn = DNN(p, logvar, layers, seed=seed, precision=precision, kernels=kernels)
         # registration order and the `lambda_3` <- lambda_4 overwrite of 01:465-468 are kept for state_dict parity
         self.dnn.register_parameter("lambda_1", self.lambda_1)
         self.dnn.register_parameter("lambda_2", self.lambda_2)
@@ -344,6 +394,8 @@ class PhysicsInformedNN():
             print(*a)
 
     def _workspace(self, n_rows):
+        if self.dnn.kernels == "general":
+            return self.dnn.general_workspace(n_rows)
         key = (n_rows, self.dnn.precision)          # the tile padding of the stash depends on the kernels used
         if key not in self._work:
             self._work.clear()
@@ -366,6 +418,23 @@ class PhysicsInformedNN():
         if drop is not None and self.dnn._mask_bits is not None:
             self.dnn._mask_pass += 1
         loss = torch.empty(4, dtype=torch.float64, device=x.device)
+
+        if self.dnn.kernels == "general":          # one launch sequence; `between` runs once the whole gradient is final
+            g = ctypes.byref(self.dnn._gnet)
+            if adam is not None:
+                rc = self._lib.pinn_gnet_train_step(g, _ptr(self.dnn.flat_params()), _ptr(x), _ptr(y), n, int(n_global),
+                                                    ctypes.byref(drop) if drop else None, _ptr(self.dnn._flat_grad), _ptr(loss),
+                                                    _ptr(work), work.numel(), _ptr(self._adam_m), _ptr(self._adam_v), adam[0], adam[1],
+                                                    _stream())
+                _lib.check(rc, "pinn_gnet_train_step")
+            else:
+                rc = self._lib.pinn_gnet_train_grads(g, _ptr(self.dnn.flat_params()), _ptr(x), _ptr(y), n, int(n_global),
+                                                     ctypes.byref(drop) if drop else None, _ptr(self.dnn._flat_grad), _ptr(loss),
+                                                     _ptr(work), work.numel(), _stream())
+                _lib.check(rc, "pinn_gnet_train_grads")
+                if between is not None:
+                    between()
+            return loss
 
         def run(phases):
             rc = self._lib.pinn_mlp_train_grads_phases(ctypes.byref(self.dnn._net), _ptr(self.dnn.flat_params()), _ptr(x), _ptr(y), n,
@@ -393,7 +462,8 @@ class PhysicsInformedNN():
 
     def _dp_step(self, xb, yb, row_offset, n_norm, has_rows):
         full = self.dnn._flat_grad_full
-        split = int(self._lib.pinn_grad_split(ctypes.byref(self.dnn._net))) if self.overlap_allreduce else 0
+        # general nets: the blocking single all-reduce (split = 0)
+        split = int(self._lib.pinn_grad_split(ctypes.byref(self.dnn._net))) if self.overlap_allreduce and self.dnn.kernels == "auto" else 0
         if not (_dp._active(self._group) and split > 0):
             if has_rows:
                 loss = self.train_step_grads(xb, yb, row_offset, n_norm)
@@ -527,7 +597,7 @@ class PhysicsInformedNN():
             lr_next = 0.01 * 0.8 ** ((epoch + 1) // 1000)
             self._log(f' {epoch:5d}  | {(ls[0] + 0.01 * ls[1]) / n_norm:10.3e} | {ls[2] / n_norm:10.3e} | {lr_next:8.1e}')
         replay = (self.use_graph and nIter >= max(2, self.graph_min_steps) and len(batches) == 1 and batches[0][:2] == (0, n) and n > 0 and not _dp._active(self._group)
-                  and self.dnn.hidden <= 256)
+                  and self.dnn.kernels == "auto" and self.dnn.hidden <= 256)
         for epoch in range(nIter):
             lr = 0.01 * 0.8 ** (epoch // 1000)
             for (s, e, n_norm) in batches:
@@ -685,6 +755,12 @@ class PhysicsInformedNN():
         out = torch.empty(3, n, device=x.device, dtype=torch.float32)
         self._mc_calls = getattr(self, "_mc_calls", 0) + 1
         drop = self.dnn.dropout_struct(0xC0000000 + (self._mc_calls << 16), row_offset)
+        if self.dnn.kernels == "general":
+            work = self.dnn.general_workspace(n, int(mc_times))
+            rc = self._lib.pinn_gnet_mc_dropout(ctypes.byref(self.dnn._gnet), _ptr(self.dnn.flat_params()), _ptr(x), n, ctypes.byref(drop),
+                                                int(mc_times), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(work), work.numel(), _stream())
+            _lib.check(rc, "pinn_gnet_mc_dropout")
+            return out[0], out[1], out[2]
         rc = self._lib.pinn_mc_dropout(ctypes.byref(self.dnn._net), _ptr(self.dnn.flat_params()), _ptr(x), n, ctypes.byref(drop),
                                        int(mc_times), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream())
         _lib.check(rc, "pinn_mc_dropout")

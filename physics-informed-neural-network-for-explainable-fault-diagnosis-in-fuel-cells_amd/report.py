@@ -95,7 +95,7 @@ def save_checkpoint(model, path):
     from .model import LAMBDA_NAMES
     dnn = model.dnn
     flat = dnn.flat_params()
-    ck = {"version": torch.tensor(CHECKPOINT_VERSION), "layers": torch.tensor([dnn.n_in] + [dnn.hidden] * dnn.n_hidden + [1])}
+    ck = {"version": torch.tensor(CHECKPOINT_VERSION), "layers": torch.tensor(dnn.layer_sizes)}
     for name, shape, off in dnn._offsets:
         n = int(np.prod(shape))
         ck["dnn." + name] = flat[off:off + n].view(shape).detach().cpu().clone()
@@ -117,7 +117,7 @@ def load_checkpoint(model, path):
     if int(ck["version"]) != CHECKPOINT_VERSION:
         raise ValueError("checkpoint version %d, expected %d" % (int(ck["version"]), CHECKPOINT_VERSION))
     dnn = model.dnn
-    layers = [dnn.n_in] + [dnn.hidden] * dnn.n_hidden + [1]
+    layers = dnn.layer_sizes
     if ck["layers"].tolist() != layers:
         raise ValueError("checkpoint is for layers %s, the model has %s" % (ck["layers"].tolist(), layers))
     flat = dnn.flat_params()
