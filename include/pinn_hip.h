@@ -330,6 +330,15 @@ int pinn_gnet_train_grads(const pinn_gnet_t* net, const float* d_params, const f
 int pinn_gnet_train_step(const pinn_gnet_t* net, float* d_params, const float* d_x, const float* d_y, long long n_rows,
                          long long n_global, const pinn_dropout_t* drop, float* d_grads, double* d_loss, void* d_work,
                          size_t work_bytes, float* d_m, float* d_v, float lr, int step, void* stream);
+/* Vector-Jacobian product of pinn_gnet_forward (torch autograd's backward).  Recomputes the forward of rows [0, n_rows) with
+ * `drop` -- the struct the forward used (PHILOX stream / row_offset, or BITS d_bits of the pass); NULL = eval -- and
+ * back-propagates d_gu[r] = dL/du_r and d_glv[r] = dL/dlogvar_r (d_glv NULL: zero).
+ * d_grads [pinn_gnet_param_count]: sum over the rows, NOT normalised, overwritten, padding zero (state_dict layout).
+ * d_gx [n_rows, 8] = dL/dx (NULL: not computed).  Workspace: pinn_gnet_workspace_bytes(net, n_rows, 0).
+ * Deterministic: no floating-point atomics; a row's d_gx does not depend on its tile, chunk or neighbours. */
+int pinn_gnet_backward(const pinn_gnet_t* net, const float* d_params, const float* d_x, long long n_rows,
+                       const pinn_dropout_t* drop, const float* d_gu, const float* d_glv, float* d_grads, float* d_gx,
+                       void* d_work, size_t work_bytes, void* stream);
 
 /* ---- results assembly: create_comprehensive_results_array_v2 (01:1877-2010) -----------------------------------
  * Fills d_out = float64 [n_rows, 22] row-major (the `comprehensive_results` layout scripts 02-05 read):

@@ -9,6 +9,8 @@
 //   gemm_kernel<kBwd>   dpre_in[r][i] = (sum_o W[o][i] dpre_out[r][o] (+ w_p[i] du[r])) * scale * keep * (1 - a^2)
 //   gemm_kernel<kWgrad> slab[s][o][i] = sum_{r in slice s} dpre_out[r][o] act_in[r][i]; column i = n_in is the bias (a ones column)
 //   heads_kernel        predict dot, variance-head dot, softplus / log, per-row dL/du, dL/dz, loss partials, d pre_v2
+//                       (kHeadGrad: dL/du, dL/dlogvar given by the caller -- the backward of torch autograd)
+//   dx_kernel           dL/dx = W_0^T dpre_0 per row (the backward's input gradient)
 //   vec_grad_kernel     the two 1-row tensors (predict, last variance layer) of the gradient, per slice
 //   reduce / finalize   fixed-order slab sums -> the flat gradient (state_dict layout); loss sums in fp64
 //   mc_moments_kernel   MC-dropout: (pass, row) pairs are virtual rows; per row, in pass order, the Welford moments of pinn_mc_dropout
@@ -472,7 +474,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
 // ---------------------------------------------------------------------------------------
 // heads: 16 lanes per row.  u = w_p . h_k + b_p;  z = w_v2 . v2 + b_v2;  logvar = log(softplus(z) + 1e-6)
 // ---------------------------------------------------------------------------------------
-enum { kHeadFwd = 0, kHeadMC = 1, kHeadTrain = 2 };
+enum { kHeadFwd = 0, kHeadMC = 1, kHeadTrain = 2, kHeadGrad = 3 };
 struct HeadArgs {
   const float* h; long long ldh; int hk;          // last hidden activation [row][ldh]
   const float* v2; long long ldv; int hv2;        // variance head's second activation [row][ldv]
@@ -480,6 +482,7 @@ struct HeadArgs {
   long long n_valid, row0;
   float* u; float* lv;                            // FWD: outputs at row0 + r; MC: chunk buffers at r
   const float* y; long long n_global;             // TRAIN
+  const float* gu; const float* glv;              // GRAD: dL/du, dL/dlogvar at row0 + r (glv NULL: zero)
   float* du; float* dz; float* dpre_v2; long long ld_dpre; int wd; double* loss_part;
 };
 
@@ -509,6 +512,27 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
       const long long o = HM == kHeadFwd ? a.row0 + r : r;
       a.u[o] = u;
       a.lv[o] = logf(softplus_f32(z) + 1e-6f);
+    }
+    return;
+  }
+  if (HM == kHeadGrad) {     // given upstream gradients: du = g_u, dz = g_lv * dlogvar/dz (the training head's expressions)
+    float du = 0.f, dz = 0.f;
+    if (valid) {
+      du = a.gu[a.row0 + r];
+      if (a.glv) {
+        const float var = softplus_f32(z) + 1e-6f;
+        const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
+        dz = a.glv[a.row0 + r] * sig / var;
+      }
+    }
+    if (g == 0) {
+      a.du[r] = du;
+      a.dz[r] = dz;
+    }
+    float* drow = a.dpre_v2 + r * a.ld_dpre;
+    for (int f = g; f < a.wd; f += 16) {
+      const float v = vrow[f];
+      drow[f] = f < a.hv2 ? a.wv2[f] * dz * (1.0f - v * v) : 0.0f;
     }
     return;
   }
@@ -584,6 +608,29 @@ __global__ __launch_bounds__(256) void vec_grad_kernel(VecArgs a) {
   }
 }
 
+// dL/dx of the valid rows: gx[row0 + r][i] = sum_o W_0[o][i] dpre_0[r][o].  16 lanes per row; lane g takes o = g, g + 16, ... in order,
+// then a fixed butterfly over the 16 lanes: a row's result depends on that row alone, not on its block or chunk.
+__global__ __launch_bounds__(256) void dx_kernel(const float* __restrict__ w0, int w, const float* __restrict__ dpre, long long ld,
+                                                 long long n_valid, long long row0, float* __restrict__ gx) {
+  const int g = threadIdx.x & 15;
+  const long long r = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);      // chunk row (every one is allocated)
+  const float* drow = dpre + r * ld;
+  f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int o = g; o < w; o += 16) {
+    const float d = drow[o];
+    const f32x4 a0 = *reinterpret_cast<const f32x4*>(w0 + (long long)o * 8);
+    const f32x4 a1 = *reinterpret_cast<const f32x4*>(w0 + (long long)o * 8 + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { s0[i] = fmaf(a0[i], d, s0[i]); s1[i] = fmaf(a1[i], d, s1[i]); }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { s0[i] = sum16(s0[i]); s1[i] = sum16(s1[i]); }
+  if (g == 0 && r < n_valid) {
+    *reinterpret_cast<f32x4*>(gx + (row0 + r) * 8) = s0;
+    *reinterpret_cast<f32x4*>(gx + (row0 + r) * 8 + 4) = s1;
+  }
+}
+
 // acc (+)= sum_s slab[s], slices in order, fp64 within the chunk
 __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ slabs, int slices, long long total, float* __restrict__ acc,
                                                      int first) {
@@ -594,7 +641,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ s
   }
 }
 
-// padded gradient regions -> flat gradient (state_dict layout, zero padding); block 0 also sums the loss partials in order
+// padded gradient regions -> flat gradient (state_dict layout, zero padding); block 0 also sums the loss partials in order (if any)
 struct FinArgs {
   const float* acc; float* grads; long long total;
   int n_mat; long long woff[kMaxMat], boff[kMaxMat], reg[kMaxMat]; int out[kMaxMat], in[kMaxMat];
@@ -615,7 +662,7 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinArgs a) {
     }
     a.grads[e] = v;
   }
-  if (blockIdx.x == 0) {
+  if (blockIdx.x == 0 && a.loss_part) {
     __shared__ double red[256];
     for (int q = 0; q < 4; ++q) {
       double s = 0.0;
@@ -805,8 +852,14 @@ static void bwd(const Shape& s, int t, const Layout& L, const float* pack, const
   hipLaunchKernelGGL(gemm_kernel<kBwd>, grid, dim3(256), 0, st, g);
 }
 
+// upstream gradients of pinn_gnet_backward: dL/du and dL/dlogvar per row (glv NULL: zero), dL/dx out (gx NULL: not computed)
+struct Upstream { const float* gu; const float* glv; float* gx; };
+
+// recomputing forward + backward of every chunk, fixed-order slab sums -> d_grads.  up == NULL: aleatoric_loss on (x, y), gradients
+// divided by n_global, loss sums -> d_loss (pinn_gnet_train_grads).  up != NULL: the given upstream gradients, raw sums, no loss, and
+// optionally dL/dx (pinn_gnet_backward).
 static int run_train(const Shape& s, const float* d_params, const float* d_x, const float* d_y, long long n_rows, long long n_global,
-                     const Drop& d, float* d_grads, double* d_loss, void* d_work, size_t work_bytes, hipStream_t st) {
+                     const Drop& d, const Upstream* up, float* d_grads, double* d_loss, void* d_work, size_t work_bytes, hipStream_t st) {
   const Layout L = train_layout(s, n_rows);
   if (!d_work || !al16(d_work)) return PINN_E_ARG;
   if (work_bytes < L.end) return PINN_E_WORKSPACE;
@@ -842,7 +895,12 @@ static int run_train(const Shape& s, const float* d_params, const float* d_x, co
     HeadArgs h = head_args(s, d_params, act[s.k - 1], s.mp[s.k - 1], act[v1m], s.mp[v1m], nv, row0);
     h.y = d_y; h.n_global = n_global; h.du = du; h.dz = dz; h.dpre_v2 = dp[0]; h.ld_dpre = s.max_wp; h.wd = s.mp[v1m];
     h.loss_part = loss_part;
-    hipLaunchKernelGGL(heads_kernel<kHeadTrain>, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, h);
+    if (up) {
+      h.gu = up->gu; h.glv = up->glv;
+      hipLaunchKernelGGL(heads_kernel<kHeadGrad>, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, h);
+    } else {
+      hipLaunchKernelGGL(heads_kernel<kHeadTrain>, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, h);
+    }
     // variance head layer 1, then layer 0 (+ the predict head), then the hidden layers top-down
     wgrad(s, v1m, L, dp[0], s.max_wp, act[v0m], s.mp[v0m], nv, slabs, st);
     bwd(s, v1m, L, pack, d, dp[0], dp[1], act[v0m], s.mp[v0m], s.k, keep, nullptr, nullptr, nv, st);
@@ -866,6 +924,9 @@ static int run_train(const Shape& s, const float* d_params, const float* d_x, co
         cur ^= 1;
       }
     }
+    if (up && up->gx)        // dp[cur] is now d pre-activation of hidden layer 0
+      hipLaunchKernelGGL(dx_kernel, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, d_params + s.woff[0], s.w[0], (const float*)dp[cur],
+                         (long long)s.max_wp, nv, row0, up->gx);
     long long gx = (s.gtotal + 255) / 256;
     if (gx > 4096) gx = 4096;
     hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)gx), dim3(256), 0, st, (const float*)slabs, L.slices, s.gtotal, acc, ch == 0 ? 1 : 0);
@@ -875,7 +936,7 @@ static int run_train(const Shape& s, const float* d_params, const float* d_x, co
   FinArgs f{};
   f.acc = acc; f.grads = d_grads; f.total = s.total; f.n_mat = s.n_mat;
   for (int t = 0; t < s.n_mat; ++t) { f.woff[t] = s.woff[t]; f.boff[t] = s.boff[t]; f.reg[t] = s.reg[t]; f.out[t] = s.out[t]; f.in[t] = s.in[t]; }
-  f.loss_part = loss_part; f.n_parts = nch * (L.rows / 16); f.loss = d_loss;
+  f.loss_part = up ? nullptr : loss_part; f.n_parts = nch * (L.rows / 16); f.loss = d_loss;
   long long gx = (s.total + 255) / 256;
   if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)gx), dim3(256), 0, st, f);
@@ -946,7 +1007,7 @@ extern "C" int pinn_gnet_train_grads(const pinn_gnet_t* net, const float* d_para
   rc = convert(s, drop, &d);
   if (rc) return rc;
   (void)hipGetLastError();
-  return run_train(s, d_params, d_x, d_y, n_rows, n_global, d, d_grads, d_loss, d_work, work_bytes, (hipStream_t)stream);
+  return run_train(s, d_params, d_x, d_y, n_rows, n_global, d, nullptr, d_grads, d_loss, d_work, work_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pinn_gnet_train_step(const pinn_gnet_t* net, float* d_params, const float* d_x, const float* d_y, long long n_rows,
@@ -957,4 +1018,21 @@ extern "C" int pinn_gnet_train_step(const pinn_gnet_t* net, float* d_params, con
   if (rc) return rc;
   const long long n = pinn_gnet_param_count(net);
   return pinn_adam_step(d_params, d_grads, d_m, d_v, n, lr, step, stream);
+}
+
+extern "C" int pinn_gnet_backward(const pinn_gnet_t* net, const float* d_params, const float* d_x, long long n_rows,
+                                  const pinn_dropout_t* drop, const float* d_gu, const float* d_glv, float* d_grads, float* d_gx,
+                                  void* d_work, size_t work_bytes, void* stream) {
+  Shape s;
+  int rc = make_shape(net, &s);
+  if (rc) return rc;
+  if (n_rows < 0 || !d_params || !al16(d_params) || !d_grads || !al16(d_grads)) return PINN_E_ARG;
+  if (n_rows == 0) return PINN_OK;
+  if (!d_x || !al16(d_x) || !d_gu || (d_gx && !al16(d_gx))) return PINN_E_ARG;
+  Drop d;
+  rc = convert(s, drop, &d);
+  if (rc) return rc;
+  (void)hipGetLastError();
+  const Upstream up{d_gu, d_glv, d_gx};
+  return run_train(s, d_params, d_x, nullptr, n_rows, n_rows, d, &up, d_grads, nullptr, d_work, work_bytes, (hipStream_t)stream);
 }

@@ -17,7 +17,9 @@ accumulation, rtol ~2e-2 -- see DNN.set_precision), `seed` (Philox dropout seed)
 data-parallel training with one all-reduce(SUM) of the flat gradient per step),
 `train_dnn(..., batch_size=)` for minibatches, and `kernels` ("auto", default: the shapes `layout.check_arch` accepts on the
 fused / wide kernels; "general": ANY layers list `layout.check_general` accepts -- unequal widths, widths 1..2048 -- on the
-exact-fp32 layer-by-layer kernels of csrc/pinn_general.hip, precision "fp32" only).
+exact-fp32 layer-by-layer kernels of csrc/pinn_general.hip, precision "fp32" only), and `autograd` (False, default: DNN
+outputs carry no grad_fn; True: they are differentiable under torch autograd with respect to the inputs and the 14 weight and
+bias tensors -- see DNN.forward).
 """
 import ctypes
 import math
@@ -54,14 +56,65 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _as_rows(g, n):
+    """An upstream gradient [n, 1] (or None) as a contiguous float32 vector of n entries."""
+    return None if g is None else g.detach().reshape(n).to(torch.float32).contiguous()
+
+
+class _DNNFunction(torch.autograd.Function):
+    """DNN.forward as one autograd node: the forward is the kernel call of DNN._run; the backward is pinn_gnet_backward (exact
+    fp32, csrc/pinn_general.hip) with the dropout masks the forward drew, and returns the gradient of every parameter tensor (views of
+    one fresh flat buffer) and, if x requires it, of x."""
+
+    @staticmethod
+    def forward(ctx, dnn, row_offset, x, *params):
+        u, lv, drop, keep = dnn._run(x, row_offset)
+        ctx.dnn = dnn
+        ctx.drop = None if drop is None else _lib.Dropout.from_buffer_copy(drop)
+        ctx.keep = keep                           # keeps the injected keep-mask tensor of the pass alive until the backward
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, *params)
+        if not dnn.logvar:
+            ctx.mark_non_differentiable(lv)
+        return u, lv
+
+    @staticmethod
+    def backward(ctx, g_u, g_lv):
+        if torch.is_grad_enabled():
+            raise RuntimeError("pinn_amd.DNN is once-differentiable under autograd: create_graph=True (double backward) is not supported")
+        return _DNNFunction._vjp(ctx, g_u, g_lv)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _vjp(ctx, g_u, g_lv):
+        x, *params = ctx.saved_tensors               # torch's version check: an in-place change since the forward raises here
+        dnn = ctx.dnn
+        n = x.shape[0]
+        total = dnn._flat.numel()
+        grads = (torch.zeros if n == 0 else torch.empty)(total, dtype=torch.float32, device=x.device)
+        gx = torch.zeros(n, 8, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[2] else None
+        if n > 0:
+            gu = _as_rows(g_u, n) if g_u is not None else torch.zeros(n, dtype=torch.float32, device=x.device)
+            glv = _as_rows(g_lv, n) if dnn.logvar else None
+            gnet, work = dnn._backward_net(n)
+            rc = dnn._lib.pinn_gnet_backward(ctypes.byref(gnet), _ptr(dnn._flat), _ptr(x), n,
+                                             ctypes.byref(ctx.drop) if ctx.drop is not None else None, _ptr(gu), _ptr(glv),
+                                             _ptr(grads), _ptr(gx), _ptr(work), work.numel(), _stream())
+            _lib.check(rc, "pinn_gnet_backward")
+        pg = [grads[off:off + nel].view(shape) for _, _, off, nel, shape in dnn._views]
+        return (None, None, gx) + tuple(pg)
+
+
 class DNN(torch.nn.Module):
     """01:389-438.  Same module tree / state_dict keys as the reference; the 14 weight and
     bias tensors are views into ONE flat float32 device buffer that the kernels read."""
 
-    def __init__(self, p, logvar, layers, seed=0, precision=None, kernels="auto"):
+    def __init__(self, p, logvar, layers, seed=0, precision=None, kernels="auto", autograd=False):
         """kernels="auto": the shapes layout.check_arch accepts, precision None = "f32x6".  kernels="general": any list
-        layout.check_general accepts (exact-fp32 layer-by-layer kernels, csrc/pinn_general.hip); precision None or "fp32"."""
+        layout.check_general accepts (exact-fp32 layer-by-layer kernels, csrc/pinn_general.hip); precision None or "fp32".
+        autograd=True: outputs are differentiable under torch autograd (see forward); not with precision "bf16"."""
         super().__init__()
+        self._autograd = False
         self.depth = len(layers) - 1
         self.p = p
         self.logvar = logvar
@@ -73,6 +126,7 @@ class DNN(torch.nn.Module):
         self._lib = _lib.load()
         self._packed = None
         self._gwork = None
+        self._bwork = None
         if kernels == "general":
             self.widths = layout.check_general(layers)
             if precision not in (None, "fp32"):
@@ -90,6 +144,11 @@ class DNN(torch.nn.Module):
             self._net = _lib.Net(self.n_in, self.hidden, self.n_hidden)
             offs, total = layout.param_offsets(self.n_in, self.hidden, self.n_hidden)
             assert self._lib.pinn_param_count(ctypes.byref(self._net)) == total
+            # the autograd backward of these nets runs on the general kernels: same flat layout, Philox stream and keep-bit words
+            bl = [self.n_in] + [self.hidden] * self.n_hidden + [1]
+            self._bwd_gnet = _lib.GNet(bl)
+            assert layout.general_offsets(bl) == (offs, total)
+            assert self._lib.pinn_gnet_param_count(ctypes.byref(self._bwd_gnet)) == total
             self.set_precision("f32x6" if precision is None else precision)
         self.layer_sizes = [self.n_in] + list(self.widths) + [1]
         self._offsets = offs
@@ -128,6 +187,19 @@ class DNN(torch.nn.Module):
         # when set, stochastic passes replay these masks instead of drawing Philox ones
         self._mask_bits = None
         self._mask_pass = 0
+        self.autograd = autograd
+
+    @property
+    def autograd(self):
+        """True: forward is differentiable under torch autograd (weights and inputs).  Settable; raises ValueError for "bf16" nets."""
+        return self._autograd
+
+    @autograd.setter
+    def autograd(self, on):
+        on = bool(on)
+        if on and self.precision == "bf16":
+            raise ValueError("autograd=True needs an fp32-accurate forward: precision 'bf16' is not (use 'f32x6', 'f32x6g6' or 'fp32')")
+        self._autograd = on
 
     def set_precision(self, precision):
         """"fp32": exact fp32 matrix math (v_mfma_f32_*_f32; hidden <= 256 only).  "f32x6" (default): fp32-ACCURATE matrix
@@ -143,6 +215,8 @@ class DNN(torch.nn.Module):
         codes = {"fp32": _lib.PREC_FP32, "bf16": _lib.PREC_BF16, "f32x6": _lib.PREC_F32X6, "f32x6g6": _lib.PREC_F32X6_G6}
         if precision not in codes:
             raise ValueError("precision must be 'fp32', 'f32x6', 'f32x6g6' or 'bf16'")
+        if precision == "bf16" and self._autograd:
+            raise ValueError("precision 'bf16' is not fp32-accurate: set dnn.autograd = False first")
         self.precision = precision
         if precision == "fp32":
             self._net = _lib.Net(self.n_in, self.hidden, self.n_hidden, _lib.PREC_FP32, None)
@@ -208,13 +282,47 @@ class DNN(torch.nn.Module):
             self._gwork = torch.empty(nb, dtype=torch.uint8, device=self._flat.device)
         return self._gwork
 
+    def _backward_net(self, n_rows):
+        """(pinn_gnet_t, workspace) that pinn_gnet_backward runs on for n_rows rows: general nets their own net and workspace,
+        fused / wide nets the equal-width general net and a workspace cached for the backward."""
+        if self.kernels == "general":
+            return self._gnet, self.general_workspace(n_rows)
+        nb = self._lib.pinn_gnet_workspace_bytes(ctypes.byref(self._bwd_gnet), int(n_rows), 0)
+        if nb == 0:
+            raise _lib.PinnError("pinn_gnet_workspace_bytes rejected the network")
+        if self._bwork is None or self._bwork.numel() < nb:
+            self._bwork = None
+            self._bwork = torch.empty(nb, dtype=torch.uint8, device=self._flat.device)
+        return self._bwd_gnet, self._bwork
+
     def inject_masks(self, bits):
         """Replay recorded keep-masks (tests only). bits: int32 [n_passes, N, words] or None."""
         self._mask_bits = None if bits is None else bits.to(self._flat.device).contiguous()
         self._mask_pass = 0
 
     def forward(self, x, row_offset=0):
-        """(out [N,1], logvar [N,1]) -- eval: dropout off; train: on-chip Philox masks (01:421-438)."""
+        """(out [N,1], logvar [N,1]) -- eval: dropout off; train: on-chip Philox masks (01:421-438).
+
+        With `autograd` on, grad mode enabled and x or a parameter requiring grad, the call is one torch.autograd.Function: the
+        same kernel call (bit-identical outputs), and a backward (pinn_gnet_backward) that recomputes the forward with the masks
+        this call drew and returns dL/dx and every parameter's gradient.  The backward is exact fp32 for every kernel family; on
+        "f32x6" / "f32x6g6" nets it is the gradient of the exact-fp32 function at the same parameters and masks, which agrees with
+        the gradient of the split-operand forward to fp32 accuracy.  Once-differentiable (create_graph=True raises).  logvar=False:
+        the logvar output is a constant zero."""
+        params = [getattr(mod, pname) for mod, pname, _, _, _ in self._views]
+        if self._autograd and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            self.flat_params()                          # re-gather re-pointed Parameters before autograd records them
+            params = [getattr(mod, pname) for mod, pname, _, _, _ in self._views]
+            xd = x.to(self._flat.device, torch.float32).contiguous()      # differentiable: x.grad comes back in x's dtype / device
+            u, lv = _DNNFunction.apply(self, int(row_offset), xd, *params)
+        else:
+            u, lv, _, _ = self._run(x.detach(), row_offset)
+        if not self.logvar:
+            lv = torch.zeros_like(u)
+        return u, lv
+
+    def _run(self, x, row_offset):
+        """The kernel call of forward -> (u, logvar, the dropout struct it used or None, the injected mask tensor or None)."""
         x = x.detach().to(self._flat.device, torch.float32).contiguous()
         n = x.shape[0]
         u = torch.empty(n, 1, device=x.device, dtype=torch.float32)
@@ -235,19 +343,19 @@ class DNN(torch.nn.Module):
             rc = self._lib.pinn_mlp_forward(ctypes.byref(self._net), _ptr(self.flat_params()), _ptr(x), n,
                                             ctypes.byref(drop) if drop is not None else None, _ptr(u), _ptr(lv), _stream())
             _lib.check(rc, "pinn_mlp_forward")
-        if not self.logvar:
-            lv = torch.zeros_like(u)
-        return u, lv
+        keep = self._mask_bits if drop is not None and drop.mode == _lib.DROP_BITS else None
+        return u, lv, drop, keep
 
 
 class PhysicsInformedNN():
     """01:441-1410."""
 
     def __init__(self, X, u, layers, x_scal, u_scal, p, logvar, *, seed=0, row_offset=0, n_global=None, process_group=None,
-                 precision=None, kernels="auto"):
+                 precision=None, kernels="auto", autograd=False):
         """kernels="general" runs any layers list layout.check_general accepts on the exact-fp32 layer-by-layer kernels
         (precision None or "fp32"); such nets train launch by launch (use_graph is ignored) and, data-parallel, with one
-        blocking all-reduce of the whole gradient per step (no two-part overlap)."""
+        blocking all-reduce of the whole gradient per step (no two-part overlap).  autograd=True: see DNN.forward (passed to
+        the DNN; `model.dnn.autograd` is settable).  The library's trainers do not use it."""
         dev = _device()
         self._lib = _lib.load()
         self.x = X[:, 0:].clone().detach().float().to(dev).contiguous().requires_grad_(True)
@@ -263,7 +371,7 @@ class PhysicsInformedNN():
         self._lambda = torch.tensor(LAMBDA_INIT, dtype=torch.float32, device=dev)
         for i, name in enumerate(LAMBDA_NAMES):
             setattr(self, name, torch.nn.Parameter(self._lambda[i:i + 1]))
-        self.dnn = DNN(p, logvar, layers, seed=seed, precision=precision, kernels=kernels)
+        self.dnn = DNN(p, logvar, layers, seed=seed, precision=precision, kernels=kernels, autograd=autograd)
         # registration order and the `lambda_3` <- lambda_4 overwrite of 01:465-468 are kept for state_dict parity
         self.dnn.register_parameter("lambda_1", self.lambda_1)
         self.dnn.register_parameter("lambda_2", self.lambda_2)
