@@ -149,6 +149,32 @@ int pinn_residuals_cached(const float* d_cache, const pinn_affine_t* aff, const 
 int pinn_net_f_t(const float* d_x, const float* d_u, const float* d_x_halo, const float* d_u_halo, const pinn_affine_t* aff,
                  const float* d_lambda, long long n_rows, float* d_f, float* d_t_pred, float* d_t_real, void* stream);
 
+/* ---- vector-Jacobian products of the two residual passes (torch autograd's backward) ------------------------------
+ * Nothing is saved between forward and backward: each call recomputes every row's terms from d_x, d_u and d_lambda with the
+ * forward's arithmetic and back-propagates them with torch's derivative rules (clamp: inclusive masks; where: nothing through
+ * the condition; abs: sign; rows where the forward is NaN give NaN where torch's autograd does).  Gradients are with respect to
+ * the NORMALISED inputs (chain rule through x_phys = (x_n - x_min) / x_scale and the y map of u).
+ * d_glambda float[17]: the SUM over the local rows of the parameter gradients (0 for the parameters the columns do not read);
+ * under row sharding the caller all-reduces it.  Deterministic: wave64 shuffles -> LDS -> one float64 partial per workgroup
+ * in d_work (pinn_residuals_workspace_bytes()) -> a fixed-order final reduction; no floating-point atomics.
+ * d_gu [n_rows] and d_gx [n_rows, 8] (16-byte aligned, like d_x): per row, overwritten; NULL = not computed.
+ *
+ * pinn_residuals_backward: pinn_residuals' per-row columns.  d_g holds upstream gradients column-major, d_g[c * ld + row],
+ * for the columns c whose bit (1u << c) is set in gmask (absent columns are not read and contribute nothing); gmask may only
+ * name columns of the models in `flags`.  d_u as for pinn_residuals (needed iff flags & PINN_RES_V); d_gu is d/d u. */
+int pinn_residuals_backward(const float* d_x, const float* d_u, const pinn_affine_t* aff, const float* d_lambda, unsigned flags,
+                            long long n_rows, const float* d_g, long long ld, unsigned gmask, float* d_glambda, float* d_gu,
+                            float* d_gx, void* d_work, size_t work_bytes, void* stream);
+/* pinn_net_f_t_backward: upstream gradients of its three outputs f_T, T_pred, T_out (float[n_rows] each, NULL = absent).
+ * Row t's step feeds x[t-1] and u[t-1] (so d_gu[n_rows-1] = 0); d_gx also holds each row's own T_out terms.  With a halo
+ * (d_x_halo, d_u_halo as for pinn_net_f_t), d_gx_halo [8] (16-byte aligned) / d_gu_halo [1] receive the gradient of the
+ * previous shard's last row from this shard's first step (NULL = not computed; a row-sharded caller adds them to that row).
+ * d_glambda holds lambda_T1..T4 (everything else 0). */
+int pinn_net_f_t_backward(const float* d_x, const float* d_u, const float* d_x_halo, const float* d_u_halo, const pinn_affine_t* aff,
+                          const float* d_lambda, long long n_rows, const float* d_gf, const float* d_gt_pred, const float* d_gt_real,
+                          float* d_glambda, float* d_gu, float* d_gx, float* d_gx_halo, float* d_gu_halo, void* d_work,
+                          size_t work_bytes, void* stream);
+
 /* ---- the network ------------------------------------------------------------------------
  * Architecture [n_in=8, hidden x n_hidden, 1] + variance head hidden -> hidden/2 -> hidden/4 -> 1
  * (01:389-438).  Parameters live in ONE flat float32 device buffer in state_dict order,

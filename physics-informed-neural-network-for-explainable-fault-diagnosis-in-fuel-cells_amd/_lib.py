@@ -105,6 +105,10 @@ _SIGS = {
     "pinn_residuals_cached": (c_int, [c_void_p, ctypes.POINTER(Affine), c_void_p, c_uint, c_ll, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_net_f_t": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Affine), c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
                              c_void_p]),
+    "pinn_residuals_backward": (c_int, [c_void_p, c_void_p, ctypes.POINTER(Affine), c_void_p, c_uint, c_ll, c_void_p, c_ll, c_uint, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_net_f_t_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(Affine), c_void_p, c_ll, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_gnet_param_count": (c_ll, [ctypes.POINTER(GNet)]),
     "pinn_gnet_workspace_bytes": (c_size_t, [ctypes.POINTER(GNet), c_ll, c_int]),
     "pinn_gnet_forward": (c_int, [ctypes.POINTER(GNet), c_void_p, c_void_p, c_ll, ctypes.POINTER(Dropout), c_void_p, c_void_p,

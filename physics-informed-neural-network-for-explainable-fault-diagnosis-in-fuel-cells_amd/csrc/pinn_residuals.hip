@@ -680,6 +680,370 @@ __global__ __launch_bounds__(kThreads) void net_f_T_kernel(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Vector-Jacobian products of the two passes above (torch autograd's backward of the oracle's restatement of 01:535-914).
+// Nothing is saved between the calls: every row's terms are recomputed from x, u and the parameters with the forward's
+// arithmetic (same denorm / load_lambdas, same -ffp-contract=off), then back-propagated op by op in the order torch's
+// derivative formulas use: a / b -> (g / b, -g * ((a / b) / b)), log -> g / x, exp -> g * exp(x), pow -> g * p x^(p-1),
+// clamp -> inclusive mask, where -> nothing through the condition, abs -> sign.  A node is visited only when an upstream
+// column that reaches it is present (gmask), so NaN rows (I >= lambda_3: log of a negative number) give NaN exactly where
+// torch's autograd does.  Gradients with respect to the de-normalised inputs become gradients of the normalised ones by
+// the chain rule of x_phys = (x_n - x_min) / x_scale.  Parameter gradients: float64 per thread, wave64 shuffle -> LDS ->
+// one partial per workgroup -> a fixed-order final reduction (no float atomics: bitwise repeatable).
+// ---------------------------------------------------------------------------------------
+#define PINN_BIT(c) (1u << (c))
+constexpr unsigned kGradColsV = PINN_BIT(PINN_C_FV) | PINN_BIT(PINN_C_VACT) | PINN_BIT(PINN_C_VOHM) | PINN_BIT(PINN_C_VCONC) |
+                                PINN_BIT(PINN_C_ENERNST) | PINN_BIT(PINN_C_VEST5) | PINN_BIT(PINN_C_I) | PINN_BIT(PINN_C_VOUT5);
+constexpr unsigned kGradColsT = PINN_BIT(PINN_C_FT) | PINN_BIT(PINN_C_TPRED) | PINN_BIT(PINN_C_TOUT);
+constexpr unsigned kGradColsH = PINN_BIT(PINN_C_FH) | PINN_BIT(PINN_C_ACTH) | PINN_BIT(PINN_C_TGTH) | PINN_BIT(PINN_C_ITOT);
+constexpr unsigned kGradColsO = PINN_BIT(PINN_C_FO) | PINN_BIT(PINN_C_ACTO) | PINN_BIT(PINN_C_TGTO) | PINN_BIT(PINN_C_QO2) |
+                                PINN_BIT(PINN_C_O2FLOW);
+
+__host__ __device__ inline unsigned grad_cols_of(unsigned flags) {
+  return ((flags & PINN_RES_V) ? kGradColsV : 0u) | ((flags & PINN_RES_T) ? kGradColsT : 0u) | ((flags & PINN_RES_H) ? kGradColsH : 0u) |
+         ((flags & PINN_RES_O) ? kGradColsO : 0u);
+}
+
+// one row: accumulates the parameter gradients into acc, returns d/d x_phys in gr[8] and d/d u in gu
+__device__ __forceinline__ void row_backward(long long row, const float* __restrict__ x, const float* __restrict__ u, const AffineDev& aff,
+                                             const LamDev& L, unsigned flags, const float* __restrict__ g, long long ld, unsigned gmask,
+                                             double (&acc)[PINN_NLAMBDA], float (&gr)[8], float& gu) {
+  const float4 xa = reinterpret_cast<const float4*>(x)[row * 2];
+  const float4 xb = reinterpret_cast<const float4*>(x)[row * 2 + 1];
+  const bool fV = flags & PINN_RES_V, fT = flags & PINN_RES_T, fH = flags & PINN_RES_H, fO = flags & PINN_RES_O;
+  const float r0 = denorm(xa.x, aff.x_min[0], aff.x_scale[0]);
+  const float r1 = fT ? denorm(xa.y, aff.x_min[1], aff.x_scale[1]) : 0.f;
+  const float r2 = fT ? denorm(xa.z, aff.x_min[2], aff.x_scale[2]) : 0.f;
+  const float r3 = fV ? denorm(xa.w, aff.x_min[3], aff.x_scale[3]) : 0.f;
+  const float r4 = fV ? denorm(xb.x, aff.x_min[4], aff.x_scale[4]) : 0.f;
+  const float r5 = (fV || fT) ? denorm(xb.y, aff.x_min[5], aff.x_scale[5]) : 0.f;
+  const float r6 = fH ? denorm(xb.z, aff.x_min[6], aff.x_scale[6]) : 0.f;
+  const float r7 = fO ? denorm(xb.w, aff.x_min[7], aff.x_scale[7]) : 0.f;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) gr[c] = 0.0f;
+  gu = 0.0f;
+  // upstream gradient of column c (absent columns are not read; gmask is wave-uniform)
+  auto G = [&](int c) -> float { return (gmask & PINN_BIT(c)) ? g[(long long)c * ld + row] : 0.0f; };
+  auto has = [&](unsigned bits) -> bool { return (gmask & bits) != 0u; };
+
+  const float i5 = r0 / 270.0f + 1e-5f;
+  const float It = i5 * 270.0f;
+  float gi5 = 0.0f;   // d / d i5 of the V, H and O models (T_simple has its own i = I/270 + 1e-6)
+
+  if (fV) {
+    const float gFV = G(PINN_C_FV), gVest = gFV + G(PINN_C_VEST5) * 5.0f;
+    const float l1 = L.l1, l2 = L.l2, l3 = L.l3;
+    float gi = G(PINN_C_I), gb = 0.0f, gTk = 0.0f;
+    const float Tk = r5 + 273.15f;
+    const float RT = 8.314f * Tk;
+    const float b = RT / 96485.0f;
+    if (has(PINN_BIT(PINN_C_FV) | PINN_BIT(PINN_C_VEST5) | PINN_BIT(PINN_C_VACT))) {      // V_act = (-b) log(i / l2)
+      const float gA = gVest + G(PINN_C_VACT);
+      const float q = i5 / l2, La = logf(q);
+      gb -= gA * La;
+      const float gq = (gA * (-b)) / q;
+      gi += gq / l2;
+      acc[PINN_L2] += (double)(-gq * (q / l2));
+    }
+    if (has(PINN_BIT(PINN_C_FV) | PINN_BIT(PINN_C_VEST5) | PINN_BIT(PINN_C_VOHM))) {      // V_ohm = -(i l1)
+      const float gp = -(gVest + G(PINN_C_VOHM));
+      gi += gp * l1;
+      acc[PINN_L1] += (double)(gp * i5);
+    }
+    if (has(PINN_BIT(PINN_C_FV) | PINN_BIT(PINN_C_VEST5) | PINN_BIT(PINN_C_VCONC))) {     // V_conc = (0.5 b) log(1 - i / l3)
+      const float gC = gVest + G(PINN_C_VCONC);
+      const float t = i5 / l3, w = 1.0f - t, Lc = logf(w);
+      gb += (gC * Lc) * 0.5f;
+      const float gt = -((gC * (0.5f * b)) / w);
+      gi += gt / l3;
+      acc[PINN_L3] += (double)(-gt * (t / l3));
+    }
+    if (has(PINN_BIT(PINN_C_FV) | PINN_BIT(PINN_C_VEST5) | PINN_BIT(PINN_C_ENERNST))) {   // E = c - (RT log(P_H2O / (pp_H2 sqrt(pp_O2)))) / 192970
+      const float gE = gVest + G(PINN_C_ENERNST);
+      const float P_H2 = r3 / 101.0f + 1.0f;
+      const float P_air = r4 / 101.0f + 1.0f;
+      const float Tk_p = powf(Tk, 1.334f);
+      const float a1 = 1.653f * i5 / Tk_p, e1 = expf(a1), q1 = P_H2 / e1;
+      const float pp_H2 = 0.5f * (q1 - L.P_H2O);
+      const float a2 = 4.192f * i5 / Tk_p, e2 = expf(a2), q2 = P_air / e2;
+      const float pp_O2 = q2 - L.P_H2O;
+      const float s = sqrtf(pp_O2), D = pp_H2 * s, z = L.P_H2O / D, LE = logf(z);
+      const float gnum = (-gE) / 192970.0f;
+      gTk += (gnum * LE) * 8.314f;
+      const float gz = (gnum * RT) / z;
+      const float gD = -gz * (z / D);
+      const float gpp1 = gD * s, gs = gD * pp_H2;
+      const float gpp2 = gs * (0.5f / s);                   // pow(x, 0.5) -> g 0.5 x^-0.5
+      const float ge2 = -gpp2 * (q2 / e2), ga2 = ge2 * e2;
+      const float gin = gpp1 * 0.5f;
+      const float ge1 = -gin * (q1 / e1), ga1 = ge1 * e1;
+      gi += (ga2 / Tk_p) * 4.192f + (ga1 / Tk_p) * 1.653f;
+      const float gTkp = -ga2 * (a2 / Tk_p) - ga1 * (a1 / Tk_p);
+      gTk += gTkp * (1.334f * powf(Tk, 0.334f));
+      gr[3] += (gin / e1) / 101.0f;
+      gr[4] += (gpp2 / e2) / 101.0f;
+    }
+    gTk += (gb / 96485.0f) * 8.314f;
+    gr[5] += gTk;
+    gi5 += gi;
+    // V_out = denorm(u) / 5 (the caller's DNN output; VOUT5 = 5 V_out)
+    const float gVout = G(PINN_C_VOUT5) * 5.0f - gFV;
+    gu = (float)((double)(gVout / 5.0f) / aff.y_scale);
+  }
+
+  if (fT) {
+    const float gF = G(PINN_C_FT);
+    gr[5] += gF + G(PINN_C_TOUT);
+    if (has(PINN_BIT(PINN_C_FT) | PINN_BIT(PINN_C_TPRED))) {    // T_pred = lT1 I + lT3 (m + 1e-6) + 0.5 T_in + lT5
+      const float gP = G(PINN_C_TPRED) - gF;
+      const float i6 = r0 / 270.0f + 1e-6f;
+      const float mc = r1 + 1e-6f;
+      const float It6 = i6 * 270.0f;
+      acc[PINN_LT1] += (double)(gP * It6);
+      acc[PINN_LT3] += (double)(gP * mc);
+      acc[PINN_LT5] += (double)gP;
+      gr[0] += ((gP * L.lT1) * 270.0f) / 270.0f;
+      gr[1] += gP * L.lT3;
+      gr[2] += gP * 0.5f;
+    }
+  }
+
+  if (fH) {
+    const float gF = G(PINN_C_FH);
+    float gIt = G(PINN_C_ITOT);
+    if (has(PINN_BIT(PINN_C_FH) | PINN_BIT(PINN_C_ACTH))) {     // act = (h2 + 1e-6) / clamp_min(Q, 1e-8)
+      const float ga = gF + G(PINN_C_ACTH);
+      const float Qp = (((It / 192970.0f) * 5.0f) * 22.4f) * 60.0f;
+      const float Q = clamp_min_t(Qp, 1e-8f);
+      const float act = (r6 + 1e-6f) / Q;
+      gr[6] += ga / Q;
+      const float gQ = -ga * (act / Q);
+      const float gQp = (Qp >= 1e-8f) ? gQ : 0.0f;
+      gIt += (((gQp * 60.0f) * 22.4f) * 5.0f) / 192970.0f;
+    }
+    if (has(PINN_BIT(PINN_C_FH) | PINN_BIT(PINN_C_TGTH))) {     // target = where(It <= lH3, lH1 + lH2 It / 100, lH1 + lH2 lH3 / 100)
+      const float gt = G(PINN_C_TGTH) - gF;
+      acc[PINN_LH1] += (double)gt;
+      if (It <= L.lH3) {
+        acc[PINN_LH2] += (double)(gt * (It / 100.0f));
+        gIt += (gt * L.lH2) / 100.0f;
+      } else {
+        acc[PINN_LH2] += (double)(gt * (L.lH3 / 100.0f));
+        acc[PINN_LH3] += (double)((gt * L.lH2) / 100.0f);
+      }
+    }
+    gi5 += gIt * 270.0f;
+  }
+
+  if (fO) {
+    const float gF = G(PINN_C_FO);
+    float gIt = 0.0f;
+    const bool pAct = has(PINN_BIT(PINN_C_FO) | PINN_BIT(PINN_C_ACTO));
+    if (pAct || has(PINN_BIT(PINN_C_QO2) | PINN_BIT(PINN_C_O2FLOW))) {
+      const float Qp = (((It * 5.0f) / 385940.0f) * 22.4f) * 60.0f;
+      const float Q = clamp_min_t(Qp, 1e-8f);
+      const float o2 = (r7 + 1e-6f) * 0.21f;
+      float gQ = G(PINN_C_QO2), go2 = G(PINN_C_O2FLOW);
+      if (pAct) {                                               // f = (act - tgt) + clamp_min(1 - act, 0) 10,  act = o2 / Q
+        const float act = o2 / Q;
+        float ga = gF + G(PINN_C_ACTO);
+        if (gmask & PINN_BIT(PINN_C_FO)) ga -= ((1.0f - act) >= 0.0f) ? gF * 10.0f : 0.0f;
+        go2 += ga / Q;
+        gQ += -ga * (act / Q);
+      }
+      if (pAct || has(PINN_BIT(PINN_C_QO2))) {
+        const float gQp = (Qp >= 1e-8f) ? gQ : 0.0f;
+        gIt += (((gQp * 60.0f) * 22.4f) / 385940.0f) * 5.0f;
+      }
+      gr[7] += go2 * 0.21f;
+    }
+    if (has(PINN_BIT(PINN_C_FO) | PINN_BIT(PINN_C_TGTO))) {     // target = clamp(where(It <= |lO3|, ...), 1.05, 15)
+      const float gt = G(PINN_C_TGTO) - gF;
+      const float thr = fabsf(L.lO3);
+      const bool lin = It <= thr;
+      const float raw = lin ? (L.lO1 + L.lO2 * (It / 100.0f)) : (L.lO1 + L.lO2 * (thr / 100.0f));
+      const float gw = (raw >= 1.05f && raw <= 15.0f) ? gt : 0.0f;
+      acc[PINN_LO1] += (double)gw;
+      if (lin) {
+        acc[PINN_LO2] += (double)(gw * (It / 100.0f));
+        gIt += (gw * L.lO2) / 100.0f;
+      } else {
+        acc[PINN_LO2] += (double)(gw * (thr / 100.0f));
+        const float sgn = (L.lO3 > 0.0f) ? 1.0f : ((L.lO3 < 0.0f) ? -1.0f : 0.0f);
+        acc[PINN_LO3] += (double)(((gw * L.lO2) / 100.0f) * sgn);
+      }
+    }
+    gi5 += gIt * 270.0f;
+  }
+  gr[0] += gi5 / 270.0f;
+}
+
+// d / d x_phys -> d / d x_n (x_phys = (x_n - x_min) / x_scale), one row of 8
+__device__ __forceinline__ void store_gx_row(float* __restrict__ gx, long long row, const float (&gr)[8], const AffineDev& aff) {
+  float o[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) o[c] = (float)((double)gr[c] / aff.x_scale[c]);
+  reinterpret_cast<float4*>(gx)[row * 2] = make_float4(o[0], o[1], o[2], o[3]);
+  reinterpret_cast<float4*>(gx)[row * 2 + 1] = make_float4(o[4], o[5], o[6], o[7]);
+}
+
+// the parameter gradients of one workgroup -> partials[blockIdx.x * PINN_NSUMS + k], k < PINN_NLAMBDA
+__device__ __forceinline__ void block_lambda_partials(const double (&acc)[PINN_NLAMBDA], double (*red)[PINN_NLAMBDA], double* __restrict__ partials) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < PINN_NLAMBDA; ++k) {
+    const double w = wave_sum(acc[k]);
+    if (lane == 0) red[wave][k] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < PINN_NLAMBDA) {
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) t += red[w][threadIdx.x];
+    partials[(long long)blockIdx.x * PINN_NSUMS + threadIdx.x] = t;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void residuals_backward_kernel(
+    const float* __restrict__ x, const float* __restrict__ u, AffineDev aff, const float* __restrict__ lambdas, unsigned flags,
+    long long n_rows, const float* __restrict__ g, long long ld, unsigned gmask, float* __restrict__ gu_out, float* __restrict__ gx_out,
+    double* __restrict__ partials) {
+  __shared__ double red[kThreads / 64][PINN_NLAMBDA];
+  const LamDev L = load_lambdas(lambdas);
+  double acc[PINN_NLAMBDA];
+#pragma unroll
+  for (int k = 0; k < PINN_NLAMBDA; ++k) acc[k] = 0.0;
+  const long long stride = (long long)gridDim.x * kThreads;
+  for (long long row = (long long)blockIdx.x * kThreads + threadIdx.x; row < n_rows; row += stride) {
+    float gr[8], gu;
+    row_backward(row, x, u, aff, L, flags, g, ld, gmask, acc, gr, gu);
+    if (gx_out != nullptr) store_gx_row(gx_out, row, gr, aff);
+    if (gu_out != nullptr) gu_out[row] = gu;
+  }
+  block_lambda_partials(acc, red, partials);
+}
+
+// fixed-order final reduction of the parameter-gradient partials (residuals_finalize's order) -> float[PINN_NLAMBDA]
+__global__ __launch_bounds__(1024) void lambda_grad_finalize(const double* __restrict__ partials, int n_blocks, float* __restrict__ glambda) {
+  __shared__ double red[32][PINN_NLAMBDA + 1];
+  const int s = threadIdx.x & 31, j = threadIdx.x >> 5;
+  double v[kMaxBlocks / 32];
+#pragma unroll
+  for (int k = 0; k < kMaxBlocks / 32; ++k) {
+    const int b = j + 32 * k;
+    v[k] = (s < PINN_NLAMBDA && b < n_blocks) ? partials[(long long)b * PINN_NSUMS + s] : 0.0;
+  }
+  double t = 0.0;
+#pragma unroll
+  for (int k = 0; k < kMaxBlocks / 32; ++k) t += v[k];
+  if (s < PINN_NLAMBDA) red[j][s] = t;
+  __syncthreads();
+  if (threadIdx.x < PINN_NLAMBDA) {
+    double r = 0.0;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) r += red[k][threadIdx.x];
+    glambda[threadIdx.x] = (float)r;
+  }
+}
+
+// Backward of one Euler step t (net_f_T_kernel's arithmetic) with respect to its predecessor row p = t - 1 (or the halo):
+// g = dL/dT_pred[t].  Returns d/d x_phys of p's columns 0, 1, 2, 5 and d/d u[p]; accumulates lambda_T1..T4.
+struct EulerGrad { float g0, g1, g2, g5, gu; };
+__device__ __forceinline__ EulerGrad euler_step_backward(float4 pa, float4 pb, float un, float g, const AffineDev& aff, float lT1, float lT2,
+                                                         float lT3, float lT4, double (&acc)[PINN_NLAMBDA]) {
+  const float r0 = denorm(pa.x, aff.x_min[0], aff.x_scale[0]);
+  const float m_cool = denorm(pa.y, aff.x_min[1], aff.x_scale[1]) + 1e-6f;
+  const float T_in = denorm(pa.z, aff.x_min[2], aff.x_scale[2]);
+  const float T_prev = denorm(pb.y, aff.x_min[5], aff.x_scale[5]);
+  const float i5 = r0 / 270.0f + 0.00001f;
+  const float I_tot = i5 * 270.0f;
+  const float Tk = T_prev + 273.15f;
+  const float V_rev = 1.229f - 0.0009f * (Tk - 298.15f);
+  const float V_cell = denorm(un, aff.y_min, aff.y_scale) / 5.0f;
+  const float A = I_tot * V_rev - I_tot * V_cell;
+  const float Q_el = A * lT4;
+  const float dTc = T_prev - T_in;
+  const float B = (m_cool * 4180.0f) * dTc;
+  const float Q_cool = B * lT1;
+  const float C = (20.0f * 0.2f) * (T_prev - 25.0f);
+  const float Q_rad = C * lT3;
+  const float dT = ((Q_el - Q_cool) - Q_rad) / lT2;
+  // T_pred = T_prev + dT 0.1
+  float gTp = g;
+  const float gdT = g * 0.1f;
+  const float gnum = gdT / lT2;
+  acc[PINN_LT2] += (double)(-gdT * (dT / lT2));
+  const float gA = gnum * lT4;                     // Q_el = A lT4
+  acc[PINN_LT4] += (double)(gnum * A);
+  const float gI = gA * V_rev - gA * V_cell;
+  gTp += (gA * I_tot) * -0.0009f;                  // V_rev = 1.229 - 0.0009 (Tk - 298.15)
+  const float gVcell = -(gA * I_tot);
+  const float gB = -gnum * lT1;                    // Q_cool = B lT1
+  acc[PINN_LT1] += (double)(-gnum * B);
+  const float gdTc = gB * (m_cool * 4180.0f);
+  gTp += gdTc;
+  const float gC = -gnum * lT3;                    // Q_rad = C lT3
+  acc[PINN_LT3] += (double)(-gnum * C);
+  gTp += gC * (20.0f * 0.2f);
+  EulerGrad e;
+  e.g0 = (gI * 270.0f) / 270.0f;
+  e.g1 = (gB * dTc) * 4180.0f;
+  e.g2 = -gdTc;
+  e.g5 = gTp;
+  e.gu = (float)((double)(gVcell / 5.0f) / aff.y_scale);
+  return e;
+}
+
+// Thread r owns row r: its own T_out terms (f = T_out - T_pred, the T_out output, T_pred[0] = T_out[0] without a halo) and the
+// step r + 1, whose gradient lands on row r (x[r], u[r]).  Global thread 0 also runs the halo step (row 0's predecessor).
+__global__ __launch_bounds__(kThreads) void net_f_T_backward_kernel(
+    const float* __restrict__ x, const float* __restrict__ u, const float* __restrict__ x_halo, const float* __restrict__ u_halo, AffineDev aff,
+    const float* __restrict__ lambdas, long long n_rows, const float* __restrict__ gf, const float* __restrict__ gpred,
+    const float* __restrict__ greal, float* __restrict__ gu_out, float* __restrict__ gx_out, float* __restrict__ gx_halo,
+    float* __restrict__ gu_halo, double* __restrict__ partials) {
+  __shared__ double red[kThreads / 64][PINN_NLAMBDA];
+  const float lT1 = lambdas[PINN_LT1], lT2 = lambdas[PINN_LT2], lT3 = lambdas[PINN_LT3], lT4 = lambdas[PINN_LT4];
+  double acc[PINN_NLAMBDA];
+#pragma unroll
+  for (int k = 0; k < PINN_NLAMBDA; ++k) acc[k] = 0.0;
+  const bool step_path = gf != nullptr || gpred != nullptr;       // T_pred reached by an upstream gradient
+  auto gp_at = [&](long long t) -> float { return (gpred ? gpred[t] : 0.0f) - (gf ? gf[t] : 0.0f); };
+  const long long stride = (long long)gridDim.x * kThreads;
+  for (long long row = (long long)blockIdx.x * kThreads + threadIdx.x; row < n_rows; row += stride) {
+    float gr[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) gr[c] = 0.0f;
+    float gu = 0.0f;
+    gr[5] = (gf ? gf[row] : 0.0f) + (greal ? greal[row] : 0.0f);
+    if (row == 0 && x_halo == nullptr && step_path) gr[5] += gp_at(0);
+    const float4 pa = reinterpret_cast<const float4*>(x)[row * 2];
+    const float4 pb = reinterpret_cast<const float4*>(x)[row * 2 + 1];
+    if (row + 1 < n_rows && step_path) {
+      const EulerGrad e = euler_step_backward(pa, pb, u[row], gp_at(row + 1), aff, lT1, lT2, lT3, lT4, acc);
+      gr[0] += e.g0; gr[1] += e.g1; gr[2] += e.g2; gr[5] += e.g5;
+      gu = e.gu;
+    }
+    if (gx_out != nullptr) store_gx_row(gx_out, row, gr, aff);
+    if (gu_out != nullptr) gu_out[row] = gu;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (gx_halo != nullptr || gu_halo != nullptr || x_halo != nullptr)) {
+    float hr[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) hr[c] = 0.0f;
+    float hu = 0.0f;
+    if (x_halo != nullptr && n_rows > 0 && step_path) {
+      const float4 pa = reinterpret_cast<const float4*>(x_halo)[0];
+      const float4 pb = reinterpret_cast<const float4*>(x_halo)[1];
+      const EulerGrad e = euler_step_backward(pa, pb, u_halo[0], gp_at(0), aff, lT1, lT2, lT3, lT4, acc);
+      hr[0] = e.g0; hr[1] = e.g1; hr[2] = e.g2; hr[5] = e.g5;
+      hu = e.gu;
+    }
+    if (gx_halo != nullptr) store_gx_row(gx_halo, 0, hr, aff);
+    if (gu_halo != nullptr) gu_halo[0] = hu;
+  }
+  block_lambda_partials(acc, red, partials);
+}
+
 }  // namespace
 
 extern "C" size_t pinn_residuals_workspace_bytes(void) { return (size_t)kMaxBlocks * PINN_NSUMS * sizeof(double); }
@@ -795,6 +1159,49 @@ extern "C" int pinn_net_f_t(const float* d_x, const float* d_u, const float* d_x
   const int blocks = (int)(want > kMaxBlocks ? kMaxBlocks : want);
   hipLaunchKernelGGL(net_f_T_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, d_x, d_u, d_x_halo, d_u_halo, a, d_lambda, n_rows,
                      d_f, d_t_pred, d_t_real);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+static bool misaligned16(const void* p) { return ((unsigned long long)(size_t)p & 15ull) != 0ull; }
+
+extern "C" int pinn_residuals_backward(const float* d_x, const float* d_u, const pinn_affine_t* aff, const float* d_lambda, unsigned flags,
+                                       long long n_rows, const float* d_g, long long ld, unsigned gmask, float* d_glambda, float* d_gu,
+                                       float* d_gx, void* d_work, size_t work_bytes, void* stream) {
+  if (n_rows < 0 || !aff || !d_lambda || !d_glambda || (flags & ~PINN_RES_ALL)) return PINN_E_ARG;
+  if (gmask & ~grad_cols_of(flags)) return PINN_E_ARG;             // a column the requested residuals do not produce
+  if (n_rows > 0 && (!d_x || misaligned16(d_x) || misaligned16(d_gx))) return PINN_E_ARG;
+  if ((flags & PINN_RES_V) && n_rows > 0 && !d_u) return PINN_E_ARG;
+  if (gmask && n_rows > 0 && (!d_g || ld < n_rows)) return PINN_E_ARG;
+  if (!d_work) return PINN_E_ARG;
+  if (work_bytes < pinn_residuals_workspace_bytes()) return PINN_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();
+  const int blocks = row_blocks(n_rows);
+  hipLaunchKernelGGL(residuals_backward_kernel, dim3(blocks), dim3(kThreads), 0, st, d_x, d_u, affine_dev(aff), d_lambda, flags, n_rows,
+                     d_g, ld, gmask, d_gu, d_gx, (double*)d_work);
+  hipLaunchKernelGGL(lambda_grad_finalize, dim3(1), dim3(1024), 0, st, (const double*)d_work, blocks, d_glambda);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+extern "C" int pinn_net_f_t_backward(const float* d_x, const float* d_u, const float* d_x_halo, const float* d_u_halo,
+                                     const pinn_affine_t* aff, const float* d_lambda, long long n_rows, const float* d_gf,
+                                     const float* d_gt_pred, const float* d_gt_real, float* d_glambda, float* d_gu, float* d_gx,
+                                     float* d_gx_halo, float* d_gu_halo, void* d_work, size_t work_bytes, void* stream) {
+  if (n_rows < 0 || !aff || !d_lambda || !d_glambda) return PINN_E_ARG;
+  if (n_rows > 0 && (!d_x || misaligned16(d_x) || misaligned16(d_gx))) return PINN_E_ARG;
+  if (n_rows > 1 && !d_u) return PINN_E_ARG;
+  if ((d_x_halo == nullptr) != (d_u_halo == nullptr) || misaligned16(d_x_halo) || misaligned16(d_gx_halo)) return PINN_E_ARG;
+  if (!d_x_halo && (d_gx_halo || d_gu_halo)) return PINN_E_ARG;
+  if (!d_work) return PINN_E_ARG;
+  if (work_bytes < pinn_residuals_workspace_bytes()) return PINN_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();
+  const int blocks = row_blocks(n_rows);
+  hipLaunchKernelGGL(net_f_T_backward_kernel, dim3(blocks), dim3(kThreads), 0, st, d_x, d_u, d_x_halo, d_u_halo, affine_dev(aff), d_lambda,
+                     n_rows, d_gf, d_gt_pred, d_gt_real, d_gu, d_gx, d_gx_halo, d_gu_halo, (double*)d_work);
+  hipLaunchKernelGGL(lambda_grad_finalize, dim3(1), dim3(1024), 0, st, (const double*)d_work, blocks, d_glambda);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PINN_OK : (int)e;
 }

@@ -19,7 +19,9 @@ data-parallel training with one all-reduce(SUM) of the flat gradient per step),
 fused / wide kernels; "general": ANY layers list `layout.check_general` accepts -- unequal widths, widths 1..2048 -- on the
 exact-fp32 layer-by-layer kernels of csrc/pinn_general.hip, precision "fp32" only), and `autograd` (False, default: DNN
 outputs carry no grad_fn; True: they are differentiable under torch autograd with respect to the inputs and the 14 weight and
-bias tensors -- see DNN.forward).
+bias tensors -- see DNN.forward), and `physics_autograd` (False, default: the physics functions return plain tensors; "lambdas":
+differentiable with respect to the physics parameters, the reference's own graph; "full": also with respect to X, halo rows and,
+through the DNN output, the weights -- see PhysicsInformedNN.physics_autograd).
 """
 import ctypes
 import math
@@ -103,6 +105,136 @@ class _DNNFunction(torch.autograd.Function):
             _lib.check(rc, "pinn_gnet_backward")
         pg = [grads[off:off + nel].view(shape) for _, _, off, nel, shape in dnn._views]
         return (None, None, gx) + tuple(pg)
+
+
+PHYSICS_AUTOGRAD_MODES = (False, "lambdas", "full")
+
+# Tuple columns of the four pinn_residuals models: (column, physics parameters it reads, reads x, reads u)
+_L = {n: i for i, n in enumerate(LAMBDA_NAMES)}
+_RES_SPECS = {
+    _lib.RES_V: (["lambda_1", "lambda_2", "lambda_3"],
+                 [("FV", (0, 1, 2), True, True), ("VACT", (1,), True, False), ("VOHM", (0,), True, False), ("VCONC", (2,), True, False),
+                  ("ENERNST", (), True, False), ("VEST5", (0, 1, 2), True, False), ("I", (), True, False), ("VOUT5", (), False, True)]),
+    _lib.RES_T: (["lambda_T1", "lambda_T3", "lambda_T5"],
+                 [("FT", (0, 1, 2), True, False), ("TPRED", (0, 1, 2), True, False), ("TOUT", (), True, False)]),
+    _lib.RES_H: (["lambda_H1", "lambda_H2", "lambda_H3"],
+                 [("FH", (0, 1, 2), True, False), ("ACTH", (), True, False), ("TGTH", (0, 1, 2), True, False), ("ITOT", (), True, False)]),
+    _lib.RES_O: (["lambda_O1", "lambda_O2", "lambda_O3"],
+                 [("FO", (0, 1, 2), True, False), ("ACTO", (), True, False), ("TGTO", (0, 1, 2), True, False), ("QO2", (), True, False),
+                  ("O2FLOW", (), True, False)]),
+}
+_EULER_LAMBDAS = ["lambda_T1", "lambda_T2", "lambda_T3", "lambda_T4"]
+
+
+def _no_double_backward(what):
+    if torch.is_grad_enabled():
+        raise RuntimeError("pinn_amd.%s is once-differentiable under autograd: create_graph=True (double backward) is not supported" % what)
+
+
+def _differentiable(lams, x, u, deps, x_dep, u_dep):
+    return (any(lams[j].requires_grad for j in deps) or (x_dep and x is not None and x.requires_grad)
+            or (u_dep and u is not None and u.requires_grad))
+
+
+class _ResidualsFunction(torch.autograd.Function):
+    """One of net_f_V / net_f_T_simple / net_f_H / net_f_O as one autograd node: the forward is today's pinn_residuals call
+    (bit-identical columns); the backward is pinn_residuals_backward, which recomputes the rows' terms from x, u and the
+    parameters the forward used.  Inputs: the normalised rows, the DNN output u (voltage model) and the model's physics
+    parameters; tuple elements that depend on nothing requiring grad are non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, model, flags, x_scal, xd, u, *lams):
+        c = model._residuals(xd, x_scal, flags, u=u)
+        ctx.model, ctx.flags, ctx.aff = model, flags, model._affine(x_scal)
+        ctx.lam = model._lambda.clone()          # the values this forward used, for the backward's recomputation
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xd, u, *lams)      # version counters: an in-place change before the backward raises there
+        names, cols = _RES_SPECS[flags]
+        outs = tuple(c[_lib.C[name]].unsqueeze(1) for name, _, _, _ in cols)
+        nd = [o for o, (_, deps, xdp, udp) in zip(outs, cols) if not _differentiable(lams, xd, u, deps, xdp, udp)]
+        if nd:
+            ctx.mark_non_differentiable(*nd)
+        return outs
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        _no_double_backward("PhysicsInformedNN residuals")
+        return _ResidualsFunction._vjp(ctx, *gouts)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _vjp(ctx, *gouts):
+        xd, u, *lams = ctx.saved_tensors
+        model, n = ctx.model, xd.shape[0]
+        names, cols = _RES_SPECS[ctx.flags]
+        dev = xd.device
+        present = [(_lib.C[name], g) for (name, _, _, _), g in zip(cols, gouts) if g is not None]
+        gmask, g = 0, None
+        if present and n > 0:
+            g = torch.zeros(max(k for k, _ in present) + 1, n, dtype=torch.float32, device=dev)
+            for k, gk in present:
+                g[k].copy_(gk.reshape(n))
+                gmask |= 1 << k
+        gx = torch.empty(n, 8, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
+        gu = torch.empty(n, dtype=torch.float32, device=dev) if ctx.needs_input_grad[4] else None
+        gl = torch.empty(_lib.NLAMBDA, dtype=torch.float32, device=dev)
+        rc = model._lib.pinn_residuals_backward(_ptr(xd.detach()), _ptr(u), ctypes.byref(ctx.aff), _ptr(ctx.lam), ctx.flags, n, _ptr(g), n,
+                                                gmask, _ptr(gl), _ptr(gu), _ptr(gx), _ptr(model._res_work), model._res_work.numel(),
+                                                _stream())
+        _lib.check(rc, "pinn_residuals_backward")
+        lg = tuple(gl[_L[nm]:_L[nm] + 1] if ctx.needs_input_grad[5 + j] else None for j, nm in enumerate(names))
+        if gu is not None:
+            gu = gu.view(u.shape)
+        return (None, None, None, gx, gu) + lg
+
+
+class _EulerFunction(torch.autograd.Function):
+    """net_f_T (the Euler model, pinn_net_f_t) as one autograd node; backward: pinn_net_f_t_backward.  Inputs: the rows, the
+    DNN output u, the optional halo row and its u, and lambda_T1..T4."""
+
+    @staticmethod
+    def forward(ctx, model, x_scal, xd, u, xh, uh, *lams):
+        n = xd.shape[0]
+        aff = model._affine(x_scal)
+        out = torch.empty(3, n, device=xd.device, dtype=torch.float32)
+        rc = model._lib.pinn_net_f_t(_ptr(xd), _ptr(u), _ptr(xh), _ptr(uh), ctypes.byref(aff), _ptr(model._lambdas()), n,
+                                     _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream())
+        _lib.check(rc, "pinn_net_f_t")
+        ctx.model, ctx.aff = model, aff
+        ctx.lam = model._lambda.clone()
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xd, u, xh, uh, *lams)
+        f, pred, real = out[0].unsqueeze(1), out[1].unsqueeze(1), out[2].unsqueeze(1)
+        step = (any(l.requires_grad for l in lams) or xd.requires_grad or any(t is not None and t.requires_grad for t in (u, xh, uh)))
+        nd = ([] if step else [f, pred]) + ([] if xd.requires_grad else [real])
+        if nd:
+            ctx.mark_non_differentiable(*nd)
+        return f, pred, real
+
+    @staticmethod
+    def backward(ctx, g_f, g_pred, g_real):
+        _no_double_backward("PhysicsInformedNN.net_f_T")
+        return _EulerFunction._vjp(ctx, g_f, g_pred, g_real)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _vjp(ctx, g_f, g_pred, g_real):
+        xd, u, xh, uh, *lams = ctx.saved_tensors
+        model, n = ctx.model, xd.shape[0]
+        dev = xd.device
+        need = ctx.needs_input_grad
+        gx = torch.empty(n, 8, dtype=torch.float32, device=dev) if need[2] else None
+        gu = torch.empty(n, dtype=torch.float32, device=dev) if need[3] else None
+        gxh = torch.empty(8, dtype=torch.float32, device=dev) if need[4] else None
+        guh = torch.empty(1, dtype=torch.float32, device=dev) if need[5] else None
+        gl = torch.empty(_lib.NLAMBDA, dtype=torch.float32, device=dev)
+        rc = model._lib.pinn_net_f_t_backward(_ptr(xd.detach()), _ptr(u), _ptr(xh), _ptr(uh), ctypes.byref(ctx.aff), _ptr(ctx.lam), n,
+                                              _ptr(_as_rows(g_f, n)), _ptr(_as_rows(g_pred, n)), _ptr(_as_rows(g_real, n)), _ptr(gl),
+                                              _ptr(gu), _ptr(gx), _ptr(gxh), _ptr(guh), _ptr(model._res_work), model._res_work.numel(),
+                                              _stream())
+        _lib.check(rc, "pinn_net_f_t_backward")
+        lg = tuple(gl[_L[nm]:_L[nm] + 1] if need[6 + j] else None for j, nm in enumerate(_EULER_LAMBDAS))
+        return (None, None, gx, None if gu is None else gu.view(u.shape), gxh, guh) + lg
 
 
 class DNN(torch.nn.Module):
@@ -351,11 +483,12 @@ class PhysicsInformedNN():
     """01:441-1410."""
 
     def __init__(self, X, u, layers, x_scal, u_scal, p, logvar, *, seed=0, row_offset=0, n_global=None, process_group=None,
-                 precision=None, kernels="auto", autograd=False):
+                 precision=None, kernels="auto", autograd=False, physics_autograd=False):
         """kernels="general" runs any layers list layout.check_general accepts on the exact-fp32 layer-by-layer kernels
         (precision None or "fp32"); such nets train launch by launch (use_graph is ignored) and, data-parallel, with one
         blocking all-reduce of the whole gradient per step (no two-part overlap).  autograd=True: see DNN.forward (passed to
-        the DNN; `model.dnn.autograd` is settable).  The library's trainers do not use it."""
+        the DNN; `model.dnn.autograd` is settable).  physics_autograd: see the `physics_autograd` property.  The library's
+        trainers use neither."""
         dev = _device()
         self._lib = _lib.load()
         self.x = X[:, 0:].clone().detach().float().to(dev).contiguous().requires_grad_(True)
@@ -388,6 +521,67 @@ class PhysicsInformedNN():
         self._sums = torch.zeros(_lib.NSUMS, dtype=torch.float64, device=dev)
         self._res_work = torch.empty(self._lib.pinn_residuals_workspace_bytes(), dtype=torch.uint8, device=dev)
         self.verbose = True
+        self._physics_autograd = False
+        self.physics_autograd = physics_autograd
+
+    @property
+    def physics_autograd(self):
+        """Whether net_f_V / net_f_T_simple / net_f_H / net_f_O / net_f_T are differentiable under torch autograd.
+
+        False (default): plain tensors, no grad_fn.  "lambdas": the reference's graph -- each function is one autograd node
+        (the same kernel call, bit-identical outputs) whose differentiable inputs are the physics parameters only; the rows
+        and the DNN output enter as constants, as the reference's numpy round trip makes them.  "full": also differentiable
+        with respect to X (when the tensor passed requires grad), to `halo` tensors that require grad and, through the DNN
+        output inside net_f_V / net_f_T, to the network's weights; needs model.dnn.autograd = True.  Both modes: nothing is
+        recorded under torch.no_grad(); once-differentiable (create_graph=True raises).  Parameter gradients are sums over
+        the local rows: under data parallelism all-reduce them like the DNN's gradients.  Settable; ValueError for other
+        values and for "full" without dnn.autograd."""
+        return self._physics_autograd
+
+    @physics_autograd.setter
+    def physics_autograd(self, mode):
+        if mode is None:
+            mode = False
+        if isinstance(mode, bool) and mode:
+            raise ValueError("physics_autograd must be False, 'lambdas' or 'full' (got True)")
+        if mode not in PHYSICS_AUTOGRAD_MODES:
+            raise ValueError("physics_autograd must be False, 'lambdas' or 'full' (got %r)" % (mode,))
+        if mode == "full" and not self.dnn.autograd:
+            raise ValueError("physics_autograd='full' differentiates through the DNN: set model.dnn.autograd = True first")
+        self._physics_autograd = mode or False
+
+    def _physics_mode(self):
+        """The mode of this call: False when off or under torch.no_grad()."""
+        mode = self._physics_autograd
+        if mode == "full" and not self.dnn.autograd:
+            raise ValueError("physics_autograd='full' needs model.dnn.autograd = True (it has been turned off)")
+        return mode if torch.is_grad_enabled() else False
+
+    def _physics_rows(self, X, mode):
+        """The rows of a physics function: in "full" mode a tensor that requires grad keeps its graph."""
+        if mode == "full" and isinstance(X, torch.Tensor) and X.requires_grad:
+            return X.to(self.x.device, torch.float32).contiguous()
+        return self._dev_rows(X)
+
+    def _physics_u(self, xd, mode):
+        """The DNN output the physics functions read: in the caller's train / eval mode (same dropout masks in every mode);
+        differentiable in "full" mode, a constant otherwise."""
+        if mode == "lambdas":
+            with torch.no_grad():
+                return self.net_u(xd)[0].reshape(-1).contiguous()
+        return self.net_u(xd)[0].reshape(-1).contiguous()
+
+    def _residual_tuple(self, X, x_scal, flags, mode):
+        """Columns of one residual model: through _ResidualsFunction when something requires grad, else today's call."""
+        names, cols = _RES_SPECS[flags]
+        xd = self._physics_rows(X, mode)
+        u = self._physics_u(xd, mode) if flags == _lib.RES_V else None
+        self._lambdas()                             # re-gather parameters re-pointed by `lambda_k.data = ...`
+        lams = [getattr(self, n) for n in names]
+        if xd.requires_grad or (u is not None and u.requires_grad) or any(l.requires_grad for l in lams):
+            return _ResidualsFunction.apply(self, flags, x_scal, xd, u, *lams)
+        c = self._residuals(xd, x_scal, flags, u=u)
+        return tuple(self._col(c, name) for name, _, _, _ in cols)
 
     # ------------------------------------------------------------------ helpers
     def _lambdas(self):
@@ -447,6 +641,10 @@ class PhysicsInformedNN():
 
     def net_f_V(self, X, x_scal):
         """01:724-765 -> (f, V_act, V_ohmic, V_conc, E_nerst, V_out_est*5, i, il, V_out*5)."""
+        mode = self._physics_mode()
+        if mode:
+            f, va, vo, vc, e, v5, i, vout5 = self._residual_tuple(X, x_scal, _lib.RES_V, mode)
+            return f, va, vo, vc, e, v5, i, self.lambda_3, vout5
         xd = self._dev_rows(X)
         u, _ = self.net_u(xd)                       # in the caller's train/eval mode, detached (01:733-734)
         c = self._residuals(xd, x_scal, _lib.RES_V, u=u.reshape(-1))
@@ -455,16 +653,25 @@ class PhysicsInformedNN():
 
     def net_f_T_simple(self, X, x_scal):
         """01:869-914 -> (f_T, T_out_predicted, T_out_real).  (The reference's unused DNN forward is not run.)"""
+        mode = self._physics_mode()
+        if mode:
+            return self._residual_tuple(X, x_scal, _lib.RES_T, mode)
         c = self._residuals(X, x_scal, _lib.RES_T)
         return self._col(c, "FT"), self._col(c, "TPRED"), self._col(c, "TOUT")
 
     def net_f_H(self, X, x_scal):
         """01:621-722 -> (f_H2, actual_excess_ratio, target_excess_ratio, I_total, I_threshold)."""
+        mode = self._physics_mode()
+        if mode:
+            return self._residual_tuple(X, x_scal, _lib.RES_H, mode) + (self.lambda_H3,)
         c = self._residuals(X, x_scal, _lib.RES_H)
         return self._col(c, "FH"), self._col(c, "ACTH"), self._col(c, "TGTH"), self._col(c, "ITOT"), self.lambda_H3
 
     def net_f_O(self, X, x_scal):
         """01:535-619 -> (f_O2, actual_excess_ratio, target_excess_ratio, Q_O2_theoretical_slpm, o2_flow_actual)."""
+        mode = self._physics_mode()
+        if mode:
+            return self._residual_tuple(X, x_scal, _lib.RES_O, mode)
         c = self._residuals(X, x_scal, _lib.RES_O)
         return self._col(c, "FO"), self._col(c, "ACTO"), self._col(c, "TGTO"), self._col(c, "QO2"), self._col(c, "O2FLOW")
 
@@ -472,18 +679,28 @@ class PhysicsInformedNN():
         """01:767-867: Euler energy balance row t-1 -> t -> (f_T, T_out_predicted_full, T_out_real_full), one fused
         kernel (pinn_net_f_t).  The DNN runs in the caller's train / eval mode on the rows, as the reference runs it on
         X[:-1] (01:826-830).  `halo` = (x_row [8], u) of the row before X[0] when X is a row shard that does not start
-        the series (device or host tensors; not in the reference, which has no sharding)."""
-        xd = self._dev_rows(X)
+        the series (device or host tensors; not in the reference, which has no sharding).  Under physics_autograd
+        (see there) one autograd node whose backward is pinn_net_f_t_backward; in "full" mode halo tensors that require
+        grad receive the gradient of that row."""
+        mode = self._physics_mode()
+        xd = self._physics_rows(X, mode) if mode else self._dev_rows(X)
         n = xd.shape[0]
         dev = xd.device
         if n < 2 and halo is None:
             z = torch.zeros(n, 1, device=dev)
             return z, z.clone(), z.clone()
-        u = self.net_u(xd)[0].reshape(-1).contiguous() if n > 0 else None
+        u = self._physics_u(xd, mode) if n > 0 else None
         xh = uh = None
         if halo is not None:
             xh = torch.as_tensor(halo[0], dtype=torch.float32).reshape(8).to(dev).contiguous()
             uh = torch.as_tensor(halo[1], dtype=torch.float32).reshape(1).to(dev).contiguous()
+            if mode != "full":
+                xh, uh = xh.detach(), uh.detach()
+        if mode:
+            self._lambdas()
+            lams = [getattr(self, nm) for nm in _EULER_LAMBDAS]
+            if any(t is not None and t.requires_grad for t in [xd, u, xh, uh] + lams):
+                return _EulerFunction.apply(self, x_scal, xd, u, xh, uh, *lams)
         out = torch.empty(3, n, device=dev, dtype=torch.float32)
         rc = self._lib.pinn_net_f_t(_ptr(xd), _ptr(u), _ptr(xh), _ptr(uh), ctypes.byref(self._affine(x_scal)), _ptr(self._lambdas()), n,
                                     _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream())
