@@ -260,7 +260,8 @@ int pinn_mlp_train_grads(const pinn_net_t* net, const float* d_params, const flo
                          float* d_grads, double* d_loss, void* d_work, size_t work_bytes, void* stream);
 
 /* The same call restricted to a subset of its kernel launches, so a benchmark can bracket one
- * kernel with events (bench.py's roofline leg).  phases = PINN_PHASE_ALL is pinn_mlp_train_grads. */
+ * kernel with events (bench.py's roofline leg).  phases = PINN_PHASE_ALL is pinn_mlp_train_grads.  Calls that together cover
+ * every phase, in dependency order and on one workspace, give PINN_PHASE_ALL's result bit for bit. */
 #define PINN_PHASE_CHAIN 1u   /* forward + loss + backward chain kernel (writes the activation stash) */
 #define PINN_PHASE_WGRAD 2u   /* the per-layer weight-gradient kernels (read the stash)              */
 #define PINN_PHASE_REDUCE 4u  /* fixed-order slab reduction -> d_grads, d_loss                       */

@@ -669,6 +669,7 @@ namespace pinn {
 int launch_train_chain_x6(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
                           long long n_global, const DropDev& drop, const TrainBuffers& b, unsigned which, int* grid_out,
                           void* stream);   // pinn_x6_train.hip; which: 1 = forward kernel, 2 = backward kernel, 3 = both
+int train_chain_x6_partials(const pinn_net_t* net, long long n_rows);     // pinn_x6_train.hip: the loss partials its forward writes
 int launch_train_chain_wide(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
                             long long n_global, const DropDev& drop, const TrainBuffers& b, int* grid_out, void* stream);  // pinn_wide.hip
 int launch_train_bf16(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
@@ -792,8 +793,7 @@ static int train_grads_impl(const pinn_net_t* net, const float* d_params, const 
       const long long t4 = w.t16 / 4;
       grid = (int)(t4 < 1024 ? (t4 < 1 ? 1 : t4) : 1024);
     } else {
-      const long long nt = (n_rows + 127) / 128;
-      grid = (int)(nt < cu_count() ? nt : cu_count());
+      grid = train_chain_x6_partials(net, n_rows);      // (64-row and quarter tiles write 2x / 4x the 128-row tiles' partials)
     }
   } else if (phases & PINN_PHASE_CHAIN) {
     const bool bits = a.drop.mode == PINN_DROP_BITS;

@@ -572,7 +572,47 @@ void launch_pack_x6(const pinn_net_t* net, const float* d_params, hipStream_t st
 
 }  // namespace x6
 
-// chain phase of pinn_mlp_train_grads for PINN_PREC_F32X6; *grid_out = workgroups (= loss partials)
+namespace x6 {
+// the kernels launch_train_chain_x6 picks for n_rows rows, and so the number of loss partials its forward kernel writes (one per
+// workgroup): the one place that decides it, for the chain's own call and for a reduction issued in a call of its own
+struct ChainPlan {
+  bool small_n;       // 4-wave kernels on 64-row tiles (else 8 waves on 128-row tiles)
+  bool quarters;      // train_fwd_small_kernel: 32-row tiles over four waves (backward on the 64-row tiles)
+  int grid;           // workgroups of the backward kernel (and of the forward unless quarters)
+  int grid_fwd;       // workgroups of the forward kernel = loss partials
+};
+static ChainPlan plan_chain(const pinn_net_t* net, long long n_rows) {
+  const int cus = cu_count_cached();
+  // the stash is padded to whole 128-row tiles: the 64-row kernel covers them too (two tiles each)
+  const long long t128 = (n_rows + 127) / 128;
+#ifdef PINN_DEBUG_HOOKS
+  static const bool force8 = getenv("PINN_X6_WAVES8") != nullptr;     // measurement builds only: always the 8-wave kernels
+#else
+  constexpr bool force8 = false;
+#endif
+  ChainPlan c{};
+  c.small_n = !force8 && 2 * t128 <= cus;           // 64-row tiles still fit one per CU
+  const long long n_tiles = c.small_n ? 2 * t128 : t128;
+  c.grid = (int)(n_tiles < cus ? n_tiles : cus);
+  // small row counts (at most one 32-row tile per CU, H = 256, packed stash): a row tile over four waves
+  // (train_fwd_small_kernel), 32 rows per workgroup
+#ifdef PINN_DEBUG_HOOKS
+  static const bool no_small = getenv("PINN_X6_NOSMALL") != nullptr;  // measurement builds only: the one-wave-per-tile kernels at every size
+#else
+  constexpr bool no_small = false;
+#endif
+  // (one round of workgroups only: at 1e4 rows the 313 32-row tiles need two rounds and lose to the 157 64-row ones, 57 against 46 us)
+  c.quarters = !no_small && c.small_n && net->precision == PINN_PREC_F32X6 && net->hidden == 256 && 4 * t128 <= cus;
+  const long long t32 = 4 * t128;
+  c.grid_fwd = c.quarters ? (int)(t32 < cus ? t32 : cus) : c.grid;
+  return c;
+}
+}  // namespace x6
+
+// loss partials of launch_train_chain_x6's forward kernel for n_rows rows (the count a reduction in another call must sum)
+int train_chain_x6_partials(const pinn_net_t* net, long long n_rows) { return x6::plan_chain(net, n_rows).grid_fwd; }
+
+// chain phase of pinn_mlp_train_grads for PINN_PREC_F32X6; *grid_out = forward workgroups (= loss partials)
 int launch_train_chain_x6(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
                           long long n_global, const DropDev& drop, const TrainBuffers& b, unsigned which, int* grid_out, void* stream) {
   using namespace x6;
@@ -583,34 +623,14 @@ int launch_train_chain_x6(const pinn_net_t* net, const float* d_params, const fl
   TrainArgsX a{};
   a.params = d_params; a.x = d_x; a.y = d_y; a.n_rows = n_rows; a.n_global = n_global; a.H = net->hidden; a.nh = net->n_hidden;
   a.drop = drop; a.b = b;
-  const int cus = cu_count_cached();
-  // the stash is padded to whole 128-row tiles: the 64-row kernel covers them too (two tiles each)
-  const long long t128 = (n_rows + 127) / 128;
-#ifdef PINN_DEBUG_HOOKS
-  static const bool force8 = getenv("PINN_X6_WAVES8") != nullptr;     // measurement builds only: always the 8-wave kernels
-#else
-  constexpr bool force8 = false;
-#endif
-  const bool small_n = !force8 && 2 * t128 <= cus;           // 64-row tiles still fit one per CU
-  const long long n_tiles = small_n ? 2 * t128 : t128;
-  const int grid = (int)(n_tiles < cus ? n_tiles : cus);
-  *grid_out = grid;
+  const ChainPlan c = plan_chain(net, n_rows);
+  const bool small_n = c.small_n;
+  const int grid = c.grid;
+  *grid_out = c.grid_fwd;
   const __bf16* packed = (const __bf16*)net->d_packed;
   const bool bits = drop.mode == PINN_DROP_BITS;
-  // small row counts (at most one 32-row tile per CU, H = 256, packed stash): a row tile over four waves
-  // (train_fwd_small_kernel), 32 rows per workgroup
-#ifdef PINN_DEBUG_HOOKS
-  static const bool no_small = getenv("PINN_X6_NOSMALL") != nullptr;  // measurement builds only: the one-wave-per-tile kernels at every size
-#else
-  constexpr bool no_small = false;
-#endif
-  // (one round of workgroups only: at 1e4 rows the 313 32-row tiles need two rounds and lose to the 157 64-row ones, 57 against 46 us)
-  const bool quarters = !no_small && small_n && fast_bwd && net->hidden == 256 && 4 * t128 <= cus;
-  if (quarters) {
-    const long long t32 = 4 * t128;
-    const int grid32 = (int)(t32 < cus ? t32 : cus);
-    *grid_out = grid32;                                                // loss partials: one per forward workgroup
-    if (run_fwd) hipLaunchKernelGGL((train_fwd_small_kernel<256>), dim3(grid32), dim3(kSmallThreads), 0, st, a, packed);
+  if (c.quarters) {
+    if (run_fwd) hipLaunchKernelGGL((train_fwd_small_kernel<256>), dim3(c.grid_fwd), dim3(kSmallThreads), 0, st, a, packed);
     if (!fwd_only) {
       if (!run_fwd) { hipError_t em = hipMemsetAsync(b.amax, 0, sizeof(unsigned), st); if (em != hipSuccess) return (int)em; }
       hipLaunchKernelGGL((train_bwd_kernel<X3, 256, 4>), dim3(grid), dim3(256), 0, st, a, packed);
