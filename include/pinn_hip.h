@@ -367,6 +367,20 @@ int pinn_gnet_backward(const pinn_gnet_t* net, const float* d_params, const floa
                        const pinn_dropout_t* drop, const float* d_gu, const float* d_glv, float* d_grads, float* d_gx,
                        void* d_work, size_t work_bytes, void* stream);
 
+/* Double backward of pinn_gnet_forward: the gradient of S = <v, dL/dx> = sum_r sum_i d_vx[r][i] * d_gx[r][i], where d_gx is what
+ * pinn_gnet_backward returns for (d_gu, d_glv), with respect to the parameters, x, g_u and g_lv (torch autograd's backward of a
+ * backward taken under create_graph=True, through dL/dx only).  Recomputes the forward and its tangent along v with `drop`, the
+ * struct the forward used.  d_vx [n_rows, 8] is required; d_glv NULL: zero.  Each output may be NULL and is then not computed:
+ * d_grads [pinn_gnet_param_count] = dS/dtheta, raw sums over the rows, overwritten, padding zero (state_dict layout; the
+ * predict bias entry is exactly 0); d_gx [n_rows, 8] = dS/dx; d_ggu, d_gglv [n_rows] = dS/dg_u, dS/dg_lv.
+ * n_rows == 0: nothing runs but d_grads (if given) is zeroed.  Workspace: pinn_gnet_backward2_workspace_bytes(net, n_rows)
+ * (0 for an unsupported net).  Deterministic like pinn_gnet_backward: a row's d_gx, d_ggu, d_gglv do not depend on its tile,
+ * chunk or neighbours. */
+size_t pinn_gnet_backward2_workspace_bytes(const pinn_gnet_t* net, long long n_rows);
+int pinn_gnet_backward2(const pinn_gnet_t* net, const float* d_params, const float* d_x, long long n_rows,
+                        const pinn_dropout_t* drop, const float* d_gu, const float* d_glv, const float* d_vx,
+                        float* d_grads, float* d_gx, float* d_ggu, float* d_gglv, void* d_work, size_t work_bytes, void* stream);
+
 /* ---- results assembly: create_comprehensive_results_array_v2 (01:1877-2010) -----------------------------------
  * Fills d_out = float64 [n_rows, 22] row-major (the `comprehensive_results` layout scripts 02-05 read):
  *   0-7 inputs and 8 target, de-normalised like sklearn's inverse_transform on float32 (aff->x_*, aff->y_*; 01:1916-1917);

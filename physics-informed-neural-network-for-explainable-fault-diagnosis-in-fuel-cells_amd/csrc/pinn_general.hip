@@ -13,6 +13,7 @@
 //   dx_kernel           dL/dx = W_0^T dpre_0 per row (the backward's input gradient)
 //   vec_grad_kernel     the two 1-row tensors (predict, last variance layer) of the gradient, per slice
 //   reduce / finalize   fixed-order slab sums -> the flat gradient (state_dict layout); loss sums in fp64
+//   gemm2_kernel, head2_kernel, vec_grad2_kernel   the double backward (pinn_gnet_backward2): see the section below
 //   mc_moments_kernel   MC-dropout: (pass, row) pairs are virtual rows; per row, in pass order, the Welford moments of pinn_mc_dropout
 //
 // Widths are padded to 32 inside the workspace only (zero weights, zero activations); the flat parameter buffer holds exactly the
@@ -110,6 +111,24 @@ static size_t take(size_t& at, size_t bytes) { const size_t o = at; at = (at + b
 
 static long long n_chunks(long long n, long long r) { return (n + r - 1) / r; }
 
+// weight-gradient slices of a chunk of `rows` rows: enough tiles to fill the chip, at most kSlabBudget of partial slabs, >= 128 rows each
+static void slice_plan(const Shape& s, long long rows, long long* slice_rows, int* slices) {
+  long long tiles = 1;
+  for (int t = 0; t < s.n_mat; ++t)
+    if (s.is_gemm(t)) {
+      const long long tt = rup(s.out[t], 64) / 64 * (rup(s.in[t] + 1, 64) / 64);
+      if (tt > tiles) tiles = tt;
+    }
+  long long sl = (2048 + tiles - 1) / tiles;
+  const long long by_rows = rows / 128 > 1 ? rows / 128 : 1;
+  const long long by_mem = (long long)(kSlabBudget / (4 * (size_t)s.gtotal)) > 1 ? (long long)(kSlabBudget / (4 * (size_t)s.gtotal)) : 1;
+  if (sl > by_rows) sl = by_rows;
+  if (sl > by_mem) sl = by_mem;
+  if (sl < 1) sl = 1;
+  *slice_rows = rup((rows + sl - 1) / sl, kBK);
+  *slices = (int)((rows + *slice_rows - 1) / *slice_rows);
+}
+
 // training: every activation of a chunk is kept for the backward pass
 static Layout train_layout(const Shape& s, long long n_rows) {
   Layout L{};
@@ -119,21 +138,7 @@ static Layout train_layout(const Shape& s, long long n_rows) {
   cap = cap < 64 ? 64 : (cap > kMaxChunkRows ? kMaxChunkRows : cap);
   L.rows = rup(n_rows < 1 ? 1 : n_rows, 64);
   if (L.rows > cap) L.rows = cap;
-  // weight-gradient slices: enough tiles to fill the chip, at most kSlabBudget of partial slabs, >= 128 rows each
-  long long tiles = 1;
-  for (int t = 0; t < s.n_mat; ++t)
-    if (s.is_gemm(t)) {
-      const long long tt = rup(s.out[t], 64) / 64 * (rup(s.in[t] + 1, 64) / 64);
-      if (tt > tiles) tiles = tt;
-    }
-  long long sl = (2048 + tiles - 1) / tiles;
-  const long long by_rows = L.rows / 128 > 1 ? L.rows / 128 : 1;
-  const long long by_mem = (long long)(kSlabBudget / (4 * (size_t)s.gtotal)) > 1 ? (long long)(kSlabBudget / (4 * (size_t)s.gtotal)) : 1;
-  if (sl > by_rows) sl = by_rows;
-  if (sl > by_mem) sl = by_mem;
-  if (sl < 1) sl = 1;
-  L.slice_rows = rup((L.rows + sl - 1) / sl, kBK);
-  L.slices = (int)((L.rows + L.slice_rows - 1) / L.slice_rows);
+  slice_plan(s, L.rows, &L.slice_rows, &L.slices);
   size_t at = 0;
   L.pack = take(at, 4 * (size_t)s.pack_total);
   for (int t = 0; t < s.n_mat; ++t) if (s.is_gemm(t)) L.act[act_index(s, t)] = take(at, 4 * (size_t)L.rows * s.mp[t]);
@@ -269,7 +274,7 @@ __device__ __forceinline__ void store_kc(float* s, const f32x4 (&r)[2], int tid)
 }
 // MN-contiguous source: element (m, k) at p[k * ld + m], 4 consecutive m per float4
 __device__ __forceinline__ void load_mc(f32x4 (&r)[2], const float* __restrict__ p, long long ld, long long m0, long long k0,
-                                        long long mv, long long kv, int tid, int ones_col) {
+                                        long long mv, long long kv, int tid, int ones_col, float one = 1.0f) {
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const long long k = k0 + (tid >> 4) + 16 * q, m = m0 + (tid & 15) * 4;
@@ -278,7 +283,7 @@ __device__ __forceinline__ void load_mc(f32x4 (&r)[2], const float* __restrict__
     if (ones_col >= 0) {          // columns >= the layer's real input width: the bias column (1 on valid rows), then zeros
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if (m + e >= ones_col) v[e] = (m + e == ones_col && k < kv) ? 1.0f : 0.0f;
+        if (m + e >= ones_col) v[e] = (m + e == ones_col && k < kv) ? one : 0.0f;
     }
     r[q] = v;
   }
@@ -943,6 +948,501 @@ static int run_train(const Shape& s, const float* d_params, const float* d_x, co
   return last_error();
 }
 
+// ---------------------------------------------------------------------------------------
+// double backward (pinn_gnet_backward2): the gradient of S = <v, dL/dx> with respect to g_u, g_lv, x and the parameters.
+//
+// Every matrix product has one weight operand for two activation streams, so each layer is one launch of a dual-accumulator
+// variant of gemm_kernel: one weight tile and two activation tiles in LDS, two accumulator sets, a paired epilogue.
+//   gemm2_kernel<kFwd>   [z ; zd] = W [a_in ; ad_in];  h = tanh z, a = c h, ad = c (1 - h^2) zd   (primal a bitwise gemm_kernel<kFwd>'s)
+//   gemm2_kernel<kBwd>   [abar ; adbar] = W^T [p ; q] (+ w_p g_u on adbar);  q_in = c (1 - h^2) adbar (bitwise the first backward's
+//                        dpre), p_in = c (1 - h^2) abar - 2 h adbar ad
+//   gemm2_kernel<kWgrad> slab[s][o][i] = sum_{r in slice s} p[r][o] a[r][i] + q[r][o] ad[r][i]; the bias column sums p alone
+//   head2_kernel         z, zd, f', f'', ud, lvd; q_v2, p_v2; the (p, q) pair below the variance head's second tanh
+//   vec_grad2_kernel     the two one-row tensors per slice: w_p (g_u^T ad_k, bias 0), w_v2 (q_v2^T ad_v1 + p_v2^T a_v1, bias sum p_v2)
+// dS/dx = W_0^T p_0 is dx_kernel on p_0; slab sums and the flat gradient are reduce_kernel / finalize_kernel.
+// ---------------------------------------------------------------------------------------
+struct Gemm2Args {
+  const float* A; long long lda; long long a_mv, a_kv;        // FWD / BWD: packed weights; WGRAD: p
+  const float* A2;                                            // WGRAD: q (same extents as A)
+  const float* B; const float* B2; long long ldb; long long b_mv, b_kv;    // primal / tangent stream (BWD: p / q)
+  long long M, K;
+  float* out; float* out2; long long ldo;
+  long long n_valid;
+  // FWD
+  const float* bias; int bias_n; int module; int map_rows; long long row0, n_rows;
+  Drop drop;
+  unsigned* keep; int keep_off;
+  // BWD
+  const float* stash; const float* stash2; long long ld_stash; int stash_module;
+  const float* wp; const float* du; int wp_n;
+  const unsigned* keep_in;
+  // WGRAD
+  long long slice_rows; float* slab; long long slab_stride; long long reg; int out_real, in_real;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256) void gemm2_kernel(Gemm2Args a) {
+  __shared__ __attribute__((aligned(16))) float As[64 * kLd];
+  __shared__ __attribute__((aligned(16))) float Bs[64 * kLd];
+  __shared__ __attribute__((aligned(16))) float Cs[64 * kLd];     // FWD / BWD: the second activation tile; WGRAD: unused
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, li = lane & 15;
+  const int wm = wave & 1, wn = wave >> 1;
+  const long long m0 = (long long)blockIdx.y * 64, n0 = (long long)blockIdx.x * 64;
+
+  f32x4 acc[2][2], acd[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      acd[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (MODE == kFwd) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long long m = m0 + 32 * wm + 16 * i + 4 * kq + r;
+          acc[i][j][r] = m < a.bias_n ? a.bias[m] : 0.0f;
+        }
+      }
+      if (MODE == kBwd && a.wp) {
+        const long long n = n0 + 32 * wn + 16 * j + li;
+        const float du = a.du[n];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long long m = m0 + 32 * wm + 16 * i + 4 * kq + r;
+          acd[i][j][r] = (m < a.wp_n ? a.wp[m] : 0.0f) * du;
+        }
+      }
+    }
+
+  if (MODE == kWgrad) {
+    // one reduction over twice the rows: the slice's rows of (p, a), then the same rows of (q, ad), into one accumulator set
+    const long long kbeg = (long long)blockIdx.z * a.slice_rows;
+    long long kend = kbeg + a.slice_rows;
+    if (kend > a.K) kend = a.K;
+    const long long len = kend > kbeg ? (kend - kbeg + kBK - 1) / kBK : 0;      // K slabs per stream
+    f32x4 ra[2], rb[2];
+    auto load = [&](long long it) {
+      const int s2 = it >= len;
+      const long long k0 = kbeg + (it - (s2 ? len : 0)) * kBK;
+      load_mc(ra, s2 ? a.A2 : a.A, a.lda, m0, k0, a.a_mv, a.a_kv, tid, -1);
+      load_mc(rb, s2 ? a.B2 : a.B, a.ldb, n0, k0, a.b_mv, a.b_kv, tid, a.in_real, s2 ? 0.0f : 1.0f);
+    };
+    if (len > 0) load(0);
+    for (long long it = 0; it < 2 * len; ++it) {
+      __syncthreads();
+      store_mc(As, ra, tid); store_mc(Bs, rb, tid);
+      __syncthreads();
+      if (it + 1 < 2 * len) load(it + 1);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        f32x4 fa[2], fb[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) fa[i] = *reinterpret_cast<const f32x4*>(As + (32 * wm + 16 * i + li) * kLd + 16 * h + 4 * kq);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const f32x4*>(Bs + (32 * wn + 16 * j + li) * kLd + 16 * h + 4 * kq);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][r], fb[j][r], acc[i][j], 0, 0, 0);
+      }
+    }
+    float* dst = a.slab + (long long)blockIdx.z * a.slab_stride + a.reg;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long long o = m0 + 32 * wm + 16 * i + 4 * kq + r, c = n0 + 32 * wn + 16 * j + li;
+          if (o < a.out_real && c <= a.in_real) dst[o * (a.in_real + 1) + c] = acc[i][j][r];
+        }
+    return;
+  }
+
+  // FWD / BWD: B rows of the input layer are rows of x (and of v): chunk row n -> row0 + n
+  auto load_b = [&](f32x4 (&r)[2], const float* __restrict__ p, long long k0) {
+    if (MODE == kFwd && a.map_rows) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const long long n = n0 + (tid >> 3) + 32 * q, k = k0 + (tid & 7) * 4;
+        r[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (n < a.n_valid && k < a.b_kv) r[q] = *reinterpret_cast<const f32x4*>(p + (a.row0 + n) * a.ldb + k);
+      }
+    } else {
+      load_kc(r, p, a.ldb, n0, k0, a.b_mv, a.b_kv, tid);
+    }
+  };
+  f32x4 ra[2], rb[2], rc[2];
+  if (a.K > 0) { load_kc(ra, a.A, a.lda, m0, 0, a.a_mv, a.a_kv, tid); load_b(rb, a.B, 0); load_b(rc, a.B2, 0); }
+  for (long long k = 0; k < a.K; k += kBK) {
+    __syncthreads();
+    store_kc(As, ra, tid); store_kc(Bs, rb, tid); store_kc(Cs, rc, tid);
+    __syncthreads();
+    if (k + kBK < a.K) { load_kc(ra, a.A, a.lda, m0, k + kBK, a.a_mv, a.a_kv, tid); load_b(rb, a.B, k + kBK); load_b(rc, a.B2, k + kBK); }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      f32x4 fa[2], fb[2], fc[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) fa[i] = *reinterpret_cast<const f32x4*>(As + (32 * wm + 16 * i + li) * kLd + 16 * h + 4 * kq);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        fb[j] = *reinterpret_cast<const f32x4*>(Bs + (32 * wn + 16 * j + li) * kLd + 16 * h + 4 * kq);
+        fc[j] = *reinterpret_cast<const f32x4*>(Cs + (32 * wn + 16 * j + li) * kLd + 16 * h + 4 * kq);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][r], fb[j][r], acc[i][j], 0, 0, 0);
+            acd[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][r], fc[j][r], acd[i][j], 0, 0, 0);
+          }
+    }
+  }
+
+  const long long mw = m0 + 32 * wm;
+  const int P = (int)(mw >> 5);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const long long n = n0 + 32 * wn + 16 * j + li;
+    const bool valid = n < a.n_valid;
+    if (MODE == kFwd) {
+      // the keep word: gemm_kernel<kFwd>'s expressions (same Philox counter, key and bit order)
+      const long long lrow = a.row0 + n;
+      const bool on = a.module >= 0 && a.drop.mode != PINN_DROP_NONE;
+      const unsigned thr = a.module >= 0 ? a.drop.thr[a.module] : 0u;
+      const float scale = on ? a.drop.scale[a.module] : 1.0f;
+      unsigned mine = 0;
+      if (on && a.drop.mode == PINN_DROP_PHILOX) {
+        const unsigned long long g = (unsigned long long)(a.drop.row_offset + lrow);
+        unsigned o[4];
+        philox4x32_10((unsigned)g, (unsigned)(g >> 32), ((unsigned)a.module << 16) | ((unsigned)P << 2) | (unsigned)kq, a.drop.stream,
+                      a.drop.seed_lo, a.drop.seed_hi, o);
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int idx = 4 * b + r;
+            const unsigned draw = (o[idx >> 1] >> (16 * (idx & 1))) & 0xFFFFu;
+            mine |= (draw >= thr ? 1u : 0u) << (16 * b + 4 * kq + r);
+          }
+      }
+      mine |= __shfl_xor(mine, 16, 64);
+      mine |= __shfl_xor(mine, 32, 64);
+      unsigned word = 0xFFFFFFFFu;
+      if (on && a.drop.mode == PINN_DROP_PHILOX) word = mine;
+      if (on && a.drop.mode == PINN_DROP_BITS && valid) word = a.drop.bits[lrow * a.drop.words + a.keep_off + P];
+      if (mw < a.M) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          f32x4 v, vd;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float t = tanh_f32(acc[i][j][r]);
+            const bool kept = (word >> (16 * i + 4 * kq + r)) & 1u;
+            v[r] = kept ? t * scale : 0.0f;
+            vd[r] = (kept && valid) ? acd[i][j][r] * (scale * (1.0f - t * t)) : 0.0f;
+          }
+          *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = v;
+          *reinterpret_cast<f32x4*>(a.out2 + n * a.ldo + mw + 16 * i + 4 * kq) = vd;
+        }
+        if (a.module >= 0 && kq == 0) a.keep[n * a.drop.words + a.keep_off + P] = word;
+      }
+    } else {      // kBwd
+      if (mw < a.M) {
+        const bool on = a.drop.mode != PINN_DROP_NONE && a.stash_module >= 0;
+        const float scale = on ? a.drop.scale[a.stash_module] : 1.0f, inv_scale = 1.0f / scale;
+        const unsigned word = a.stash_module >= 0 ? a.keep_in[n * a.drop.words + a.keep_off + P] : 0xFFFFFFFFu;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const f32x4 h = *reinterpret_cast<const f32x4*>(a.stash + n * a.ld_stash + mw + 16 * i + 4 * kq);
+          const f32x4 hd = *reinterpret_cast<const f32x4*>(a.stash2 + n * a.ld_stash + mw + 16 * i + 4 * kq);
+          f32x4 vp, vq;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float t = h[r] * inv_scale;
+            const float d = scale * (1.0f - t * t);
+            const float gq = acd[i][j][r] * d;                                   // the first backward's dpre, bit for bit
+            const float gp = acc[i][j][r] * d - 2.0f * t * acd[i][j][r] * hd[r];
+            const bool kept = valid && ((word >> (16 * i + 4 * kq + r)) & 1u);
+            vq[r] = kept ? gq : 0.0f;
+            vp[r] = kept ? gp : 0.0f;
+          }
+          *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = vp;
+          *reinterpret_cast<f32x4*>(a.out2 + n * a.ldo + mw + 16 * i + 4 * kq) = vq;
+        }
+      }
+    }
+  }
+}
+
+// per row (16 lanes): z, zd, f'(z), f''(z); ud = w_p . ad_k, lvd = f' zd (the gradients of S with respect to g_u, g_lv);
+// q_v2 = g_lv f', p_v2 = g_lv f'' zd, and the (p, q) pair below the variance head's second tanh (no dropout there: c = 1)
+struct Head2Args {
+  const float* hd; long long ldh; int hk;                   // tangent of the last hidden activation
+  const float* v2; const float* v2d; long long ldv; int hv2;
+  const float* wp; const float* wv2; const float* bv2;
+  long long n_valid, row0;
+  const float* gu; const float* glv;
+  float* ggu; float* gglv;                                  // outputs at row0 + r (NULL: not written)
+  float* du; float* qz; float* pz;                          // chunk buffers: g_u, q_v2, p_v2
+  float* dp; float* dq; long long ld_dpre; int wd;
+};
+__global__ __launch_bounds__(256) void head2_kernel(Head2Args a) {
+  const int g = threadIdx.x & 15;
+  const long long r = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const float* hrow = a.hd + r * a.ldh;
+  const float* vrow = a.v2 + r * a.ldv;
+  const float* vdrow = a.v2d + r * a.ldv;
+  float su = 0.f, sz = 0.f, sd = 0.f;
+  for (int f = g; f < a.hk; f += 16) su = fmaf(a.wp[f], hrow[f], su);
+  for (int f = g; f < a.hv2; f += 16) { sz = fmaf(a.wv2[f], vrow[f], sz); sd = fmaf(a.wv2[f], vdrow[f], sd); }
+  const float ud = sum16(su);
+  const float z = sum16(sz) + a.bv2[0];
+  const float zd = sum16(sd);
+  const bool valid = r < a.n_valid;
+  float du = 0.f, qz = 0.f, pz = 0.f;
+  if (valid) {
+    const float var = softplus_f32(z) + 1e-6f;
+    const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
+    const float f1 = sig / var;
+    const float f2 = sig * (1.0f - sig) / var - f1 * f1;
+    du = a.gu[a.row0 + r];
+    if (a.glv) {
+      const float glv = a.glv[a.row0 + r];
+      qz = glv * sig / var;               // pinn_gnet_backward's dz
+      pz = glv * f2 * zd;
+    }
+    if (g == 0) {
+      if (a.ggu) a.ggu[a.row0 + r] = ud;
+      if (a.gglv) a.gglv[a.row0 + r] = f1 * zd;
+    }
+  }
+  if (g == 0) { a.du[r] = du; a.qz[r] = qz; a.pz[r] = pz; }
+  float* prow = a.dp + r * a.ld_dpre;
+  float* qrow = a.dq + r * a.ld_dpre;
+  for (int f = g; f < a.wd; f += 16) {
+    float vp = 0.f, vq = 0.f;
+    if (f < a.hv2 && valid) {
+      const float v = vrow[f], w = a.wv2[f];
+      vq = w * qz * (1.0f - v * v);
+      vp = (w * pz) * (1.0f - v * v) - 2.0f * v * (w * qz) * vdrow[f];
+    }
+    prow[f] = vp;
+    qrow[f] = vq;
+  }
+}
+
+struct Vec2Args {
+  const float* hd; long long ldh; int hk;
+  const float* v2; const float* v2d; long long ldv; int hv2;
+  const float* du; const float* qz; const float* pz;
+  long long K, slice_rows;
+  float* slab; long long slab_stride, reg_p, reg_v2;
+};
+__global__ __launch_bounds__(256) void vec_grad2_kernel(Vec2Args a) {
+  const int c = blockIdx.y * 256 + threadIdx.x;
+  const long long r0 = (long long)blockIdx.x * a.slice_rows;
+  long long r1 = r0 + a.slice_rows;
+  if (r1 > a.K) r1 = a.K;
+  float* dst = a.slab + (long long)blockIdx.x * a.slab_stride;
+  if (c <= a.hk) {
+    float s = 0.f;
+    if (c < a.hk)
+      for (long long r = r0; r < r1; ++r) s = fmaf(a.du[r], a.hd[r * a.ldh + c], s);
+    dst[a.reg_p + c] = s;                  // c == hk: dS/db_p = 0 exactly
+  } else if (c - (a.hk + 1) <= a.hv2) {
+    const int j = c - (a.hk + 1);
+    float s = 0.f;
+    for (long long r = r0; r < r1; ++r) {
+      if (j < a.hv2) s = fmaf(a.pz[r], a.v2[r * a.ldv + j], fmaf(a.qz[r], a.v2d[r * a.ldv + j], s));
+      else s += a.pz[r];
+    }
+    dst[a.reg_v2 + j] = s;
+  }
+}
+
+// the double backward keeps a primal and a tangent activation per layer and two (p, q) ping-pong pairs: about twice
+// train_layout's bytes per row, so about half its chunk
+struct Layout2 {
+  long long rows; int slices; long long slice_rows;
+  size_t pack, act[kMaxHidden + 2], tan[kMaxHidden + 2], keep, dp[2], dq[2], du, qz, pz, slabs, acc, end;
+};
+static Layout2 backward2_layout(const Shape& s, long long n_rows) {
+  Layout2 L{};
+  long long per_row = s.words + 4LL * s.max_wp + 3;
+  for (int t = 0; t < s.n_mat; ++t) if (s.is_gemm(t)) per_row += 2LL * s.mp[t];
+  long long cap = (long long)(kTrainBudget / (4 * (size_t)per_row)) / 64 * 64;
+  cap = cap < 64 ? 64 : (cap > kMaxChunkRows ? kMaxChunkRows : cap);
+  L.rows = rup(n_rows < 1 ? 1 : n_rows, 64);
+  if (L.rows > cap) L.rows = cap;
+  slice_plan(s, L.rows, &L.slice_rows, &L.slices);
+  size_t at = 0;
+  L.pack = take(at, 4 * (size_t)s.pack_total);
+  for (int t = 0; t < s.n_mat; ++t)
+    if (s.is_gemm(t)) {
+      L.act[act_index(s, t)] = take(at, 4 * (size_t)L.rows * s.mp[t]);
+      L.tan[act_index(s, t)] = take(at, 4 * (size_t)L.rows * s.mp[t]);
+    }
+  L.keep = take(at, 4 * (size_t)L.rows * s.words);
+  for (int b = 0; b < 2; ++b) {
+    L.dp[b] = take(at, 4 * (size_t)L.rows * s.max_wp);
+    L.dq[b] = take(at, 4 * (size_t)L.rows * s.max_wp);
+  }
+  L.du = take(at, 4 * (size_t)L.rows);
+  L.qz = take(at, 4 * (size_t)L.rows);
+  L.pz = take(at, 4 * (size_t)L.rows);
+  L.slabs = take(at, 4 * (size_t)L.slices * s.gtotal);
+  L.acc = take(at, 4 * (size_t)s.gtotal);
+  L.end = at;
+  return L;
+}
+
+struct Second { const float* gu; const float* glv; const float* vx; float* grads; float* gx; float* ggu; float* gglv; };
+
+static int run_backward2(const Shape& s, const float* d_params, const float* d_x, long long n_rows, const Drop& d, const Second& o,
+                         void* d_work, size_t work_bytes, hipStream_t st) {
+  const Layout2 L = backward2_layout(s, n_rows);
+  if (!d_work || !al16(d_work)) return PINN_E_ARG;
+  if (work_bytes < L.end) return PINN_E_WORKSPACE;
+  char* base = (char*)d_work;
+  const float* pack = (const float*)(base + L.pack);
+  int rc = launch_pack(s, d_params, (float*)(base + L.pack), st);
+  if (rc) return rc;
+  float* act[kMaxMat]; float* tan[kMaxMat];
+  for (int t = 0; t < s.n_mat; ++t) {
+    act[t] = s.is_gemm(t) ? (float*)(base + L.act[act_index(s, t)]) : nullptr;
+    tan[t] = s.is_gemm(t) ? (float*)(base + L.tan[act_index(s, t)]) : nullptr;
+  }
+  unsigned* keep = (unsigned*)(base + L.keep);
+  float* dp[2] = {(float*)(base + L.dp[0]), (float*)(base + L.dp[1])};
+  float* dq[2] = {(float*)(base + L.dq[0]), (float*)(base + L.dq[1])};
+  float* du = (float*)(base + L.du);
+  float* qz = (float*)(base + L.qz);
+  float* pz = (float*)(base + L.pz);
+  float* slabs = (float*)(base + L.slabs);
+  float* acc = (float*)(base + L.acc);
+  const int v0m = s.mat_v0(), v1m = s.mat_v1();
+  const bool want_w = o.grads != nullptr, want_back = want_w || o.gx;
+  const dim3 blk(256);
+
+  auto wgrad2 = [&](int t, const float* p, const float* q, const float* a_in, const float* ad_in, long long ld_in, long long nv) {
+    Gemm2Args g{};
+    g.A = p; g.A2 = q; g.lda = s.max_wp; g.a_mv = s.mp[t]; g.a_kv = nv;
+    g.B = a_in; g.B2 = ad_in; g.ldb = ld_in; g.b_mv = ld_in; g.b_kv = nv;
+    g.K = L.rows; g.n_valid = nv;
+    g.slice_rows = L.slice_rows; g.slab = slabs; g.slab_stride = s.gtotal; g.reg = s.reg[t];
+    g.out_real = s.out[t]; g.in_real = s.in[t];
+    g.module = -1; g.stash_module = -1;
+    const dim3 grid((unsigned)((s.in[t] + 1 + 63) / 64), (unsigned)((s.out[t] + 63) / 64), (unsigned)L.slices);
+    hipLaunchKernelGGL(gemm2_kernel<kWgrad>, grid, blk, 0, st, g);
+  };
+  // (p, q) of the layer feeding matrix t, from (p, q) of matrix t and the stored (a, ad) of that layer
+  auto bwd2 = [&](int t, int from, int to, int src, int module, const float* wp, long long nv) {
+    Gemm2Args g{};
+    g.A = pack + s.pt[t]; g.lda = s.mp[t]; g.a_mv = s.kp[t]; g.a_kv = s.mp[t];
+    g.B = dp[from]; g.B2 = dq[from]; g.ldb = s.max_wp; g.b_mv = L.rows; g.b_kv = s.mp[t];
+    g.M = s.kp[t]; g.K = s.mp[t];
+    g.out = dp[to]; g.out2 = dq[to]; g.ldo = s.max_wp;
+    g.n_valid = nv;
+    g.drop = d;
+    g.module = -1;
+    g.stash = act[src]; g.stash2 = tan[src]; g.ld_stash = s.mp[src]; g.stash_module = module;
+    g.keep_in = keep; g.keep_off = s.word_off[module];
+    g.wp = wp; g.du = du; g.wp_n = wp ? s.hk : 0;
+    const dim3 grid((unsigned)(L.rows / 64), (unsigned)((s.kp[t] + 63) / 64));
+    hipLaunchKernelGGL(gemm2_kernel<kBwd>, grid, blk, 0, st, g);
+  };
+
+  const long long nch = n_chunks(n_rows, L.rows);
+  for (long long ch = 0; ch < nch; ++ch) {
+    const long long row0 = ch * L.rows;
+    const long long nv = n_rows - row0 < L.rows ? n_rows - row0 : L.rows;
+    const float* x = d_x + row0 * 8;
+    const float* vx = o.vx + row0 * 8;
+    for (int step = 0; step < s.k + 2; ++step) {       // tangent forward: hidden layers, variance head 0 and 1
+      const int t = step < s.k ? step : (step == s.k ? v0m : v1m);
+      const int src = t == 0 ? -1 : (t < s.k ? t - 1 : (t == v0m ? s.k - 1 : v0m));
+      Gemm2Args g{};
+      g.A = pack + s.pf[t]; g.lda = s.kp[t]; g.a_mv = s.mp[t]; g.a_kv = s.kp[t];
+      g.B = src < 0 ? d_x : act[src]; g.B2 = src < 0 ? o.vx : tan[src];
+      g.ldb = src < 0 ? 8 : s.mp[src]; g.b_mv = L.rows; g.b_kv = t == 0 ? 8 : s.kp[t];
+      g.M = s.mp[t]; g.K = s.kp[t];
+      g.out = act[t]; g.out2 = tan[t]; g.ldo = s.mp[t];
+      g.n_valid = nv;
+      g.bias = d_params + s.boff[t]; g.bias_n = s.out[t];
+      g.module = t < s.k ? t : (t == v0m ? s.k : -1);
+      g.map_rows = t == 0;
+      g.row0 = row0; g.n_rows = n_rows;
+      g.drop = d;
+      g.keep = keep;
+      g.keep_off = g.module >= 0 ? s.word_off[g.module] : 0;
+      g.stash_module = -1;
+      const dim3 grid((unsigned)(L.rows / 64), (unsigned)((s.mp[t] + 63) / 64));
+      hipLaunchKernelGGL(gemm2_kernel<kFwd>, grid, blk, 0, st, g);
+    }
+    {
+      Head2Args h{};
+      h.hd = tan[s.k - 1]; h.ldh = s.mp[s.k - 1]; h.hk = s.hk;
+      h.v2 = act[v1m]; h.v2d = tan[v1m]; h.ldv = s.mp[v1m]; h.hv2 = s.hv2;
+      h.wp = d_params + s.woff[s.mat_pred()]; h.wv2 = d_params + s.woff[s.mat_v2()]; h.bv2 = d_params + s.boff[s.mat_v2()];
+      h.n_valid = nv; h.row0 = row0;
+      h.gu = o.gu; h.glv = o.glv; h.ggu = o.ggu; h.gglv = o.gglv;
+      h.du = du; h.qz = qz; h.pz = pz; h.dp = dp[0]; h.dq = dq[0]; h.ld_dpre = s.max_wp; h.wd = s.mp[v1m];
+      hipLaunchKernelGGL(head2_kernel, dim3((unsigned)(L.rows / 16)), blk, 0, st, h);
+    }
+    if (want_back) {
+      // variance head layer 1, then layer 0 (+ the predict head on the q stream), then the hidden layers top-down
+      if (want_w) wgrad2(v1m, dp[0], dq[0], act[v0m], tan[v0m], s.mp[v0m], nv);
+      bwd2(v1m, 0, 1, v0m, s.k, nullptr, nv);
+      if (want_w) {
+        wgrad2(v0m, dp[1], dq[1], act[s.k - 1], tan[s.k - 1], s.mp[s.k - 1], nv);
+        Vec2Args va{};
+        va.hd = tan[s.k - 1]; va.ldh = s.mp[s.k - 1]; va.hk = s.hk;
+        va.v2 = act[v1m]; va.v2d = tan[v1m]; va.ldv = s.mp[v1m]; va.hv2 = s.hv2;
+        va.du = du; va.qz = qz; va.pz = pz; va.K = L.rows; va.slice_rows = L.slice_rows;
+        va.slab = slabs; va.slab_stride = s.gtotal; va.reg_p = s.reg[s.mat_pred()]; va.reg_v2 = s.reg[s.mat_v2()];
+        const int cols = s.hk + 1 + s.hv2 + 1;
+        hipLaunchKernelGGL(vec_grad2_kernel, dim3((unsigned)L.slices, (unsigned)((cols + 255) / 256)), blk, 0, st, va);
+      }
+      bwd2(v0m, 1, 0, s.k - 1, s.k - 1, d_params + s.woff[s.mat_pred()], nv);
+      int cur = 0;
+      for (int l = s.k - 1; l >= 0; --l) {
+        if (want_w) {
+          if (l == 0) wgrad2(0, dp[cur], dq[cur], x, vx, 8, nv);
+          else wgrad2(l, dp[cur], dq[cur], act[l - 1], tan[l - 1], s.mp[l - 1], nv);
+        }
+        if (l > 0) {
+          bwd2(l, cur, cur ^ 1, l - 1, l - 1, nullptr, nv);
+          cur ^= 1;
+        }
+      }
+      if (o.gx)        // dS/dx = W_0^T p_0
+        hipLaunchKernelGGL(dx_kernel, dim3((unsigned)(L.rows / 16)), blk, 0, st, d_params + s.woff[0], s.w[0], (const float*)dp[cur],
+                           (long long)s.max_wp, nv, row0, o.gx);
+      if (want_w) {
+        long long gx = (s.gtotal + 255) / 256;
+        if (gx > 4096) gx = 4096;
+        hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)gx), blk, 0, st, (const float*)slabs, L.slices, s.gtotal, acc, ch == 0 ? 1 : 0);
+      }
+    }
+    rc = last_error();
+    if (rc) return rc;
+  }
+  if (want_w) {
+    FinArgs f{};
+    f.acc = acc; f.grads = o.grads; f.total = s.total; f.n_mat = s.n_mat;
+    for (int t = 0; t < s.n_mat; ++t) { f.woff[t] = s.woff[t]; f.boff[t] = s.boff[t]; f.reg[t] = s.reg[t]; f.out[t] = s.out[t]; f.in[t] = s.in[t]; }
+    long long gx = (s.total + 255) / 256;
+    if (gx > 4096) gx = 4096;
+    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)gx), blk, 0, st, f);
+  }
+  return last_error();
+}
+
 }  // namespace gen
 }  // namespace pinn
 
@@ -1035,4 +1535,32 @@ extern "C" int pinn_gnet_backward(const pinn_gnet_t* net, const float* d_params,
   (void)hipGetLastError();
   const Upstream up{d_gu, d_glv, d_gx};
   return run_train(s, d_params, d_x, nullptr, n_rows, n_rows, d, &up, d_grads, nullptr, d_work, work_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t pinn_gnet_backward2_workspace_bytes(const pinn_gnet_t* net, long long n_rows) {
+  Shape s;
+  if (make_shape(net, &s) || n_rows < 0) return 0;
+  return backward2_layout(s, n_rows).end;
+}
+
+extern "C" int pinn_gnet_backward2(const pinn_gnet_t* net, const float* d_params, const float* d_x, long long n_rows,
+                                   const pinn_dropout_t* drop, const float* d_gu, const float* d_glv, const float* d_vx, float* d_grads,
+                                   float* d_gx, float* d_ggu, float* d_gglv, void* d_work, size_t work_bytes, void* stream) {
+  Shape s;
+  int rc = make_shape(net, &s);
+  if (rc) return rc;
+  if (n_rows < 0 || !d_params || !al16(d_params) || (d_grads && !al16(d_grads))) return PINN_E_ARG;
+  if (n_rows == 0) {
+    if (!d_grads) return PINN_OK;
+    (void)hipGetLastError();
+    const hipError_t e = hipMemsetAsync(d_grads, 0, sizeof(float) * (size_t)s.total, (hipStream_t)stream);
+    return e == hipSuccess ? PINN_OK : (int)e;
+  }
+  if (!d_x || !al16(d_x) || !d_gu || !d_vx || !al16(d_vx) || (d_gx && !al16(d_gx))) return PINN_E_ARG;
+  Drop d;
+  rc = convert(s, drop, &d);
+  if (rc) return rc;
+  (void)hipGetLastError();
+  const Second o{d_gu, d_glv, d_vx, d_grads, d_gx, d_ggu, d_gglv};
+  return run_backward2(s, d_params, d_x, n_rows, d, o, d_work, work_bytes, (hipStream_t)stream);
 }

@@ -19,7 +19,8 @@ data-parallel training with one all-reduce(SUM) of the flat gradient per step),
 fused / wide kernels; "general": ANY layers list `layout.check_general` accepts -- unequal widths, widths 1..2048 -- on the
 exact-fp32 layer-by-layer kernels of csrc/pinn_general.hip, precision "fp32" only), and `autograd` (False, default: DNN
 outputs carry no grad_fn; True: they are differentiable under torch autograd with respect to the inputs and the 14 weight and
-bias tensors -- see DNN.forward), and `physics_autograd` (False, default: the physics functions return plain tensors; "lambdas":
+bias tensors -- see DNN.forward; "double": also twice differentiable through dL/dx, so that a loss may contain
+`torch.autograd.grad(u.sum(), x, create_graph=True)[0]` -- see DNN.autograd), and `physics_autograd` (False, default: the physics functions return plain tensors; "lambdas":
 differentiable with respect to the physics parameters, the reference's own graph; "full": also with respect to X, halo rows and,
 through the DNN output, the weights -- see PhysicsInformedNN.physics_autograd).
 """
@@ -83,28 +84,91 @@ class _DNNFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_u, g_lv):
         if torch.is_grad_enabled():
-            raise RuntimeError("pinn_amd.DNN is once-differentiable under autograd: create_graph=True (double backward) is not supported")
+            if ctx.dnn._autograd != "double":
+                raise RuntimeError("pinn_amd.DNN is once-differentiable under autograd: create_graph=True (double backward) is not supported")
+            x, *params = ctx.saved_tensors
+            out = _DNNGradFunction.apply(ctx.dnn, ctx.drop, ctx.keep, ctx.needs_input_grad[2], g_u, g_lv, x, *params)
+            return (None, None) + tuple(out)
         return _DNNFunction._vjp(ctx, g_u, g_lv)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def _vjp(ctx, g_u, g_lv):
         x, *params = ctx.saved_tensors               # torch's version check: an in-place change since the forward raises here
+        return (None, None) + _dnn_vjp(ctx.dnn, ctx.drop, ctx.needs_input_grad[2], g_u, g_lv, x)
+
+
+def _dnn_vjp(dnn, drop, want_gx, g_u, g_lv, x):
+    """The pinn_gnet_backward call of the DNN node -> (dL/dx or None, every parameter's gradient as views of one fresh flat buffer)."""
+    n = x.shape[0]
+    total = dnn._flat.numel()
+    grads = (torch.zeros if n == 0 else torch.empty)(total, dtype=torch.float32, device=x.device)
+    gx = torch.zeros(n, 8, dtype=torch.float32, device=x.device) if want_gx else None
+    if n > 0:
+        gu = _as_rows(g_u, n) if g_u is not None else torch.zeros(n, dtype=torch.float32, device=x.device)
+        glv = _as_rows(g_lv, n) if dnn.logvar else None
+        gnet, work = dnn._backward_net(n)
+        rc = dnn._lib.pinn_gnet_backward(ctypes.byref(gnet), _ptr(dnn._flat), _ptr(x), n,
+                                         ctypes.byref(drop) if drop is not None else None, _ptr(gu), _ptr(glv),
+                                         _ptr(grads), _ptr(gx), _ptr(work), work.numel(), _stream())
+        _lib.check(rc, "pinn_gnet_backward")
+    pg = [grads[off:off + nel].view(shape) for _, _, off, nel, shape in dnn._views]
+    return (gx,) + tuple(pg)
+
+
+class _DNNGradFunction(torch.autograd.Function):
+    """The backward of _DNNFunction as an autograd node of its own (autograd="double", backward taken under create_graph=True):
+    the forward is the same pinn_gnet_backward call; the backward is pinn_gnet_backward2 (csrc/pinn_general.hip), the gradient of
+    <v, dL/dx> with respect to g_u, g_lv, x and the parameters for the cotangent v that arrives on dL/dx.  Second order goes
+    through dL/dx only: a cotangent on a parameter gradient (a Hessian-vector product in the weights) raises."""
+
+    @staticmethod
+    def forward(ctx, dnn, drop, keep, want_gx, g_u, g_lv, x, *params):
+        ctx.dnn, ctx.drop, ctx.keep = dnn, drop, keep
+        ctx.have = (g_u is not None, g_lv is not None)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*([t for t in (g_u, g_lv) if t is not None] + [x] + list(params)))
+        return _dnn_vjp(dnn, drop, want_gx, g_u, g_lv, x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v_x, *v_params):
+        if any(v is not None for v in v_params):
+            raise RuntimeError("pinn_amd.DNN autograd='double' differentiates twice through dL/dx only: a gradient flowing back into a "
+                               "parameter gradient (a Hessian-vector product with respect to the weights) is not supported")
+        saved = list(ctx.saved_tensors)              # torch's version check, as in the first backward
+        g_u = saved.pop(0) if ctx.have[0] else None
+        g_lv = saved.pop(0) if ctx.have[1] else None
+        x, params = saved[0], saved[1:]
+        none = (None,) * (7 + len(params))
+        if v_x is None:
+            return none
         dnn = ctx.dnn
         n = x.shape[0]
-        total = dnn._flat.numel()
-        grads = (torch.zeros if n == 0 else torch.empty)(total, dtype=torch.float32, device=x.device)
-        gx = torch.zeros(n, 8, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[2] else None
-        if n > 0:
-            gu = _as_rows(g_u, n) if g_u is not None else torch.zeros(n, dtype=torch.float32, device=x.device)
-            glv = _as_rows(g_lv, n) if dnn.logvar else None
-            gnet, work = dnn._backward_net(n)
-            rc = dnn._lib.pinn_gnet_backward(ctypes.byref(gnet), _ptr(dnn._flat), _ptr(x), n,
-                                             ctypes.byref(ctx.drop) if ctx.drop is not None else None, _ptr(gu), _ptr(glv),
-                                             _ptr(grads), _ptr(gx), _ptr(work), work.numel(), _stream())
-            _lib.check(rc, "pinn_gnet_backward")
-        pg = [grads[off:off + nel].view(shape) for _, _, off, nel, shape in dnn._views]
-        return (None, None, gx) + tuple(pg)
+        dev = x.device
+        need = ctx.needs_input_grad
+        want_gu = g_u is not None and need[4]
+        want_glv = g_lv is not None and dnn.logvar and need[5]
+        want_w = any(need[7:])
+        if n == 0:
+            return (None,) * 4 + (torch.zeros_like(g_u) if want_gu else None, torch.zeros_like(g_lv) if want_glv else None,
+                                  torch.zeros_like(x) if need[6] else None) + tuple(torch.zeros_like(p) if w else None
+                                                                                    for p, w in zip(params, need[7:]))
+        grads = torch.empty(dnn._flat.numel(), dtype=torch.float32, device=dev) if want_w else None
+        gx = torch.empty(n, 8, dtype=torch.float32, device=dev) if need[6] else None
+        ggu = torch.empty(n, dtype=torch.float32, device=dev) if want_gu else None
+        gglv = torch.empty(n, dtype=torch.float32, device=dev) if want_glv else None
+        gu = _as_rows(g_u, n) if g_u is not None else torch.zeros(n, dtype=torch.float32, device=dev)
+        glv = _as_rows(g_lv, n) if dnn.logvar else None
+        vx = v_x.detach().to(torch.float32).contiguous()
+        gnet, work = dnn._backward2_net(n)
+        rc = dnn._lib.pinn_gnet_backward2(ctypes.byref(gnet), _ptr(dnn._flat), _ptr(x), n,
+                                          ctypes.byref(ctx.drop) if ctx.drop is not None else None, _ptr(gu), _ptr(glv), _ptr(vx),
+                                          _ptr(grads), _ptr(gx), _ptr(ggu), _ptr(gglv), _ptr(work), work.numel(), _stream())
+        _lib.check(rc, "pinn_gnet_backward2")
+        pg = tuple(grads[off:off + nel].view(shape) if w else None
+                   for (_, _, off, nel, shape), w in zip(dnn._views, need[7:]))
+        return (None,) * 4 + (ggu.view_as(g_u) if want_gu else None, gglv.view_as(g_lv) if want_glv else None, gx) + pg
 
 
 PHYSICS_AUTOGRAD_MODES = (False, "lambdas", "full")
@@ -244,7 +308,8 @@ class DNN(torch.nn.Module):
     def __init__(self, p, logvar, layers, seed=0, precision=None, kernels="auto", autograd=False):
         """kernels="auto": the shapes layout.check_arch accepts, precision None = "f32x6".  kernels="general": any list
         layout.check_general accepts (exact-fp32 layer-by-layer kernels, csrc/pinn_general.hip); precision None or "fp32".
-        autograd=True: outputs are differentiable under torch autograd (see forward); not with precision "bf16"."""
+        autograd=True: outputs are differentiable under torch autograd (see forward); "double": twice, through dL/dx (see the
+        `autograd` property); neither with precision "bf16"."""
         super().__init__()
         self._autograd = False
         self.depth = len(layers) - 1
@@ -259,6 +324,7 @@ class DNN(torch.nn.Module):
         self._packed = None
         self._gwork = None
         self._bwork = None
+        self._b2work = None
         if kernels == "general":
             self.widths = layout.check_general(layers)
             if precision not in (None, "fp32"):
@@ -323,14 +389,21 @@ class DNN(torch.nn.Module):
 
     @property
     def autograd(self):
-        """True: forward is differentiable under torch autograd (weights and inputs).  Settable; raises ValueError for "bf16" nets."""
+        """True: forward is differentiable under torch autograd (weights and inputs), once.  "double": also twice, through dL/dx: a
+        backward taken under create_graph=True returns a dL/dx that losses can contain (pinn_gnet_backward2).  Returns what was
+        set.  Settable; raises ValueError for "bf16" nets and for any other string."""
         return self._autograd
 
     @autograd.setter
     def autograd(self, on):
-        on = bool(on)
+        if isinstance(on, str):
+            if on != "double":
+                raise ValueError("autograd must be False, True or 'double' (got %r)" % (on,))
+        else:
+            on = bool(on)
         if on and self.precision == "bf16":
-            raise ValueError("autograd=True needs an fp32-accurate forward: precision 'bf16' is not (use 'f32x6', 'f32x6g6' or 'fp32')")
+            raise ValueError("autograd=%r needs an fp32-accurate forward: precision 'bf16' is not (use 'f32x6', 'f32x6g6' or 'fp32')"
+                             % (on,))
         self._autograd = on
 
     def set_precision(self, precision):
@@ -427,6 +500,17 @@ class DNN(torch.nn.Module):
             self._bwork = torch.empty(nb, dtype=torch.uint8, device=self._flat.device)
         return self._bwd_gnet, self._bwork
 
+    def _backward2_net(self, n_rows):
+        """(pinn_gnet_t, workspace) of pinn_gnet_backward2 for n_rows rows: the net of _backward_net, a workspace of its own."""
+        gnet = self._gnet if self.kernels == "general" else self._bwd_gnet
+        nb = self._lib.pinn_gnet_backward2_workspace_bytes(ctypes.byref(gnet), int(n_rows))
+        if nb == 0:
+            raise _lib.PinnError("pinn_gnet_backward2_workspace_bytes rejected the network")
+        if self._b2work is None or self._b2work.numel() < nb:
+            self._b2work = None
+            self._b2work = torch.empty(nb, dtype=torch.uint8, device=self._flat.device)
+        return gnet, self._b2work
+
     def inject_masks(self, bits):
         """Replay recorded keep-masks (tests only). bits: int32 [n_passes, N, words] or None."""
         self._mask_bits = None if bits is None else bits.to(self._flat.device).contiguous()
@@ -439,7 +523,9 @@ class DNN(torch.nn.Module):
         same kernel call (bit-identical outputs), and a backward (pinn_gnet_backward) that recomputes the forward with the masks
         this call drew and returns dL/dx and every parameter's gradient.  The backward is exact fp32 for every kernel family; on
         "f32x6" / "f32x6g6" nets it is the gradient of the exact-fp32 function at the same parameters and masks, which agrees with
-        the gradient of the split-operand forward to fp32 accuracy.  Once-differentiable (create_graph=True raises).  logvar=False:
+        the gradient of the split-operand forward to fp32 accuracy.  Once-differentiable (create_graph=True raises) unless `autograd` is "double": then a backward under create_graph=True is
+        the same pinn_gnet_backward call recorded as a node whose backward is pinn_gnet_backward2 (exact fp32, same masks), for
+        cotangents on dL/dx only; a third derivative, or a cotangent on a parameter gradient, raises.  logvar=False:
         the logvar output is a constant zero."""
         params = [getattr(mod, pname) for mod, pname, _, _, _ in self._views]
         if self._autograd and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
@@ -486,7 +572,7 @@ class PhysicsInformedNN():
                  precision=None, kernels="auto", autograd=False, physics_autograd=False):
         """kernels="general" runs any layers list layout.check_general accepts on the exact-fp32 layer-by-layer kernels
         (precision None or "fp32"); such nets train launch by launch (use_graph is ignored) and, data-parallel, with one
-        blocking all-reduce of the whole gradient per step (no two-part overlap).  autograd=True: see DNN.forward (passed to
+        blocking all-reduce of the whole gradient per step (no two-part overlap).  autograd=True / "double": see DNN.forward (passed to
         the DNN; `model.dnn.autograd` is settable).  physics_autograd: see the `physics_autograd` property.  The library's
         trainers use neither."""
         dev = _device()
