@@ -5,16 +5,16 @@
 // tiled GEMM on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain: exact fp32) with the layer's elementwise work fused into its
 // epilogue, and activations go through HBM in caller-provided workspace, one bounded row chunk at a time.
 //
-//   gemm_kernel<kFwd>   act_out^T[f][r] = tanh(b[f] + sum_k W[f][k] act_in[r][k]), then dropout (Philox or injected bits)
-//   gemm_kernel<kBwd>   dpre_in[r][i] = (sum_o W[o][i] dpre_out[r][o] (+ w_p[i] du[r])) * scale * keep * (1 - a^2)
-//   gemm_kernel<kWgrad> slab[s][o][i] = sum_{r in slice s} dpre_out[r][o] act_in[r][i]; column i = n_in is the bias (a ones column)
-//   heads_kernel        predict dot, variance-head dot, softplus / log, per-row dL/du, dL/dz, loss partials, d pre_v2
-//                       (kHeadGrad: dL/du, dL/dlogvar given by the caller -- the backward of torch autograd)
-//   dx_kernel           dL/dx = W_0^T dpre_0 per row (the backward's input gradient)
-//   vec_grad_kernel     the two 1-row tensors (predict, last variance layer) of the gradient, per slice
-//   reduce / finalize   fixed-order slab sums -> the flat gradient (state_dict layout); loss sums in fp64
-//   gemm2_kernel, head2_kernel, vec_grad2_kernel   the double backward (pinn_gnet_backward2): see the section below
-//   mc_moments_kernel   MC-dropout: (pass, row) pairs are virtual rows; per row, in pass order, the Welford moments of pinn_mc_dropout
+//   gemm_kernel<kFwd, 1>   act_out^T[f][r] = tanh(b[f] + sum_k W[f][k] act_in[r][k]), then dropout (Philox or injected bits)
+//   gemm_kernel<kBwd, 1>   dpre_in[r][i] = (sum_o W[o][i] dpre_out[r][o] (+ w_p[i] du[r])) * scale * keep * (1 - a^2)
+//   gemm_kernel<kWgrad, 1> slab[s][o][i] = sum_{r in slice s} dpre_out[r][o] act_in[r][i]; column i = n_in is the bias (a ones column)
+//   heads_kernel           predict dot, variance-head dot, softplus / log, per-row dL/du, dL/dz, loss partials, d pre_v2
+//                          (kHeadGrad: dL/du, dL/dlogvar given by the caller -- the backward of torch autograd)
+//   dx_kernel              dL/dx = W_0^T dpre_0 per row (the backward's input gradient)
+//   vec_grad_kernel        the two 1-row tensors (predict, last variance layer) of the gradient, per slice
+//   reduce / finalize      fixed-order slab sums -> the flat gradient (state_dict layout); loss sums in fp64
+//   gemm_kernel<., 2>, head2_kernel, vec_grad2_kernel   the double backward (pinn_gnet_backward2): see the section below
+//   mc_moments_kernel      MC-dropout: (pass, row) pairs are virtual rows; per row, in pass order, the Welford moments of pinn_mc_dropout
 //
 // Widths are padded to 32 inside the workspace only (zero weights, zero activations); the flat parameter buffer holds exactly the
 // reference's tensors.  Determinism: no floating-point atomics; every output element's K order is fixed by the layer alone (the
@@ -104,7 +104,8 @@ static int act_index(const Shape& s, int t) { return t < s.k ? t : (t == s.mat_v
 struct Layout {
   long long rows;              // rows (virtual rows) per chunk
   int slices; long long slice_rows;
-  size_t pack, act[kMaxHidden + 2], keep, dpre[2], du, dz, slabs, acc, loss, ubuf, lvbuf, state, end;
+  // [stream]: 0 = the primal activations / p, 1 = the double backward's tangent activations / q.  Inference: act[0][0..2] ping-pong
+  size_t pack, act[2][kMaxHidden + 2], keep, dpre[2][2], du, dz, pz, slabs, acc, loss, ubuf, lvbuf, state, end;
 };
 
 static size_t take(size_t& at, size_t bytes) { const size_t o = at; at = (at + bytes + 255) / 256 * 256; return o; }
@@ -129,11 +130,13 @@ static void slice_plan(const Shape& s, long long rows, long long* slice_rows, in
   *slices = (int)((rows + *slice_rows - 1) / *slice_rows);
 }
 
-// training: every activation of a chunk is kept for the backward pass
-static Layout train_layout(const Shape& s, long long n_rows) {
+// training: every activation of a chunk is kept for the backward pass.  ns = 1: pinn_gnet_train_grads / pinn_gnet_backward (with the
+// loss partials).  ns = 2: the double backward keeps a primal and a tangent activation per layer, two (p, q) ping-pong pairs and a third
+// per-row scalar (du = g_u, dz = q_v2, pz = p_v2): about twice the bytes per row, so about half the chunk
+static Layout train_layout(const Shape& s, long long n_rows, int ns) {
   Layout L{};
-  long long per_row = s.words + 2LL * s.max_wp + 2;
-  for (int t = 0; t < s.n_mat; ++t) if (s.is_gemm(t)) per_row += s.mp[t];
+  long long per_row = s.words + 2LL * ns * s.max_wp + ns + 1;
+  for (int t = 0; t < s.n_mat; ++t) if (s.is_gemm(t)) per_row += (long long)ns * s.mp[t];
   long long cap = (long long)(kTrainBudget / (4 * (size_t)per_row)) / 64 * 64;
   cap = cap < 64 ? 64 : (cap > kMaxChunkRows ? kMaxChunkRows : cap);
   L.rows = rup(n_rows < 1 ? 1 : n_rows, 64);
@@ -141,15 +144,18 @@ static Layout train_layout(const Shape& s, long long n_rows) {
   slice_plan(s, L.rows, &L.slice_rows, &L.slices);
   size_t at = 0;
   L.pack = take(at, 4 * (size_t)s.pack_total);
-  for (int t = 0; t < s.n_mat; ++t) if (s.is_gemm(t)) L.act[act_index(s, t)] = take(at, 4 * (size_t)L.rows * s.mp[t]);
+  for (int t = 0; t < s.n_mat; ++t)
+    if (s.is_gemm(t))
+      for (int q = 0; q < ns; ++q) L.act[q][act_index(s, t)] = take(at, 4 * (size_t)L.rows * s.mp[t]);
   L.keep = take(at, 4 * (size_t)L.rows * s.words);
-  L.dpre[0] = take(at, 4 * (size_t)L.rows * s.max_wp);
-  L.dpre[1] = take(at, 4 * (size_t)L.rows * s.max_wp);
+  for (int b = 0; b < 2; ++b)
+    for (int q = 0; q < ns; ++q) L.dpre[q][b] = take(at, 4 * (size_t)L.rows * s.max_wp);
   L.du = take(at, 4 * (size_t)L.rows);
   L.dz = take(at, 4 * (size_t)L.rows);
+  if (ns == 2) L.pz = take(at, 4 * (size_t)L.rows);
   L.slabs = take(at, 4 * (size_t)L.slices * s.gtotal);
   L.acc = take(at, 4 * (size_t)s.gtotal);
-  L.loss = take(at, 8 * 8 * (size_t)(n_chunks(n_rows, L.rows) * (L.rows / 16)));
+  if (ns == 1) L.loss = take(at, 8 * 8 * (size_t)(n_chunks(n_rows, L.rows) * (L.rows / 16)));
   L.end = at;
   return L;
 }
@@ -165,9 +171,9 @@ static Layout infer_layout(const Shape& s, long long n_rows, int n_passes) {
   if (L.rows > cap) L.rows = cap;
   size_t at = 0;
   L.pack = take(at, 4 * (size_t)s.pack_total);
-  L.act[0] = take(at, 4 * (size_t)L.rows * s.max_wp);
-  L.act[1] = take(at, 4 * (size_t)L.rows * s.max_wp);
-  L.act[2] = take(at, 4 * (size_t)L.rows * s.max_wp);
+  L.act[0][0] = take(at, 4 * (size_t)L.rows * s.max_wp);
+  L.act[0][1] = take(at, 4 * (size_t)L.rows * s.max_wp);
+  L.act[0][2] = take(at, 4 * (size_t)L.rows * s.max_wp);
   L.ubuf = take(at, 4 * (size_t)L.rows);
   L.lvbuf = take(at, 4 * (size_t)L.rows);
   L.state = take(at, 4 * 4 * (size_t)(n_passes > 0 ? n_rows : 0));
@@ -236,6 +242,10 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
 // the layer GEMM: 64 x 64 output tile per 256-thread workgroup, 32 x 32 per wave (2 x 2 MFMA blocks), K slabs of 32.
 // FWD / BWD: M = features (A: packed weights, K-contiguous), N = rows (B: activations [row][k], K-contiguous).
 // WGRAD:     M = output features (A: d pre-activations [row][o]), N = input features (B: activations [row][i]), K = rows.
+// One kernel for one activation stream (NS = 1: forward, MC-dropout, the first-order backward) and for two that share the weight
+// operand (NS = 2, the double backward: primal / tangent activations in FWD, the (p, q) pair in BWD and WGRAD; expressions in the
+// double-backward section below).  FWD / BWD with NS = 2 hold one weight tile and two activation tiles in LDS and two accumulator
+// sets; WGRAD is one reduction over the rows of stream 0 and then of stream 1 into one accumulator set.
 // ---------------------------------------------------------------------------------------
 struct GemmArgs {
   const float* A; long long lda; long long a_mv, a_kv;
@@ -246,7 +256,7 @@ struct GemmArgs {
   // FWD
   const float* bias; int bias_n; int module;   // dropout module of the output (-1: tanh only)
   int map_rows;                  // B rows are input rows: chunk row n -> row0 + n (MC: virtual row -> row % n_rows)
-  int mc;
+  int mc;                        // virtual rows (pass, row) of MC-dropout; NS = 1 only
   long long row0, n_rows;
   Drop drop;
   unsigned* keep; int keep_off;  // keep words [row][drop.words] (training), module word offset
@@ -256,6 +266,8 @@ struct GemmArgs {
   const unsigned* keep_in;
   // WGRAD
   long long slice_rows; float* slab; long long slab_stride; long long reg; int out_real, in_real;
+  // the second stream (NS = 2; same strides and extents as the first): WGRAD q; the tangent input / BWD q; their outputs; the kept tangent
+  const float* A2; const float* B2; float* out2; const float* stash2;
 };
 
 // one 64 x 32 operand tile: K-contiguous source (row m, 4 consecutive k per float4)
@@ -297,9 +309,11 @@ __device__ __forceinline__ void store_mc(float* s, const f32x4 (&r)[2], int tid)
   }
 }
 
-// row context of chunk row n in FWD: input row (for x and the Philox / bit-mask keys) and pass (-1: MC eval pass, dropout off)
+// row context of chunk row n in FWD: input row (for x and the Philox / bit-mask keys) and pass (-1: MC eval pass, dropout off).
+// MC virtual rows come with one stream only
+template <int NS>
 __device__ __forceinline__ void row_ctx(const GemmArgs& a, long long n, long long& lrow, int& pass) {
-  if (a.mc) {
+  if (NS == 1 && a.mc) {
     const long long v = a.row0 + n;
     const long long q = v / a.n_rows;
     lrow = v - q * a.n_rows;
@@ -310,91 +324,149 @@ __device__ __forceinline__ void row_ctx(const GemmArgs& a, long long n, long lon
   }
 }
 
-template <int MODE>
+// The keep word of the FWD output module for input row lrow (valid: the chunk row exists) in pass `pass`, feature group P (32
+// features): bit 16 i + 4 kq + r keeps feature 32 P + 16 i + 4 kq + r.  Every pass over a row -- forward, MC-dropout, the first- and
+// the second-order backward's recomputing forwards -- takes its masks from here, so they cannot disagree about them.
+// on = the module drops in this pass.  Philox: lane quarter kq draws its own 8 bits (counter = global row, key word = module, P, kq;
+// stream + pass) and the four quarters of a row are OR-ed by two shuffles, so all 64 lanes of the wave must call.
+__device__ __forceinline__ unsigned keep_word(const GemmArgs& a, bool on, long long lrow, int pass, bool valid, int P, int kq) {
+  const unsigned thr = a.module >= 0 ? a.drop.thr[a.module] : 0u;
+  unsigned mine = 0;
+  if (on && a.drop.mode == PINN_DROP_PHILOX) {
+    const unsigned long long g = (unsigned long long)(a.drop.row_offset + lrow);
+    unsigned o[4];
+    philox4x32_10((unsigned)g, (unsigned)(g >> 32), ((unsigned)a.module << 16) | ((unsigned)P << 2) | (unsigned)kq,
+                  a.drop.stream + (unsigned)pass, a.drop.seed_lo, a.drop.seed_hi, o);
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int idx = 4 * b + r;
+        const unsigned draw = (o[idx >> 1] >> (16 * (idx & 1))) & 0xFFFFu;
+        mine |= (draw >= thr ? 1u : 0u) << (16 * b + 4 * kq + r);
+      }
+  }
+  mine |= __shfl_xor(mine, 16, 64);
+  mine |= __shfl_xor(mine, 32, 64);
+  unsigned word = 0xFFFFFFFFu;
+  if (on && a.drop.mode == PINN_DROP_PHILOX) word = mine;
+  if (on && a.drop.mode == PINN_DROP_BITS && valid)
+    word = a.drop.bits[((long long)pass * a.n_rows + lrow) * a.drop.words + a.keep_off + P];
+  return word;
+}
+
+template <int MODE, int NS>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
+  constexpr int NB = MODE == kWgrad ? 1 : NS;      // activation tiles in LDS and accumulator sets
   __shared__ __attribute__((aligned(16))) float As[64 * kLd];
-  __shared__ __attribute__((aligned(16))) float Bs[64 * kLd];
+  __shared__ __attribute__((aligned(16))) float Bs[NB][64 * kLd];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, li = lane & 15;
   const int wm = wave & 1, wn = wave >> 1;
   const long long m0 = (long long)blockIdx.y * 64, n0 = (long long)blockIdx.x * 64;
-  long long kbeg = 0, kend = a.K;
+  long long kbeg = 0, kend = a.K, span = 0;
   if (MODE == kWgrad) {
     kbeg = (long long)blockIdx.z * a.slice_rows;
     kend = kbeg + a.slice_rows;
     if (kend > a.K) kend = a.K;
+    if (NS == 2) {               // the slice's rows of (p, a) at k in [kbeg, kbeg + span), then the same rows of (q, ad);
+                                 // slice_rows and K are multiples of kBK, so span is whole K slabs
+      span = kend - kbeg;
+      kend += span;
+    }
   }
 
-  f32x4 acc[2][2];
+  // NS = 2: acc[0] is the primal pre-activation (FWD) / abar, which becomes p (BWD); acc[1] the tangent / adbar, which becomes q
+  f32x4 acc[NB][2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < NB; ++s) acc[s][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (MODE == kFwd) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const long long m = m0 + 32 * wm + 16 * i + 4 * kq + r;
-          acc[i][j][r] = m < a.bias_n ? a.bias[m] : 0.0f;
+          acc[0][i][j][r] = m < a.bias_n ? a.bias[m] : 0.0f;
         }
       }
-      if (MODE == kBwd && a.wp) {
+      if (MODE == kBwd && a.wp) {       // the predict head joins the stream of the first-order chain
         const long long n = n0 + 32 * wn + 16 * j + li;
         const float du = a.du[n];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const long long m = m0 + 32 * wm + 16 * i + 4 * kq + r;
-          acc[i][j][r] = (m < a.wp_n ? a.wp[m] : 0.0f) * du;
+          acc[NB - 1][i][j][r] = (m < a.wp_n ? a.wp[m] : 0.0f) * du;
         }
       }
     }
 
-  // B rows of the FWD input layer are input rows (x), possibly virtual (MC)
-  auto load_b = [&](f32x4 (&r)[2], long long k0) {
+  // WGRAD with NS = 2: the K slabs from kbeg + span on belong to the second stream (its bias column is 0), rows k0 - span
+  auto second = [&](long long k0) { return MODE == kWgrad && NS == 2 && k0 >= kbeg + span; };
+  // B rows of the FWD input layer are input rows (x, and v for the tangent), possibly virtual (MC)
+  auto load_b = [&](f32x4 (&r)[2], const float* __restrict__ p, long long k0) {
     if (MODE == kWgrad) {
-      load_mc(r, a.B, a.ldb, n0, k0, a.b_mv, a.b_kv, tid, a.in_real);
+      const bool s2 = second(k0);
+      load_mc(r, s2 ? a.B2 : a.B, a.ldb, n0, s2 ? k0 - span : k0, a.b_mv, a.b_kv, tid, a.in_real, s2 ? 0.0f : 1.0f);
     } else if (MODE == kFwd && a.map_rows) {
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const long long n = n0 + (tid >> 3) + 32 * q, k = k0 + (tid & 7) * 4;
         long long lrow; int pass;
-        row_ctx(a, n, lrow, pass);
+        row_ctx<NS>(a, n, lrow, pass);
         r[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (n < a.n_valid && k < a.b_kv) r[q] = *reinterpret_cast<const f32x4*>(a.B + lrow * a.ldb + k);
+        if (n < a.n_valid && k < a.b_kv) r[q] = *reinterpret_cast<const f32x4*>(p + lrow * a.ldb + k);
       }
     } else {
-      load_kc(r, a.B, a.ldb, n0, k0, a.b_mv, a.b_kv, tid);
+      load_kc(r, p, a.ldb, n0, k0, a.b_mv, a.b_kv, tid);
     }
   };
   auto load_a = [&](f32x4 (&r)[2], long long k0) {
-    if (MODE == kWgrad) load_mc(r, a.A, a.lda, m0, k0, a.a_mv, a.a_kv, tid, -1);
+    const bool s2 = second(k0);
+    if (MODE == kWgrad) load_mc(r, s2 ? a.A2 : a.A, a.lda, m0, s2 ? k0 - span : k0, a.a_mv, a.a_kv, tid, -1);
     else load_kc(r, a.A, a.lda, m0, k0, a.a_mv, a.a_kv, tid);
   };
-
-  f32x4 ra[2], rb[2];
-  if (kbeg < kend) { load_a(ra, kbeg); load_b(rb, kbeg); }
+  f32x4 ra[2], rb[NB][2];
+  if (kbeg < kend) {
+    load_a(ra, kbeg);
+#pragma unroll
+    for (int s = 0; s < NB; ++s) load_b(rb[s], s ? a.B2 : a.B, kbeg);
+  }
   for (long long k = kbeg; k < kend; k += kBK) {
     __syncthreads();
-    if (MODE == kWgrad) { store_mc(As, ra, tid); store_mc(Bs, rb, tid); }
-    else { store_kc(As, ra, tid); store_kc(Bs, rb, tid); }
+    if (MODE == kWgrad) store_mc(As, ra, tid); else store_kc(As, ra, tid);
+#pragma unroll
+    for (int s = 0; s < NB; ++s) {
+      if (MODE == kWgrad) store_mc(Bs[s], rb[s], tid); else store_kc(Bs[s], rb[s], tid);
+    }
     __syncthreads();
-    if (k + kBK < kend) { load_a(ra, k + kBK); load_b(rb, k + kBK); }
+    if (k + kBK < kend) {      // spelled out twice: one lambda around the pair costs the single-stream forward 8 VGPRs and 2 % at thin layers
+      load_a(ra, k + kBK);
+#pragma unroll
+      for (int s = 0; s < NB; ++s) load_b(rb[s], s ? a.B2 : a.B, k + kBK);
+    }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      f32x4 fa[2], fb[2];
+      f32x4 fa[2], fb[NB][2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) fa[i] = *reinterpret_cast<const f32x4*>(As + (32 * wm + 16 * i + li) * kLd + 16 * h + 4 * kq);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const f32x4*>(Bs + (32 * wn + 16 * j + li) * kLd + 16 * h + 4 * kq);
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int s = 0; s < NB; ++s) fb[s][j] = *reinterpret_cast<const f32x4*>(Bs[s] + (32 * wn + 16 * j + li) * kLd + 16 * h + 4 * kq);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][r], fb[j][r], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int s = 0; s < NB; ++s)
+              acc[s][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][r], fb[s][j][r], acc[s][i][j], 0, 0, 0);
     }
   }
 
-  // acc[i][j][r] = C[m = m0 + 32 wm + 16 i + 4 kq + r][n = n0 + 32 wn + 16 j + li]
+  // acc[s][i][j][r] = C_s[m = m0 + 32 wm + 16 i + 4 kq + r][n = n0 + 32 wn + 16 j + li]
   const long long mw = m0 + 32 * wm;          // first feature of this wave's 32-feature group
   if (MODE == kWgrad) {
     float* dst = a.slab + (long long)blockIdx.z * a.slab_stride + a.reg;
@@ -405,7 +477,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const long long o = mw + 16 * i + 4 * kq + r, c = n0 + 32 * wn + 16 * j + li;
-          if (o < a.out_real && c <= a.in_real) dst[o * (a.in_real + 1) + c] = acc[i][j][r];
+          if (o < a.out_real && c <= a.in_real) dst[o * (a.in_real + 1) + c] = acc[0][i][j][r];
         }
     return;
   }
@@ -413,43 +485,26 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const long long n = n0 + 32 * wn + 16 * j + li;
-    if (MODE == kFwd) {
+    const bool valid = n < a.n_valid;
+    if (MODE == kFwd) {      // NS = 2: a = c h (bitwise the single stream's), ad = c (1 - h^2) zd
       long long lrow; int pass;
-      row_ctx(a, n, lrow, pass);
+      row_ctx<NS>(a, n, lrow, pass);
       const bool on = a.module >= 0 && a.drop.mode != PINN_DROP_NONE && pass >= 0;
-      const unsigned thr = a.module >= 0 ? a.drop.thr[a.module] : 0u;
       const float scale = on ? a.drop.scale[a.module] : 1.0f;
-      unsigned mine = 0;
-      if (on && a.drop.mode == PINN_DROP_PHILOX) {
-        const unsigned long long g = (unsigned long long)(a.drop.row_offset + lrow);
-        unsigned o[4];
-        philox4x32_10((unsigned)g, (unsigned)(g >> 32), ((unsigned)a.module << 16) | ((unsigned)P << 2) | (unsigned)kq,
-                      a.drop.stream + (unsigned)pass, a.drop.seed_lo, a.drop.seed_hi, o);
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int idx = 4 * b + r;
-            const unsigned draw = (o[idx >> 1] >> (16 * (idx & 1))) & 0xFFFFu;
-            mine |= (draw >= thr ? 1u : 0u) << (16 * b + 4 * kq + r);
-          }
-      }
-      mine |= __shfl_xor(mine, 16, 64);
-      mine |= __shfl_xor(mine, 32, 64);
-      unsigned word = 0xFFFFFFFFu;
-      if (on && a.drop.mode == PINN_DROP_PHILOX) word = mine;
-      if (on && a.drop.mode == PINN_DROP_BITS && n < a.n_valid)
-        word = a.drop.bits[((long long)pass * a.n_rows + lrow) * a.drop.words + a.keep_off + P];
+      const unsigned word = keep_word(a, on, lrow, pass, valid, P, kq);
       if (mw < a.M) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-          f32x4 v;
+          f32x4 v, vd;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float t = tanh_f32(acc[i][j][r]);
-            v[r] = ((word >> (16 * i + 4 * kq + r)) & 1u) ? t * scale : 0.0f;
+            const float t = tanh_f32(acc[0][i][j][r]);
+            const bool kept = (word >> (16 * i + 4 * kq + r)) & 1u;
+            v[r] = kept ? t * scale : 0.0f;
+            if (NS == 2) vd[r] = (kept && valid) ? acc[NB - 1][i][j][r] * (scale * (1.0f - t * t)) : 0.0f;
           }
           *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = v;
+          if (NS == 2) *reinterpret_cast<f32x4*>(a.out2 + n * a.ldo + mw + 16 * i + 4 * kq) = vd;
         }
         if (a.keep && a.module >= 0 && kq == 0) a.keep[n * a.drop.words + a.keep_off + P] = word;
       }
@@ -458,18 +513,23 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
         const bool on = a.drop.mode != PINN_DROP_NONE && a.stash_module >= 0;
         const float scale = on ? a.drop.scale[a.stash_module] : 1.0f, inv_scale = 1.0f / scale;
         const unsigned word = a.stash_module >= 0 ? a.keep_in[n * a.drop.words + a.keep_off + P] : 0xFFFFFFFFu;
-        const bool valid = n < a.n_valid;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const f32x4 h = *reinterpret_cast<const f32x4*>(a.stash + n * a.ld_stash + mw + 16 * i + 4 * kq);
-          f32x4 v;
+          f32x4 hd, vp, vq;
+          if (NS == 2) hd = *reinterpret_cast<const f32x4*>(a.stash2 + n * a.ld_stash + mw + 16 * i + 4 * kq);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float t = h[r] * inv_scale;
-            const float g = acc[i][j][r] * (scale * (1.0f - t * t));
-            v[r] = (valid && ((word >> (16 * i + 4 * kq + r)) & 1u)) ? g : 0.0f;
+            const float d = scale * (1.0f - t * t);
+            const float gq = acc[NB - 1][i][j][r] * d;                          // NS = 2: the first backward's dpre, bit for bit
+            const float gp = NS == 2 ? acc[0][i][j][r] * d - 2.0f * t * acc[NB - 1][i][j][r] * hd[r] : 0.0f;
+            const bool kept = valid && ((word >> (16 * i + 4 * kq + r)) & 1u);
+            vq[r] = kept ? gq : 0.0f;
+            if (NS == 2) vp[r] = kept ? gp : 0.0f;
           }
-          *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = v;
+          if (NS == 2) *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = vp;
+          *reinterpret_cast<f32x4*>((NS == 2 ? a.out2 : a.out) + n * a.ldo + mw + 16 * i + 4 * kq) = vq;
         }
       }
     }
@@ -737,12 +797,33 @@ static int launch_pack(const Shape& s, const float* params, float* pack, hipStre
 }
 
 
+template <int MODE>
+static void launch_gemm(const GemmArgs& g, bool paired, dim3 grid, hipStream_t st) {
+  if (paired) hipLaunchKernelGGL((gemm_kernel<MODE, 2>), grid, dim3(256), 0, st, g);
+  else hipLaunchKernelGGL((gemm_kernel<MODE, 1>), grid, dim3(256), 0, st, g);
+}
+
 // every GEMM layer of the forward pass for one chunk of (virtual) rows
 struct ChunkIO {
   const float* in[kMaxMat]; long long ld_in[kMaxMat];
   float* out[kMaxMat]; long long ld_out[kMaxMat];
+  const float* in2[kMaxMat]; float* out2[kMaxMat];      // the tangent stream of the double backward (same strides); NULL: none
   unsigned* keep;          // training: keep words written here
 };
+
+// training: matrix t reads the kept activation of the layer below it (matrix 0: the input rows, set per call) and keeps its own
+static ChunkIO train_io(const Shape& s, float* const* act, float* const* tan, unsigned* keep) {
+  ChunkIO io{};
+  for (int t = 0; t < s.n_mat; ++t) {
+    if (!s.is_gemm(t)) continue;
+    const int src = t == 0 ? -1 : (t < s.k ? t - 1 : (t == s.mat_v0() ? s.k - 1 : s.mat_v0()));
+    io.out[t] = act[t]; io.ld_out[t] = s.mp[t];
+    io.in[t] = src < 0 ? nullptr : act[src]; io.ld_in[t] = src < 0 ? 8 : s.mp[src];
+    if (tan) { io.out2[t] = tan[t]; io.in2[t] = src < 0 ? nullptr : tan[src]; }
+  }
+  io.keep = keep;
+  return io;
+}
 
 static void forward_layers(const Shape& s, const float* params, const float* pack, const Drop& d, const ChunkIO& io, long long row0,
                            long long nv, long long rows, long long n_rows, bool mc, hipStream_t st) {
@@ -750,9 +831,9 @@ static void forward_layers(const Shape& s, const float* params, const float* pac
     const int t = step < s.k ? step : (step == s.k ? s.mat_v0() : s.mat_v1());
     GemmArgs g{};
     g.A = pack + s.pf[t]; g.lda = s.kp[t]; g.a_mv = s.mp[t]; g.a_kv = s.kp[t];
-    g.B = io.in[t]; g.ldb = io.ld_in[t]; g.b_mv = rows; g.b_kv = t == 0 ? 8 : s.kp[t];
+    g.B = io.in[t]; g.B2 = io.in2[t]; g.ldb = io.ld_in[t]; g.b_mv = rows; g.b_kv = t == 0 ? 8 : s.kp[t];
     g.M = s.mp[t]; g.K = s.kp[t];
-    g.out = io.out[t]; g.ldo = io.ld_out[t];
+    g.out = io.out[t]; g.out2 = io.out2[t]; g.ldo = io.ld_out[t];
     g.n_valid = nv;
     g.bias = params + s.boff[t]; g.bias_n = s.out[t];
     g.module = t < s.k ? t : (t == s.mat_v0() ? s.k : -1);
@@ -763,8 +844,7 @@ static void forward_layers(const Shape& s, const float* params, const float* pac
     g.keep = io.keep;
     g.keep_off = g.module >= 0 ? s.word_off[g.module] : 0;
     g.stash_module = -1;
-    const dim3 grid((unsigned)(rows / 64), (unsigned)((s.mp[t] + 63) / 64));
-    hipLaunchKernelGGL(gemm_kernel<kFwd>, grid, dim3(256), 0, st, g);
+    launch_gemm<kFwd>(g, io.out2[t] != nullptr, dim3((unsigned)(rows / 64), (unsigned)((s.mp[t] + 63) / 64)), st);
   }
 }
 
@@ -790,7 +870,7 @@ static int run_infer(const Shape& s, const float* d_params, const float* d_x, lo
   const float* pack = (const float*)(base + L.pack);
   int rc = launch_pack(s, d_params, (float*)(base + L.pack), st);
   if (rc) return rc;
-  float* buf[3] = {(float*)(base + L.act[0]), (float*)(base + L.act[1]), (float*)(base + L.act[2])};
+  float* buf[3] = {(float*)(base + L.act[0][0]), (float*)(base + L.act[0][1]), (float*)(base + L.act[0][2])};
   ChunkIO io{};
   for (int t = 0; t < s.k; ++t) {       // hidden layer t writes buf[t & 1]; v0 the other one; v1 buf[2]
     io.in[t] = t == 0 ? d_x : buf[(t - 1) & 1];
@@ -824,37 +904,57 @@ static int run_infer(const Shape& s, const float* d_params, const float* d_x, lo
   return last_error();
 }
 
+// weight gradient of matrix t, per slice.  Double backward: dpre = p with x_in = a, dpre2 = q with x_in2 = ad (same strides)
 static void wgrad(const Shape& s, int t, const Layout& L, const float* dpre, long long ld_dpre, const float* x_in, long long ld_in,
-                  long long nv, float* slabs, hipStream_t st) {
+                  long long nv, float* slabs, hipStream_t st, const float* dpre2 = nullptr, const float* x_in2 = nullptr) {
   GemmArgs g{};
-  g.A = dpre; g.lda = ld_dpre; g.a_mv = s.mp[t]; g.a_kv = nv;
-  g.B = x_in; g.ldb = ld_in; g.b_mv = ld_in; g.b_kv = nv;
+  g.A = dpre; g.A2 = dpre2; g.lda = ld_dpre; g.a_mv = s.mp[t]; g.a_kv = nv;
+  g.B = x_in; g.B2 = x_in2; g.ldb = ld_in; g.b_mv = ld_in; g.b_kv = nv;
   g.K = L.rows;
   g.n_valid = nv;
   g.slice_rows = L.slice_rows; g.slab = slabs; g.slab_stride = s.gtotal; g.reg = s.reg[t];
   g.out_real = s.out[t]; g.in_real = s.in[t];
   g.module = -1; g.stash_module = -1;
   const dim3 grid((unsigned)((s.in[t] + 1 + 63) / 64), (unsigned)((s.out[t] + 63) / 64), (unsigned)L.slices);
-  hipLaunchKernelGGL(gemm_kernel<kWgrad>, grid, dim3(256), 0, st, g);
+  launch_gemm<kWgrad>(g, dpre2 != nullptr, grid, st);
 }
 
-// d pre-activation of the layer feeding matrix t: (W_t^T dpre_t (+ w_p du)) * tanh' * mask
+// d pre-activation of the layer feeding matrix t: (W_t^T dpre_t (+ w_p du)) * tanh' * mask.  Double backward: (dpre, dpre2) = (p, q) of
+// matrix t, (dpre_in, dpre_in2) = (p, q) of that layer, from its kept activation and tangent (stash, stash2); w_p du joins the q stream
 static void bwd(const Shape& s, int t, const Layout& L, const float* pack, const Drop& d, const float* dpre, float* dpre_in,
                 const float* stash, long long ld_stash, int module, const unsigned* keep, const float* wp, const float* du, long long nv,
-                hipStream_t st) {
+                hipStream_t st, const float* dpre2 = nullptr, float* dpre_in2 = nullptr, const float* stash2 = nullptr) {
   GemmArgs g{};
   g.A = pack + s.pt[t]; g.lda = s.mp[t]; g.a_mv = s.kp[t]; g.a_kv = s.mp[t];
-  g.B = dpre; g.ldb = s.max_wp; g.b_mv = L.rows; g.b_kv = s.mp[t];
+  g.B = dpre; g.B2 = dpre2; g.ldb = s.max_wp; g.b_mv = L.rows; g.b_kv = s.mp[t];
   g.M = s.kp[t]; g.K = s.mp[t];
-  g.out = dpre_in; g.ldo = s.max_wp;
+  g.out = dpre_in; g.out2 = dpre_in2; g.ldo = s.max_wp;
   g.n_valid = nv;
   g.drop = d;
   g.module = -1;
-  g.stash = stash; g.ld_stash = ld_stash; g.stash_module = module;
+  g.stash = stash; g.stash2 = stash2; g.ld_stash = ld_stash; g.stash_module = module;
   g.keep_in = keep; g.keep_off = s.word_off[module];
   g.wp = wp; g.du = du; g.wp_n = wp ? s.hk : 0;
-  const dim3 grid((unsigned)(L.rows / 64), (unsigned)((s.kp[t] + 63) / 64));
-  hipLaunchKernelGGL(gemm_kernel<kBwd>, grid, dim3(256), 0, st, g);
+  launch_gemm<kBwd>(g, dpre2 != nullptr, dim3((unsigned)(L.rows / 64), (unsigned)((s.kp[t] + 63) / 64)), st);
+}
+
+// acc (+)= the chunk's slab sums
+static void launch_reduce(const Shape& s, const Layout& L, const float* slabs, float* acc, bool first, hipStream_t st) {
+  long long gx = (s.gtotal + 255) / 256;
+  if (gx > 4096) gx = 4096;
+  hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)gx), dim3(256), 0, st, slabs, L.slices, s.gtotal, acc, first ? 1 : 0);
+}
+
+// acc -> the flat gradient; loss_part != NULL: also the loss sums of its n_parts partials
+static void launch_finalize(const Shape& s, const float* acc, float* grads, const double* loss_part, long long n_parts, double* loss,
+                            hipStream_t st) {
+  FinArgs f{};
+  f.acc = acc; f.grads = grads; f.total = s.total; f.n_mat = s.n_mat;
+  for (int t = 0; t < s.n_mat; ++t) { f.woff[t] = s.woff[t]; f.boff[t] = s.boff[t]; f.reg[t] = s.reg[t]; f.out[t] = s.out[t]; f.in[t] = s.in[t]; }
+  f.loss_part = loss_part; f.n_parts = n_parts; f.loss = loss;
+  long long gx = (s.total + 255) / 256;
+  if (gx > 4096) gx = 4096;
+  hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)gx), dim3(256), 0, st, f);
 }
 
 // upstream gradients of pinn_gnet_backward: dL/du and dL/dlogvar per row (glv NULL: zero), dL/dx out (gx NULL: not computed)
@@ -865,7 +965,7 @@ struct Upstream { const float* gu; const float* glv; float* gx; };
 // optionally dL/dx (pinn_gnet_backward).
 static int run_train(const Shape& s, const float* d_params, const float* d_x, const float* d_y, long long n_rows, long long n_global,
                      const Drop& d, const Upstream* up, float* d_grads, double* d_loss, void* d_work, size_t work_bytes, hipStream_t st) {
-  const Layout L = train_layout(s, n_rows);
+  const Layout L = train_layout(s, n_rows, 1);
   if (!d_work || !al16(d_work)) return PINN_E_ARG;
   if (work_bytes < L.end) return PINN_E_WORKSPACE;
   char* base = (char*)d_work;
@@ -873,29 +973,22 @@ static int run_train(const Shape& s, const float* d_params, const float* d_x, co
   int rc = launch_pack(s, d_params, (float*)(base + L.pack), st);
   if (rc) return rc;
   float* act[kMaxMat];
-  for (int t = 0; t < s.n_mat; ++t) act[t] = s.is_gemm(t) ? (float*)(base + L.act[act_index(s, t)]) : nullptr;
+  for (int t = 0; t < s.n_mat; ++t) act[t] = s.is_gemm(t) ? (float*)(base + L.act[0][act_index(s, t)]) : nullptr;
   unsigned* keep = (unsigned*)(base + L.keep);
-  float* dp[2] = {(float*)(base + L.dpre[0]), (float*)(base + L.dpre[1])};
+  float* dp[2] = {(float*)(base + L.dpre[0][0]), (float*)(base + L.dpre[0][1])};
   float* du = (float*)(base + L.du);
   float* dz = (float*)(base + L.dz);
   float* slabs = (float*)(base + L.slabs);
   float* acc = (float*)(base + L.acc);
   double* loss_part = (double*)(base + L.loss);
-  ChunkIO io{};
-  for (int t = 0; t < s.n_mat; ++t) {
-    if (!s.is_gemm(t)) continue;
-    const int src = t == 0 ? -1 : (t < s.k ? t - 1 : (t == s.mat_v0() ? s.k - 1 : s.mat_v0()));
-    io.out[t] = act[t]; io.ld_out[t] = s.mp[t];
-    io.in[t] = src < 0 ? nullptr : act[src]; io.ld_in[t] = src < 0 ? 8 : s.mp[src];
-  }
-  io.keep = keep;
+  ChunkIO io = train_io(s, act, nullptr, keep);
+  io.in[0] = d_x;
   const int v0m = s.mat_v0(), v1m = s.mat_v1();
   const long long nch = n_chunks(n_rows, L.rows);
   for (long long ch = 0; ch < nch; ++ch) {
     const long long row0 = ch * L.rows;
     const long long nv = n_rows - row0 < L.rows ? n_rows - row0 : L.rows;
     const float* x = d_x + row0 * 8;
-    io.in[0] = d_x;
     forward_layers(s, d_params, pack, d, io, row0, nv, L.rows, n_rows, false, st);
     HeadArgs h = head_args(s, d_params, act[s.k - 1], s.mp[s.k - 1], act[v1m], s.mp[v1m], nv, row0);
     h.y = d_y; h.n_global = n_global; h.du = du; h.dz = dz; h.dpre_v2 = dp[0]; h.ld_dpre = s.max_wp; h.wd = s.mp[v1m];
@@ -932,253 +1025,26 @@ static int run_train(const Shape& s, const float* d_params, const float* d_x, co
     if (up && up->gx)        // dp[cur] is now d pre-activation of hidden layer 0
       hipLaunchKernelGGL(dx_kernel, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, d_params + s.woff[0], s.w[0], (const float*)dp[cur],
                          (long long)s.max_wp, nv, row0, up->gx);
-    long long gx = (s.gtotal + 255) / 256;
-    if (gx > 4096) gx = 4096;
-    hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)gx), dim3(256), 0, st, (const float*)slabs, L.slices, s.gtotal, acc, ch == 0 ? 1 : 0);
+    launch_reduce(s, L, slabs, acc, ch == 0, st);
     rc = last_error();
     if (rc) return rc;
   }
-  FinArgs f{};
-  f.acc = acc; f.grads = d_grads; f.total = s.total; f.n_mat = s.n_mat;
-  for (int t = 0; t < s.n_mat; ++t) { f.woff[t] = s.woff[t]; f.boff[t] = s.boff[t]; f.reg[t] = s.reg[t]; f.out[t] = s.out[t]; f.in[t] = s.in[t]; }
-  f.loss_part = up ? nullptr : loss_part; f.n_parts = nch * (L.rows / 16); f.loss = d_loss;
-  long long gx = (s.total + 255) / 256;
-  if (gx > 4096) gx = 4096;
-  hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)gx), dim3(256), 0, st, f);
+  launch_finalize(s, acc, d_grads, up ? nullptr : loss_part, nch * (L.rows / 16), d_loss, st);
   return last_error();
 }
 
 // ---------------------------------------------------------------------------------------
 // double backward (pinn_gnet_backward2): the gradient of S = <v, dL/dx> with respect to g_u, g_lv, x and the parameters.
 //
-// Every matrix product has one weight operand for two activation streams, so each layer is one launch of a dual-accumulator
-// variant of gemm_kernel: one weight tile and two activation tiles in LDS, two accumulator sets, a paired epilogue.
-//   gemm2_kernel<kFwd>   [z ; zd] = W [a_in ; ad_in];  h = tanh z, a = c h, ad = c (1 - h^2) zd   (primal a bitwise gemm_kernel<kFwd>'s)
-//   gemm2_kernel<kBwd>   [abar ; adbar] = W^T [p ; q] (+ w_p g_u on adbar);  q_in = c (1 - h^2) adbar (bitwise the first backward's
-//                        dpre), p_in = c (1 - h^2) abar - 2 h adbar ad
-//   gemm2_kernel<kWgrad> slab[s][o][i] = sum_{r in slice s} p[r][o] a[r][i] + q[r][o] ad[r][i]; the bias column sums p alone
-//   head2_kernel         z, zd, f', f'', ud, lvd; q_v2, p_v2; the (p, q) pair below the variance head's second tanh
-//   vec_grad2_kernel     the two one-row tensors per slice: w_p (g_u^T ad_k, bias 0), w_v2 (q_v2^T ad_v1 + p_v2^T a_v1, bias sum p_v2)
+// Every matrix product has one weight operand for two activation streams, so each layer is one launch of gemm_kernel<., 2>:
+//   gemm_kernel<kFwd, 2>   [z ; zd] = W [a_in ; ad_in];  h = tanh z, a = c h, ad = c (1 - h^2) zd   (primal a bitwise gemm_kernel<kFwd, 1>'s)
+//   gemm_kernel<kBwd, 2>   [abar ; adbar] = W^T [p ; q] (+ w_p g_u on adbar);  q_in = c (1 - h^2) adbar (bitwise the first backward's
+//                          dpre), p_in = c (1 - h^2) abar - 2 h adbar ad
+//   gemm_kernel<kWgrad, 2> slab[s][o][i] = sum_{r in slice s} p[r][o] a[r][i] + q[r][o] ad[r][i]; the bias column sums p alone
+//   head2_kernel           z, zd, f', f'', ud, lvd; q_v2, p_v2; the (p, q) pair below the variance head's second tanh
+//   vec_grad2_kernel       the two one-row tensors per slice: w_p (g_u^T ad_k, bias 0), w_v2 (q_v2^T ad_v1 + p_v2^T a_v1, bias sum p_v2)
 // dS/dx = W_0^T p_0 is dx_kernel on p_0; slab sums and the flat gradient are reduce_kernel / finalize_kernel.
 // ---------------------------------------------------------------------------------------
-struct Gemm2Args {
-  const float* A; long long lda; long long a_mv, a_kv;        // FWD / BWD: packed weights; WGRAD: p
-  const float* A2;                                            // WGRAD: q (same extents as A)
-  const float* B; const float* B2; long long ldb; long long b_mv, b_kv;    // primal / tangent stream (BWD: p / q)
-  long long M, K;
-  float* out; float* out2; long long ldo;
-  long long n_valid;
-  // FWD
-  const float* bias; int bias_n; int module; int map_rows; long long row0, n_rows;
-  Drop drop;
-  unsigned* keep; int keep_off;
-  // BWD
-  const float* stash; const float* stash2; long long ld_stash; int stash_module;
-  const float* wp; const float* du; int wp_n;
-  const unsigned* keep_in;
-  // WGRAD
-  long long slice_rows; float* slab; long long slab_stride; long long reg; int out_real, in_real;
-};
-
-template <int MODE>
-__global__ __launch_bounds__(256) void gemm2_kernel(Gemm2Args a) {
-  __shared__ __attribute__((aligned(16))) float As[64 * kLd];
-  __shared__ __attribute__((aligned(16))) float Bs[64 * kLd];
-  __shared__ __attribute__((aligned(16))) float Cs[64 * kLd];     // FWD / BWD: the second activation tile; WGRAD: unused
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, li = lane & 15;
-  const int wm = wave & 1, wn = wave >> 1;
-  const long long m0 = (long long)blockIdx.y * 64, n0 = (long long)blockIdx.x * 64;
-
-  f32x4 acc[2][2], acd[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      acd[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (MODE == kFwd) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const long long m = m0 + 32 * wm + 16 * i + 4 * kq + r;
-          acc[i][j][r] = m < a.bias_n ? a.bias[m] : 0.0f;
-        }
-      }
-      if (MODE == kBwd && a.wp) {
-        const long long n = n0 + 32 * wn + 16 * j + li;
-        const float du = a.du[n];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const long long m = m0 + 32 * wm + 16 * i + 4 * kq + r;
-          acd[i][j][r] = (m < a.wp_n ? a.wp[m] : 0.0f) * du;
-        }
-      }
-    }
-
-  if (MODE == kWgrad) {
-    // one reduction over twice the rows: the slice's rows of (p, a), then the same rows of (q, ad), into one accumulator set
-    const long long kbeg = (long long)blockIdx.z * a.slice_rows;
-    long long kend = kbeg + a.slice_rows;
-    if (kend > a.K) kend = a.K;
-    const long long len = kend > kbeg ? (kend - kbeg + kBK - 1) / kBK : 0;      // K slabs per stream
-    f32x4 ra[2], rb[2];
-    auto load = [&](long long it) {
-      const int s2 = it >= len;
-      const long long k0 = kbeg + (it - (s2 ? len : 0)) * kBK;
-      load_mc(ra, s2 ? a.A2 : a.A, a.lda, m0, k0, a.a_mv, a.a_kv, tid, -1);
-      load_mc(rb, s2 ? a.B2 : a.B, a.ldb, n0, k0, a.b_mv, a.b_kv, tid, a.in_real, s2 ? 0.0f : 1.0f);
-    };
-    if (len > 0) load(0);
-    for (long long it = 0; it < 2 * len; ++it) {
-      __syncthreads();
-      store_mc(As, ra, tid); store_mc(Bs, rb, tid);
-      __syncthreads();
-      if (it + 1 < 2 * len) load(it + 1);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        f32x4 fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) fa[i] = *reinterpret_cast<const f32x4*>(As + (32 * wm + 16 * i + li) * kLd + 16 * h + 4 * kq);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) fb[j] = *reinterpret_cast<const f32x4*>(Bs + (32 * wn + 16 * j + li) * kLd + 16 * h + 4 * kq);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][r], fb[j][r], acc[i][j], 0, 0, 0);
-      }
-    }
-    float* dst = a.slab + (long long)blockIdx.z * a.slab_stride + a.reg;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const long long o = m0 + 32 * wm + 16 * i + 4 * kq + r, c = n0 + 32 * wn + 16 * j + li;
-          if (o < a.out_real && c <= a.in_real) dst[o * (a.in_real + 1) + c] = acc[i][j][r];
-        }
-    return;
-  }
-
-  // FWD / BWD: B rows of the input layer are rows of x (and of v): chunk row n -> row0 + n
-  auto load_b = [&](f32x4 (&r)[2], const float* __restrict__ p, long long k0) {
-    if (MODE == kFwd && a.map_rows) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const long long n = n0 + (tid >> 3) + 32 * q, k = k0 + (tid & 7) * 4;
-        r[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (n < a.n_valid && k < a.b_kv) r[q] = *reinterpret_cast<const f32x4*>(p + (a.row0 + n) * a.ldb + k);
-      }
-    } else {
-      load_kc(r, p, a.ldb, n0, k0, a.b_mv, a.b_kv, tid);
-    }
-  };
-  f32x4 ra[2], rb[2], rc[2];
-  if (a.K > 0) { load_kc(ra, a.A, a.lda, m0, 0, a.a_mv, a.a_kv, tid); load_b(rb, a.B, 0); load_b(rc, a.B2, 0); }
-  for (long long k = 0; k < a.K; k += kBK) {
-    __syncthreads();
-    store_kc(As, ra, tid); store_kc(Bs, rb, tid); store_kc(Cs, rc, tid);
-    __syncthreads();
-    if (k + kBK < a.K) { load_kc(ra, a.A, a.lda, m0, k + kBK, a.a_mv, a.a_kv, tid); load_b(rb, a.B, k + kBK); load_b(rc, a.B2, k + kBK); }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      f32x4 fa[2], fb[2], fc[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) fa[i] = *reinterpret_cast<const f32x4*>(As + (32 * wm + 16 * i + li) * kLd + 16 * h + 4 * kq);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        fb[j] = *reinterpret_cast<const f32x4*>(Bs + (32 * wn + 16 * j + li) * kLd + 16 * h + 4 * kq);
-        fc[j] = *reinterpret_cast<const f32x4*>(Cs + (32 * wn + 16 * j + li) * kLd + 16 * h + 4 * kq);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][r], fb[j][r], acc[i][j], 0, 0, 0);
-            acd[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][r], fc[j][r], acd[i][j], 0, 0, 0);
-          }
-    }
-  }
-
-  const long long mw = m0 + 32 * wm;
-  const int P = (int)(mw >> 5);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const long long n = n0 + 32 * wn + 16 * j + li;
-    const bool valid = n < a.n_valid;
-    if (MODE == kFwd) {
-      // the keep word: gemm_kernel<kFwd>'s expressions (same Philox counter, key and bit order)
-      const long long lrow = a.row0 + n;
-      const bool on = a.module >= 0 && a.drop.mode != PINN_DROP_NONE;
-      const unsigned thr = a.module >= 0 ? a.drop.thr[a.module] : 0u;
-      const float scale = on ? a.drop.scale[a.module] : 1.0f;
-      unsigned mine = 0;
-      if (on && a.drop.mode == PINN_DROP_PHILOX) {
-        const unsigned long long g = (unsigned long long)(a.drop.row_offset + lrow);
-        unsigned o[4];
-        philox4x32_10((unsigned)g, (unsigned)(g >> 32), ((unsigned)a.module << 16) | ((unsigned)P << 2) | (unsigned)kq, a.drop.stream,
-                      a.drop.seed_lo, a.drop.seed_hi, o);
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int idx = 4 * b + r;
-            const unsigned draw = (o[idx >> 1] >> (16 * (idx & 1))) & 0xFFFFu;
-            mine |= (draw >= thr ? 1u : 0u) << (16 * b + 4 * kq + r);
-          }
-      }
-      mine |= __shfl_xor(mine, 16, 64);
-      mine |= __shfl_xor(mine, 32, 64);
-      unsigned word = 0xFFFFFFFFu;
-      if (on && a.drop.mode == PINN_DROP_PHILOX) word = mine;
-      if (on && a.drop.mode == PINN_DROP_BITS && valid) word = a.drop.bits[lrow * a.drop.words + a.keep_off + P];
-      if (mw < a.M) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          f32x4 v, vd;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float t = tanh_f32(acc[i][j][r]);
-            const bool kept = (word >> (16 * i + 4 * kq + r)) & 1u;
-            v[r] = kept ? t * scale : 0.0f;
-            vd[r] = (kept && valid) ? acd[i][j][r] * (scale * (1.0f - t * t)) : 0.0f;
-          }
-          *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = v;
-          *reinterpret_cast<f32x4*>(a.out2 + n * a.ldo + mw + 16 * i + 4 * kq) = vd;
-        }
-        if (a.module >= 0 && kq == 0) a.keep[n * a.drop.words + a.keep_off + P] = word;
-      }
-    } else {      // kBwd
-      if (mw < a.M) {
-        const bool on = a.drop.mode != PINN_DROP_NONE && a.stash_module >= 0;
-        const float scale = on ? a.drop.scale[a.stash_module] : 1.0f, inv_scale = 1.0f / scale;
-        const unsigned word = a.stash_module >= 0 ? a.keep_in[n * a.drop.words + a.keep_off + P] : 0xFFFFFFFFu;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const f32x4 h = *reinterpret_cast<const f32x4*>(a.stash + n * a.ld_stash + mw + 16 * i + 4 * kq);
-          const f32x4 hd = *reinterpret_cast<const f32x4*>(a.stash2 + n * a.ld_stash + mw + 16 * i + 4 * kq);
-          f32x4 vp, vq;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float t = h[r] * inv_scale;
-            const float d = scale * (1.0f - t * t);
-            const float gq = acd[i][j][r] * d;                                   // the first backward's dpre, bit for bit
-            const float gp = acc[i][j][r] * d - 2.0f * t * acd[i][j][r] * hd[r];
-            const bool kept = valid && ((word >> (16 * i + 4 * kq + r)) & 1u);
-            vq[r] = kept ? gq : 0.0f;
-            vp[r] = kept ? gp : 0.0f;
-          }
-          *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = vp;
-          *reinterpret_cast<f32x4*>(a.out2 + n * a.ldo + mw + 16 * i + 4 * kq) = vq;
-        }
-      }
-    }
-  }
-}
-
 // per row (16 lanes): z, zd, f'(z), f''(z); ud = w_p . ad_k, lvd = f' zd (the gradients of S with respect to g_u, g_lv);
 // q_v2 = g_lv f', p_v2 = g_lv f'' zd, and the (p, q) pair below the variance head's second tanh (no dropout there: c = 1)
 struct Head2Args {
@@ -1265,47 +1131,11 @@ __global__ __launch_bounds__(256) void vec_grad2_kernel(Vec2Args a) {
   }
 }
 
-// the double backward keeps a primal and a tangent activation per layer and two (p, q) ping-pong pairs: about twice
-// train_layout's bytes per row, so about half its chunk
-struct Layout2 {
-  long long rows; int slices; long long slice_rows;
-  size_t pack, act[kMaxHidden + 2], tan[kMaxHidden + 2], keep, dp[2], dq[2], du, qz, pz, slabs, acc, end;
-};
-static Layout2 backward2_layout(const Shape& s, long long n_rows) {
-  Layout2 L{};
-  long long per_row = s.words + 4LL * s.max_wp + 3;
-  for (int t = 0; t < s.n_mat; ++t) if (s.is_gemm(t)) per_row += 2LL * s.mp[t];
-  long long cap = (long long)(kTrainBudget / (4 * (size_t)per_row)) / 64 * 64;
-  cap = cap < 64 ? 64 : (cap > kMaxChunkRows ? kMaxChunkRows : cap);
-  L.rows = rup(n_rows < 1 ? 1 : n_rows, 64);
-  if (L.rows > cap) L.rows = cap;
-  slice_plan(s, L.rows, &L.slice_rows, &L.slices);
-  size_t at = 0;
-  L.pack = take(at, 4 * (size_t)s.pack_total);
-  for (int t = 0; t < s.n_mat; ++t)
-    if (s.is_gemm(t)) {
-      L.act[act_index(s, t)] = take(at, 4 * (size_t)L.rows * s.mp[t]);
-      L.tan[act_index(s, t)] = take(at, 4 * (size_t)L.rows * s.mp[t]);
-    }
-  L.keep = take(at, 4 * (size_t)L.rows * s.words);
-  for (int b = 0; b < 2; ++b) {
-    L.dp[b] = take(at, 4 * (size_t)L.rows * s.max_wp);
-    L.dq[b] = take(at, 4 * (size_t)L.rows * s.max_wp);
-  }
-  L.du = take(at, 4 * (size_t)L.rows);
-  L.qz = take(at, 4 * (size_t)L.rows);
-  L.pz = take(at, 4 * (size_t)L.rows);
-  L.slabs = take(at, 4 * (size_t)L.slices * s.gtotal);
-  L.acc = take(at, 4 * (size_t)s.gtotal);
-  L.end = at;
-  return L;
-}
-
 struct Second { const float* gu; const float* glv; const float* vx; float* grads; float* gx; float* ggu; float* gglv; };
 
 static int run_backward2(const Shape& s, const float* d_params, const float* d_x, long long n_rows, const Drop& d, const Second& o,
                          void* d_work, size_t work_bytes, hipStream_t st) {
-  const Layout2 L = backward2_layout(s, n_rows);
+  const Layout L = train_layout(s, n_rows, 2);
   if (!d_work || !al16(d_work)) return PINN_E_ARG;
   if (work_bytes < L.end) return PINN_E_WORKSPACE;
   char* base = (char*)d_work;
@@ -1314,76 +1144,29 @@ static int run_backward2(const Shape& s, const float* d_params, const float* d_x
   if (rc) return rc;
   float* act[kMaxMat]; float* tan[kMaxMat];
   for (int t = 0; t < s.n_mat; ++t) {
-    act[t] = s.is_gemm(t) ? (float*)(base + L.act[act_index(s, t)]) : nullptr;
-    tan[t] = s.is_gemm(t) ? (float*)(base + L.tan[act_index(s, t)]) : nullptr;
+    act[t] = s.is_gemm(t) ? (float*)(base + L.act[0][act_index(s, t)]) : nullptr;
+    tan[t] = s.is_gemm(t) ? (float*)(base + L.act[1][act_index(s, t)]) : nullptr;
   }
   unsigned* keep = (unsigned*)(base + L.keep);
-  float* dp[2] = {(float*)(base + L.dp[0]), (float*)(base + L.dp[1])};
-  float* dq[2] = {(float*)(base + L.dq[0]), (float*)(base + L.dq[1])};
+  float* dp[2] = {(float*)(base + L.dpre[0][0]), (float*)(base + L.dpre[0][1])};
+  float* dq[2] = {(float*)(base + L.dpre[1][0]), (float*)(base + L.dpre[1][1])};
   float* du = (float*)(base + L.du);
-  float* qz = (float*)(base + L.qz);
+  float* qz = (float*)(base + L.dz);
   float* pz = (float*)(base + L.pz);
   float* slabs = (float*)(base + L.slabs);
   float* acc = (float*)(base + L.acc);
+  ChunkIO io = train_io(s, act, tan, keep);
+  io.in[0] = d_x; io.in2[0] = o.vx;
   const int v0m = s.mat_v0(), v1m = s.mat_v1();
   const bool want_w = o.grads != nullptr, want_back = want_w || o.gx;
   const dim3 blk(256);
-
-  auto wgrad2 = [&](int t, const float* p, const float* q, const float* a_in, const float* ad_in, long long ld_in, long long nv) {
-    Gemm2Args g{};
-    g.A = p; g.A2 = q; g.lda = s.max_wp; g.a_mv = s.mp[t]; g.a_kv = nv;
-    g.B = a_in; g.B2 = ad_in; g.ldb = ld_in; g.b_mv = ld_in; g.b_kv = nv;
-    g.K = L.rows; g.n_valid = nv;
-    g.slice_rows = L.slice_rows; g.slab = slabs; g.slab_stride = s.gtotal; g.reg = s.reg[t];
-    g.out_real = s.out[t]; g.in_real = s.in[t];
-    g.module = -1; g.stash_module = -1;
-    const dim3 grid((unsigned)((s.in[t] + 1 + 63) / 64), (unsigned)((s.out[t] + 63) / 64), (unsigned)L.slices);
-    hipLaunchKernelGGL(gemm2_kernel<kWgrad>, grid, blk, 0, st, g);
-  };
-  // (p, q) of the layer feeding matrix t, from (p, q) of matrix t and the stored (a, ad) of that layer
-  auto bwd2 = [&](int t, int from, int to, int src, int module, const float* wp, long long nv) {
-    Gemm2Args g{};
-    g.A = pack + s.pt[t]; g.lda = s.mp[t]; g.a_mv = s.kp[t]; g.a_kv = s.mp[t];
-    g.B = dp[from]; g.B2 = dq[from]; g.ldb = s.max_wp; g.b_mv = L.rows; g.b_kv = s.mp[t];
-    g.M = s.kp[t]; g.K = s.mp[t];
-    g.out = dp[to]; g.out2 = dq[to]; g.ldo = s.max_wp;
-    g.n_valid = nv;
-    g.drop = d;
-    g.module = -1;
-    g.stash = act[src]; g.stash2 = tan[src]; g.ld_stash = s.mp[src]; g.stash_module = module;
-    g.keep_in = keep; g.keep_off = s.word_off[module];
-    g.wp = wp; g.du = du; g.wp_n = wp ? s.hk : 0;
-    const dim3 grid((unsigned)(L.rows / 64), (unsigned)((s.kp[t] + 63) / 64));
-    hipLaunchKernelGGL(gemm2_kernel<kBwd>, grid, blk, 0, st, g);
-  };
-
   const long long nch = n_chunks(n_rows, L.rows);
   for (long long ch = 0; ch < nch; ++ch) {
     const long long row0 = ch * L.rows;
     const long long nv = n_rows - row0 < L.rows ? n_rows - row0 : L.rows;
     const float* x = d_x + row0 * 8;
     const float* vx = o.vx + row0 * 8;
-    for (int step = 0; step < s.k + 2; ++step) {       // tangent forward: hidden layers, variance head 0 and 1
-      const int t = step < s.k ? step : (step == s.k ? v0m : v1m);
-      const int src = t == 0 ? -1 : (t < s.k ? t - 1 : (t == v0m ? s.k - 1 : v0m));
-      Gemm2Args g{};
-      g.A = pack + s.pf[t]; g.lda = s.kp[t]; g.a_mv = s.mp[t]; g.a_kv = s.kp[t];
-      g.B = src < 0 ? d_x : act[src]; g.B2 = src < 0 ? o.vx : tan[src];
-      g.ldb = src < 0 ? 8 : s.mp[src]; g.b_mv = L.rows; g.b_kv = t == 0 ? 8 : s.kp[t];
-      g.M = s.mp[t]; g.K = s.kp[t];
-      g.out = act[t]; g.out2 = tan[t]; g.ldo = s.mp[t];
-      g.n_valid = nv;
-      g.bias = d_params + s.boff[t]; g.bias_n = s.out[t];
-      g.module = t < s.k ? t : (t == v0m ? s.k : -1);
-      g.map_rows = t == 0;
-      g.row0 = row0; g.n_rows = n_rows;
-      g.drop = d;
-      g.keep = keep;
-      g.keep_off = g.module >= 0 ? s.word_off[g.module] : 0;
-      g.stash_module = -1;
-      const dim3 grid((unsigned)(L.rows / 64), (unsigned)((s.mp[t] + 63) / 64));
-      hipLaunchKernelGGL(gemm2_kernel<kFwd>, grid, blk, 0, st, g);
-    }
+    forward_layers(s, d_params, pack, d, io, row0, nv, L.rows, n_rows, false, st);      // primal and tangent
     {
       Head2Args h{};
       h.hd = tan[s.k - 1]; h.ldh = s.mp[s.k - 1]; h.hk = s.hk;
@@ -1396,10 +1179,10 @@ static int run_backward2(const Shape& s, const float* d_params, const float* d_x
     }
     if (want_back) {
       // variance head layer 1, then layer 0 (+ the predict head on the q stream), then the hidden layers top-down
-      if (want_w) wgrad2(v1m, dp[0], dq[0], act[v0m], tan[v0m], s.mp[v0m], nv);
-      bwd2(v1m, 0, 1, v0m, s.k, nullptr, nv);
+      if (want_w) wgrad(s, v1m, L, dp[0], s.max_wp, act[v0m], s.mp[v0m], nv, slabs, st, dq[0], tan[v0m]);
+      bwd(s, v1m, L, pack, d, dp[0], dp[1], act[v0m], s.mp[v0m], s.k, keep, nullptr, nullptr, nv, st, dq[0], dq[1], tan[v0m]);
       if (want_w) {
-        wgrad2(v0m, dp[1], dq[1], act[s.k - 1], tan[s.k - 1], s.mp[s.k - 1], nv);
+        wgrad(s, v0m, L, dp[1], s.max_wp, act[s.k - 1], s.mp[s.k - 1], nv, slabs, st, dq[1], tan[s.k - 1]);
         Vec2Args va{};
         va.hd = tan[s.k - 1]; va.ldh = s.mp[s.k - 1]; va.hk = s.hk;
         va.v2 = act[v1m]; va.v2d = tan[v1m]; va.ldv = s.mp[v1m]; va.hv2 = s.hv2;
@@ -1408,38 +1191,29 @@ static int run_backward2(const Shape& s, const float* d_params, const float* d_x
         const int cols = s.hk + 1 + s.hv2 + 1;
         hipLaunchKernelGGL(vec_grad2_kernel, dim3((unsigned)L.slices, (unsigned)((cols + 255) / 256)), blk, 0, st, va);
       }
-      bwd2(v0m, 1, 0, s.k - 1, s.k - 1, d_params + s.woff[s.mat_pred()], nv);
+      bwd(s, v0m, L, pack, d, dp[1], dp[0], act[s.k - 1], s.mp[s.k - 1], s.k - 1, keep, d_params + s.woff[s.mat_pred()], du, nv, st,
+          dq[1], dq[0], tan[s.k - 1]);
       int cur = 0;
       for (int l = s.k - 1; l >= 0; --l) {
         if (want_w) {
-          if (l == 0) wgrad2(0, dp[cur], dq[cur], x, vx, 8, nv);
-          else wgrad2(l, dp[cur], dq[cur], act[l - 1], tan[l - 1], s.mp[l - 1], nv);
+          if (l == 0) wgrad(s, 0, L, dp[cur], s.max_wp, x, 8, nv, slabs, st, dq[cur], vx);
+          else wgrad(s, l, L, dp[cur], s.max_wp, act[l - 1], s.mp[l - 1], nv, slabs, st, dq[cur], tan[l - 1]);
         }
         if (l > 0) {
-          bwd2(l, cur, cur ^ 1, l - 1, l - 1, nullptr, nv);
+          bwd(s, l, L, pack, d, dp[cur], dp[cur ^ 1], act[l - 1], s.mp[l - 1], l - 1, keep, nullptr, nullptr, nv, st, dq[cur], dq[cur ^ 1],
+              tan[l - 1]);
           cur ^= 1;
         }
       }
       if (o.gx)        // dS/dx = W_0^T p_0
         hipLaunchKernelGGL(dx_kernel, dim3((unsigned)(L.rows / 16)), blk, 0, st, d_params + s.woff[0], s.w[0], (const float*)dp[cur],
                            (long long)s.max_wp, nv, row0, o.gx);
-      if (want_w) {
-        long long gx = (s.gtotal + 255) / 256;
-        if (gx > 4096) gx = 4096;
-        hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)gx), blk, 0, st, (const float*)slabs, L.slices, s.gtotal, acc, ch == 0 ? 1 : 0);
-      }
+      if (want_w) launch_reduce(s, L, slabs, acc, ch == 0, st);
     }
     rc = last_error();
     if (rc) return rc;
   }
-  if (want_w) {
-    FinArgs f{};
-    f.acc = acc; f.grads = o.grads; f.total = s.total; f.n_mat = s.n_mat;
-    for (int t = 0; t < s.n_mat; ++t) { f.woff[t] = s.woff[t]; f.boff[t] = s.boff[t]; f.reg[t] = s.reg[t]; f.out[t] = s.out[t]; f.in[t] = s.in[t]; }
-    long long gx = (s.total + 255) / 256;
-    if (gx > 4096) gx = 4096;
-    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)gx), blk, 0, st, f);
-  }
+  if (want_w) launch_finalize(s, acc, o.grads, nullptr, 0, nullptr, st);
   return last_error();
 }
 
@@ -1457,7 +1231,7 @@ extern "C" long long pinn_gnet_param_count(const pinn_gnet_t* net) {
 extern "C" size_t pinn_gnet_workspace_bytes(const pinn_gnet_t* net, long long n_rows, int n_passes) {
   Shape s;
   if (make_shape(net, &s) || n_rows < 0 || n_passes < 0) return 0;
-  const size_t a = train_layout(s, n_rows).end, b = infer_layout(s, n_rows, n_passes).end;
+  const size_t a = train_layout(s, n_rows, 1).end, b = infer_layout(s, n_rows, n_passes).end;
   return a > b ? a : b;
 }
 
@@ -1540,7 +1314,7 @@ extern "C" int pinn_gnet_backward(const pinn_gnet_t* net, const float* d_params,
 extern "C" size_t pinn_gnet_backward2_workspace_bytes(const pinn_gnet_t* net, long long n_rows) {
   Shape s;
   if (make_shape(net, &s) || n_rows < 0) return 0;
-  return backward2_layout(s, n_rows).end;
+  return train_layout(s, n_rows, 2).end;
 }
 
 extern "C" int pinn_gnet_backward2(const pinn_gnet_t* net, const float* d_params, const float* d_x, long long n_rows,

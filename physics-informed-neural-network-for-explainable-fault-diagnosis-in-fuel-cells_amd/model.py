@@ -477,39 +477,33 @@ class DNN(torch.nn.Module):
             d.d_bits = self._mask_bits[self._mask_pass].data_ptr()
         return d
 
+    def _grown(self, cache, query, gnet, *args):
+        """The uint8 tensor cached in attribute `cache`, grown to the bytes that the library's `query`(gnet, *args) asks for."""
+        nb = getattr(self._lib, query)(ctypes.byref(gnet), *args)
+        if nb == 0:
+            raise _lib.PinnError(query + " rejected the network")
+        work = getattr(self, cache)
+        if work is None or work.numel() < nb:
+            setattr(self, cache, None)          # free the smaller one first
+            work = torch.empty(nb, dtype=torch.uint8, device=self._flat.device)
+            setattr(self, cache, work)
+        return work
+
     def general_workspace(self, n_rows, n_passes=0):
         """Workspace of the general kernels for n_rows rows (and n_passes MC passes); cached, grown on demand."""
-        nb = self._lib.pinn_gnet_workspace_bytes(ctypes.byref(self._gnet), int(n_rows), int(n_passes))
-        if nb == 0:
-            raise _lib.PinnError("pinn_gnet_workspace_bytes rejected the network")
-        if self._gwork is None or self._gwork.numel() < nb:
-            self._gwork = None
-            self._gwork = torch.empty(nb, dtype=torch.uint8, device=self._flat.device)
-        return self._gwork
+        return self._grown("_gwork", "pinn_gnet_workspace_bytes", self._gnet, int(n_rows), int(n_passes))
 
     def _backward_net(self, n_rows):
         """(pinn_gnet_t, workspace) that pinn_gnet_backward runs on for n_rows rows: general nets their own net and workspace,
         fused / wide nets the equal-width general net and a workspace cached for the backward."""
         if self.kernels == "general":
             return self._gnet, self.general_workspace(n_rows)
-        nb = self._lib.pinn_gnet_workspace_bytes(ctypes.byref(self._bwd_gnet), int(n_rows), 0)
-        if nb == 0:
-            raise _lib.PinnError("pinn_gnet_workspace_bytes rejected the network")
-        if self._bwork is None or self._bwork.numel() < nb:
-            self._bwork = None
-            self._bwork = torch.empty(nb, dtype=torch.uint8, device=self._flat.device)
-        return self._bwd_gnet, self._bwork
+        return self._bwd_gnet, self._grown("_bwork", "pinn_gnet_workspace_bytes", self._bwd_gnet, int(n_rows), 0)
 
     def _backward2_net(self, n_rows):
         """(pinn_gnet_t, workspace) of pinn_gnet_backward2 for n_rows rows: the net of _backward_net, a workspace of its own."""
         gnet = self._gnet if self.kernels == "general" else self._bwd_gnet
-        nb = self._lib.pinn_gnet_backward2_workspace_bytes(ctypes.byref(gnet), int(n_rows))
-        if nb == 0:
-            raise _lib.PinnError("pinn_gnet_backward2_workspace_bytes rejected the network")
-        if self._b2work is None or self._b2work.numel() < nb:
-            self._b2work = None
-            self._b2work = torch.empty(nb, dtype=torch.uint8, device=self._flat.device)
-        return gnet, self._b2work
+        return gnet, self._grown("_b2work", "pinn_gnet_backward2_workspace_bytes", gnet, int(n_rows))
 
     def inject_masks(self, bits):
         """Replay recorded keep-masks (tests only). bits: int32 [n_passes, N, words] or None."""
