@@ -395,6 +395,59 @@ int pinn_results_assemble(const float* d_x, const float* d_y, const pinn_affine_
                           const float* d_a_u, const float* d_e_u, const float* d_cols, long long ld,
                           const float* d_labels, long long n_rows, double* d_out, void* stream);
 
+/* ---- risk function RF(t) and first alarm: reference script 04 (cited as 04:<line>) ---------------------------
+ * All arrays are float64.  d_arr is row-major with leading dimension ld (the 22-column results array, or any array that
+ * holds the residual columns); a column list col[] names the D <= 8 residual columns (04: res, pV, pT, pH, pO = 12..16).
+ * Positions, rows and segment starts are 64-bit.  Results do not depend on the run: every reduction has a fixed order. */
+#define PINN_RF_MAX_COLS 8
+#define PINN_RF_MAX_LAYERS 4
+#define PINN_RF_ABOVE 0      /* first position with series >= threshold */
+#define PINN_RF_BELOW 1      /* first position with series <= threshold */
+
+/* host struct, copied at call time */
+typedef struct pinn_rf_params {
+  int n_cols;                          /* D */
+  int n_layers;                        /* <= 4 */
+  int col[PINN_RF_MAX_COLS];           /* column of d_arr per residual */
+  int layer_of[PINN_RF_MAX_COLS];      /* layer of each residual, -1: in no layer */
+  double w[PINN_RF_MAX_COLS];          /* feature weights */
+  double beta[PINN_RF_MAX_LAYERS];     /* layer weights, summed in layer order */
+  double p_layer, z_safe, lambda_decay, k_logistic, c0_logistic, c_max, alpha_smooth;
+} pinn_rf_params_t;
+
+/* estimate_mu_sigma_normal (04:181-197): nanmean and nanstd(ddof=1) of the columns over the rows whose label column,
+ * truncated to an integer, is one of normal_labels[n_normal] (host array, <= 8).  A NaN removes its row from its own
+ * column only; sigma == 0 becomes 1e-6.  Two passes (mean, centred squares).  d_mu, d_sigma: [n_cols].  d_count (may be
+ * NULL): long long [9], the values counted per column and, at [8], the normal rows.  cols: host array. */
+size_t pinn_rf_stats_workspace_bytes(void);
+int pinn_rf_stats(const double* d_arr, long long ld, long long n_rows, const int* cols, int n_cols, int label_col,
+                  const long long* normal_labels, int n_normal, double* d_mu, double* d_sigma, long long* d_count,
+                  void* d_ws, size_t ws_bytes, void* stream);
+
+/* compute_rf_time_series (04:201-285) over n positions.  Position j reads row d_row_index[j] of d_arr (NULL: row j; an
+ * index outside [0, n_arr_rows) reads nothing and gives a NaN row).  d_seg_start[n_segments]: strictly ascending
+ * positions at which both recurrences restart, d_seg_start[0] == 0 (n_segments == 0: one segment).  d_carry_in (may be
+ * NULL) and d_carry_out (may be NULL): [n_segments][2] = (C, RF_smooth) before the first / at the last position of every
+ * segment.  Without carry-in C[first] = 0 (S_tot[first] unused, as the reference's loop starts at t = 1) and
+ * RF_smooth[first] = RF_inst[first]; with it C[first] = lambda C_prev + S_tot[first] and RF_smooth[first] =
+ * alpha RF_inst[first] + (1 - alpha) RF_smooth_prev.  Outputs, each [n] and each may be NULL: d_S_tot, d_C, d_RF_inst,
+ * d_RF_smooth; d_S_layers [n_layers][n].  n <= 2048 runs as one launch and needs no workspace (d_ws may be NULL,
+ * pinn_rf_workspace_bytes returns 0); otherwise five launches, the workspace holding two [n] arrays and the tile sums. */
+size_t pinn_rf_workspace_bytes(long long n_rows, long long n_segments);
+int pinn_rf_series(const double* d_arr, long long ld, long long n_arr_rows, const pinn_rf_params_t* prm,
+                   const double* d_mu, const double* d_sigma, const long long* d_row_index, long long n,
+                   const long long* d_seg_start, long long n_segments, const double* d_carry_in, double* d_S_layers,
+                   double* d_S_tot, double* d_C, double* d_RF_inst, double* d_RF_smooth, double* d_carry_out,
+                   void* d_ws, size_t ws_bytes, void* stream);
+
+/* find_first_alarm_index (04:289-300) per segment: d_first[s] = the first position, counted from the segment's start, whose
+ * value is >= (PINN_RF_ABOVE) or <= (PINN_RF_BELOW) the threshold, or -1.  NaN never matches.  Position j reads
+ * d_series[row * stride] with row = d_row_index[j] (NULL: j).  relative != 0: the threshold of a segment is the value at
+ * its first position plus `threshold` (04:389: V[0] - 0.1), read on the device. */
+int pinn_rf_first_alarm(const double* d_series, long long stride, long long n_src_rows, const long long* d_row_index,
+                        long long n, const long long* d_seg_start, long long n_segments, int mode, int relative,
+                        double threshold, long long* d_first, void* stream);
+
 int pinn_abi_version(void);
 
 #ifdef __cplusplus

@@ -4,7 +4,9 @@ Public surface mirrors the reference's `01_train_pinn_multiphysics_model.py`:
 `PhysicsInformedNN`, `DNN`, `get_MC_samples`, `create_comprehensive_results_array_v2`,
 `create_fault_labels`, `smooth_by_segments`, `_moving_average_centered`; the steps either side of the hot path:
 `load_data_normal_raw`, `load_data_fault_raw`, `combine_and_normalize_datasets`, `add_noise_to_combined_data` (ingest),
-`plot_model_results_detailed_split` (its statistics; no figure), and `save_checkpoint` / `load_checkpoint`.
+`plot_model_results_detailed_split` (its statistics; no figure), and `save_checkpoint` / `load_checkpoint`; and the
+stage after the results array, script 04's risk function: `estimate_mu_sigma_normal`, `compute_rf_time_series`,
+`find_first_alarm_index`, `compute_rf_advance_for_condition`, with `rf_advance_for_conditions` and `RiskMonitor` (risk).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -18,6 +20,8 @@ _LAZY = {
     "combine_and_normalize_datasets": "ingest",
     "model_statistics": "report", "plot_model_results_detailed_split": "report",
     "save_checkpoint": "report", "load_checkpoint": "report",
+    "estimate_mu_sigma_normal": "risk", "compute_rf_time_series": "risk", "find_first_alarm_index": "risk",
+    "compute_rf_advance_for_condition": "risk", "rf_advance_for_conditions": "risk", "rf_series": "risk", "RiskMonitor": "risk",
 }
 
 

@@ -28,6 +28,8 @@ BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC"]
 SOURCES = [
     ("pinn_residuals.hip", ["-ffp-contract=off"]),
     ("pinn_results.hip", ["-ffp-contract=off"]),
+    # float64 restatement of numpy expressions: every operation rounded on its own
+    ("pinn_risk.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

@@ -61,6 +61,17 @@ class Dropout(ctypes.Structure):
                 ("row_offset", c_ll), ("d_bits", c_void_p), ("d_step_counter", c_void_p)]
 
 
+class RFParams(ctypes.Structure):
+    """pinn_rf_params_t (pinn_risk.hip)."""
+    _fields_ = [("n_cols", c_int), ("n_layers", c_int), ("col", c_int * 8), ("layer_of", c_int * 8), ("w", ctypes.c_double * 8),
+                ("beta", ctypes.c_double * 4), ("p_layer", ctypes.c_double), ("z_safe", ctypes.c_double),
+                ("lambda_decay", ctypes.c_double), ("k_logistic", ctypes.c_double), ("c0_logistic", ctypes.c_double),
+                ("c_max", ctypes.c_double), ("alpha_smooth", ctypes.c_double)]
+
+
+RF_ABOVE, RF_BELOW, RF_TILE = 0, 1, 2048
+
+
 class PinnError(RuntimeError):
     pass
 
@@ -126,6 +137,14 @@ _SIGS = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_results_assemble": (c_int, [c_void_p, c_void_p, ctypes.POINTER(Affine), ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p]),
+    "pinn_rf_stats_workspace_bytes": (c_size_t, []),
+    "pinn_rf_stats": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_ll), c_int, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_rf_workspace_bytes": (c_size_t, [c_ll, c_ll]),
+    "pinn_rf_series": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(RFParams), c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_ll,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_rf_first_alarm": (c_int, [c_void_p, c_ll, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, ctypes.c_double, c_void_p,
+                                    c_void_p]),
 }
 
 _lib = None

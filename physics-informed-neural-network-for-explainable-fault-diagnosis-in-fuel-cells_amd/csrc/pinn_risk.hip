@@ -1,0 +1,648 @@
+// Risk function RF(t) and first-alarm search on the device (reference script 04, cited as 04:<line>):
+//   pinn_rf_stats       mu / sigma of the residual columns over the normal rows      (04:181-197)
+//   pinn_rf_series      S_tot -> decaying integral C -> logistic RF_inst -> smoothed  (04:201-285)
+//   pinn_rf_first_alarm first sample at or past a threshold, per segment              (04:289-300)
+// All arithmetic is float64 and separately rounded (built with -ffp-contract=off).
+//
+// The two recurrences  C(t) = lambda C(t-1) + S(t)  and  RF_s(t) = alpha RF(t) + (1-alpha) RF_s(t-1)  are scans over
+// (flag, multiplier, offset) triples; a flag marks a segment start and discards everything to its left.  They run as
+// reduce-then-scan: one launch reduces every 2048-row tile to one triple, a one-workgroup launch turns the triples
+// into the value entering each tile (tile order, fixed), a third launch finishes each tile.  Stream order between
+// launches is the only dependency between workgroups: no workgroup ever waits on another inside a launch.  A call of
+// at most one tile is a single launch.  Reductions are fixed-order (shuffle tree, then partials in index order): the
+// same call gives the same bytes every time.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "../../include/pinn_hip.h"
+
+namespace pinn {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kItems = 8;                       // consecutive rows per thread in the scans
+constexpr int kTile = kThreads * kItems;        // rows per workgroup
+constexpr int kPad = kTile + kTile / kItems;    // LDS image: one pad word per 8 values (conflict-free blocked reads)
+constexpr int kStatBlocks = 1024;               // upper limit of partial sums in pinn_rf_stats
+
+struct RiskDev {
+  int n_cols, n_layers, p_is_two, pad_;
+  int col[PINN_RF_MAX_COLS], layer_of[PINN_RF_MAX_COLS];
+  double w[PINN_RF_MAX_COLS], beta[PINN_RF_MAX_LAYERS];
+  double p, inv_p, z_safe, lambda, k, c0, c_max, alpha, one_minus_alpha, l0, denom;
+};
+
+struct StatsDev {
+  int n_cols, n_normal, label_col, pass;
+  int col[PINN_RF_MAX_COLS];
+  long long normal[PINN_RF_MAX_COLS];
+};
+
+// x -> f ? b : m x + b.  f is kept as a 64-bit word so that the struct has no padding in the workspace.
+struct Op {
+  double m, b;
+  long long f;
+};
+
+__device__ __forceinline__ Op op_identity() { Op o; o.m = 1.0; o.b = 0.0; o.f = 0; return o; }
+
+// "l, then r".  m is always finite (a product of multipliers), so an identity on either side changes no bit.
+__device__ __forceinline__ Op combine(const Op& l, const Op& r) {
+  Op o;
+  o.m = r.f ? r.m : r.m * l.m;
+  o.b = r.f ? r.b : r.m * l.b + r.b;
+  o.f = r.f | l.f;
+  return o;
+}
+
+__device__ __forceinline__ double apply(const Op& o, double x) { return o.f ? o.b : o.m * x + o.b; }
+
+__device__ __forceinline__ int pidx(int i) { return i + (i >> 3); }
+
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
+
+// np.clip: NaN stays NaN (fmin / fmax would return the bound)
+__device__ __forceinline__ double clip_nan(double x, double lo, double hi) {
+  if (x != x) return x;
+  x = x < lo ? lo : x;
+  return x > hi ? hi : x;
+}
+
+// segment of position j: the last s with seg_start[s] <= j; segment 0 always starts at 0
+__device__ __forceinline__ long long seg_of(const long long* __restrict__ ss, long long ns, long long j) {
+  if (!ss || ns <= 1) return 0;
+  long long lo = 0, hi = ns;
+  while (hi - lo > 1) {
+    const long long mid = (lo + hi) >> 1;
+    if (ss[mid] <= j) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ long long seg_begin(const long long* __restrict__ ss, long long s) { return (ss && s > 0) ? ss[s] : 0; }
+
+__device__ __forceinline__ long long seg_next(const long long* __restrict__ ss, long long ns, long long s, long long n) {
+  return (ss && s + 1 < ns) ? ss[s + 1] : n;
+}
+
+// Exclusive prefix of the threads' aggregates in thread order (identity for thread 0); *total = the workgroup's aggregate.
+__device__ __forceinline__ Op block_exclusive(const Op& mine, Op* s_wave, Op* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Op inc = mine;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    Op o;
+    o.m = __shfl_up(inc.m, d, 64);
+    o.b = __shfl_up(inc.b, d, 64);
+    o.f = __shfl_up(inc.f, d, 64);
+    if (lane >= d) inc = combine(o, inc);
+  }
+  Op prev;
+  prev.m = __shfl_up(inc.m, 1, 64);
+  prev.b = __shfl_up(inc.b, 1, 64);
+  prev.f = __shfl_up(inc.f, 1, 64);
+  if (lane == 0) prev = op_identity();
+  if (lane == 63) s_wave[wave] = inc;
+  __syncthreads();
+  Op pre = op_identity(), tot = op_identity();
+#pragma unroll
+  for (int w = 0; w < kThreads / 64; ++w) {
+    const Op a = s_wave[w];
+    if (w < wave) pre = combine(pre, a);
+    tot = combine(tot, a);
+  }
+  __syncthreads();                        // s_wave may be reused by the next scan
+  *total = tot;
+  return combine(pre, prev);
+}
+
+// ---- per-row instantaneous intensity S_tot (04:233-259), rows taken striped so that neighbouring lanes read neighbouring rows
+__device__ __forceinline__ void stage_s(const RiskDev& a, const double* __restrict__ arr, long long ld, long long n_arr,
+                                        const double* __restrict__ mu, const double* __restrict__ sigma,
+                                        const long long* __restrict__ ridx, long long tile0, long long n, double* __restrict__ S_out,
+                                        double* __restrict__ S_layers, double* s_val) {
+  double m[PINN_RF_MAX_COLS], sg[PINN_RF_MAX_COLS];
+#pragma unroll
+  for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+    m[d] = d < a.n_cols ? mu[d] : 0.0;
+    sg[d] = d < a.n_cols ? sigma[d] : 1.0;
+  }
+#pragma unroll 2
+  for (int k = 0; k < kItems; ++k) {
+    const int i = k * kThreads + threadIdx.x;
+    const long long j = tile0 + i;
+    if (j >= n) break;
+    const long long row = ridx ? ridx[j] : j;
+    const bool ok = row >= 0 && row < n_arr;                  // a gather index outside the array reads nothing: the row is NaN
+    const double* r = arr + (ok ? row : 0) * ld;
+    double term[PINN_RF_MAX_COLS];
+#pragma unroll
+    for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+      term[d] = 0.0;
+      if (d < a.n_cols) {
+        const double R = ok ? r[a.col[d]] : quiet_nan();
+        const double z = (R - m[d]) / sg[d];
+        const double t = fabs(z) - a.z_safe;
+        const double at = (t > 0.0 || t != t) ? t : 0.0;        // np.maximum(0, .): NaN propagates
+        term[d] = a.w[d] * (a.p_is_two ? at * at : pow(at, a.p));
+      }
+    }
+    double S = 0.0;
+#pragma unroll
+    for (int L = 0; L < PINN_RF_MAX_LAYERS; ++L) {
+      if (L < a.n_layers) {
+        double acc = 0.0;
+        bool used = false;
+#pragma unroll
+        for (int d = 0; d < PINN_RF_MAX_COLS; ++d)
+          if (d < a.n_cols && a.layer_of[d] == L) { acc = used ? acc + term[d] : term[d]; used = true; }
+        const double Sl = used ? (a.p_is_two ? sqrt(acc) : pow(acc, a.inv_p)) : 0.0;
+        if (S_layers) S_layers[(long long)L * n + j] = Sl;
+        S += a.beta[L] * Sl;
+      }
+    }
+    if (S_out) S_out[j] = S;
+    s_val[pidx(i)] = S;
+  }
+}
+
+// striped global <-> LDS image <-> blocked registers
+__device__ __forceinline__ void load_tile(const double* __restrict__ src, long long tile0, long long n, double* s_val) {
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) {
+    const int i = k * kThreads + threadIdx.x;
+    if (tile0 + i < n) s_val[pidx(i)] = src[tile0 + i];
+  }
+}
+
+__device__ __forceinline__ void store_tile(const double v[kItems], double* __restrict__ dst, long long tile0, long long n, double* s_val) {
+  __syncthreads();                        // every blocked read of the previous image is done
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) s_val[pidx(threadIdx.x * kItems + k)] = v[k];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) {
+    const int i = k * kThreads + threadIdx.x;
+    if (tile0 + i < n) dst[tile0 + i] = s_val[pidx(i)];
+  }
+}
+
+__device__ __forceinline__ void blocked_from_lds(const double* s_val, double v[kItems]) {
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) v[k] = s_val[pidx(threadIdx.x * kItems + k)];
+}
+
+// One tile of one recurrence.  WHICH 0: C from S (04:262-264), WHICH 1: RF_smooth from RF_inst (04:276-279).
+// `entering` is the value of the recurrence just before the tile (ignored where a segment starts).  With agg_only the
+// tile's aggregate is all that is produced.  The 8 values of a thread are then advanced with the reference's own
+// expression, so inside a thread's run the operation sequence is the sequential loop's.
+template <int WHICH>
+__device__ __forceinline__ Op tile_recurrence(const RiskDev& a, const double v[kItems], long long tile0, long long n,
+                                              const long long* __restrict__ ss, long long ns, const double* __restrict__ cin,
+                                              double* __restrict__ cout, double entering, bool agg_only, Op* s_wave,
+                                              double out[kItems]) {
+  const long long j0 = tile0 + (long long)threadIdx.x * kItems;
+  Op ops[kItems];
+  long long seg[kItems];
+  bool last[kItems];
+  long long s = 0, begin = 0, next = n;
+  if (j0 < n) {
+    s = seg_of(ss, ns, j0);
+    begin = seg_begin(ss, s);
+    next = seg_next(ss, ns, s, n);
+  }
+  Op agg = op_identity();
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) {
+    const long long j = j0 + k;
+    ops[k] = op_identity();
+    seg[k] = 0;
+    last[k] = false;
+    if (j < n) {
+      while (j >= next && s + 1 < ns) {
+        ++s;
+        begin = seg_begin(ss, s);
+        next = seg_next(ss, ns, s, n);
+      }
+      Op o;
+      if (j == begin) {
+        o.f = 1;
+        o.m = 0.0;
+        if (WHICH == 0) o.b = cin ? a.lambda * cin[2 * s] + v[k] : 0.0;               // 04:262-263: C[0] = 0, S_tot[0] unused
+        else o.b = cin ? a.alpha * v[k] + a.one_minus_alpha * cin[2 * s + 1] : v[k];    // 04:277
+      } else {
+        o.f = 0;
+        o.m = WHICH == 0 ? a.lambda : a.one_minus_alpha;
+        o.b = WHICH == 0 ? v[k] : a.alpha * v[k];
+      }
+      ops[k] = o;
+      seg[k] = s;
+      last[k] = j + 1 == next || j + 1 == n;
+      agg = combine(agg, o);
+    }
+  }
+  Op total;
+  const Op excl = block_exclusive(agg, s_wave, &total);
+  if (agg_only) return total;
+  double x = apply(excl, entering);
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) {
+    x = apply(ops[k], x);
+    out[k] = x;
+    if (last[k] && cout) cout[2 * seg[k] + WHICH] = x;
+  }
+  return total;
+}
+
+__device__ __forceinline__ double rf_inst(const RiskDev& a, double C) {
+  const double cc = clip_nan(C, 0.0, a.c_max);
+  const double L = 1.0 / (1.0 + exp(-a.k * (cc - a.c0)));
+  return clip_nan((L - a.l0) / a.denom, 0.0, 1.0);
+}
+
+#define RF_ROWS_ARGS                                                                                                         \
+  const double *__restrict__ arr, long long ld, long long n_arr, const double *__restrict__ mu, const double *__restrict__ sigma, \
+      const long long *__restrict__ ridx, long long n, const long long *__restrict__ ss, long long ns, const double *__restrict__ cin
+
+// n <= kTile: everything in one workgroup and one launch (the monitor's chunk)
+__global__ __launch_bounds__(kThreads) void rf_single_kernel(RiskDev a, RF_ROWS_ARGS, double* __restrict__ S_layers,
+                                                              double* __restrict__ S_out, double* __restrict__ C_out,
+                                                              double* __restrict__ RF_out, double* __restrict__ RFs_out,
+                                                              double* __restrict__ cout) {
+  __shared__ double s_val[kPad];
+  __shared__ Op s_wave[kThreads / 64];
+  stage_s(a, arr, ld, n_arr, mu, sigma, ridx, 0, n, S_out, S_layers, s_val);
+  __syncthreads();
+  double v[kItems], c[kItems], rf[kItems], rs[kItems];
+  blocked_from_lds(s_val, v);
+  tile_recurrence<0>(a, v, 0, n, ss, ns, cin, cout, 0.0, false, s_wave, c);
+  if (C_out) store_tile(c, C_out, 0, n, s_val);
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) rf[k] = rf_inst(a, c[k]);
+  if (RF_out) store_tile(rf, RF_out, 0, n, s_val);
+  tile_recurrence<1>(a, rf, 0, n, ss, ns, cin, cout, 0.0, false, s_wave, rs);
+  if (RFs_out) store_tile(rs, RFs_out, 0, n, s_val);
+}
+
+// pass 1: S_tot of every row (stored) and the tile aggregates of the C recurrence
+__global__ __launch_bounds__(kThreads) void rf_pass1_kernel(RiskDev a, RF_ROWS_ARGS, double* __restrict__ S_layers,
+                                                             double* __restrict__ S_out, Op* __restrict__ agg) {
+  __shared__ double s_val[kPad];
+  __shared__ Op s_wave[kThreads / 64];
+  const long long tile0 = (long long)blockIdx.x * kTile;
+  stage_s(a, arr, ld, n_arr, mu, sigma, ridx, tile0, n, S_out, S_layers, s_val);
+  __syncthreads();
+  double v[kItems], unused[kItems];
+  blocked_from_lds(s_val, v);
+  const Op total = tile_recurrence<0>(a, v, tile0, n, ss, ns, cin, nullptr, 0.0, true, s_wave, unused);
+  if (threadIdx.x == 0) agg[blockIdx.x] = total;
+}
+
+// the value entering every tile, from the tile aggregates in tile order: one workgroup, each thread a run of consecutive tiles
+__global__ __launch_bounds__(kThreads) void rf_carry_kernel(const Op* __restrict__ agg, long long n_tiles, double* __restrict__ entering) {
+  __shared__ Op s_wave[kThreads / 64];
+  const long long chunk = (n_tiles + kThreads - 1) / kThreads;
+  const long long t0 = (long long)threadIdx.x * chunk;
+  const long long t1 = t0 + chunk < n_tiles ? t0 + chunk : n_tiles;
+  Op mine = op_identity();
+  for (long long t = t0; t < t1; ++t) mine = combine(mine, agg[t]);
+  Op total;
+  const Op excl = block_exclusive(mine, s_wave, &total);
+  double x = apply(excl, 0.0);          // tile 0 begins with a segment start, so this 0 never reaches a result
+  for (long long t = t0; t < t1; ++t) {
+    entering[t] = x;
+    x = apply(agg[t], x);
+  }
+}
+
+// pass 2: finish C, the pointwise logistic, and the tile aggregates of the smoothing recurrence
+__global__ __launch_bounds__(kThreads) void rf_pass2_kernel(RiskDev a, const double* __restrict__ S_in, long long n,
+                                                             const long long* __restrict__ ss, long long ns,
+                                                             const double* __restrict__ cin, const double* __restrict__ entering,
+                                                             double* __restrict__ C_out, double* __restrict__ RF_out,
+                                                             double* __restrict__ cout, Op* __restrict__ agg) {
+  __shared__ double s_val[kPad];
+  __shared__ Op s_wave[kThreads / 64];
+  const long long tile0 = (long long)blockIdx.x * kTile;
+  load_tile(S_in, tile0, n, s_val);
+  __syncthreads();
+  double v[kItems], c[kItems], rf[kItems], unused[kItems];
+  blocked_from_lds(s_val, v);
+  tile_recurrence<0>(a, v, tile0, n, ss, ns, cin, cout, entering[blockIdx.x], false, s_wave, c);
+  if (C_out) store_tile(c, C_out, tile0, n, s_val);
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) rf[k] = rf_inst(a, c[k]);
+  store_tile(rf, RF_out, tile0, n, s_val);
+  const Op total = tile_recurrence<1>(a, rf, tile0, n, ss, ns, cin, nullptr, 0.0, true, s_wave, unused);
+  if (threadIdx.x == 0) agg[blockIdx.x] = total;
+}
+
+// pass 3: finish RF_smooth
+__global__ __launch_bounds__(kThreads) void rf_pass3_kernel(RiskDev a, const double* __restrict__ RF_in, long long n,
+                                                             const long long* __restrict__ ss, long long ns,
+                                                             const double* __restrict__ cin, const double* __restrict__ entering,
+                                                             double* __restrict__ RFs_out, double* __restrict__ cout) {
+  __shared__ double s_val[kPad];
+  __shared__ Op s_wave[kThreads / 64];
+  const long long tile0 = (long long)blockIdx.x * kTile;
+  load_tile(RF_in, tile0, n, s_val);
+  __syncthreads();
+  double v[kItems], rs[kItems];
+  blocked_from_lds(s_val, v);
+  tile_recurrence<1>(a, v, tile0, n, ss, ns, cin, cout, entering[blockIdx.x], false, s_wave, rs);
+  if (RFs_out) store_tile(rs, RFs_out, tile0, n, s_val);
+}
+
+// ---- first alarm: only the first position of a run of matches (or a matching segment start) reaches the atomic
+__global__ void alarm_init_kernel(unsigned long long* out, long long ns) {
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (i < ns) out[i] = ~0ull;           // reads as -1 (no alarm) when nothing lowers it
+}
+
+__device__ __forceinline__ double alarm_value(const double* __restrict__ series, long long stride, long long n_src,
+                                              const long long* __restrict__ ridx, long long j) {
+  const long long row = ridx ? ridx[j] : j;
+  return (row >= 0 && row < n_src) ? series[row * stride] : quiet_nan();
+}
+
+__global__ __launch_bounds__(kThreads) void alarm_kernel(const double* __restrict__ series, long long stride, long long n_src,
+                                                          const long long* __restrict__ ridx, long long n,
+                                                          const long long* __restrict__ ss, long long ns, int below, int relative,
+                                                          double thr, unsigned long long* __restrict__ out) {
+  const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (j >= n) return;
+  const long long s = seg_of(ss, ns, j);
+  long long begin = seg_begin(ss, s);
+  if (begin > j) begin = j;
+  const double t = relative ? alarm_value(series, stride, n_src, ridx, begin) + thr : thr;
+  const double v = alarm_value(series, stride, n_src, ridx, j);
+  const bool hit = below ? v <= t : v >= t;          // NaN never matches
+  if (!hit) return;
+  if (j > begin) {
+    const double pv = alarm_value(series, stride, n_src, ridx, j - 1);
+    if (below ? pv <= t : pv >= t) return;           // an earlier position of this segment matches as well
+  }
+  atomicMin(out + s, (unsigned long long)(j - begin));
+}
+
+// ---- mu / sigma over the normal rows: per-workgroup partials, then one workgroup sums them in index order
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+  return v;
+}
+
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+  return v;
+}
+
+// sums s[8] and counts c[9] of the workgroup, valid in thread 0
+__device__ __forceinline__ void block_sums(double s[PINN_RF_MAX_COLS], long long c[PINN_RF_MAX_COLS + 1], double* s_d, long long* s_c) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+    const double v = wave_sum(s[d]);
+    if (lane == 0) s_d[wave * PINN_RF_MAX_COLS + d] = v;
+  }
+#pragma unroll
+  for (int d = 0; d <= PINN_RF_MAX_COLS; ++d) {
+    const long long v = wave_sum(c[d]);
+    if (lane == 0) s_c[wave * (PINN_RF_MAX_COLS + 1) + d] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+      double v = s_d[d];
+      for (int w = 1; w < kThreads / 64; ++w) v += s_d[w * PINN_RF_MAX_COLS + d];
+      s[d] = v;
+    }
+    for (int d = 0; d <= PINN_RF_MAX_COLS; ++d) {
+      long long v = s_c[d];
+      for (int w = 1; w < kThreads / 64; ++w) v += s_c[w * (PINN_RF_MAX_COLS + 1) + d];
+      c[d] = v;
+    }
+  }
+}
+
+// pass 0: sums of the values; pass 1: sums of the squares centred on mu (numpy's two-pass nanstd)
+__global__ __launch_bounds__(kThreads) void stats_partial_kernel(StatsDev a, const double* __restrict__ arr, long long ld, long long n,
+                                                                  const double* __restrict__ mu, double* __restrict__ part,
+                                                                  long long* __restrict__ cpart) {
+  __shared__ double s_d[(kThreads / 64) * PINN_RF_MAX_COLS];
+  __shared__ long long s_c[(kThreads / 64) * (PINN_RF_MAX_COLS + 1)];
+  double s[PINN_RF_MAX_COLS], m[PINN_RF_MAX_COLS];
+  long long c[PINN_RF_MAX_COLS + 1];
+#pragma unroll
+  for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+    s[d] = 0.0;
+    c[d] = 0;
+    m[d] = (a.pass == 1 && d < a.n_cols) ? mu[d] : 0.0;
+  }
+  c[PINN_RF_MAX_COLS] = 0;
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
+    const double* r = arr + i * ld;
+    const double lab = r[a.label_col];
+    if (lab != lab) continue;
+    const long long li = (long long)lab;               // astype(int): truncation
+    bool normal = false;
+    for (int q = 0; q < a.n_normal; ++q) normal = normal || li == a.normal[q];
+    if (!normal) continue;
+    ++c[PINN_RF_MAX_COLS];
+#pragma unroll
+    for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+      if (d < a.n_cols) {
+        const double v = r[a.col[d]];
+        if (v == v) {                                   // a NaN leaves this column only
+          const double dv = v - m[d];
+          s[d] += a.pass == 1 ? dv * dv : v;
+          ++c[d];
+        }
+      }
+    }
+  }
+  block_sums(s, c, s_d, s_c);
+  if (threadIdx.x == 0) {
+    for (int d = 0; d < PINN_RF_MAX_COLS; ++d) part[(long long)blockIdx.x * PINN_RF_MAX_COLS + d] = s[d];
+    for (int d = 0; d <= PINN_RF_MAX_COLS; ++d) cpart[(long long)blockIdx.x * (PINN_RF_MAX_COLS + 1) + d] = c[d];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void stats_final_kernel(StatsDev a, const double* __restrict__ part, const long long* __restrict__ cpart,
+                                                                int n_part, double* __restrict__ mu, double* __restrict__ sigma,
+                                                                long long* __restrict__ count) {
+  __shared__ double s_d[(kThreads / 64) * PINN_RF_MAX_COLS];
+  __shared__ long long s_c[(kThreads / 64) * (PINN_RF_MAX_COLS + 1)];
+  double s[PINN_RF_MAX_COLS];
+  long long c[PINN_RF_MAX_COLS + 1];
+#pragma unroll
+  for (int d = 0; d < PINN_RF_MAX_COLS; ++d) { s[d] = 0.0; c[d] = 0; }
+  c[PINN_RF_MAX_COLS] = 0;
+  for (int g = threadIdx.x; g < n_part; g += kThreads) {
+#pragma unroll
+    for (int d = 0; d < PINN_RF_MAX_COLS; ++d) s[d] += part[(long long)g * PINN_RF_MAX_COLS + d];
+#pragma unroll
+    for (int d = 0; d <= PINN_RF_MAX_COLS; ++d) c[d] += cpart[(long long)g * (PINN_RF_MAX_COLS + 1) + d];
+  }
+  block_sums(s, c, s_d, s_c);
+  if (threadIdx.x == 0) {
+    for (int d = 0; d < a.n_cols; ++d) {
+      if (a.pass == 0) {
+        mu[d] = s[d] / (double)c[d];                    // 0 / 0 = NaN for a column without values, as nanmean
+      } else {
+        double sg = c[d] > 1 ? sqrt(s[d] / (double)(c[d] - 1)) : quiet_nan();      // ddof = 1
+        if (sg == 0.0) sg = 1e-6;                       // 04:196
+        sigma[d] = sg;
+      }
+    }
+    if (a.pass == 0 && count)
+      for (int d = 0; d <= PINN_RF_MAX_COLS; ++d) count[d] = c[d];
+  }
+}
+
+inline bool misaligned8(const void* p) { return ((unsigned long long)p & 7) != 0; }
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+inline long long n_tiles_of(long long n) { return (n + kTile - 1) / kTile; }
+
+}  // namespace
+}  // namespace pinn
+
+extern "C" size_t pinn_rf_stats_workspace_bytes(void) {
+  return (size_t)pinn::kStatBlocks * (PINN_RF_MAX_COLS * sizeof(double) + (PINN_RF_MAX_COLS + 1) * sizeof(long long));
+}
+
+extern "C" int pinn_rf_stats(const double* d_arr, long long ld, long long n_rows, const int* cols, int n_cols, int label_col,
+                             const long long* normal_labels, int n_normal, double* d_mu, double* d_sigma, long long* d_count,
+                             void* d_ws, size_t ws_bytes, void* stream) {
+  using namespace pinn;
+  if (n_rows < 0 || ld < 1 || !cols || n_cols < 1 || n_cols > PINN_RF_MAX_COLS || !normal_labels || n_normal < 1 ||
+      n_normal > PINN_RF_MAX_COLS || label_col < 0 || label_col >= ld)
+    return PINN_E_ARG;
+  for (int d = 0; d < n_cols; ++d)
+    if (cols[d] < 0 || cols[d] >= ld) return PINN_E_ARG;
+  if (!d_mu || !d_sigma || !d_ws || (n_rows > 0 && !d_arr)) return PINN_E_ARG;
+  if (misaligned8(d_arr) || misaligned8(d_mu) || misaligned8(d_sigma) || misaligned8(d_count) || misaligned8(d_ws)) return PINN_E_ARG;
+  if (ws_bytes < pinn_rf_stats_workspace_bytes()) return PINN_E_WORKSPACE;
+  StatsDev a;
+  a.n_cols = n_cols; a.n_normal = n_normal; a.label_col = label_col;
+  for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+    a.col[d] = d < n_cols ? cols[d] : 0;
+    a.normal[d] = d < n_normal ? normal_labels[d] : 0;
+  }
+  long long blocks = (n_rows + kThreads - 1) / kThreads;
+  blocks = blocks < 1 ? 1 : (blocks > kStatBlocks ? kStatBlocks : blocks);
+  double* part = static_cast<double*>(d_ws);
+  long long* cpart = reinterpret_cast<long long*>(part + (size_t)kStatBlocks * PINN_RF_MAX_COLS);
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();
+  for (int pass = 0; pass < 2; ++pass) {
+    a.pass = pass;
+    hipLaunchKernelGGL(stats_partial_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, a, d_arr, ld, n_rows, d_mu, part, cpart);
+    hipLaunchKernelGGL(stats_final_kernel, dim3(1), dim3(kThreads), 0, st, a, part, cpart, (int)blocks, d_mu, d_sigma, d_count);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+extern "C" size_t pinn_rf_workspace_bytes(long long n_rows, long long n_segments) {
+  using namespace pinn;
+  (void)n_segments;                       // segments cost no workspace: starts are looked up, not expanded into flags
+  if (n_rows <= kTile) return 0;          // a single launch needs none
+  const size_t t = (size_t)n_tiles_of(n_rows);
+  return 2 * align256((size_t)n_rows * sizeof(double)) + 2 * align256(t * sizeof(Op)) + 2 * align256(t * sizeof(double));
+}
+
+extern "C" int pinn_rf_series(const double* d_arr, long long ld, long long n_arr_rows, const pinn_rf_params_t* prm,
+                              const double* d_mu, const double* d_sigma, const long long* d_row_index, long long n,
+                              const long long* d_seg_start, long long n_segments, const double* d_carry_in, double* d_S_layers,
+                              double* d_S_tot, double* d_C, double* d_RF_inst, double* d_RF_smooth, double* d_carry_out,
+                              void* d_ws, size_t ws_bytes, void* stream) {
+  using namespace pinn;
+  if (!prm || n < 0 || n_arr_rows < 0 || ld < 1 || n_segments < 0 || (n_segments > 0 && !d_seg_start)) return PINN_E_ARG;
+  if (prm->n_cols < 1 || prm->n_cols > PINN_RF_MAX_COLS || prm->n_layers < 0 || prm->n_layers > PINN_RF_MAX_LAYERS) return PINN_E_ARG;
+  for (int d = 0; d < prm->n_cols; ++d)
+    if (prm->col[d] < 0 || prm->col[d] >= ld || prm->layer_of[d] >= prm->n_layers || !isfinite(prm->w[d])) return PINN_E_ARG;
+  const double scal[7] = {prm->p_layer, prm->z_safe, prm->lambda_decay, prm->k_logistic, prm->c0_logistic, prm->c_max, prm->alpha_smooth};
+  for (double v : scal)
+    if (!isfinite(v)) return PINN_E_ARG;
+  if (prm->p_layer == 0.0) return PINN_E_ARG;
+  if (d_row_index == nullptr && n > n_arr_rows) return PINN_E_ARG;
+  if (n == 0) return PINN_OK;
+  if (!d_arr || !d_mu || !d_sigma) return PINN_E_ARG;
+  if (misaligned8(d_arr) || misaligned8(d_mu) || misaligned8(d_sigma) || misaligned8(d_row_index) || misaligned8(d_seg_start) ||
+      misaligned8(d_carry_in) || misaligned8(d_S_layers) || misaligned8(d_S_tot) || misaligned8(d_C) || misaligned8(d_RF_inst) ||
+      misaligned8(d_RF_smooth) || misaligned8(d_carry_out) || misaligned8(d_ws))
+    return PINN_E_ARG;
+  const long long ns = n_segments > 0 ? n_segments : 1;
+  RiskDev a;
+  a.n_cols = prm->n_cols; a.n_layers = prm->n_layers; a.p_is_two = prm->p_layer == 2.0; a.pad_ = 0;
+  for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+    const bool in = d < prm->n_cols;
+    a.col[d] = in ? prm->col[d] : 0;
+    a.layer_of[d] = in ? prm->layer_of[d] : -1;
+    a.w[d] = in ? prm->w[d] : 0.0;
+  }
+  for (int l = 0; l < PINN_RF_MAX_LAYERS; ++l) a.beta[l] = l < prm->n_layers ? prm->beta[l] : 0.0;
+  a.p = prm->p_layer; a.inv_p = 1.0 / prm->p_layer; a.z_safe = prm->z_safe; a.lambda = prm->lambda_decay;
+  a.k = prm->k_logistic; a.c0 = prm->c0_logistic; a.c_max = prm->c_max;
+  a.alpha = prm->alpha_smooth; a.one_minus_alpha = 1.0 - prm->alpha_smooth;
+  a.l0 = 1.0 / (1.0 + exp(-a.k * (0.0 - a.c0)));                                   // 04:268-270
+  const double l_max = 1.0 / (1.0 + exp(-a.k * (a.c_max - a.c0)));
+  a.denom = (l_max - a.l0) != 0.0 ? (l_max - a.l0) : 1e-6;
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();
+  if (n <= kTile) {
+    hipLaunchKernelGGL(rf_single_kernel, dim3(1), dim3(kThreads), 0, st, a, d_arr, ld, n_arr_rows, d_mu, d_sigma, d_row_index, n,
+                       d_seg_start, ns, d_carry_in, d_S_layers, d_S_tot, d_C, d_RF_inst, d_RF_smooth, d_carry_out);
+  } else {
+    if (!d_ws) return PINN_E_ARG;
+    if (ws_bytes < pinn_rf_workspace_bytes(n, ns)) return PINN_E_WORKSPACE;
+    const long long tiles = n_tiles_of(n);
+    if (tiles > 0x7fffffffLL) return PINN_E_ARG;
+    char* w = static_cast<char*>(d_ws);
+    double* s_buf = reinterpret_cast<double*>(w); w += align256((size_t)n * sizeof(double));
+    double* rf_buf = reinterpret_cast<double*>(w); w += align256((size_t)n * sizeof(double));
+    Op* agg_c = reinterpret_cast<Op*>(w); w += align256((size_t)tiles * sizeof(Op));
+    Op* agg_r = reinterpret_cast<Op*>(w); w += align256((size_t)tiles * sizeof(Op));
+    double* ent_c = reinterpret_cast<double*>(w); w += align256((size_t)tiles * sizeof(double));
+    double* ent_r = reinterpret_cast<double*>(w);
+    double* S = d_S_tot ? d_S_tot : s_buf;
+    double* RF = d_RF_inst ? d_RF_inst : rf_buf;
+    const dim3 grid((unsigned)tiles), block(kThreads);
+    hipLaunchKernelGGL(rf_pass1_kernel, grid, block, 0, st, a, d_arr, ld, n_arr_rows, d_mu, d_sigma, d_row_index, n, d_seg_start, ns,
+                       d_carry_in, d_S_layers, S, agg_c);
+    hipLaunchKernelGGL(rf_carry_kernel, dim3(1), block, 0, st, agg_c, tiles, ent_c);
+    hipLaunchKernelGGL(rf_pass2_kernel, grid, block, 0, st, a, S, n, d_seg_start, ns, d_carry_in, ent_c, d_C, RF, d_carry_out, agg_r);
+    hipLaunchKernelGGL(rf_carry_kernel, dim3(1), block, 0, st, agg_r, tiles, ent_r);
+    hipLaunchKernelGGL(rf_pass3_kernel, grid, block, 0, st, a, RF, n, d_seg_start, ns, d_carry_in, ent_r, d_RF_smooth, d_carry_out);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+extern "C" int pinn_rf_first_alarm(const double* d_series, long long stride, long long n_src_rows, const long long* d_row_index,
+                                   long long n, const long long* d_seg_start, long long n_segments, int mode, int relative,
+                                   double threshold, long long* d_first, void* stream) {
+  using namespace pinn;
+  if (n < 0 || n_src_rows < 0 || stride < 1 || n_segments < 0 || (n_segments > 0 && !d_seg_start) || !d_first) return PINN_E_ARG;
+  if (mode != PINN_RF_ABOVE && mode != PINN_RF_BELOW) return PINN_E_ARG;
+  if (threshold != threshold) return PINN_E_ARG;
+  if (d_row_index == nullptr && n > n_src_rows) return PINN_E_ARG;
+  if (n > 0 && !d_series) return PINN_E_ARG;
+  if (misaligned8(d_series) || misaligned8(d_row_index) || misaligned8(d_seg_start) || misaligned8(d_first)) return PINN_E_ARG;
+  const long long ns = n_segments > 0 ? n_segments : 1;
+  const long long blocks = (n + kThreads - 1) / kThreads;
+  if (blocks > 0x7fffffffLL || (ns + kThreads - 1) / kThreads > 0x7fffffffLL) return PINN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(d_first);
+  hipLaunchKernelGGL(alarm_init_kernel, dim3((unsigned)((ns + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, out, ns);
+  if (n > 0)
+    hipLaunchKernelGGL(alarm_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, d_series, stride, n_src_rows, d_row_index, n,
+                       d_seg_start, ns, mode == PINN_RF_BELOW ? 1 : 0, relative ? 1 : 0, threshold, out);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}

@@ -69,10 +69,11 @@ def create_fault_labels(n_samples, data_info, verbose=False):
     return fault_labels
 
 
-def create_comprehensive_results_array_v2(model, dataset, mc_times=2000, dropout=0.2):
+def create_comprehensive_results_array_v2(model, dataset, mc_times=2000, dropout=0.2, device_output=False):
     """01:1877-2010.  Accepts the 7- or 9-tuple dataset (01:1900-1903); returns float64 [N, 22]:
     0-7 inputs, 8 y_true, 9 y_pred, 10 ale (smoothed), 11 epi (smoothed), 12 y_true - y_pred,
-    13 f_V, 14 f_T, 15 f_H2, 16 f_O2, 17 label, 18 V_phys*5, 19 T_phys, 20 ratio_H, 21 ratio_O."""
+    13 f_V, 14 f_T, 15 f_H2, 16 f_O2, 17 label, 18 V_phys*5, 19 T_phys, 20 ratio_H, 21 ratio_O.
+    device_output=True (not in the reference) returns the device tensor, so that pinn_amd.risk continues without a host copy."""
     if len(dataset) == 9:
         x_train, y_train, x_val, y_val, x_test, y_test, scaler_X, scaler_Y, data_info = dataset
     else:
@@ -120,4 +121,4 @@ def create_comprehensive_results_array_v2(model, dataset, mc_times=2000, dropout
         pred_mean.data_ptr(), a_u.data_ptr(), e_u.data_ptr(), cols.data_ptr(), n_samples, labels.data_ptr(), n_samples,
         out.data_ptr(), torch.cuda.current_stream().cuda_stream)
     _lib.check(rc, "pinn_results_assemble")
-    return out.cpu().numpy()
+    return out if device_output else out.cpu().numpy()
