@@ -448,6 +448,75 @@ int pinn_rf_first_alarm(const double* d_series, long long stride, long long n_sr
                         long long n, const long long* d_seg_start, long long n_segments, int mode, int relative,
                         double threshold, long long* d_first, void* stream);
 
+/* ---- Gaussian-mixture fault diagnosis: reference script 03 (cited as 03:<line>) ---------------------------------
+ * A full-covariance mixture of n_comp <= 32 components over n_feat <= 8 columns, float64 throughout.  Rows are read in
+ * place: position j reads row d_row_index[j] of d_arr (NULL: row j; an index outside [0, n_arr_rows) reads nothing,
+ * adds nothing to a sum and gives NaN outputs), columns cols[n_feat] (host array) of a row-major array with leading
+ * dimension ld.  Every reduction has a fixed order: the same call gives the same bytes.
+ *
+ * The model lives in a device-resident state block of pinn_gmm_state_bytes() bytes, 8-byte words:
+ *   [PINN_GMM_ST_ITER] iterations done, [.._CONVERGED] 1 once |change| < tol, [.._STATUS] 0 or PINN_GMM_SINGULAR,
+ *   [.._K], [.._D] (64-bit integers); [.._LOWER] lower bound, [.._PREV] the one before, [.._CHANGE] their difference
+ *   (doubles); then weights[K], means[K][D], covariances[K][D][D], precisions_cholesky[K][D][D] (upper triangular, as
+ *   scikit-learn's attribute of that name), log-determinants of precisions_cholesky [K].
+ * A caller may also fill the block itself (means_init / precisions_init, k-means centres).  Once CONVERGED or STATUS is
+ * set, every later launch of pinn_gmm_em / pinn_gmm_kmeans returns at once and leaves the parameters untouched.  A
+ * covariance that is not positive definite sets STATUS and is not stored: the block keeps the last good parameters.
+ * After pinn_gmm_mstep_init and pinn_gmm_em the workspace begins with the summed moments of the last pass,
+ * [K][1 + D + D (D + 1) / 2] = (sum r, sum r d_i, sum r d_i d_j for i <= j, by columns j) with d = x - the mean the pass
+ * started from. */
+#define PINN_GMM_MAX_COMP 32
+#define PINN_GMM_MAX_FEAT 8
+#define PINN_GMM_MAX_CLASSES 16
+#define PINN_GMM_SINGULAR 1
+#define PINN_GMM_ST_ITER 0
+#define PINN_GMM_ST_CONVERGED 1
+#define PINN_GMM_ST_STATUS 2
+#define PINN_GMM_ST_K 3
+#define PINN_GMM_ST_D 4
+#define PINN_GMM_ST_LOWER 5
+#define PINN_GMM_ST_PREV 6
+#define PINN_GMM_ST_CHANGE 7
+
+size_t pinn_gmm_state_bytes(int n_comp, int n_feat);                       /* 0 for sizes outside the limits */
+size_t pinn_gmm_workspace_bytes(long long n_rows, int n_comp, int n_feat);
+
+/* scikit-learn's _initialize: parameters from responsibilities d_resp [n][n_comp] or from one label per position d_labels
+ * (one-hot; exactly one of the two is non-NULL): n_k = sum r + 10 eps, means, covariances about them (two passes)
+ * + reg_covar on the diagonal, weights n_k / n.  Resets the header (iterations 0, lower bound -inf). */
+int pinn_gmm_mstep_init(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                        const long long* d_row_index, long long n, int n_comp, const double* d_resp,
+                        const long long* d_labels, double reg_covar, double* d_state, void* d_ws, size_t ws_bytes,
+                        void* stream);
+
+/* n_iters EM iterations, two launches each and no host synchronisation: E-step with the state's parameters fused with
+ * the moment sums, then the M-step (weights n_k / sum n_k), Cholesky, lower bound = mean log_prob_norm of that E-step,
+ * and scikit-learn's test |lower bound - previous| < tol, which sets CONVERGED after the M-step of that iteration. */
+int pinn_gmm_em(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                const long long* d_row_index, long long n, int n_comp, int n_iters, double tol, double reg_covar,
+                double* d_state, void* d_ws, size_t ws_bytes, void* stream);
+
+/* n_iters Lloyd iterations on the state's means as centres (nearest centre, the first of equals; an empty cluster keeps
+ * its centre; CONVERGED once no centre moves; LOWER = inertia).  d_labels (may be NULL): the assignment to the final centres. */
+int pinn_gmm_kmeans(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                    const long long* d_row_index, long long n, int n_comp, int n_iters, double* d_state, long long* d_labels,
+                    void* d_ws, size_t ws_bytes, void* stream);
+
+/* Label-posterior mapping (03:394-414): d_map [n_comp][n_classes] = sum over positions of responsibility x
+ * one-hot(d_class[j]) (a class outside [0, n_classes) adds nothing), normalised per component; 1 / n_classes where a
+ * component's sum is not positive.  n_classes <= 16. */
+int pinn_gmm_label_map(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                       const long long* d_row_index, long long n, int n_comp, const double* d_state, const long long* d_class,
+                       int n_classes, double* d_map, void* d_ws, size_t ws_bytes, void* stream);
+
+/* One launch.  Outputs, each may be NULL: d_log_prob_norm [n] (score_samples), d_resp [n][n_comp] (predict_proba) and,
+ * with d_map [n_comp][n_classes]: d_y_prob [n][n_classes] = clip(resp @ map, 1e-12, 1) renormalised (03:418-421) and
+ * d_y_pred [n] its first maximum. */
+int pinn_gmm_posterior(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                       const long long* d_row_index, long long n, int n_comp, const double* d_state, const double* d_map,
+                       int n_classes, double* d_log_prob_norm, double* d_resp, double* d_y_prob, long long* d_y_pred,
+                       void* stream);
+
 int pinn_abi_version(void);
 
 #ifdef __cplusplus

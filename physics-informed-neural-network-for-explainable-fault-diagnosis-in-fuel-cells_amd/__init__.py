@@ -6,7 +6,9 @@ Public surface mirrors the reference's `01_train_pinn_multiphysics_model.py`:
 `load_data_normal_raw`, `load_data_fault_raw`, `combine_and_normalize_datasets`, `add_noise_to_combined_data` (ingest),
 `plot_model_results_detailed_split` (its statistics; no figure), and `save_checkpoint` / `load_checkpoint`; and the
 stage after the results array, script 04's risk function: `estimate_mu_sigma_normal`, `compute_rf_time_series`,
-`find_first_alarm_index`, `compute_rf_advance_for_condition`, with `rf_advance_for_conditions` and `RiskMonitor` (risk).
+`find_first_alarm_index`, `compute_rf_advance_for_condition`, with `rf_advance_for_conditions` and `RiskMonitor` (risk); and script 03's Gaussian-mixture
+fault diagnosis: `fit_gmm_and_get_probabilities`, `extract_X_y`, the spec parsers, with `DeviceGMM`, `FaultDiagnoser` and
+`classification_metrics` (diagnosis).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -22,6 +24,9 @@ _LAZY = {
     "save_checkpoint": "report", "load_checkpoint": "report",
     "estimate_mu_sigma_normal": "risk", "compute_rf_time_series": "risk", "find_first_alarm_index": "risk",
     "compute_rf_advance_for_condition": "risk", "rf_advance_for_conditions": "risk", "rf_series": "risk", "RiskMonitor": "risk",
+    "DeviceGMM": "diagnosis", "FaultDiagnoser": "diagnosis", "fit_gmm_and_get_probabilities": "diagnosis",
+    "classification_metrics": "diagnosis", "extract_X_y": "diagnosis", "parse_features": "diagnosis",
+    "parse_group_spec": "diagnosis", "build_label_mapper": "diagnosis", "normalize_feature_spec": "diagnosis",
 }
 
 

@@ -71,6 +71,10 @@ class RFParams(ctypes.Structure):
 
 RF_ABOVE, RF_BELOW, RF_TILE = 0, 1, 2048
 
+# pinn_gmm.hip: limits, status and the 8-byte words of the state header
+GMM_MAX_COMP, GMM_MAX_FEAT, GMM_MAX_CLASSES, GMM_SINGULAR, GMM_TILE = 32, 8, 16, 1, 128
+GMM_ST_ITER, GMM_ST_CONVERGED, GMM_ST_STATUS, GMM_ST_K, GMM_ST_D, GMM_ST_LOWER, GMM_ST_PREV, GMM_ST_CHANGE, GMM_ST_HEADER = range(9)
+
 
 class PinnError(RuntimeError):
     pass
@@ -145,6 +149,18 @@ _SIGS = {
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_rf_first_alarm": (c_int, [c_void_p, c_ll, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, ctypes.c_double, c_void_p,
                                     c_void_p]),
+    "pinn_gmm_state_bytes": (c_size_t, [c_int, c_int]),
+    "pinn_gmm_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_gmm_mstep_init": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
+                                    ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_em": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, ctypes.c_double,
+                            ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_kmeans": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_label_map": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
+                                   c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_posterior": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
+                                   c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

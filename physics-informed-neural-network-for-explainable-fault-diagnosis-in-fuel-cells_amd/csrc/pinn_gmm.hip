@@ -1,0 +1,619 @@
+// Full-covariance Gaussian mixture for fault diagnosis on the device (reference script 03, cited as 03:<line>):
+//   pinn_gmm_mstep_init  parameters from initial responsibilities or labels (scikit-learn's _initialize)
+//   pinn_gmm_em          EM iterations without a host synchronisation between them, with scikit-learn's stopping rule
+//   pinn_gmm_posterior   log_prob_norm, responsibilities, fault probabilities and argmax per row        (03:416-424)
+//   pinn_gmm_label_map   P(fault | component) from training rows                                        (03:394-414)
+//   pinn_gmm_kmeans      Lloyd iterations for the package's own initialisation
+// All arithmetic is float64.
+//
+// One row pass serves all of them: a workgroup takes tiles of 128 rows, one thread per row writes the row's weights over
+// the K components (responsibilities of the E-step, given responsibilities, a one-hot label, or the nearest centre) into
+// LDS; then every thread owns up to 12 of the K x F output sums and adds the tile's 128 terms to them in row order.  The
+// F columns are (1, d, d d^T upper triangle) with d = x - mean_k of the state the pass started from: second moments are
+// accumulated about the previous mean and corrected by the mean's move, never as raw moments.  Workgroup sums go to the
+// workspace; a one-workgroup launch adds them in index order, does the M-step and the K Cholesky factorisations, the lower
+// bound and the convergence test.  No float atomics, no workgroup waits on another: stream order is the only dependency,
+// and the same call gives the same bytes every time.  Once the state's converged flag or status word is set every later
+// launch returns at once and the parameters stay as they are.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "../../include/pinn_hip.h"
+
+namespace pinn {
+namespace {
+
+constexpr int kRows = 128;                  // rows per tile = threads per workgroup of the row pass
+constexpr int kMaxK = PINN_GMM_MAX_COMP, kMaxD = PINN_GMM_MAX_FEAT, kMaxC = PINN_GMM_MAX_CLASSES;
+constexpr int kTri = kMaxD * (kMaxD + 1) / 2;
+constexpr int kMaxOut = (kMaxK * (1 + kMaxD + kTri) + kRows - 1) / kRows;      // output sums per thread: 12
+constexpr int kMaxBlocks = 1024;            // workgroups of a row pass = partial sums per output
+constexpr int kFinThreads = 256;
+constexpr int kHdr = 8;                     // 8-byte words of the state header
+
+enum { SRC_ESTEP = 0, SRC_RESP = 1, SRC_LABELS = 2, SRC_NEAREST = 3 };
+enum { OUT_MOMENTS = 0, OUT_CLASS = 1 };
+enum { FIN_MEANS = 0, FIN_INIT = 1, FIN_EM = 2, FIN_KMEANS = 3, FIN_MAP = 4 };
+
+struct Rows {
+  const double* arr;
+  long long ld, n_arr, n;
+  const long long* ridx;
+  int D, K;
+  int col[kMaxD];
+};
+
+// state block: header words, then weights[K], means[K][D], covariances[K][D][D], precisions_cholesky[K][D][D], logdet[K]
+__host__ __device__ inline size_t st_weights() { return kHdr; }
+__host__ __device__ inline size_t st_means(int K) { return kHdr + (size_t)K; }
+__host__ __device__ inline size_t st_cov(int K, int D) { return st_means(K) + (size_t)K * D; }
+__host__ __device__ inline size_t st_chol(int K, int D) { return st_cov(K, D) + (size_t)K * D * D; }
+__host__ __device__ inline size_t st_logdet(int K, int D) { return st_chol(K, D) + (size_t)K * D * D; }
+__host__ __device__ inline size_t st_words(int K, int D) { return st_logdet(K, D) + (size_t)K; }
+
+__device__ __forceinline__ bool stopped(const double* st) {
+  const long long* h = reinterpret_cast<const long long*>(st);
+  return h[PINN_GMM_ST_CONVERGED] != 0 || h[PINN_GMM_ST_STATUS] != 0;
+}
+
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
+
+__device__ __forceinline__ int tri(int i, int j) { return j * (j + 1) / 2 + i; }      // i <= j
+
+// parameters of the state in LDS: means, upper-triangular precisions_cholesky (packed by columns), logdet, log weights
+struct Staged {
+  double* mu;      // [K][D]
+  double* U;       // [K][D (D + 1) / 2]
+  double* ld;      // [K]
+  double* lw;      // [K]
+};
+
+__device__ __forceinline__ void stage_params(const double* __restrict__ st, int K, int D, const Staged& s, bool density) {
+  const int T = D * (D + 1) / 2;
+  for (int e = threadIdx.x; e < K * D; e += blockDim.x) s.mu[e] = st[st_means(K) + e];
+  if (density) {
+    for (int e = threadIdx.x; e < K * T; e += blockDim.x) {
+      const int k = e / T, t = e - k * T;
+      int j = 0;
+      while ((j + 1) * (j + 2) / 2 <= t) ++j;
+      const int i = t - j * (j + 1) / 2;
+      s.U[e] = st[st_chol(K, D) + ((size_t)k * D + i) * D + j];
+    }
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+      s.ld[k] = st[st_logdet(K, D) + k];
+      s.lw[k] = log(st[st_weights() + k]);
+    }
+  }
+  __syncthreads();
+}
+
+// log(w_k N(x | mu_k, Sigma_k)) for every k into lp[k * stride]; returns log_prob_norm (scipy's logsumexp: max, sum, log)
+__device__ __forceinline__ double estep_row(const double x[kMaxD], int K, int D, const Staged& s, double* lp, int stride) {
+  const double c = (double)D * 1.8378770664093453;          // D log(2 pi)
+  double m = -INFINITY;
+  for (int k = 0; k < K; ++k) {
+    double d[kMaxD];
+#pragma unroll
+    for (int i = 0; i < kMaxD; ++i) d[i] = i < D ? x[i] - s.mu[k * D + i] : 0.0;
+    const double* U = s.U + k * (D * (D + 1) / 2);
+    double q = 0.0;
+#pragma unroll
+    for (int j = 0; j < kMaxD; ++j) {
+      if (j < D) {
+        double y = 0.0;
+#pragma unroll
+        for (int i = 0; i <= j; ++i) y += d[i] * U[tri(i, j)];
+        q += y * y;
+      }
+    }
+    const double v = (-0.5 * (c + q) + s.ld[k]) + s.lw[k];
+    lp[k * stride] = v;
+    m = v > m ? v : m;
+  }
+  if (m == -INFINITY) return m;                             // every density underflowed: nothing to normalise
+  double sum = 0.0;
+  for (int k = 0; k < K; ++k) sum += exp(lp[k * stride] - m);
+  return log(sum) + m;
+}
+
+__device__ __forceinline__ bool load_row(const Rows& a, long long j, double x[kMaxD]) {
+  const long long row = a.ridx ? a.ridx[j] : j;
+  const bool ok = row >= 0 && row < a.n_arr;               // a gather index outside the array reads nothing
+  const double* r = a.arr + (ok ? row : 0) * a.ld;
+#pragma unroll
+  for (int i = 0; i < kMaxD; ++i) x[i] = (ok && i < a.D) ? r[a.col[i]] : 0.0;
+  return ok;
+}
+
+// ---- the row pass: K x F sums per workgroup.  F = n_f columns; OUT_MOMENTS: (1, d_i, d_i d_j i <= j) cut to n_f, OUT_CLASS:
+// one column per class.  part: [gridDim.x][K * n_f]; part_l: [gridDim.x] sums of log_prob_norm (SRC_ESTEP) or of the
+// squared distance to the nearest centre (SRC_NEAREST).
+__global__ __launch_bounds__(kRows) void gmm_rows_kernel(Rows a, const double* __restrict__ st, int src, int out, int n_f,
+                                                         const double* __restrict__ resp_in, const long long* __restrict__ lab_in,
+                                                         const long long* __restrict__ cls_in, long long* __restrict__ lab_out,
+                                                         int force, double* __restrict__ part, double* __restrict__ part_l) {
+  __shared__ double s_r[kRows * (kMaxK + 1)];
+  __shared__ double s_x[kRows * (kMaxD + 1)];
+  __shared__ double s_mu[kMaxK * kMaxD], s_U[kMaxK * kTri], s_ld[kMaxK], s_lw[kMaxK];
+  __shared__ double s_l[kRows];
+  __shared__ int s_cls[kRows];
+  if (!force && stopped(st)) return;
+  const int K = a.K, D = a.D, Kp = K | 1, Dp = D | 1, t = threadIdx.x;
+  const Staged sp{s_mu, s_U, s_ld, s_lw};
+  stage_params(st, K, D, sp, src == SRC_ESTEP);
+
+  // the outputs of this thread: o = t + q kRows -> (component, column)
+  const int KF = K * n_f;
+  int ok_[kMaxOut], oi[kMaxOut], oj[kMaxOut];
+  double acc[kMaxOut];
+#pragma unroll
+  for (int q = 0; q < kMaxOut; ++q) {
+    const int o = t + q * kRows;
+    acc[q] = 0.0;
+    ok_[q] = -1; oi[q] = -1; oj[q] = -1;
+    if (o < KF) {
+      const int k = o / n_f, f = o - k * n_f;
+      ok_[q] = k;
+      if (out == OUT_CLASS) {
+        oi[q] = f;
+      } else if (f >= 1 && f <= D) {
+        oi[q] = f - 1;
+      } else if (f > D) {
+        const int p = f - 1 - D;
+        int j = 0;
+        while ((j + 1) * (j + 2) / 2 <= p) ++j;
+        oi[q] = p - j * (j + 1) / 2;
+        oj[q] = j;
+      }
+    }
+  }
+
+  double lsum = 0.0;
+  const long long tiles = (a.n + kRows - 1) / kRows;
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long long j = tile * kRows + t;
+    double x[kMaxD];
+    bool ok = false;
+    if (j < a.n) ok = load_row(a, j, x);
+    else {
+#pragma unroll
+      for (int i = 0; i < kMaxD; ++i) x[i] = 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < kMaxD; ++i)
+      if (i < D) s_x[t * Dp + i] = x[i];
+    double* r = s_r + t * Kp;
+    if (!ok) {
+      for (int k = 0; k < K; ++k) r[k] = 0.0;
+    } else if (src == SRC_ESTEP) {
+      const double lpn = estep_row(x, K, D, sp, r, 1);
+      for (int k = 0; k < K; ++k) r[k] = exp(r[k] - lpn);
+      lsum += lpn;
+    } else if (src == SRC_RESP) {
+      for (int k = 0; k < K; ++k) r[k] = resp_in[j * K + k];
+    } else if (src == SRC_LABELS) {
+      const long long l = lab_in[j];
+      for (int k = 0; k < K; ++k) r[k] = (l == k) ? 1.0 : 0.0;
+    } else {                                                  // nearest centre, the first of equals
+      int best = 0;
+      double bd = INFINITY;
+      for (int k = 0; k < K; ++k) {
+        double d2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < kMaxD; ++i)
+          if (i < D) { const double d = x[i] - s_mu[k * D + i]; d2 += d * d; }
+        if (d2 < bd) { bd = d2; best = k; }
+      }
+      for (int k = 0; k < K; ++k) r[k] = (k == best) ? 1.0 : 0.0;
+      if (lab_out) lab_out[j] = best;
+      lsum += bd;
+    }
+    if (out == OUT_CLASS) s_cls[t] = (ok && cls_in) ? (int)cls_in[j] : -1;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kMaxOut; ++q) {
+      const int k = ok_[q];
+      if (k >= 0) {
+        const int i = oi[q], jj = oj[q];
+        double s = acc[q];
+        if (out == OUT_CLASS) {
+          for (int rr = 0; rr < kRows; ++rr) s += s_cls[rr] == i ? s_r[rr * Kp + k] : 0.0;
+        } else if (i < 0) {
+          for (int rr = 0; rr < kRows; ++rr) s += s_r[rr * Kp + k];
+        } else if (jj < 0) {
+          const double m = s_mu[k * D + i];
+          for (int rr = 0; rr < kRows; ++rr) s += s_r[rr * Kp + k] * (s_x[rr * Dp + i] - m);
+        } else {
+          const double mi = s_mu[k * D + i], mj = s_mu[k * D + jj];
+          for (int rr = 0; rr < kRows; ++rr) s += s_r[rr * Kp + k] * ((s_x[rr * Dp + i] - mi) * (s_x[rr * Dp + jj] - mj));
+        }
+        acc[q] = s;
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < kMaxOut; ++q)
+    if (ok_[q] >= 0) part[(size_t)blockIdx.x * KF + t + q * kRows] = acc[q];
+  s_l[t] = lsum;
+  __syncthreads();
+  if (t == 0) {
+    double s = 0.0;
+    for (int rr = 0; rr < kRows; ++rr) s += s_l[rr];
+    part_l[blockIdx.x] = s;
+  }
+}
+
+// ---- sums of the partials in index order, then what the mode asks for.  One workgroup.
+// tot: [K * n_f] totals (kept in the workspace for the caller), then [1] the total of part_l.
+__global__ __launch_bounds__(kFinThreads) void gmm_final_kernel(double* __restrict__ st, int K, int D, int C, int mode, int n_f, int n_part,
+                                                                 long long n, double reg, double tol, const double* __restrict__ part,
+                                                                 const double* __restrict__ part_l, double* __restrict__ tot,
+                                                                 double* __restrict__ map_out) {
+  __shared__ double n_mu[kMaxK * kMaxD], n_cov[kMaxK * kMaxD * kMaxD], n_U[kMaxK * kMaxD * kMaxD], n_ld[kMaxK], n_nk[kMaxK];
+  __shared__ int s_fail[kMaxK];
+  __shared__ double s_sum;
+  long long* hdr = reinterpret_cast<long long*>(st);
+  if (mode != FIN_MAP && mode != FIN_MEANS && mode != FIN_INIT && stopped(st)) return;
+  const int KF = K * n_f, t = threadIdx.x;
+  for (int o = t; o < KF; o += kFinThreads) {
+    double s = 0.0;
+    for (int g = 0; g < n_part; ++g) s += part[(size_t)g * KF + o];
+    tot[o] = s;
+  }
+  if (t == 0) {
+    double s = 0.0;
+    for (int g = 0; g < n_part; ++g) s += part_l[g];
+    tot[KF] = s;
+  }
+  __syncthreads();
+
+  if (mode == FIN_MAP) {                                      // 03:397-414
+    if (t < K) {
+      double s = 0.0;
+      for (int c = 0; c < C; ++c) s += tot[t * C + c];
+      for (int c = 0; c < C; ++c) map_out[t * C + c] = s > 0.0 ? tot[t * C + c] / s : 1.0 / (double)C;
+    }
+    return;
+  }
+  const double* mean = st + st_means(K);
+  const double eps10 = 10.0 * 2.220446049250313e-16;
+  if (mode == FIN_KMEANS) {
+    if (t < K) {
+      const double s0 = tot[t * n_f];
+      int moved = 0;
+      for (int i = 0; i < D; ++i) {
+        const double old = mean[t * D + i];
+        const double nw = s0 > 0.0 ? old + tot[t * n_f + 1 + i] / s0 : old;     // an empty cluster keeps its centre
+        n_mu[t * D + i] = nw;
+        moved |= nw != old;
+      }
+      s_fail[t] = moved;
+    }
+    __syncthreads();
+    if (t < K)
+      for (int i = 0; i < D; ++i) st[st_means(K) + t * D + i] = n_mu[t * D + i];
+    if (t == 0) {
+      int moved = 0;
+      for (int k = 0; k < K; ++k) moved |= s_fail[k];
+      hdr[PINN_GMM_ST_ITER] += 1;
+      st[PINN_GMM_ST_LOWER] = tot[KF];                        // inertia of the assignment to the previous centres
+      if (!moved) hdr[PINN_GMM_ST_CONVERGED] = 1;
+    }
+    return;
+  }
+
+  if (t < K) {
+    const double s0 = tot[t * n_f], nk = s0 + eps10, frac = s0 / nk;
+    n_nk[t] = nk;
+    double dm[kMaxD], e[kMaxD];
+    for (int i = 0; i < D; ++i) {
+      const double sh = mean[t * D + i];
+      dm[i] = tot[t * n_f + 1 + i] / nk;                      // sum r (x - shift) / n_k
+      const double mu = dm[i] + sh * frac;                    // = sum r x / n_k
+      n_mu[t * D + i] = mu;
+      e[i] = mu - sh;
+    }
+    int fail = 0;
+    if (mode != FIN_MEANS) {
+      // covariance about the new mean from the moments about the shift: S2 / n_k - e dm^T - dm e^T + (S0 / n_k) e e^T
+      double* cv = n_cov + t * D * D;
+      for (int j = 0; j < D; ++j)
+        for (int i = 0; i <= j; ++i) {
+          double v = tot[t * n_f + 1 + D + tri(i, j)] / nk - e[i] * dm[j] - dm[i] * e[j] + frac * e[i] * e[j];
+          if (i == j) v += reg;
+          cv[i * D + j] = v;
+          cv[j * D + i] = v;
+        }
+      // Cholesky cov = L L^T (L kept in n_U's lower part for now), then U = L^-T
+      double L[kMaxD][kMaxD];
+      for (int j = 0; j < D && !fail; ++j) {
+        double s = cv[j * D + j];
+        for (int p = 0; p < j; ++p) s -= L[j][p] * L[j][p];
+        if (!(s > 0.0) || !(s < INFINITY)) { fail = 1; break; }
+        const double piv = sqrt(s);
+        L[j][j] = piv;
+        for (int i = j + 1; i < D; ++i) {
+          double v = cv[i * D + j];
+          for (int p = 0; p < j; ++p) v -= L[i][p] * L[j][p];
+          L[i][j] = v / piv;
+        }
+      }
+      if (!fail) {
+        double ld = 0.0;
+        double* U = n_U + t * D * D;
+        for (int c = 0; c < D; ++c) {                         // column c of L^-1 by forward substitution; U[c][r] = Linv[r][c]
+          double z[kMaxD];
+          for (int r = 0; r < D; ++r) {
+            double v = r == c ? 1.0 : 0.0;
+            for (int p = c; p < r; ++p) v -= L[r][p] * z[p];
+            z[r] = r < c ? 0.0 : v / L[r][r];
+            U[c * D + r] = z[r];
+          }
+        }
+        for (int i = 0; i < D; ++i) ld += log(U[i * D + i]);
+        n_ld[t] = ld;
+        if (!(ld == ld)) fail = 1;
+      }
+    }
+    s_fail[t] = fail;
+  }
+  __syncthreads();
+  if (t == 0) {
+    int fail = 0;
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) { fail |= s_fail[k]; s += n_nk[k]; }
+    s_sum = s;
+    if (fail) hdr[PINN_GMM_ST_STATUS] = PINN_GMM_SINGULAR;
+    s_fail[0] = fail;
+  }
+  __syncthreads();
+  if (s_fail[0]) return;                                      // the state keeps the last good parameters
+  if (t < K) {
+    for (int i = 0; i < D; ++i) st[st_means(K) + t * D + i] = n_mu[t * D + i];
+    if (mode != FIN_MEANS) {
+      st[st_weights() + t] = n_nk[t] / (mode == FIN_INIT ? (double)n : s_sum);
+      for (int i = 0; i < D * D; ++i) {
+        st[st_cov(K, D) + (size_t)t * D * D + i] = n_cov[t * D * D + i];
+        st[st_chol(K, D) + (size_t)t * D * D + i] = n_U[t * D * D + i];
+      }
+      st[st_logdet(K, D) + t] = n_ld[t];
+    }
+  }
+  if (t == 0 && mode == FIN_INIT) {
+    hdr[PINN_GMM_ST_ITER] = 0;
+    hdr[PINN_GMM_ST_K] = K;
+    hdr[PINN_GMM_ST_D] = D;
+    st[PINN_GMM_ST_LOWER] = -INFINITY;
+    st[PINN_GMM_ST_PREV] = -INFINITY;
+    st[PINN_GMM_ST_CHANGE] = INFINITY;
+  }
+  if (t == 0 && mode == FIN_EM) {                             // scikit-learn's loop: mean log_prob_norm of the E-step just done
+    const double lb = tot[KF] / (double)n, prev = st[PINN_GMM_ST_LOWER], change = lb - prev;
+    st[PINN_GMM_ST_PREV] = prev;
+    st[PINN_GMM_ST_LOWER] = lb;
+    st[PINN_GMM_ST_CHANGE] = change;
+    hdr[PINN_GMM_ST_ITER] += 1;
+    if (fabs(change) < tol) hdr[PINN_GMM_ST_CONVERGED] = 1;
+  }
+}
+
+// ---- posterior of given rows: one thread per row, every output optional
+__global__ __launch_bounds__(kRows) void gmm_posterior_kernel(Rows a, const double* __restrict__ st, const double* __restrict__ map, int C,
+                                                              double* __restrict__ lpn_out, double* __restrict__ resp_out,
+                                                              double* __restrict__ prob_out, long long* __restrict__ pred_out) {
+  __shared__ double s_r[kRows * (kMaxK + 1)];
+  __shared__ double s_mu[kMaxK * kMaxD], s_U[kMaxK * kTri], s_ld[kMaxK], s_lw[kMaxK];
+  __shared__ double s_map[kMaxK * kMaxC];
+  const int K = a.K, D = a.D, Kp = K | 1, t = threadIdx.x;
+  const Staged sp{s_mu, s_U, s_ld, s_lw};
+  if (map)
+    for (int e = t; e < K * C; e += kRows) s_map[e] = map[e];
+  stage_params(st, K, D, sp, true);
+  const long long j = (long long)blockIdx.x * kRows + t;
+  if (j >= a.n) return;
+  double x[kMaxD];
+  const bool ok = load_row(a, j, x);
+  double* r = s_r + t * Kp;
+  double lpn = quiet_nan();
+  if (ok) {
+    lpn = estep_row(x, K, D, sp, r, 1);
+    for (int k = 0; k < K; ++k) r[k] = exp(r[k] - lpn);
+  } else {
+    for (int k = 0; k < K; ++k) r[k] = quiet_nan();
+  }
+  if (lpn_out) lpn_out[j] = lpn;
+  if (resp_out)
+    for (int k = 0; k < K; ++k) resp_out[j * K + k] = r[k];
+  if (map && (prob_out || pred_out)) {                        // 03:418-424
+    double y[kMaxC];
+    double sum = 0.0;
+#pragma unroll
+    for (int c = 0; c < kMaxC; ++c) {
+      y[c] = 0.0;
+      if (c < C) {
+        double v = 0.0;
+        for (int k = 0; k < K; ++k) v += r[k] * s_map[k * C + c];
+        if (v == v) v = v < 1e-12 ? 1e-12 : (v > 1.0 ? 1.0 : v);
+        y[c] = v;
+        sum += v;
+      }
+    }
+    int best = 0;
+    double bv = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < kMaxC; ++c) {
+      if (c < C) {
+        const double v = y[c] / sum;
+        if (prob_out) prob_out[j * C + c] = v;
+        if (v > bv) { bv = v; best = c; }
+      }
+    }
+    if (pred_out) pred_out[j] = best;
+  }
+}
+
+inline bool misaligned8(const void* p) { return ((unsigned long long)p & 7) != 0; }
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+inline int n_moments(int D) { return 1 + D + D * (D + 1) / 2; }
+
+inline int n_blocks(long long n) {
+  const long long tiles = (n + kRows - 1) / kRows;
+  return (int)(tiles < 1 ? 1 : (tiles > kMaxBlocks ? kMaxBlocks : tiles));
+}
+
+// checks shared by every entry point that reads rows; fills `a`
+inline int make_rows(const double* d_arr, long long ld, long long n_arr, const int* cols, int n_feat, int n_comp,
+                     const long long* d_row_index, long long n, Rows* a) {
+  if (n < 0 || n_arr < 0 || ld < 1 || !cols || n_feat < 1 || n_feat > kMaxD || n_comp < 1 || n_comp > kMaxK) return PINN_E_ARG;
+  for (int i = 0; i < n_feat; ++i)
+    if (cols[i] < 0 || cols[i] >= ld) return PINN_E_ARG;
+  if (!d_row_index && n > n_arr) return PINN_E_ARG;
+  if (n > 0 && !d_arr) return PINN_E_ARG;
+  if (misaligned8(d_arr) || misaligned8(d_row_index)) return PINN_E_ARG;
+  a->arr = d_arr; a->ld = ld; a->n_arr = n_arr; a->n = n; a->ridx = d_row_index; a->D = n_feat; a->K = n_comp;
+  for (int i = 0; i < kMaxD; ++i) a->col[i] = i < n_feat ? cols[i] : 0;
+  return PINN_OK;
+}
+
+struct Ws {
+  double *tot, *part, *part_l;
+};
+
+// workspace: totals [K F + 1] (first, so that the caller can read the summed moments), partials, log-likelihood partials
+inline Ws carve(void* d_ws, int K, int D) {
+  char* w = static_cast<char*>(d_ws);
+  Ws s;
+  const size_t KF = (size_t)K * n_moments(D) > (size_t)K * kMaxC ? (size_t)K * n_moments(D) : (size_t)K * kMaxC;
+  s.tot = reinterpret_cast<double*>(w); w += align256((KF + 1) * sizeof(double));
+  s.part = reinterpret_cast<double*>(w); w += align256((size_t)kMaxBlocks * KF * sizeof(double));
+  s.part_l = reinterpret_cast<double*>(w);
+  return s;
+}
+
+inline void launch_rows(const Rows& a, const double* st, int src, int out, int n_f, const double* resp, const long long* lab,
+                        const long long* cls, long long* lab_out, int force, const Ws& w, hipStream_t s) {
+  hipLaunchKernelGGL(gmm_rows_kernel, dim3((unsigned)n_blocks(a.n)), dim3(kRows), 0, s, a, st, src, out, n_f, resp, lab, cls, lab_out,
+                     force, w.part, w.part_l);
+}
+
+inline void launch_final(double* st, const Rows& a, int C, int mode, int n_f, double reg, double tol, const Ws& w, double* map_out,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(gmm_final_kernel, dim3(1), dim3(kFinThreads), 0, s, st, a.K, a.D, C, mode, n_f, n_blocks(a.n), a.n, reg, tol,
+                     w.part, w.part_l, w.tot, map_out);
+}
+
+}  // namespace
+}  // namespace pinn
+
+extern "C" size_t pinn_gmm_state_bytes(int n_comp, int n_feat) {
+  if (n_comp < 1 || n_comp > pinn::kMaxK || n_feat < 1 || n_feat > pinn::kMaxD) return 0;
+  return pinn::st_words(n_comp, n_feat) * sizeof(double);
+}
+
+extern "C" size_t pinn_gmm_workspace_bytes(long long n_rows, int n_comp, int n_feat) {
+  using namespace pinn;
+  if (n_rows < 0 || n_comp < 1 || n_comp > kMaxK || n_feat < 1 || n_feat > kMaxD) return 0;
+  const size_t KF = (size_t)n_comp * n_moments(n_feat) > (size_t)n_comp * kMaxC ? (size_t)n_comp * n_moments(n_feat) : (size_t)n_comp * kMaxC;
+  return align256((KF + 1) * sizeof(double)) + align256((size_t)kMaxBlocks * KF * sizeof(double)) + align256(kMaxBlocks * sizeof(double));
+}
+
+#define GMM_COMMON_CHECKS()                                                                      \
+  Rows a;                                                                                        \
+  {                                                                                              \
+    const int rc_ = make_rows(d_arr, ld, n_arr_rows, cols, n_feat, n_comp, d_row_index, n, &a);  \
+    if (rc_ != PINN_OK) return rc_;                                                              \
+  }                                                                                              \
+  if (!d_state || !d_ws || misaligned8(d_state) || misaligned8(d_ws)) return PINN_E_ARG;         \
+  if (ws_bytes < pinn_gmm_workspace_bytes(n, n_comp, n_feat)) return PINN_E_WORKSPACE;           \
+  const Ws w = carve(d_ws, n_comp, n_feat);                                                      \
+  hipStream_t st = (hipStream_t)stream;                                                          \
+  (void)hipGetLastError()
+
+extern "C" int pinn_gmm_mstep_init(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                                   const long long* d_row_index, long long n, int n_comp, const double* d_resp,
+                                   const long long* d_labels, double reg_covar, double* d_state, void* d_ws, size_t ws_bytes,
+                                   void* stream) {
+  using namespace pinn;
+  GMM_COMMON_CHECKS();
+  if ((d_resp == nullptr) == (d_labels == nullptr) || n < 1 || !(reg_covar >= 0.0) || misaligned8(d_resp) || misaligned8(d_labels))
+    return PINN_E_ARG;
+  const int src = d_resp ? SRC_RESP : SRC_LABELS, F = n_moments(n_feat);
+  hipError_t e = hipMemsetAsync(d_state, 0, pinn_gmm_state_bytes(n_comp, n_feat), st);      // shift 0 for the first pass
+  if (e != hipSuccess) return (int)e;
+  launch_rows(a, d_state, src, OUT_MOMENTS, 1 + n_feat, d_resp, d_labels, nullptr, nullptr, 1, w, st);
+  launch_final(d_state, a, 0, FIN_MEANS, 1 + n_feat, reg_covar, 0.0, w, nullptr, st);
+  launch_rows(a, d_state, src, OUT_MOMENTS, F, d_resp, d_labels, nullptr, nullptr, 1, w, st);    // second pass: about the means
+  launch_final(d_state, a, 0, FIN_INIT, F, reg_covar, 0.0, w, nullptr, st);
+  e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+extern "C" int pinn_gmm_em(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                           const long long* d_row_index, long long n, int n_comp, int n_iters, double tol, double reg_covar,
+                           double* d_state, void* d_ws, size_t ws_bytes, void* stream) {
+  using namespace pinn;
+  GMM_COMMON_CHECKS();
+  if (n < 1 || n_iters < 0 || n_iters > 100000 || !(tol >= 0.0) || !(reg_covar >= 0.0)) return PINN_E_ARG;
+  const int F = n_moments(n_feat);
+  for (int it = 0; it < n_iters; ++it) {
+    launch_rows(a, d_state, SRC_ESTEP, OUT_MOMENTS, F, nullptr, nullptr, nullptr, nullptr, 0, w, st);
+    launch_final(d_state, a, 0, FIN_EM, F, reg_covar, tol, w, nullptr, st);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+extern "C" int pinn_gmm_kmeans(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                               const long long* d_row_index, long long n, int n_comp, int n_iters, double* d_state,
+                               long long* d_labels, void* d_ws, size_t ws_bytes, void* stream) {
+  using namespace pinn;
+  GMM_COMMON_CHECKS();
+  if (n < 1 || n_iters < 0 || n_iters > 100000 || misaligned8(d_labels)) return PINN_E_ARG;
+  const int F = 1 + n_feat;
+  for (int it = 0; it < n_iters; ++it) {
+    launch_rows(a, d_state, SRC_NEAREST, OUT_MOMENTS, F, nullptr, nullptr, nullptr, nullptr, 0, w, st);
+    launch_final(d_state, a, 0, FIN_KMEANS, F, 0.0, 0.0, w, nullptr, st);
+  }
+  if (d_labels)                                             // the assignment to the final centres
+    launch_rows(a, d_state, SRC_NEAREST, OUT_MOMENTS, F, nullptr, nullptr, nullptr, d_labels, 1, w, st);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+extern "C" int pinn_gmm_label_map(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                                  const long long* d_row_index, long long n, int n_comp, const double* d_state,
+                                  const long long* d_class, int n_classes, double* d_map, void* d_ws, size_t ws_bytes,
+                                  void* stream) {
+  using namespace pinn;
+  GMM_COMMON_CHECKS();
+  if (n_classes < 1 || n_classes > kMaxC || !d_map || (n > 0 && !d_class) || misaligned8(d_class) || misaligned8(d_map)) return PINN_E_ARG;
+  launch_rows(a, d_state, SRC_ESTEP, OUT_CLASS, n_classes, nullptr, nullptr, d_class, nullptr, 1, w, st);
+  launch_final(const_cast<double*>(d_state), a, n_classes, FIN_MAP, n_classes, 0.0, 0.0, w, d_map, st);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+extern "C" int pinn_gmm_posterior(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                                  const long long* d_row_index, long long n, int n_comp, const double* d_state,
+                                  const double* d_map, int n_classes, double* d_log_prob_norm, double* d_resp, double* d_y_prob,
+                                  long long* d_y_pred, void* stream) {
+  using namespace pinn;
+  Rows a;
+  const int rc = make_rows(d_arr, ld, n_arr_rows, cols, n_feat, n_comp, d_row_index, n, &a);
+  if (rc != PINN_OK) return rc;
+  if (!d_state || misaligned8(d_state) || misaligned8(d_map) || misaligned8(d_log_prob_norm) || misaligned8(d_resp) ||
+      misaligned8(d_y_prob) || misaligned8(d_y_pred))
+    return PINN_E_ARG;
+  if (d_map ? (n_classes < 1 || n_classes > kMaxC) : (d_y_prob || d_y_pred)) return PINN_E_ARG;
+  if (n == 0) return PINN_OK;
+  const long long tiles = (n + kRows - 1) / kRows;
+  if (tiles > 0x7fffffffLL) return PINN_E_ARG;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gmm_posterior_kernel, dim3((unsigned)tiles), dim3(kRows), 0, (hipStream_t)stream, a, d_state, d_map, n_classes,
+                     d_log_prob_norm, d_resp, d_y_prob, d_y_pred);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
