@@ -1,0 +1,69 @@
+"""Fault detection on the device: a synthetic results array with twelve fault segments, script 02's four feature groups
+(`epi,res` / `x0,x3,x4,x5` / `res` / `y_true`) each fitted with StandardScaler + logistic regression on a tenth of the rows
+and judged by the ROC AUC of 1 - P(normal) on the rest, then the recording replayed in chunks through the online detector
+of the first group.  Nothing leaves the GPU but the printed numbers.
+
+    python examples/fault_detection.py [--normal-rows 20000] [--fault-rows 1500] [--five-class]
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from pinn_amd import detection  # noqa: E402
+
+
+def synthetic_results(n_normal, n_fault, seed=0):
+    """[n, 22] in the layout of the results array: noise on normal rows, and in every fault segment a ramp on res, epi,
+    y_true and one of x3..x5 of about the size of the noise."""
+    rng = np.random.default_rng(seed)
+    n = n_normal + 12 * n_fault
+    a = np.zeros((n, 22))
+    a[:, 0] = rng.choice([108.0, 270.0, 405.0], n) + rng.normal(0.0, 2.0, n)
+    for col, (mu, sd) in {3: (60.0, 1.5), 4: (2.0, 0.15), 5: (1.5, 0.1), 8: (3.0, 0.05), 12: (0.0, 0.03)}.items():
+        a[:, col] = rng.normal(mu, sd, n)
+    a[:, 11] = np.abs(rng.normal(0.02, 0.006, n))
+    ramp = np.linspace(0.2, 1.0, n_fault)
+    for k in range(1, 13):
+        rows = slice(n_normal + (k - 1) * n_fault, n_normal + k * n_fault)
+        cls, amp = (k - 1) // 3, (0.8, 1.3, 1.8)[(k - 1) % 3]
+        a[rows, 17] = k
+        a[rows, 12] += amp * 0.03 * ramp * (1.0 + 0.3 * cls)
+        a[rows, 11] += amp * 0.005 * ramp * (1 + cls % 3)
+        a[rows, 8] -= amp * 0.04 * ramp
+        a[rows, 3 + cls % 3] += amp * (1.5, 0.15, 0.1)[cls % 3] * ramp
+    return a
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--normal-rows", type=int, default=20000)
+    ap.add_argument("--fault-rows", type=int, default=1500)
+    ap.add_argument("--five-class", action="store_true", help="normal and the four fault classes instead of normal / fault")
+    args = ap.parse_args()
+
+    results = torch.from_numpy(synthetic_results(args.normal_rows, args.fault_rows)).cuda()
+    spec = detection.FIVE_CLASS_GROUP_SPEC if args.five_class else detection.DEFAULT_GROUP_SPEC
+    groups = detection.evaluate_feature_groups(results, group_spec=spec)
+    print("%-14s %8s %8s %6s %9s %9s %8s" % ("features", "train", "test", "iters", "accuracy", "macro F1", "AUC"))
+    for g in groups:
+        lr = g["clf"].named_steps["logreg"]
+        print("%-14s %8d %8d %6d %9.4f %9.4f %8.4f" % (g["spec"], g["n_train"], g["n_test"], lr.n_iter_, g["accuracy"], g["metrics"]["macro_f1"],
+                                                      g["auc"]))
+    for e in detection.explain_coefficients(groups[0]["clf"], groups[0]["features"], groups[0]["class_names"]):
+        print("coefficients of %r in the standardised space: %s" % (e["class"], ", ".join("%s %+.3f" % p for p in e["positive"])))
+
+    detector = detection.FaultDetector(groups[0]["clf"], features=detection.FEAT_GRP1, normal_class=0)
+    print("\n%8s %10s %12s %s" % ("rows", "label", "mean p_fault", "share flagged"))
+    for s in range(0, results.shape[0], 4096):
+        chunk = results[s:s + 4096]
+        p_fault, pred = detector.update(chunk)
+        print("%8d %10d %12.4f %.3f" % (s + chunk.shape[0], int(chunk[-1, 17]), float(p_fault.mean()), float((pred != 0).double().mean())))
+
+
+if __name__ == "__main__":
+    main()

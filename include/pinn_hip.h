@@ -517,6 +517,102 @@ int pinn_gmm_posterior(const double* d_arr, long long ld, long long n_arr_rows, 
                        int n_classes, double* d_log_prob_norm, double* d_resp, double* d_y_prob, long long* d_y_pred,
                        void* stream);
 
+/* ---- fault detection: reference script 02 (cited as 02:<line>) ---------------------------------------------------
+ * StandardScaler + multinomial logistic regression with an L2 penalty (02:195-207) and the ROC curve / AUC of
+ * 1 - P(normal) (02:552-557), float64 throughout.  Rows are read in place as for the mixture above (column list, optional
+ * gather list, leading dimension; an index outside [0, n_arr_rows) reads nothing and adds nothing).  d_y holds one class
+ * index per position; a class outside [0, n_classes) adds nothing.  Every reduction has a fixed order.
+ *
+ * Limits: 2 <= n_classes <= PINN_LR_MAX_CLASSES, 1 <= n_feat <= PINN_LR_MAX_FEAT and
+ * n_classes (n_classes + 1) / 2 x (n_feat + 1) (n_feat + 2) / 2 <= PINN_LR_MAX_HESS (the Hessian sums of a row pass):
+ * every (C, D) with C <= 5, D <= 8 and with C <= 13, D <= 4 is inside.  Outside: PINN_E_ARG, sizes 0.
+ *
+ * With z = (x - mean) / scale, s_c = W_c . z + b_c, sample weights sw = class_weight[y], the fit minimises
+ *   F(W, b) = sum_i sw_i (logsumexp_c s_ic - s_i,y_i) + l2 / 2 sum_c |W_c|^2        (l2 = 1 / C of scikit-learn)
+ * by damped Newton iterations.  The state block (pinn_lr_state_bytes() bytes, 8-byte words) holds the header
+ *   [.._ITER] accepted iterations, [.._CONVERGED] 1 once max |grad F| / sum sw <= tol, [.._STATUS] 0 or PINN_LR_SINGULAR /
+ *   _NAN / _STALLED, [.._C], [.._D], [.._PASSES] row passes judged, [.._PHASE] 0 until the first point is accepted,
+ *   [.._NSEEN] rows counted by the scaler, [.._MAXITER] iterations after which every launch returns at once (64-bit
+ *   integers); [.._F] F at the accepted point, [.._STEP] the step length of the proposed point, [.._DD] grad . direction at
+ *   the accepted point, [.._GMAX] max |grad F| / sum sw there, [.._SWSUM] sum sw (doubles);
+ * then theta [C][D + 1] (coefficients of a class, then its intercept: the point the next pass evaluates), the accepted
+ * point, the Newton direction and the gradient at the accepted point (each [C][D + 1]), mean [D], scale [D], var [D],
+ * class_weight [C], class_count [C] (64-bit integers).  The caller zeroes the block, writes the starting point into theta
+ * and MAXITER, and calls pinn_lr_scaler (or fills mean / scale / class_weight / SWSUM itself).  Once CONVERGED or STATUS
+ * is set or MAXITER is reached every later launch returns at once; a failed factorisation or a NaN stores nothing: theta
+ * is the last accepted point. */
+#define PINN_LR_MAX_CLASSES 13
+#define PINN_LR_MAX_FEAT 8
+#define PINN_LR_MAX_HESS 1365
+#define PINN_LR_SINGULAR 1
+#define PINN_LR_NAN 2
+#define PINN_LR_STALLED 3
+#define PINN_LR_ST_ITER 0
+#define PINN_LR_ST_CONVERGED 1
+#define PINN_LR_ST_STATUS 2
+#define PINN_LR_ST_C 3
+#define PINN_LR_ST_D 4
+#define PINN_LR_ST_F 5
+#define PINN_LR_ST_STEP 6
+#define PINN_LR_ST_DD 7
+#define PINN_LR_ST_PASSES 8
+#define PINN_LR_ST_GMAX 9
+#define PINN_LR_ST_SWSUM 10
+#define PINN_LR_ST_PHASE 11
+#define PINN_LR_ST_NSEEN 12
+#define PINN_LR_ST_MAXITER 13
+#define PINN_LR_ST_HEADER 16
+
+size_t pinn_lr_state_bytes(int n_classes, int n_feat);                      /* 0 for sizes outside the limits */
+size_t pinn_lr_workspace_bytes(long long n_rows, int n_classes, int n_feat);
+
+/* StandardScaler.fit and the class weights, four launches: mean (pass 1), var = mean of (x - mean)^2 (pass 2), scale =
+ * sqrt(var), 1 where scikit-learn takes the feature for constant; class counts; class_weight = n / (C count) with
+ * balanced != 0, else 1; SWSUM, NSEEN, C, D. */
+int pinn_lr_scaler(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                   const long long* d_row_index, long long n, const long long* d_y, int n_classes, int balanced,
+                   double* d_state, void* d_ws, size_t ws_bytes, void* stream);
+
+/* One row pass at the state's theta, whatever the header says; the state is not changed.  Afterwards the workspace begins
+ * with the sums [1 + P + H]: the loss sum; the gradient sums [C][D + 1] of sw (p_c - y_c) (z, 1); the Hessian sums of
+ * sw p_c (delta_cd - p_d) (z, 1)_i (z, 1)_j for c <= d (pairs by columns d) and i <= j (by columns j).  No penalty. */
+int pinn_lr_pass(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                 const long long* d_row_index, long long n, const long long* d_y, int n_classes, const double* d_state,
+                 void* d_ws, size_t ws_bytes, void* stream);
+
+/* n_passes times (row pass at theta, one-workgroup judgement), no host synchronisation.  The judgement accepts the point
+ * (the first one always; later ones by Armijo's rule F <= F_acc + 1e-4 step DD, with a floor of 4 n eps loss for the
+ * rounding of the sum), or restores the accepted point with half the step.  After accepting it tests the tolerance,
+ * factorises the Hessian (Cholesky; + sum sw / C on every pair of intercepts, which pins their sum) and proposes the
+ * Newton step.  fit_intercept == 0 leaves the intercepts where they start. */
+int pinn_lr_newton(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                   const long long* d_row_index, long long n, const long long* d_y, int n_classes, int n_passes, double tol,
+                   double l2, int fit_intercept, double* d_state, void* d_ws, size_t ws_bytes, void* stream);
+
+/* One launch.  d_model: mean [D], scale [D], W [R][D], b [R] with R = 1 for two classes (scikit-learn's coef_ [1, D]:
+ * the scores are (-d, d)) and R = n_classes otherwise.  Outputs, each may be NULL: d_decision [n] (two classes) or
+ * [n][n_classes], d_proba [n][n_classes] = softmax of the scores, d_pred [n] the first maximum, d_p_fault [n] =
+ * 1 - proba[normal_class].  A row that reads nothing gives NaN and -1. */
+int pinn_lr_posterior(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                      const long long* d_row_index, long long n, int n_classes, const double* d_model, int normal_class,
+                      double* d_decision, double* d_proba, long long* d_pred, double* d_p_fault, void* stream);
+
+/* ROC curve of scores sorted descending (d_pos_sorted: non-zero = positive, in the same order), six launches.  d_counts
+ * [PINN_LR_ROC_COUNTS]: positives, negatives, distinct scores, points kept (without the origin), and the area as the
+ * integer U2 = sum dfps (tps_prev + tps): AUC = U2 / (2 positives negatives).  Curve outputs, each may be NULL and each
+ * with room for n + 1 entries: point 0 is (0, 0, inf), then the kept points; drop_intermediate != 0 keeps the first, the
+ * last and every point where the second difference of fps or tps is not zero, as scikit-learn does. */
+#define PINN_LR_ROC_POS 0
+#define PINN_LR_ROC_N 1
+#define PINN_LR_ROC_M 2
+#define PINN_LR_ROC_KEPT 3
+#define PINN_LR_ROC_U2 4
+#define PINN_LR_ROC_COUNTS 8
+size_t pinn_lr_roc_workspace_bytes(long long n);
+int pinn_lr_roc(const double* d_score_sorted, const long long* d_pos_sorted, long long n, int drop_intermediate,
+                long long* d_counts, long long* d_fps, long long* d_tps, double* d_thresholds, double* d_fpr, double* d_tpr,
+                void* d_ws, size_t ws_bytes, void* stream);
+
 int pinn_abi_version(void);
 
 #ifdef __cplusplus

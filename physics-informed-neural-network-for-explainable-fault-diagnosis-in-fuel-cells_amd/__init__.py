@@ -8,7 +8,10 @@ Public surface mirrors the reference's `01_train_pinn_multiphysics_model.py`:
 stage after the results array, script 04's risk function: `estimate_mu_sigma_normal`, `compute_rf_time_series`,
 `find_first_alarm_index`, `compute_rf_advance_for_condition`, with `rf_advance_for_conditions` and `RiskMonitor` (risk); and script 03's Gaussian-mixture
 fault diagnosis: `fit_gmm_and_get_probabilities`, `extract_X_y`, the spec parsers, with `DeviceGMM`, `FaultDiagnoser` and
-`classification_metrics` (diagnosis).
+`classification_metrics` (diagnosis); and script 02's fault detection: `build_classifier`, `explain_coefficients`, with
+`DeviceStandardScaler`, `DeviceLogisticRegression`, `roc_curve`, `auc`, `auc_score`, `stratified_split`,
+`evaluate_feature_groups`, `FaultDetector`, and script 05's `run_supervised_lr`, `compute_macro_metrics` (detection; its
+`parse_features` and `parse_group_spec` are script 02's variants and stay in the submodule).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -27,6 +30,10 @@ _LAZY = {
     "DeviceGMM": "diagnosis", "FaultDiagnoser": "diagnosis", "fit_gmm_and_get_probabilities": "diagnosis",
     "classification_metrics": "diagnosis", "extract_X_y": "diagnosis", "parse_features": "diagnosis",
     "parse_group_spec": "diagnosis", "build_label_mapper": "diagnosis", "normalize_feature_spec": "diagnosis",
+    "DeviceStandardScaler": "detection", "DeviceLogisticRegression": "detection", "build_classifier": "detection",
+    "explain_coefficients": "detection", "roc_curve": "detection", "auc": "detection", "auc_score": "detection",
+    "stratified_split": "detection", "evaluate_feature_groups": "detection", "FaultDetector": "detection",
+    "run_supervised_lr": "detection", "compute_macro_metrics": "detection",
 }
 
 

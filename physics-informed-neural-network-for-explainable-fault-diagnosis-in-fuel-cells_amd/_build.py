@@ -32,6 +32,8 @@ SOURCES = [
     ("pinn_risk.hip", ["-ffp-contract=off"]),
     # float64 mixture model; contraction is allowed here (gates are tolerances, the summation order is what is fixed)
     ("pinn_gmm.hip", []),
+    # float64 logistic regression and ROC; as the mixture: tolerances on sums of a fixed order, integers for the curve
+    ("pinn_lr.hip", []),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

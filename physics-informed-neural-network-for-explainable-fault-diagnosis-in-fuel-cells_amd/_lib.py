@@ -75,6 +75,13 @@ RF_ABOVE, RF_BELOW, RF_TILE = 0, 1, 2048
 GMM_MAX_COMP, GMM_MAX_FEAT, GMM_MAX_CLASSES, GMM_SINGULAR, GMM_TILE = 32, 8, 16, 1, 128
 GMM_ST_ITER, GMM_ST_CONVERGED, GMM_ST_STATUS, GMM_ST_K, GMM_ST_D, GMM_ST_LOWER, GMM_ST_PREV, GMM_ST_CHANGE, GMM_ST_HEADER = range(9)
 
+# pinn_lr.hip: limits, status and the 8-byte words of the state header and of the ROC counts
+LR_MAX_CLASSES, LR_MAX_FEAT, LR_MAX_HESS, LR_SINGULAR, LR_NAN, LR_STALLED, LR_TILE = 13, 8, 1365, 1, 2, 3, 128
+(LR_ST_ITER, LR_ST_CONVERGED, LR_ST_STATUS, LR_ST_C, LR_ST_D, LR_ST_F, LR_ST_STEP, LR_ST_DD, LR_ST_PASSES, LR_ST_GMAX, LR_ST_SWSUM,
+ LR_ST_PHASE, LR_ST_NSEEN, LR_ST_MAXITER) = range(14)
+LR_ST_HEADER = 16
+LR_ROC_POS, LR_ROC_N, LR_ROC_M, LR_ROC_KEPT, LR_ROC_U2, LR_ROC_COUNTS = 0, 1, 2, 3, 4, 8
+
 
 class PinnError(RuntimeError):
     pass
@@ -161,6 +168,19 @@ _SIGS = {
                                    c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_gmm_posterior": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_lr_state_bytes": (c_size_t, [c_int, c_int]),
+    "pinn_lr_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_lr_scaler": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_int, c_int, c_void_p,
+                               c_void_p, c_size_t, c_void_p]),
+    "pinn_lr_pass": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p,
+                             c_size_t, c_void_p]),
+    "pinn_lr_newton": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_int, c_int,
+                               ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_lr_posterior": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_lr_roc_workspace_bytes": (c_size_t, [c_ll]),
+    "pinn_lr_roc": (c_int, [c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,775 @@
+// Fault detection on the device (reference script 02, cited as 02:<line>): StandardScaler + multinomial logistic
+// regression (02:195-207) and the ROC curve / AUC of 1 - P(normal) (02:552-557).  All arithmetic is float64.
+//   pinn_lr_scaler     mean_, var_, scale_, class counts and class weights of the training rows (two passes)
+//   pinn_lr_pass       loss, gradient and Hessian sums of one row pass at the state's point (for tests and tools)
+//   pinn_lr_newton     damped Newton iterations, two launches each, no host synchronisation between them
+//   pinn_lr_posterior  decision_function, predict_proba, predict and p_fault per row, one launch
+//   pinn_lr_roc        boundaries of the sorted scores, fps / tps, drop_intermediate, fpr / tpr and the integer area
+//
+// The row pass follows pinn_gmm.hip: a workgroup takes tiles of 128 rows, one thread per row standardises its row and
+// writes (z, 1), the class probabilities, the sample weight and the loss term into LDS; then every thread owns up to 12 of
+// the 1 + P + H output sums (loss; gradient, P = C (D + 1); Hessian blocks c <= d, upper triangles, H = C (C + 1) / 2 x
+// (D + 1) (D + 2) / 2) and adds the tile's 128 terms to them in row order, in registers.  Workgroup sums go to the
+// workspace; a one-workgroup launch adds them in index order, adds the penalty and decides the step.  No float atomics, no
+// workgroup waits on another: stream order is the only dependency and the same call gives the same bytes every time.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "../../include/pinn_hip.h"
+
+namespace pinn {
+namespace {
+
+constexpr int kRows = 128;                  // rows per tile = threads per workgroup of the row pass
+constexpr int kMaxC = PINN_LR_MAX_CLASSES, kMaxD = PINN_LR_MAX_FEAT, kMaxH = PINN_LR_MAX_HESS;
+constexpr int kMaxP = 65;                   // largest C (D + 1) under the three limits (C = 13, D = 4)
+constexpr int kMaxSums = 1 + kMaxP + kMaxH;
+constexpr int kMaxOut = (kMaxSums + kRows - 1) / kRows;                        // output sums per thread: 12
+constexpr int kMaxBlocks = 1024;            // workgroups of a row pass = partial sums per output
+constexpr int kFinThreads = 256;
+constexpr int kHdr = PINN_LR_ST_HEADER;
+constexpr double kEps = 2.220446049250313e-16;
+
+enum { FIN_SUMS = 0, FIN_NEWTON = 1 };
+
+struct Rows {
+  const double* arr;
+  long long ld, n_arr, n;
+  const long long* ridx;
+  int D, C;
+  int col[kMaxD];
+};
+
+// state block: header, then theta [P] (the point the next pass evaluates), accepted [P], direction [P], gradient [P] of the
+// accepted point, mean [D], scale [D], var [D], class_weight [C], class_count [C] (64-bit integers).
+// theta is laid out [C][D + 1]: the D coefficients of a class, then its intercept.
+__host__ __device__ inline int n_par(int C, int D) { return C * (D + 1); }
+__host__ __device__ inline int n_hess(int C, int D) { return (C * (C + 1) / 2) * ((D + 1) * (D + 2) / 2); }
+__host__ __device__ inline size_t st_theta() { return kHdr; }
+__host__ __device__ inline size_t st_prev(int C, int D) { return kHdr + (size_t)n_par(C, D); }
+__host__ __device__ inline size_t st_dir(int C, int D) { return kHdr + 2 * (size_t)n_par(C, D); }
+__host__ __device__ inline size_t st_grad(int C, int D) { return kHdr + 3 * (size_t)n_par(C, D); }
+__host__ __device__ inline size_t st_mean(int C, int D) { return kHdr + 4 * (size_t)n_par(C, D); }
+__host__ __device__ inline size_t st_scale(int C, int D) { return st_mean(C, D) + D; }
+__host__ __device__ inline size_t st_var(int C, int D) { return st_mean(C, D) + 2 * D; }
+__host__ __device__ inline size_t st_cw(int C, int D) { return st_mean(C, D) + 3 * D; }
+__host__ __device__ inline size_t st_count(int C, int D) { return st_cw(C, D) + C; }
+__host__ __device__ inline size_t st_words(int C, int D) { return st_count(C, D) + C; }
+
+inline bool in_limits(int C, int D) {
+  return C >= 2 && C <= kMaxC && D >= 1 && D <= kMaxD && n_hess(C, D) <= kMaxH && n_par(C, D) <= kMaxP;
+}
+
+__device__ __forceinline__ bool stopped(const double* st) {
+  const long long* h = reinterpret_cast<const long long*>(st);
+  return h[PINN_LR_ST_CONVERGED] != 0 || h[PINN_LR_ST_STATUS] != 0 || h[PINN_LR_ST_ITER] >= h[PINN_LR_ST_MAXITER];
+}
+
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
+
+__device__ __forceinline__ int tri(int i, int j) { return j * (j + 1) / 2 + i; }      // i <= j
+
+__device__ __forceinline__ void untri(int p, int* i, int* j) {
+  int jj = 0;
+  while ((jj + 1) * (jj + 2) / 2 <= p) ++jj;
+  *j = jj;
+  *i = p - jj * (jj + 1) / 2;
+}
+
+__device__ __forceinline__ bool load_row(const Rows& a, long long j, double x[kMaxD]) {
+  const long long row = a.ridx ? a.ridx[j] : j;
+  const bool ok = row >= 0 && row < a.n_arr;               // a gather index outside the array reads nothing
+  const double* r = a.arr + (ok ? row : 0) * a.ld;
+#pragma unroll
+  for (int i = 0; i < kMaxD; ++i) x[i] = (ok && i < a.D) ? r[a.col[i]] : 0.0;
+  return ok;
+}
+
+// The model of a row, shared by the fit and the posterior: z = (x - mean) / scale into u[0..D), the scores of the R
+// parameter rows W [R][ldw] (+ intercept at W[r][D] when with_b) into s[r * stride]: products added in feature order.
+__device__ __forceinline__ void row_scores(const double x[kMaxD], int D, int R, const double* mean, const double* scale,
+                                           const double* W, int ldw, bool with_b, double* u, double* s, int stride) {
+#pragma unroll
+  for (int i = 0; i < kMaxD; ++i)
+    if (i < D) u[i] = (x[i] - mean[i]) / scale[i];
+  for (int r = 0; r < R; ++r) {
+    double v = 0.0;
+    for (int i = 0; i < D; ++i) v += W[r * ldw + i] * u[i];
+    if (with_b) v += W[r * ldw + D];
+    s[r * stride] = v;
+  }
+}
+
+// softmax in place over s[0..C): returns logsumexp (scipy's order: max, sum, log); s becomes exp(s - max) / sum
+__device__ __forceinline__ double softmax_inplace(double* s, int C) {
+  double m = s[0];
+  for (int c = 1; c < C; ++c) m = s[c] > m ? s[c] : m;
+  double sum = 0.0;
+  for (int c = 0; c < C; ++c) { s[c] = exp(s[c] - m); sum += s[c]; }
+  for (int c = 0; c < C; ++c) s[c] /= sum;
+  return log(sum) + m;
+}
+
+// ---- the row pass.  part: [gridDim.x][n_sums]
+__global__ __launch_bounds__(kRows) void lr_rows_kernel(Rows a, const double* __restrict__ st, const long long* __restrict__ y_in,
+                                                        int force, double* __restrict__ part) {
+  __shared__ double s_p[kRows * kMaxC];          // probabilities, row stride C | 1
+  __shared__ double s_u[kRows * (kMaxD + 1)];    // (z, 1), row stride (D + 1) | 1
+  __shared__ double s_w[kRows], s_l[kRows];
+  __shared__ int s_y[kRows];
+  __shared__ double s_th[kMaxP], s_mean[kMaxD], s_scale[kMaxD], s_cw[kMaxC];
+  if (!force && stopped(st)) return;
+  const int C = a.C, D = a.D, Cp = C | 1, Up = (D + 1) | 1, t = threadIdx.x, P = n_par(C, D);
+  for (int e = t; e < P; e += kRows) s_th[e] = st[st_theta() + e];
+  if (t < D) { s_mean[t] = st[st_mean(C, D) + t]; s_scale[t] = st[st_scale(C, D) + t]; }
+  if (t < C) s_cw[t] = st[st_cw(C, D) + t];
+  __syncthreads();
+
+  // the outputs of this thread: o = t + q kRows -> loss | gradient (c, i) | Hessian (c <= d, i <= j)
+  const int nT = (D + 1) * (D + 2) / 2, n_sums = 1 + P + n_hess(C, D);
+  int oc[kMaxOut], od[kMaxOut], oi[kMaxOut], oj[kMaxOut];
+  double acc[kMaxOut];
+#pragma unroll
+  for (int q = 0; q < kMaxOut; ++q) {
+    const int o = t + q * kRows;
+    acc[q] = 0.0;
+    oc[q] = -2; od[q] = -1; oi[q] = 0; oj[q] = 0;
+    if (o == 0) {
+      oc[q] = -1;
+    } else if (o <= P) {
+      oc[q] = (o - 1) / (D + 1);
+      oi[q] = (o - 1) - oc[q] * (D + 1);
+    } else if (o < n_sums) {
+      const int h = o - 1 - P, pc = h / nT;
+      untri(pc, &oc[q], &od[q]);
+      untri(h - pc * nT, &oi[q], &oj[q]);
+    }
+  }
+
+  const long long tiles = (a.n + kRows - 1) / kRows;
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long long j = tile * kRows + t;
+    double x[kMaxD];
+    bool ok = false;
+    long long cls = -1;
+    if (j < a.n) {
+      ok = load_row(a, j, x);
+      cls = y_in[j];
+    }
+    ok = ok && cls >= 0 && cls < C;                           // a class outside [0, C) adds nothing
+    double* p = s_p + t * Cp;
+    double* u = s_u + t * Up;
+    if (ok) {
+      row_scores(x, D, C, s_mean, s_scale, s_th, D + 1, true, u, p, 1);
+      u[D] = 1.0;
+      const double sy = p[cls];
+      const double lse = softmax_inplace(p, C);
+      s_w[t] = s_cw[cls];
+      s_l[t] = s_cw[cls] * (lse - sy);
+      s_y[t] = (int)cls;
+    } else {
+      for (int c = 0; c < C; ++c) p[c] = 0.0;
+      for (int i = 0; i <= D; ++i) u[i] = 0.0;
+      s_w[t] = 0.0; s_l[t] = 0.0; s_y[t] = -1;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kMaxOut; ++q) {
+      const int c = oc[q];
+      if (c == -2) continue;
+      double s = acc[q];
+      if (c == -1) {
+#pragma unroll 4
+        for (int rr = 0; rr < kRows; ++rr) s += s_l[rr];
+      } else if (od[q] < 0) {
+        const int i = oi[q];
+#pragma unroll 4
+        for (int rr = 0; rr < kRows; ++rr) s += s_w[rr] * (s_p[rr * Cp + c] - (s_y[rr] == c ? 1.0 : 0.0)) * s_u[rr * Up + i];
+      } else {
+        const int d = od[q], i = oi[q], jj = oj[q];
+        const double delta = c == d ? 1.0 : 0.0;
+#pragma unroll 4
+        for (int rr = 0; rr < kRows; ++rr)
+          s += s_w[rr] * s_p[rr * Cp + c] * (delta - s_p[rr * Cp + d]) * (s_u[rr * Up + i] * s_u[rr * Up + jj]);
+      }
+      acc[q] = s;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < kMaxOut; ++q)
+    if (oc[q] != -2) part[(size_t)blockIdx.x * n_sums + t + q * kRows] = acc[q];
+}
+
+// ---- sums of the partials in index order, then the step.  One workgroup.  tot: [n_sums] (kept in the workspace).
+__global__ __launch_bounds__(kFinThreads) void lr_final_kernel(double* __restrict__ st, int C, int D, int mode, int n_part, long long n,
+                                                               double tol, double l2, int fit_intercept,
+                                                               const double* __restrict__ part, double* __restrict__ tot) {
+  __shared__ double A[kMaxP * kMaxP];
+  __shared__ double g[kMaxP], dirv[kMaxP];
+  __shared__ int s_flag;
+  long long* hdr = reinterpret_cast<long long*>(st);
+  if (mode == FIN_NEWTON && stopped(st)) return;
+  const int P = n_par(C, D), nT = (D + 1) * (D + 2) / 2, n_sums = 1 + P + n_hess(C, D), t = threadIdx.x, D1 = D + 1;
+  for (int o = t; o < n_sums; o += kFinThreads) {
+    double s = 0.0;
+    for (int b = 0; b < n_part; ++b) s += part[(size_t)b * n_sums + o];
+    tot[o] = s;
+  }
+  __syncthreads();
+  if (mode == FIN_SUMS) return;
+
+  double* theta = st + st_theta();
+  double* prev = st + st_prev(C, D);
+  double* dir = st + st_dir(C, D);
+  const double sw_sum = st[PINN_LR_ST_SWSUM];
+  // F = loss + l2 / 2 |W|^2; gradient + l2 W; a parameter that is not fitted has gradient 0
+  if (t == 0) {
+    double pen = 0.0;
+    for (int c = 0; c < C; ++c)
+      for (int i = 0; i < D; ++i) pen += theta[c * D1 + i] * theta[c * D1 + i];
+    const double F = tot[0] + 0.5 * l2 * pen;
+    int bad = !(F == F) || !(fabs(F) < INFINITY);
+    for (int p = 0; p < P; ++p) {
+      const int i = p % D1;
+      double v = tot[1 + p] + (i < D ? l2 * theta[p] : 0.0);
+      if (i == D && !fit_intercept) v = 0.0;
+      if (!(v == v)) bad = 1;
+      g[p] = v;
+    }
+    int flag = 0;                                             // 0 accept, 1 reject, 2 fail
+    const long long phase = hdr[PINN_LR_ST_PHASE];
+    if (phase == 0) {
+      if (bad) flag = 2;
+    } else {
+      // Armijo on the stored directional derivative, with a floor at the rounding of the loss sum itself
+      const double Fp = st[PINN_LR_ST_F], step = st[PINN_LR_ST_STEP], dd = st[PINN_LR_ST_DD];
+      const double floor_ = 4.0 * (double)n * kEps * fabs(tot[0]);
+      if (bad || !(F <= Fp + 1e-4 * step * dd + floor_)) flag = 1;
+    }
+    if (flag == 1) {
+      const double step = 0.5 * st[PINN_LR_ST_STEP];
+      hdr[PINN_LR_ST_PASSES] += 1;
+      if (step < 9.094947017729282e-13) {                     // 2^-40: the direction gives no decrease
+        for (int p = 0; p < P; ++p) theta[p] = prev[p];
+        hdr[PINN_LR_ST_STATUS] = PINN_LR_STALLED;
+      } else {
+        st[PINN_LR_ST_STEP] = step;
+        for (int p = 0; p < P; ++p) theta[p] = prev[p] + step * dir[p];
+      }
+    } else if (flag == 2) {
+      hdr[PINN_LR_ST_STATUS] = PINN_LR_NAN;
+    } else {
+      double gmax = 0.0;
+      for (int p = 0; p < P; ++p) {
+        prev[p] = theta[p];
+        st[st_grad(C, D) + p] = g[p];
+        gmax = fabs(g[p]) > gmax ? fabs(g[p]) : gmax;
+      }
+      st[PINN_LR_ST_F] = F;
+      st[PINN_LR_ST_GMAX] = gmax / sw_sum;
+      hdr[PINN_LR_ST_PASSES] += 1;
+      if (phase != 0) hdr[PINN_LR_ST_ITER] += 1;
+      hdr[PINN_LR_ST_PHASE] = 1;
+      if (gmax / sw_sum <= tol) { hdr[PINN_LR_ST_CONVERGED] = 1; flag = 3; }
+    }
+    s_flag = flag;
+  }
+  __syncthreads();
+  if (s_flag != 0) return;
+
+  // Hessian, full P x P from the upper triangles: H[(c,i),(d,j)] = T[pair(c,d)][tri(min(i,j), max(i,j))], + l2 on the
+  // coefficients' diagonal, + kappa on every pair of intercepts: the rank-one term that pins the sum of the intercepts.
+  const double kappa = sw_sum / (double)C;
+  // Far from the minimum the probabilities saturate and the factorisation can fail in rounding: it is then repeated with a
+  // ridge of 1e-6, 1e-4, 1e-2 sum sw on the diagonal, which changes the direction (still one of descent), not the minimiser.
+  for (int attempt = 0; attempt < 4; ++attempt) {
+    const double ridge = attempt == 0 ? 0.0 : sw_sum * (attempt == 1 ? 1e-6 : (attempt == 2 ? 1e-4 : 1e-2));
+    for (int e = t; e < P * P; e += kFinThreads) {
+      const int r = e / P, q = e - r * P;
+      int c = r / D1, i = r - c * D1, d = q / D1, j = q - d * D1;
+      if (c > d) { const int tc = c; c = d; d = tc; }
+      const int lo = i < j ? i : j, hi = i < j ? j : i;
+      double v = tot[1 + P + tri(c, d) * nT + tri(lo, hi)];
+      if (r == q && i < D) v += l2;
+      if (i == D && j == D) v += kappa;
+      if (r == q) v += ridge;
+      if (!fit_intercept && (i == D || j == D)) v = r == q ? 1.0 : 0.0;
+      A[e] = v;
+    }
+    __syncthreads();
+    if (t == 0) s_flag = 0;
+    __syncthreads();
+    // Cholesky A = L L^T, right-looking, L in the lower triangle
+    for (int k = 0; k < P; ++k) {
+      if (t == 0) {
+        const double piv = A[k * P + k];
+        if (!(piv > 0.0) || !(piv < INFINITY)) s_flag = 2; else A[k * P + k] = sqrt(piv);
+      }
+      __syncthreads();
+      if (s_flag == 2) break;
+      const double lkk = A[k * P + k];
+      for (int r = k + 1 + t; r < P; r += kFinThreads) A[r * P + k] /= lkk;
+      __syncthreads();
+      const int m = P - k - 1;
+      for (int e = t; e < m * m; e += kFinThreads) {
+        const int r = k + 1 + e / m, q = k + 1 + e % m;
+        if (q <= r) A[r * P + q] -= A[r * P + k] * A[q * P + k];
+      }
+      __syncthreads();
+    }
+    if (s_flag != 2) break;
+  }
+  if (t == 0) {
+    if (s_flag == 2) {
+      for (int p = 0; p < P; ++p) theta[p] = prev[p];
+      hdr[PINN_LR_ST_STATUS] = PINN_LR_SINGULAR;
+    } else {
+      for (int r = 0; r < P; ++r) {                           // L w = -g
+        double v = -g[r];
+        for (int q = 0; q < r; ++q) v -= A[r * P + q] * dirv[q];
+        dirv[r] = v / A[r * P + r];
+      }
+      for (int r = P - 1; r >= 0; --r) {                      // L^T dir = w
+        double v = dirv[r];
+        for (int q = r + 1; q < P; ++q) v -= A[q * P + r] * dirv[q];
+        dirv[r] = v / A[r * P + r];
+      }
+      double dd = 0.0;
+      int bad = 0;
+      for (int p = 0; p < P; ++p) { dd += g[p] * dirv[p]; bad |= !(dirv[p] == dirv[p]); }
+      if (bad || !(dd < 0.0)) {
+        // dd == 0 only with a zero gradient, which the tolerance test has already taken unless tol is 0
+        if (!bad && dd == 0.0) hdr[PINN_LR_ST_CONVERGED] = 1; else hdr[PINN_LR_ST_STATUS] = bad ? PINN_LR_NAN : PINN_LR_SINGULAR;
+      } else {
+        st[PINN_LR_ST_DD] = dd;
+        st[PINN_LR_ST_STEP] = 1.0;
+        for (int p = 0; p < P; ++p) { dir[p] = dirv[p]; theta[p] = prev[p] + dirv[p]; }
+      }
+    }
+  }
+}
+
+// ---- scaler: sums of x (pass 0) or of (x - mean)^2 (pass 1) per feature, class counts.  part: [grid][D], cnt: [grid][C]
+__global__ __launch_bounds__(kRows) void lr_stats_kernel(Rows a, const double* __restrict__ st, const long long* __restrict__ y_in, int pass,
+                                                         double* __restrict__ part, long long* __restrict__ cnt) {
+  __shared__ double s_x[kRows * (kMaxD + 1)];
+  __shared__ int s_y[kRows];
+  const int C = a.C, D = a.D, Dp = D | 1, t = threadIdx.x;
+  const double mean = (pass == 1 && t < D) ? st[st_mean(C, D) + t] : 0.0;
+  double acc = 0.0;
+  long long count = 0;
+  const long long tiles = (a.n + kRows - 1) / kRows;
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long long j = tile * kRows + t;
+    double x[kMaxD];
+    bool ok = false;
+    long long cls = -1;
+    if (j < a.n) {
+      ok = load_row(a, j, x);
+      cls = y_in ? y_in[j] : 0;
+    }
+    ok = ok && cls >= 0 && cls < C;
+    s_y[t] = ok ? (int)cls : -1;
+#pragma unroll
+    for (int i = 0; i < kMaxD; ++i)
+      if (i < D) s_x[t * Dp + i] = ok ? x[i] : (pass == 1 ? quiet_nan() : 0.0);
+    __syncthreads();
+    if (t < D) {
+      for (int rr = 0; rr < kRows; ++rr) {
+        if (pass == 0) acc += s_x[rr * Dp + t];
+        else if (s_y[rr] >= 0) { const double d = s_x[rr * Dp + t] - mean; acc += d * d; }
+      }
+    } else if (t - kMaxD >= 0 && t - kMaxD < C) {
+      for (int rr = 0; rr < kRows; ++rr) count += s_y[rr] == t - kMaxD ? 1 : 0;
+    }
+    __syncthreads();
+  }
+  if (t < D) part[(size_t)blockIdx.x * D + t] = acc;
+  else if (t - kMaxD >= 0 && t - kMaxD < C) cnt[(size_t)blockIdx.x * C + (t - kMaxD)] = count;
+}
+
+__global__ __launch_bounds__(64) void lr_stats_final_kernel(double* __restrict__ st, int C, int D, int pass, int balanced, int n_part,
+                                                            const double* __restrict__ part, const long long* __restrict__ cnt) {
+  __shared__ long long s_cnt[kMaxC];
+  long long* hdr = reinterpret_cast<long long*>(st);
+  const int t = threadIdx.x;
+  if (t < C) {
+    long long s = 0;
+    for (int b = 0; b < n_part; ++b) s += cnt[(size_t)b * C + t];
+    s_cnt[t] = s;
+  }
+  __syncthreads();
+  long long n = 0;
+  for (int c = 0; c < C; ++c) n += s_cnt[c];
+  if (t < D) {
+    double s = 0.0;
+    for (int b = 0; b < n_part; ++b) s += part[(size_t)b * D + t];
+    if (pass == 0) {
+      st[st_mean(C, D) + t] = n > 0 ? s / (double)n : 0.0;
+    } else {
+      const double var = n > 0 ? s / (double)n : 0.0, mean = st[st_mean(C, D) + t];
+      double scale = sqrt(var);
+      // scikit-learn's _is_constant_feature and _handle_zeros_in_scale
+      const double nm = (double)n * mean * kEps, bound = (double)n * kEps * var + nm * nm;
+      if (var <= bound || scale < 10.0 * kEps) scale = 1.0;
+      st[st_var(C, D) + t] = var;
+      st[st_scale(C, D) + t] = scale;
+    }
+  }
+  if (pass == 1 && t == 0) {
+    double sw = 0.0;
+    for (int c = 0; c < C; ++c) {
+      const double w = !balanced ? 1.0 : (s_cnt[c] > 0 ? (double)n / ((double)C * (double)s_cnt[c]) : 0.0);
+      st[st_cw(C, D) + c] = w;
+      reinterpret_cast<long long*>(st)[st_count(C, D) + c] = s_cnt[c];
+      sw += w * (double)s_cnt[c];
+    }
+    st[PINN_LR_ST_SWSUM] = sw;
+    hdr[PINN_LR_ST_NSEEN] = n;
+    hdr[PINN_LR_ST_C] = C;
+    hdr[PINN_LR_ST_D] = D;
+  }
+}
+
+// ---- posterior of given rows: one thread per row, every output optional.
+// model: mean [D], scale [D], W [R][D], b [R]; R = 1 for two classes (scikit-learn's coef_ [1, D]: scores (-d, d)), else C.
+__global__ __launch_bounds__(kRows) void lr_posterior_kernel(Rows a, const double* __restrict__ model, int normal, double* __restrict__ dec_out,
+                                                             double* __restrict__ proba_out, long long* __restrict__ pred_out,
+                                                             double* __restrict__ pf_out) {
+  __shared__ double s_p[kRows * kMaxC];
+  __shared__ double s_mean[kMaxD], s_scale[kMaxD], s_W[kMaxC * (kMaxD + 1)];
+  const int C = a.C, D = a.D, Cp = C | 1, R = C == 2 ? 1 : C, t = threadIdx.x;
+  if (t < D) { s_mean[t] = model[t]; s_scale[t] = model[D + t]; }
+  for (int e = t; e < R * (D + 1); e += kRows) {
+    const int r = e / (D + 1), i = e - r * (D + 1);
+    s_W[e] = i < D ? model[2 * D + r * D + i] : model[2 * D + R * D + r];
+  }
+  __syncthreads();
+  const long long j = (long long)blockIdx.x * kRows + t;
+  if (j >= a.n) return;
+  double x[kMaxD], u[kMaxD];
+  const bool ok = load_row(a, j, x);
+  double* p = s_p + t * Cp;
+  if (ok) {
+    row_scores(x, D, R, s_mean, s_scale, s_W, D + 1, true, u, p, 1);
+    if (R == 1) { p[1] = p[0]; p[0] = -p[1]; }
+  } else {
+    for (int c = 0; c < C; ++c) p[c] = quiet_nan();
+  }
+  if (dec_out) {
+    if (R == 1) dec_out[j] = p[1];
+    else for (int c = 0; c < C; ++c) dec_out[j * C + c] = p[c];
+  }
+  int best = 0;
+  for (int c = 1; c < C; ++c) best = p[c] > p[best] ? c : best;       // the first maximum
+  if (pred_out) pred_out[j] = ok ? best : -1;
+  if (proba_out || pf_out) {
+    if (ok) softmax_inplace(p, C);
+    if (proba_out)
+      for (int c = 0; c < C; ++c) proba_out[j * C + c] = p[c];
+    if (pf_out) pf_out[j] = 1.0 - p[normal];
+  }
+}
+
+// ---- ROC.  Scores come sorted descending; element i closes a group of equal scores when score[i] != score[i + 1].
+// Integer scans with tile sums: a launch sums tiles, a one-workgroup launch scans the tile sums, a launch rescans its tile
+// with the offset.  Stage 1 compacts (fps, tps, threshold) at the boundaries; stage 2 keeps the corners
+// (drop_intermediate) and divides.
+constexpr int kTile = 256;
+
+__device__ __forceinline__ void block_scan2(long long* sa, long long* sb, int t) {      // inclusive, in place, kTile entries
+  for (int off = 1; off < kTile; off <<= 1) {
+    const long long va = t >= off ? sa[t - off] : 0, vb = t >= off ? sb[t - off] : 0;
+    __syncthreads();
+    sa[t] += va; sb[t] += vb;
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ bool roc_boundary(const double* score, long long i, long long n) {
+  return i == n - 1 || score[i] != score[i + 1];
+}
+
+__global__ __launch_bounds__(kTile) void roc_tiles1_kernel(const double* __restrict__ score, const long long* __restrict__ pos, long long n,
+                                                           long long* __restrict__ tile_pos, long long* __restrict__ tile_flag) {
+  __shared__ long long sa[kTile], sb[kTile];
+  const int t = threadIdx.x;
+  const long long i = (long long)blockIdx.x * kTile + t;
+  sa[t] = i < n ? (pos[i] != 0) : 0;
+  sb[t] = i < n ? roc_boundary(score, i, n) : 0;
+  __syncthreads();
+  block_scan2(sa, sb, t);
+  if (t == kTile - 1) { tile_pos[blockIdx.x] = sa[t]; tile_flag[blockIdx.x] = sb[t]; }
+}
+
+// exclusive scan of nt tile sums in place (both arrays; b may be NULL); totals to tot_a / tot_b.  One workgroup.
+__global__ __launch_bounds__(kTile) void roc_scan_tiles_kernel(long long* __restrict__ a, long long* __restrict__ b, long long nt,
+                                                               long long* __restrict__ tot_a, long long* __restrict__ tot_b) {
+  __shared__ long long sa[kTile], sb[kTile];
+  const int t = threadIdx.x;
+  const long long per = (nt + kTile - 1) / kTile, lo = t * per, hi = lo + per < nt ? lo + per : nt;
+  long long xa = 0, xb = 0;
+  for (long long k = lo; k < hi; ++k) { xa += a[k]; if (b) xb += b[k]; }
+  sa[t] = xa; sb[t] = xb;
+  __syncthreads();
+  block_scan2(sa, sb, t);
+  long long ra = sa[t] - xa, rb = sb[t] - xb;
+  for (long long k = lo; k < hi; ++k) {
+    const long long va = a[k];
+    a[k] = ra; ra += va;
+    if (b) { const long long vb = b[k]; b[k] = rb; rb += vb; }
+  }
+  if (t == kTile - 1) { *tot_a = sa[t]; if (tot_b) *tot_b = sb[t]; }
+}
+
+__global__ __launch_bounds__(kTile) void roc_emit1_kernel(const double* __restrict__ score, const long long* __restrict__ pos, long long n,
+                                                          const long long* __restrict__ tile_pos, const long long* __restrict__ tile_flag,
+                                                          long long* __restrict__ fps, long long* __restrict__ tps, double* __restrict__ thr) {
+  __shared__ long long sa[kTile], sb[kTile];
+  const int t = threadIdx.x;
+  const long long i = (long long)blockIdx.x * kTile + t;
+  const bool bd = i < n && roc_boundary(score, i, n);
+  sa[t] = i < n ? (pos[i] != 0) : 0;
+  sb[t] = bd;
+  __syncthreads();
+  block_scan2(sa, sb, t);
+  if (bd) {
+    const long long k = tile_flag[blockIdx.x] + sb[t] - 1, tp = tile_pos[blockIdx.x] + sa[t];
+    tps[k] = tp;
+    fps[k] = 1 + i - tp;
+    thr[k] = score[i];
+  }
+}
+
+// per boundary k < m: the area term dfps (tps[k - 1] + tps[k]) and the corner flag; tile sums of both
+__global__ __launch_bounds__(kTile) void roc_tiles2_kernel(const long long* __restrict__ fps, const long long* __restrict__ tps,
+                                                           const long long* __restrict__ d_m, int drop, long long* __restrict__ keep,
+                                                           long long* __restrict__ tile_keep, long long* __restrict__ tile_area) {
+  __shared__ long long sa[kTile], sb[kTile];
+  const int t = threadIdx.x;
+  const long long m = *d_m, k = (long long)blockIdx.x * kTile + t;
+  long long kp = 0, area = 0;
+  if (k < m) {
+    const long long f0 = k > 0 ? fps[k - 1] : 0, t0 = k > 0 ? tps[k - 1] : 0;
+    area = (fps[k] - f0) * (t0 + tps[k]);
+    kp = 1;
+    if (drop && m > 2 && k > 0 && k < m - 1)
+      kp = (fps[k + 1] - 2 * fps[k] + fps[k - 1]) != 0 || (tps[k + 1] - 2 * tps[k] + tps[k - 1]) != 0;
+    keep[k] = kp;
+  }
+  sa[t] = kp; sb[t] = area;
+  __syncthreads();
+  block_scan2(sa, sb, t);
+  if (t == kTile - 1) { tile_keep[blockIdx.x] = sa[t]; tile_area[blockIdx.x] = sb[t]; }
+}
+
+__global__ __launch_bounds__(kTile) void roc_emit2_kernel(const long long* __restrict__ fps, const long long* __restrict__ tps,
+                                                          const double* __restrict__ thr, const long long* __restrict__ keep,
+                                                          const long long* __restrict__ tile_keep, long long n, long long* __restrict__ cnt,
+                                                          long long* __restrict__ o_fps, long long* __restrict__ o_tps, double* __restrict__ o_thr,
+                                                          double* __restrict__ o_fpr, double* __restrict__ o_tpr) {
+  __shared__ long long sa[kTile], sb[kTile];
+  const int t = threadIdx.x;
+  const long long m = cnt[PINN_LR_ROC_M], k = (long long)blockIdx.x * kTile + t;
+  const long long kp = k < m ? keep[k] : 0;
+  sa[t] = kp; sb[t] = 0;
+  __syncthreads();
+  block_scan2(sa, sb, t);
+  if (kp) {
+    // output point 0 is scikit-learn's (0, 0, inf)
+    const long long q = 1 + tile_keep[blockIdx.x] + sa[t] - 1;
+    const long long P = cnt[PINN_LR_ROC_POS], N = n - P;
+    if (o_fps) o_fps[q] = fps[k];
+    if (o_tps) o_tps[q] = tps[k];
+    if (o_thr) o_thr[q] = thr[k];
+    if (o_fpr) o_fpr[q] = N > 0 ? (double)fps[k] / (double)N : quiet_nan();
+    if (o_tpr) o_tpr[q] = P > 0 ? (double)tps[k] / (double)P : quiet_nan();
+  }
+  if (k == 0) {
+    cnt[PINN_LR_ROC_N] = n - cnt[PINN_LR_ROC_POS];
+    if (o_fps) o_fps[0] = 0;
+    if (o_tps) o_tps[0] = 0;
+    if (o_thr) o_thr[0] = INFINITY;
+    if (o_fpr) o_fpr[0] = 0.0;
+    if (o_tpr) o_tpr[0] = 0.0;
+  }
+}
+
+inline bool misaligned8(const void* p) { return ((unsigned long long)p & 7) != 0; }
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+inline int n_blocks(long long n) {
+  const long long tiles = (n + kRows - 1) / kRows;
+  return (int)(tiles < 1 ? 1 : (tiles > kMaxBlocks ? kMaxBlocks : tiles));
+}
+
+// checks shared by every entry point that reads rows; fills `a`
+inline int make_rows(const double* d_arr, long long ld, long long n_arr, const int* cols, int n_feat, int n_classes,
+                     const long long* d_row_index, long long n, Rows* a) {
+  if (n < 0 || n_arr < 0 || ld < 1 || !cols || !in_limits(n_classes, n_feat)) return PINN_E_ARG;
+  for (int i = 0; i < n_feat; ++i)
+    if (cols[i] < 0 || cols[i] >= ld) return PINN_E_ARG;
+  if (!d_row_index && n > n_arr) return PINN_E_ARG;
+  if (n > 0 && !d_arr) return PINN_E_ARG;
+  if (misaligned8(d_arr) || misaligned8(d_row_index)) return PINN_E_ARG;
+  a->arr = d_arr; a->ld = ld; a->n_arr = n_arr; a->n = n; a->ridx = d_row_index; a->D = n_feat; a->C = n_classes;
+  for (int i = 0; i < kMaxD; ++i) a->col[i] = i < n_feat ? cols[i] : 0;
+  return PINN_OK;
+}
+
+struct Ws {
+  double *tot, *part;
+  long long* cnt;
+};
+
+// workspace: totals [n_sums] (first, so that the caller can read the summed pass), partials, class-count partials
+inline Ws carve(void* d_ws, int C, int D) {
+  char* w = static_cast<char*>(d_ws);
+  Ws s;
+  const size_t n_sums = 1 + (size_t)n_par(C, D) + n_hess(C, D);
+  s.tot = reinterpret_cast<double*>(w); w += align256(n_sums * sizeof(double));
+  s.part = reinterpret_cast<double*>(w); w += align256((size_t)kMaxBlocks * n_sums * sizeof(double));
+  s.cnt = reinterpret_cast<long long*>(w);
+  return s;
+}
+
+}  // namespace
+}  // namespace pinn
+
+extern "C" size_t pinn_lr_state_bytes(int n_classes, int n_feat) {
+  if (!pinn::in_limits(n_classes, n_feat)) return 0;
+  return pinn::st_words(n_classes, n_feat) * sizeof(double);
+}
+
+extern "C" size_t pinn_lr_workspace_bytes(long long n_rows, int n_classes, int n_feat) {
+  using namespace pinn;
+  if (n_rows < 0 || !in_limits(n_classes, n_feat)) return 0;
+  const size_t n_sums = 1 + (size_t)n_par(n_classes, n_feat) + n_hess(n_classes, n_feat);
+  return align256(n_sums * sizeof(double)) + align256((size_t)kMaxBlocks * n_sums * sizeof(double)) +
+         align256((size_t)kMaxBlocks * kMaxC * sizeof(long long));
+}
+
+#define LR_COMMON_CHECKS()                                                                          \
+  Rows a;                                                                                           \
+  {                                                                                                 \
+    const int rc_ = make_rows(d_arr, ld, n_arr_rows, cols, n_feat, n_classes, d_row_index, n, &a);  \
+    if (rc_ != PINN_OK) return rc_;                                                                 \
+  }                                                                                                 \
+  if (!d_state || !d_ws || !d_y || misaligned8(d_state) || misaligned8(d_ws) || misaligned8(d_y)) return PINN_E_ARG; \
+  if (n < 1) return PINN_E_ARG;                                                                     \
+  if (ws_bytes < pinn_lr_workspace_bytes(n, n_classes, n_feat)) return PINN_E_WORKSPACE;            \
+  const Ws w = carve(d_ws, n_classes, n_feat);                                                      \
+  hipStream_t st = (hipStream_t)stream;                                                             \
+  (void)hipGetLastError()
+
+extern "C" int pinn_lr_scaler(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                              const long long* d_row_index, long long n, const long long* d_y, int n_classes, int balanced,
+                              double* d_state, void* d_ws, size_t ws_bytes, void* stream) {
+  using namespace pinn;
+  LR_COMMON_CHECKS();
+  const int nb = n_blocks(n);
+  for (int pass = 0; pass < 2; ++pass) {
+    hipLaunchKernelGGL(lr_stats_kernel, dim3((unsigned)nb), dim3(kRows), 0, st, a, d_state, d_y, pass, w.part, w.cnt);
+    hipLaunchKernelGGL(lr_stats_final_kernel, dim3(1), dim3(64), 0, st, d_state, n_classes, n_feat, pass, balanced, nb, w.part, w.cnt);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+extern "C" int pinn_lr_pass(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                            const long long* d_row_index, long long n, const long long* d_y, int n_classes,
+                            const double* d_state, void* d_ws, size_t ws_bytes, void* stream) {
+  using namespace pinn;
+  LR_COMMON_CHECKS();
+  const int nb = n_blocks(n);
+  hipLaunchKernelGGL(lr_rows_kernel, dim3((unsigned)nb), dim3(kRows), 0, st, a, d_state, d_y, 1, w.part);
+  hipLaunchKernelGGL(lr_final_kernel, dim3(1), dim3(kFinThreads), 0, st, const_cast<double*>(d_state), n_classes, n_feat, FIN_SUMS, nb, n,
+                     0.0, 0.0, 1, w.part, w.tot);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+extern "C" int pinn_lr_newton(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                              const long long* d_row_index, long long n, const long long* d_y, int n_classes, int n_passes,
+                              double tol, double l2, int fit_intercept, double* d_state, void* d_ws, size_t ws_bytes,
+                              void* stream) {
+  using namespace pinn;
+  LR_COMMON_CHECKS();
+  if (n_passes < 0 || n_passes > 100000 || !(tol >= 0.0) || !(l2 > 0.0) || !(l2 < INFINITY)) return PINN_E_ARG;
+  const int nb = n_blocks(n);
+  for (int it = 0; it < n_passes; ++it) {
+    hipLaunchKernelGGL(lr_rows_kernel, dim3((unsigned)nb), dim3(kRows), 0, st, a, d_state, d_y, 0, w.part);
+    hipLaunchKernelGGL(lr_final_kernel, dim3(1), dim3(kFinThreads), 0, st, d_state, n_classes, n_feat, FIN_NEWTON, nb, n, tol, l2,
+                       fit_intercept, w.part, w.tot);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+extern "C" int pinn_lr_posterior(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                                 const long long* d_row_index, long long n, int n_classes, const double* d_model,
+                                 int normal_class, double* d_decision, double* d_proba, long long* d_pred, double* d_p_fault,
+                                 void* stream) {
+  using namespace pinn;
+  Rows a;
+  const int rc = make_rows(d_arr, ld, n_arr_rows, cols, n_feat, n_classes, d_row_index, n, &a);
+  if (rc != PINN_OK) return rc;
+  if (!d_model || misaligned8(d_model) || misaligned8(d_decision) || misaligned8(d_proba) || misaligned8(d_pred) || misaligned8(d_p_fault))
+    return PINN_E_ARG;
+  if (normal_class < 0 || normal_class >= n_classes) return PINN_E_ARG;
+  if (n == 0) return PINN_OK;
+  const long long tiles = (n + kRows - 1) / kRows;
+  if (tiles > 0x7fffffffLL) return PINN_E_ARG;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(lr_posterior_kernel, dim3((unsigned)tiles), dim3(kRows), 0, (hipStream_t)stream, a, d_model, normal_class,
+                     d_decision, d_proba, d_pred, d_p_fault);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
+
+// ROC workspace: tile sums (4 arrays), then fps, tps, thresholds and keep flags at the boundaries, [n] each
+extern "C" size_t pinn_lr_roc_workspace_bytes(long long n) {
+  using namespace pinn;
+  if (n < 0) return 0;
+  const size_t nt = (size_t)((n + kTile - 1) / kTile) + 1;
+  return 4 * align256(nt * 8) + 4 * align256((size_t)(n + 1) * 8);
+}
+
+extern "C" int pinn_lr_roc(const double* d_score_sorted, const long long* d_pos_sorted, long long n, int drop_intermediate,
+                           long long* d_counts, long long* d_fps, long long* d_tps, double* d_thresholds, double* d_fpr,
+                           double* d_tpr, void* d_ws, size_t ws_bytes, void* stream) {
+  using namespace pinn;
+  if (n < 1 || !d_score_sorted || !d_pos_sorted || !d_counts || !d_ws) return PINN_E_ARG;
+  if (misaligned8(d_score_sorted) || misaligned8(d_pos_sorted) || misaligned8(d_counts) || misaligned8(d_fps) || misaligned8(d_tps) ||
+      misaligned8(d_thresholds) || misaligned8(d_fpr) || misaligned8(d_tpr) || misaligned8(d_ws))
+    return PINN_E_ARG;
+  if (ws_bytes < pinn_lr_roc_workspace_bytes(n)) return PINN_E_WORKSPACE;
+  const long long nt = (n + kTile - 1) / kTile;
+  if (nt > 0x7fffffffLL) return PINN_E_ARG;
+  char* w = static_cast<char*>(d_ws);
+  const size_t tb = align256((size_t)(nt + 1) * 8), nb = align256((size_t)(n + 1) * 8);
+  long long* tile_a = reinterpret_cast<long long*>(w); w += tb;
+  long long* tile_b = reinterpret_cast<long long*>(w); w += tb;
+  long long* tile_c = reinterpret_cast<long long*>(w); w += tb;
+  long long* tile_d = reinterpret_cast<long long*>(w); w += tb;
+  long long* fps = reinterpret_cast<long long*>(w); w += nb;
+  long long* tps = reinterpret_cast<long long*>(w); w += nb;
+  double* thr = reinterpret_cast<double*>(w); w += nb;
+  long long* keep = reinterpret_cast<long long*>(w);
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();
+  hipError_t e = hipMemsetAsync(d_counts, 0, PINN_LR_ROC_COUNTS * sizeof(long long), st);
+  if (e != hipSuccess) return (int)e;
+  const dim3 grid((unsigned)nt), block(kTile);
+  hipLaunchKernelGGL(roc_tiles1_kernel, grid, block, 0, st, d_score_sorted, d_pos_sorted, n, tile_a, tile_b);
+  hipLaunchKernelGGL(roc_scan_tiles_kernel, dim3(1), block, 0, st, tile_a, tile_b, nt, d_counts + PINN_LR_ROC_POS, d_counts + PINN_LR_ROC_M);
+  hipLaunchKernelGGL(roc_emit1_kernel, grid, block, 0, st, d_score_sorted, d_pos_sorted, n, tile_a, tile_b, fps, tps, thr);
+  // the number of boundaries stays on the device: the second stage is launched for n and every workgroup beyond it idles
+  hipLaunchKernelGGL(roc_tiles2_kernel, grid, block, 0, st, fps, tps, d_counts + PINN_LR_ROC_M, drop_intermediate, keep, tile_c, tile_d);
+  hipLaunchKernelGGL(roc_scan_tiles_kernel, dim3(1), block, 0, st, tile_c, tile_d, nt, d_counts + PINN_LR_ROC_KEPT, d_counts + PINN_LR_ROC_U2);
+  hipLaunchKernelGGL(roc_emit2_kernel, grid, block, 0, st, fps, tps, thr, keep, tile_c, n, d_counts, d_fps, d_tps, d_thresholds, d_fpr, d_tpr);
+  e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
