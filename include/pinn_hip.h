@@ -613,6 +613,99 @@ int pinn_lr_roc(const double* d_score_sorted, const long long* d_pos_sorted, lon
                 long long* d_counts, long long* d_fps, long long* d_tps, double* d_thresholds, double* d_fpr, double* d_tpr,
                 void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- clustering baselines of the method comparison: reference script 05 (cited as 05:<line>) -------------------------
+ * k-means and Ward agglomerative clustering with nearest-centre assignment, float64 throughout, every operation rounded on
+ * its own.  Rows are read in place as for the mixture above (column list, optional gather list, leading dimension; an index
+ * outside [0, n_arr_rows) reads nothing and adds nothing).  Every reduction has a fixed order, there are no float atomics
+ * and no workgroup waits on another: the same call gives the same bytes.
+ *
+ * Limits: n_feat <= PINN_CL_MAX_FEAT; n_clusters <= PINN_CL_MAX_CLUSTERS for k-means, the label means and the assignment;
+ * n_classes <= PINN_CL_MAX_CLASSES.  Outside: PINN_E_ARG, sizes 0.  Ward takes any number of rows below 2^31.
+ *
+ * Both state blocks begin with PINN_CL_ST_HEADER 8-byte words, of which [PINN_CL_ST_ITER] (Lloyd iterations / chain steps
+ * done), [.._CONVERGED] and [.._STATUS] (0 or PINN_CL_NAN) are common.  Once CONVERGED or STATUS is set, every later
+ * queued Lloyd or Ward launch returns at its first instruction. */
+#define PINN_CL_MAX_CLUSTERS 32
+#define PINN_CL_MAX_FEAT 8
+#define PINN_CL_MAX_CLASSES 16
+#define PINN_CL_NAN 1
+#define PINN_CL_ST_ITER 0
+#define PINN_CL_ST_CONVERGED 1
+#define PINN_CL_ST_STATUS 2
+#define PINN_CL_ST_HEADER 16
+
+/* k-means state: header; centres [K][D]; counts [K] (doubles: rows of every cluster in the last pass); column means [D];
+ * labels [n] (64-bit integers).  Header: [.._K], [.._D], [.._N]; [.._INERTIA] (after an iteration: of the assignment to the
+ * centres it started from; after the finishing pass: to the final centres), [.._SHIFT] = sum |new - old|^2 of the last
+ * iteration, [.._TOL_ABS] = tol x the mean over columns of the variance (doubles); [.._STRICT] 1 when the stop was "the labels
+ * equal the previous ones", [.._CHANGED] labels changed by the last iteration, [.._DONE] 1 after the finishing pass. */
+#define PINN_KM_ST_K 3
+#define PINN_KM_ST_D 4
+#define PINN_KM_ST_INERTIA 5
+#define PINN_KM_ST_SHIFT 6
+#define PINN_KM_ST_TOL_ABS 7
+#define PINN_KM_ST_STRICT 8
+#define PINN_KM_ST_CHANGED 9
+#define PINN_KM_ST_DONE 10
+#define PINN_KM_ST_N 11
+
+size_t pinn_km_state_bytes(long long n_rows, int n_clusters, int n_feat);    /* 0 for sizes outside the limits */
+size_t pinn_km_workspace_bytes(long long n_rows, int n_clusters, int n_feat);
+
+/* Lloyd iterations with scikit-learn 1.7's stopping rule on the centres the caller wrote into the state.
+ * init != 0: labels = -1, then two row passes for the column means and variances, which set TOL_ABS from `tol` and reset the
+ * header.  n_iters times two launches, no host synchronisation: every row goes to the nearest centre (sum (x - c)^2, the
+ * first of equals) and overwrites its label, counting the changed ones; per-tile sums in a fixed order give the new centres
+ * (old + sum (x - old) / count; an empty cluster keeps its centre, where scikit-learn relocates it); CONVERGED is set when no
+ * label changed (STRICT) or else when SHIFT <= TOL_ABS.  finish != 0: the finishing pass, whatever the header says: unless
+ * STRICT one more assignment against the final centres; inertia to the final centres; DONE.
+ * After every pass the workspace begins with the summed terms [K][1 + 2 D] = (count, sum d_i, sum d_i^2), d = x - the
+ * centre the pass started from. */
+int pinn_km_lloyd(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                  const long long* d_row_index, long long n, int n_clusters, int init, int n_iters, double tol, int finish,
+                  double* d_state, void* d_ws, size_t ws_bytes, void* stream);
+
+/* d_centres [n_clusters][n_feat] += mean of (x - d_centres) over the positions whose d_labels entry names the cluster (a
+ * label outside [0, n_clusters) adds nothing; a cluster without rows keeps what it holds); d_counts [n_clusters] (may be
+ * NULL).  Workspace as for pinn_km_lloyd. */
+int pinn_cluster_means(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                       const long long* d_row_index, long long n, int n_clusters, const long long* d_labels,
+                       double* d_centres, double* d_counts, void* d_ws, size_t ws_bytes, void* stream);
+
+/* Ward state: header; slot arrays mean [n][D] and size [n] (0: inactive); the chain stack [n]; the merge records lo [n],
+ * hi [n] (slot numbers, lo < hi) and height [n] (n - 1 used), in the order the merges were made; sizes, chain and slots are
+ * 64-bit integers.  Header: [.._N], [.._D], [.._MERGES], [.._CHAIN] the chain's length, [.._FIRST] a lower bound of the
+ * first active slot. */
+#define PINN_WARD_ST_N 3
+#define PINN_WARD_ST_D 4
+#define PINN_WARD_ST_MERGES 5
+#define PINN_WARD_ST_CHAIN 6
+#define PINN_WARD_ST_FIRST 7
+
+size_t pinn_ward_state_bytes(long long n_rows, int n_feat);                 /* 0 for sizes outside the limits */
+size_t pinn_ward_workspace_bytes(long long n_rows, int n_feat);
+
+/* The Ward dendrogram of n positions by the nearest-neighbour chain on cluster means and sizes,
+ * d^2(A, B) = 2 |A| |B| / (|A| + |B|) |mean_A - mean_B|^2, on O(n) memory.  init != 0: every position becomes a slot of
+ * size 1 (0 when it reads nothing) and the chain starts at the first active slot.  n_steps chain steps of two launches, no
+ * host synchronisation: a scan of all slots for the minimum of d^2(tip, j) by (d^2, j); then scipy's rule: the chain's
+ * predecessor is the candidate to begin with and the scan's minimum replaces it only when strictly smaller.  If the
+ * predecessor stays, the step merges: record (lo, hi, sqrt(d^2)), slot hi takes the size-weighted mean and the summed size,
+ * slot lo becomes inactive, two slots leave the chain, and an empty chain restarts at the first active slot.  Otherwise the
+ * minimum is pushed.  CONVERGED after n - 1 merges (or when no second active slot is left); 3 (n - 1) steps always suffice. */
+int pinn_ward_tree(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                   const long long* d_row_index, long long n, int init, int n_steps, double* d_state, void* d_ws,
+                   size_t ws_bytes, void* stream);
+
+/* One launch, one thread per position.  d_centres [n_clusters][n_feat], d_map [n_clusters][n_classes] (may be NULL).
+ * Outputs, each may be NULL: d_cluster [n] the nearest centre by sum (x - c)^2 (the first of equals), d_dist2 [n] that sum,
+ * d_y_prob [n][n_classes] the map's row of that cluster (05:388-390), d_y_pred [n] its first maximum.  A position that
+ * reads nothing gives -1 and NaN. */
+int pinn_cluster_assign(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                        const long long* d_row_index, long long n, int n_clusters, const double* d_centres,
+                        const double* d_map, int n_classes, long long* d_cluster, double* d_dist2, double* d_y_prob,
+                        long long* d_y_pred, void* stream);
+
 int pinn_abi_version(void);
 
 #ifdef __cplusplus

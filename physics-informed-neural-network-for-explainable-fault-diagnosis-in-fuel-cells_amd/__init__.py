@@ -11,7 +11,9 @@ fault diagnosis: `fit_gmm_and_get_probabilities`, `extract_X_y`, the spec parser
 `classification_metrics` (diagnosis); and script 02's fault detection: `build_classifier`, `explain_coefficients`, with
 `DeviceStandardScaler`, `DeviceLogisticRegression`, `roc_curve`, `auc`, `auc_score`, `stratified_split`,
 `evaluate_feature_groups`, `FaultDetector`, and script 05's `run_supervised_lr`, `compute_macro_metrics` (detection; its
-`parse_features` and `parse_group_spec` are script 02's variants and stay in the submodule).
+`parse_features` and `parse_group_spec` are script 02's variants and stay in the submodule); and the rest of script 05, the method comparison:
+`fit_kmeans_posterior`, `fit_agglomerative_posterior`, `fit_gmm_and_get_predictions`, `load_data_for_fault_4class`, with
+`DeviceKMeans`, `DeviceWard`, `compare_methods` and `ClusterDiagnoser` (comparison).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -34,6 +36,10 @@ _LAZY = {
     "explain_coefficients": "detection", "roc_curve": "detection", "auc": "detection", "auc_score": "detection",
     "stratified_split": "detection", "evaluate_feature_groups": "detection", "FaultDetector": "detection",
     "run_supervised_lr": "detection", "compute_macro_metrics": "detection",
+    "DeviceKMeans": "comparison", "DeviceWard": "comparison", "compare_methods": "comparison", "ClusterDiagnoser": "comparison",
+    "fit_kmeans_posterior": "comparison", "fit_agglomerative_posterior": "comparison", "fit_gmm_and_get_predictions": "comparison",
+    "load_data_for_fault_4class": "comparison", "cluster_class_map": "comparison", "assign_clusters": "comparison",
+    "CLASS_NAMES_EN": "comparison", "N_CLASSES": "comparison",
 }
 
 

@@ -34,6 +34,8 @@ SOURCES = [
     ("pinn_gmm.hip", []),
     # float64 logistic regression and ROC; as the mixture: tolerances on sums of a fixed order, integers for the curve
     ("pinn_lr.hip", []),
+    # float64 clustering baselines: every operation rounded on its own, so that the host backend states the same arithmetic
+    ("pinn_cluster.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),
@@ -45,7 +47,7 @@ SOURCES = [
     ("pinn_optim.hip", []),
     ("pinn_general.hip", []),
 ]
-HEADERS = ["pinn_mlp_core.h", "pinn_bf16_core.h", "pinn_x6_core.h", "pinn_wgrad_args.h", os.path.join("..", "..", "include", "pinn_hip.h")]
+HEADERS = ["pinn_mlp_core.h", "pinn_bf16_core.h", "pinn_x6_core.h", "pinn_wgrad_args.h", "pinn_rows.h", os.path.join("..", "..", "include", "pinn_hip.h")]
 
 
 class BuildError(RuntimeError):

@@ -75,6 +75,12 @@ RF_ABOVE, RF_BELOW, RF_TILE = 0, 1, 2048
 GMM_MAX_COMP, GMM_MAX_FEAT, GMM_MAX_CLASSES, GMM_SINGULAR, GMM_TILE = 32, 8, 16, 1, 128
 GMM_ST_ITER, GMM_ST_CONVERGED, GMM_ST_STATUS, GMM_ST_K, GMM_ST_D, GMM_ST_LOWER, GMM_ST_PREV, GMM_ST_CHANGE, GMM_ST_HEADER = range(9)
 
+# pinn_cluster.hip: limits, status and the 8-byte words of the state headers
+CL_MAX_CLUSTERS, CL_MAX_FEAT, CL_MAX_CLASSES, CL_NAN, CL_TILE, CL_ST_HEADER = 32, 8, 16, 1, 128, 16
+CL_ST_ITER, CL_ST_CONVERGED, CL_ST_STATUS = 0, 1, 2
+KM_ST_K, KM_ST_D, KM_ST_INERTIA, KM_ST_SHIFT, KM_ST_TOL_ABS, KM_ST_STRICT, KM_ST_CHANGED, KM_ST_DONE, KM_ST_N = range(3, 12)
+WARD_ST_N, WARD_ST_D, WARD_ST_MERGES, WARD_ST_CHAIN, WARD_ST_FIRST = range(3, 8)
+
 # pinn_lr.hip: limits, status and the 8-byte words of the state header and of the ROC counts
 LR_MAX_CLASSES, LR_MAX_FEAT, LR_MAX_HESS, LR_SINGULAR, LR_NAN, LR_STALLED, LR_TILE = 13, 8, 1365, 1, 2, 3, 128
 (LR_ST_ITER, LR_ST_CONVERGED, LR_ST_STATUS, LR_ST_C, LR_ST_D, LR_ST_F, LR_ST_STEP, LR_ST_DD, LR_ST_PASSES, LR_ST_GMAX, LR_ST_SWSUM,
@@ -181,6 +187,18 @@ _SIGS = {
     "pinn_lr_roc_workspace_bytes": (c_size_t, [c_ll]),
     "pinn_lr_roc": (c_int, [c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_size_t, c_void_p]),
+    "pinn_km_state_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_km_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_km_lloyd": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, c_int, ctypes.c_double,
+                              c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_cluster_means": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_ward_state_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_ward_workspace_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_ward_tree": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
+    "pinn_cluster_assign": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
+                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "../../include/pinn_hip.h"
+#include "pinn_rows.h"
 
 namespace pinn {
 namespace {
@@ -35,14 +36,6 @@ enum { SRC_ESTEP = 0, SRC_RESP = 1, SRC_LABELS = 2, SRC_NEAREST = 3 };
 enum { OUT_MOMENTS = 0, OUT_CLASS = 1 };
 enum { FIN_MEANS = 0, FIN_INIT = 1, FIN_EM = 2, FIN_KMEANS = 3, FIN_MAP = 4 };
 
-struct Rows {
-  const double* arr;
-  long long ld, n_arr, n;
-  const long long* ridx;
-  int D, K;
-  int col[kMaxD];
-};
-
 // state block: header words, then weights[K], means[K][D], covariances[K][D][D], precisions_cholesky[K][D][D], logdet[K]
 __host__ __device__ inline size_t st_weights() { return kHdr; }
 __host__ __device__ inline size_t st_means(int K) { return kHdr + (size_t)K; }
@@ -55,8 +48,6 @@ __device__ __forceinline__ bool stopped(const double* st) {
   const long long* h = reinterpret_cast<const long long*>(st);
   return h[PINN_GMM_ST_CONVERGED] != 0 || h[PINN_GMM_ST_STATUS] != 0;
 }
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 __device__ __forceinline__ int tri(int i, int j) { return j * (j + 1) / 2 + i; }      // i <= j
 
@@ -114,15 +105,6 @@ __device__ __forceinline__ double estep_row(const double x[kMaxD], int K, int D,
   double sum = 0.0;
   for (int k = 0; k < K; ++k) sum += exp(lp[k * stride] - m);
   return log(sum) + m;
-}
-
-__device__ __forceinline__ bool load_row(const Rows& a, long long j, double x[kMaxD]) {
-  const long long row = a.ridx ? a.ridx[j] : j;
-  const bool ok = row >= 0 && row < a.n_arr;               // a gather index outside the array reads nothing
-  const double* r = a.arr + (ok ? row : 0) * a.ld;
-#pragma unroll
-  for (int i = 0; i < kMaxD; ++i) x[i] = (ok && i < a.D) ? r[a.col[i]] : 0.0;
-  return ok;
 }
 
 // ---- the row pass: K x F sums per workgroup.  F = n_f columns; OUT_MOMENTS: (1, d_i, d_i d_j i <= j) cut to n_f, OUT_CLASS:
@@ -453,29 +435,11 @@ __global__ __launch_bounds__(kRows) void gmm_posterior_kernel(Rows a, const doub
   }
 }
 
-inline bool misaligned8(const void* p) { return ((unsigned long long)p & 7) != 0; }
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline int n_moments(int D) { return 1 + D + D * (D + 1) / 2; }
 
 inline int n_blocks(long long n) {
   const long long tiles = (n + kRows - 1) / kRows;
   return (int)(tiles < 1 ? 1 : (tiles > kMaxBlocks ? kMaxBlocks : tiles));
-}
-
-// checks shared by every entry point that reads rows; fills `a`
-inline int make_rows(const double* d_arr, long long ld, long long n_arr, const int* cols, int n_feat, int n_comp,
-                     const long long* d_row_index, long long n, Rows* a) {
-  if (n < 0 || n_arr < 0 || ld < 1 || !cols || n_feat < 1 || n_feat > kMaxD || n_comp < 1 || n_comp > kMaxK) return PINN_E_ARG;
-  for (int i = 0; i < n_feat; ++i)
-    if (cols[i] < 0 || cols[i] >= ld) return PINN_E_ARG;
-  if (!d_row_index && n > n_arr) return PINN_E_ARG;
-  if (n > 0 && !d_arr) return PINN_E_ARG;
-  if (misaligned8(d_arr) || misaligned8(d_row_index)) return PINN_E_ARG;
-  a->arr = d_arr; a->ld = ld; a->n_arr = n_arr; a->n = n; a->ridx = d_row_index; a->D = n_feat; a->K = n_comp;
-  for (int i = 0; i < kMaxD; ++i) a->col[i] = i < n_feat ? cols[i] : 0;
-  return PINN_OK;
 }
 
 struct Ws {
