@@ -9,7 +9,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 LISTS = [[8, 32, 32, 32, 1], [8, 100, 100, 1], [8, 64, 200, 48, 1], [8, 7, 1, 4, 1], [8, 2000, 300, 1], [8, 256, 256, 256, 1],
-         [8, 2048] + [5] * 6 + [4, 1]]
+         [8, 2048] + [5] * 6 + [4, 1],
+         # the lists of test_gpu_regimes.py: one and eight hidden layers, widths beside the 32-wide padding and the 64 x 64 tile edge,
+         # kMaxWidth as an output and as an input width
+         [8, 33, 65, 7, 1], [8, 130, 1], [8, 40, 24, 72, 8, 96, 31, 64, 36, 1], [8, 2048, 8, 1], [8, 4, 2048, 1]]
 
 
 @pytest.fixture(scope="module")
@@ -20,7 +23,7 @@ def lib():
     return _lib.load(build_if_missing=False)
 
 
-@pytest.mark.parametrize("layers", LISTS[:6])
+@pytest.mark.parametrize("layers", LISTS[:6] + LISTS[7:])
 def test_general_offsets_match_oracle_shapes_and_names(layers):
     import pinn_oracle as O
     from pinn_amd import layout
