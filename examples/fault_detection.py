@@ -1,7 +1,8 @@
 """Fault detection on the device: a synthetic results array with twelve fault segments, script 02's four feature groups
 (`epi,res` / `x0,x3,x4,x5` / `res` / `y_true`) each fitted with StandardScaler + logistic regression on a tenth of the rows
-and judged by the ROC AUC of 1 - P(normal) on the rest, then the recording replayed in chunks through the online detector
-of the first group.  Nothing leaves the GPU but the printed numbers.
+and judged by the ROC AUC of 1 - P(normal) on the rest; for the first group also the unsupervised AUC of an isolation forest
+fitted on the normal training rows alone (no fault labels); then the recording replayed in chunks through the online detector
+and the anomaly monitor of the first group.  Nothing leaves the GPU but the printed numbers.
 
     python examples/fault_detection.py [--normal-rows 20000] [--fault-rows 1500] [--five-class]
 """
@@ -14,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from pinn_amd import detection  # noqa: E402
+from pinn_amd import anomaly, detection  # noqa: E402
 
 
 def synthetic_results(n_normal, n_fault, seed=0):
@@ -48,21 +49,27 @@ def main():
 
     results = torch.from_numpy(synthetic_results(args.normal_rows, args.fault_rows)).cuda()
     spec = detection.FIVE_CLASS_GROUP_SPEC if args.five_class else detection.DEFAULT_GROUP_SPEC
-    groups = detection.evaluate_feature_groups(results, group_spec=spec)
+    groups = detection.evaluate_feature_groups(results, group_spec=spec, unsupervised=True)
     print("%-14s %8s %8s %6s %9s %9s %8s" % ("features", "train", "test", "iters", "accuracy", "macro F1", "AUC"))
     for g in groups:
         lr = g["clf"].named_steps["logreg"]
         print("%-14s %8d %8d %6d %9.4f %9.4f %8.4f" % (g["spec"], g["n_train"], g["n_test"], lr.n_iter_, g["accuracy"], g["metrics"]["macro_f1"],
                                                       g["auc"]))
+    forest = groups[0]["iforest"]
+    print("unsupervised, %s: isolation forest of %d trees on %d rows each, AUC %.4f (supervised %.4f)"
+          % (groups[0]["spec"], len(forest.trees_), forest.max_samples_, groups[0]["auc_unsup"], groups[0]["auc"]))
     for e in detection.explain_coefficients(groups[0]["clf"], groups[0]["features"], groups[0]["class_names"]):
         print("coefficients of %r in the standardised space: %s" % (e["class"], ", ".join("%s %+.3f" % p for p in e["positive"])))
 
     detector = detection.FaultDetector(groups[0]["clf"], features=detection.FEAT_GRP1, normal_class=0)
-    print("\n%8s %10s %12s %s" % ("rows", "label", "mean p_fault", "share flagged"))
+    monitor = anomaly.AnomalyMonitor(forest, features=detection.FEAT_GRP1)
+    print("\n%8s %10s %12s %13s %12s %s" % ("rows", "label", "mean p_fault", "share flagged", "mean anomaly", "share outlying"))
     for s in range(0, results.shape[0], 4096):
         chunk = results[s:s + 4096]
         p_fault, pred = detector.update(chunk)
-        print("%8d %10d %12.4f %.3f" % (s + chunk.shape[0], int(chunk[-1, 17]), float(p_fault.mean()), float((pred != 0).double().mean())))
+        score, outlying = monitor.update(chunk)
+        print("%8d %10d %12.4f %13.3f %12.4f %.3f" % (s + chunk.shape[0], int(chunk[-1, 17]), float(p_fault.mean()), float((pred != 0).double().mean()),
+                                                      float(score.mean()), float((outlying < 0).double().mean())))
 
 
 if __name__ == "__main__":

@@ -706,6 +706,70 @@ int pinn_cluster_assign(const double* d_arr, long long ld, long long n_arr_rows,
                         const double* d_map, int n_classes, long long* d_cluster, double* d_dist2, double* d_y_prob,
                         long long* d_y_pred, void* stream);
 
+/* ---- isolation forest: the unsupervised anomaly score of reference script 02 (cited as 02:<line>) ---------------------
+ * Scoring a given forest restates scikit-learn's IsolationForest.score_samples: the row is cast to float32, descends every
+ * tree by x32 <= threshold, the leaf values (depth + 1) + c(n_node_samples) - 1 are added in tree order in float64, and the
+ * score is -2^(-sum / den), den = n_trees c(max_samples).  Fitting is the package's own counter-based construction with
+ * scikit-learn's rules (not its draws).  Rows are read in place as above; a position that reads nothing gives NaN.
+ *
+ * Limits: n_trees <= PINN_IF_MAX_TREES, max_samples <= PINN_IF_MAX_SAMPLES, n_feat <= PINN_IF_MAX_FEAT, a tree of at most
+ * PINN_IF_MAX_NODES nodes, at most PINN_IF_MAX_LEAF_VALUES distinct leaf values in a forest.  Outside: PINN_E_ARG, size 0.
+ *
+ * The forest block (8-byte aligned), written by the host:
+ *   header          PINN_IF_HEADER 8-byte words: [PINN_IF_H_MAGIC] = PINN_IF_MAGIC, [.._TREES], [.._NODES] (the largest node
+ *                   count of a tree), [.._FEAT], [.._LEAF_VALUES], [.._TOTAL_NODES], [.._GROUPS] (64-bit integers) and
+ *                   [.._DEN] (double; 0 gives the exponent -1, as scikit-learn does for one training row)
+ *   leaf table      PINN_IF_MAX_LEAF_VALUES doubles: the distinct leaf values, computed on the host with numpy
+ *   tree offsets    PINN_IF_MAX_TREES + 2 32-bit integers: tree t owns nodes [off[t], off[t + 1]) of the node array
+ *   group starts    PINN_IF_MAX_TREES + 2 32-bit integers: group g is trees [grp[g], grp[g + 1]), consecutive trees whose
+ *                   nodes together are at most PINN_IF_LDS_NODES: what a workgroup holds in LDS at a time
+ *   nodes           8 bytes each, the root of a tree first, the two children of a node adjacent (left, then right):
+ *                   word 0: inner node: the float32 threshold, the largest float32 <= the float64 threshold (for a float32
+ *                           x, x <= t64 exactly when x <= that float32); leaf: index into the leaf table
+ *                   word 1: bits 0-15 the left child (node number inside the tree), bits 16-18 the feature, bit 31 leaf */
+#define PINN_IF_MAX_TREES 1024
+#define PINN_IF_MAX_SAMPLES 1024
+#define PINN_IF_MAX_FEAT 8
+#define PINN_IF_MAX_NODES 2047
+#define PINN_IF_MAX_LEAF_VALUES 16384
+#define PINN_IF_LDS_NODES 4096
+#define PINN_IF_MAGIC 0x49464f52
+#define PINN_IF_HEADER 16
+#define PINN_IF_H_MAGIC 0
+#define PINN_IF_H_TREES 1
+#define PINN_IF_H_NODES 2
+#define PINN_IF_H_FEAT 3
+#define PINN_IF_H_LEAF_VALUES 4
+#define PINN_IF_H_TOTAL_NODES 5
+#define PINN_IF_H_GROUPS 6
+#define PINN_IF_H_DEN 7
+
+size_t pinn_if_forest_bytes(int n_trees, int max_nodes_per_tree);            /* 0 for sizes outside the limits */
+
+/* One launch, no workgroup waits on another, every position on its own: the result does not depend on the grid or on how the
+ * caller cuts the rows into calls.  Outputs, each may be NULL: d_depth_sum [n] the float64 sum of the leaf values in tree
+ * order, d_score [n] = -2^(-sum / den), d_pred [n] = +1 when score - offset >= 0, else -1.  A position that reads nothing
+ * or whose float32 features are not all finite gives NaN, NaN and -1.  n_feat must be the forest's.
+ * variant 0: the trees pass through LDS group by group while a thread keeps its rows' features in registers;
+ * variant 1: every node is read from global memory (the L2 cache); kept for measurements, the same results. */
+int pinn_if_score(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                  const long long* d_row_index, long long n, const void* d_forest, double offset, double* d_depth_sum,
+                  double* d_score, long long* d_pred, int variant, void* stream);
+
+/* Fits n_trees trees in one launch, one workgroup per tree, no host synchronisation.  Tree t draws max_samples distinct
+ * positions of the n: position i of the subsample is i sent through a four-round Feistel permutation of [0, 4^k) keyed by
+ * Philox4x32-10 at counter (t, 0, 1, 0) under the key `seed`, walked until it falls below n.  The rows are gathered as
+ * float32.  A node splits while depth < max_depth and it holds more than one row and some feature is not constant on it:
+ * Philox at counter (t, node, 0, 0) gives r0, r1; the feature is number floor(r0 c / 2^32) of the c non-constant ones, the
+ * threshold t = lo + r1 2^-32 (hi - lo) in float64, t = lo when t >= hi; rows with x <= t go left.  Outputs in
+ * scikit-learn's shape, nodes in pre-order, stride 2 max_samples - 1 per tree: d_feature, d_left, d_right, d_n_node (32-bit
+ * integers), d_threshold (doubles); leaves carry -2, -2.0, -1, -1.  d_node_count [n_trees], d_samples [n_trees][max_samples]
+ * (64-bit positions), d_status [n_trees]: 1 when a drawn row lies outside the array or is not finite (it then counts as 0). */
+int pinn_if_fit(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                const long long* d_row_index, long long n, int n_trees, int max_samples, int max_depth,
+                unsigned long long seed, int* d_feature, double* d_threshold, int* d_left, int* d_right, int* d_n_node,
+                int* d_node_count, long long* d_samples, int* d_status, void* stream);
+
 int pinn_abi_version(void);
 
 #ifdef __cplusplus

@@ -13,7 +13,8 @@ fault diagnosis: `fit_gmm_and_get_probabilities`, `extract_X_y`, the spec parser
 `evaluate_feature_groups`, `FaultDetector`, and script 05's `run_supervised_lr`, `compute_macro_metrics` (detection; its
 `parse_features` and `parse_group_spec` are script 02's variants and stay in the submodule); and the rest of script 05, the method comparison:
 `fit_kmeans_posterior`, `fit_agglomerative_posterior`, `fit_gmm_and_get_predictions`, `load_data_for_fault_4class`, with
-`DeviceKMeans`, `DeviceWard`, `compare_methods` and `ClusterDiagnoser` (comparison).
+`DeviceKMeans`, `DeviceWard`, `compare_methods` and `ClusterDiagnoser` (comparison); and script 02's unsupervised detector, the
+isolation forest: `DeviceIsolationForest` and `AnomalyMonitor` (anomaly).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -40,6 +41,7 @@ _LAZY = {
     "fit_kmeans_posterior": "comparison", "fit_agglomerative_posterior": "comparison", "fit_gmm_and_get_predictions": "comparison",
     "load_data_for_fault_4class": "comparison", "cluster_class_map": "comparison", "assign_clusters": "comparison",
     "CLASS_NAMES_EN": "comparison", "N_CLASSES": "comparison",
+    "DeviceIsolationForest": "anomaly", "AnomalyMonitor": "anomaly",
 }
 
 

@@ -36,6 +36,8 @@ SOURCES = [
     ("pinn_lr.hip", []),
     # float64 clustering baselines: every operation rounded on its own, so that the host backend states the same arithmetic
     ("pinn_cluster.hip", ["-ffp-contract=off"]),
+    # isolation forest: float64 sums of host-computed leaf values in tree order; the host backend states the same arithmetic
+    ("pinn_iforest.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

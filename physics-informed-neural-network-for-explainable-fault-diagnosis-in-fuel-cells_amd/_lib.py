@@ -88,6 +88,11 @@ LR_MAX_CLASSES, LR_MAX_FEAT, LR_MAX_HESS, LR_SINGULAR, LR_NAN, LR_STALLED, LR_TI
 LR_ST_HEADER = 16
 LR_ROC_POS, LR_ROC_N, LR_ROC_M, LR_ROC_KEPT, LR_ROC_U2, LR_ROC_COUNTS = 0, 1, 2, 3, 4, 8
 
+# pinn_iforest.hip: limits and the 8-byte words of the forest block's header
+IF_MAX_TREES, IF_MAX_SAMPLES, IF_MAX_FEAT, IF_MAX_NODES, IF_MAX_LEAF_VALUES, IF_LDS_NODES = 1024, 1024, 8, 2047, 16384, 4096
+IF_MAGIC, IF_HEADER = 0x49464f52, 16
+IF_H_MAGIC, IF_H_TREES, IF_H_NODES, IF_H_FEAT, IF_H_LEAF_VALUES, IF_H_TOTAL_NODES, IF_H_GROUPS, IF_H_DEN = range(8)
+
 
 class PinnError(RuntimeError):
     pass
@@ -199,6 +204,11 @@ _SIGS = {
                                c_size_t, c_void_p]),
     "pinn_cluster_assign": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_if_forest_bytes": (c_size_t, [c_int, c_int]),
+    "pinn_if_score": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, ctypes.c_double, c_void_p,
+                              c_void_p, c_void_p, c_int, c_void_p]),
+    "pinn_if_fit": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, c_int, ctypes.c_ulonglong,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -6,7 +6,8 @@ A StandardScaler + multinomial logistic regression is fitted on feature columns 
 normal from faulty rows.  Script 02's names, defaults and error types are kept: `parse_features`, `parse_group_spec`,
 `build_label_mapper`, `extract_X_y`, `build_classifier`, `explain_coefficients`; from script 05 `run_supervised_lr` and
 `compute_macro_metrics`.  Added: `DeviceStandardScaler`, `DeviceLogisticRegression`, `roc_curve`, `auc`, `auc_score`,
-`stratified_split`, `evaluate_feature_groups` (script 02's main loop without figures) and `FaultDetector` (online use).
+`stratified_split`, `evaluate_feature_groups` (script 02's main loop without figures; its unsupervised curve comes from
+anomaly.py) and `FaultDetector` (online use).
 
 The model.  With z = (x - mean_) / scale_, sample weights sw_i = n / (C count[y_i]) ("balanced"; 1 otherwise) the fit minimises
     F(W, b) = sum_i sw_i (logsumexp_c s_ic - s_i,y_i) + 1 / (2 C_reg) sum_c |W_c|^2,   s_ic = W_c . z_i + b_c
@@ -803,13 +804,20 @@ def run_supervised_lr(X_tr, y_tr, X_te, backend="auto", **lr_args):
 
 
 def evaluate_feature_groups(results, feature_groups=FEATURE_GROUPS, group_spec=DEFAULT_GROUP_SPEC, test_size=DEFAULT_TEST_SIZE,
-                            random_state=DEFAULT_RANDOM_STATE, balanced=DEFAULT_BALANCED, split=None, backend="auto", **lr_args):
+                            random_state=DEFAULT_RANDOM_STATE, balanced=DEFAULT_BALANCED, split=None, backend="auto", unsupervised=False,
+                            **lr_args):
     """Script 02's main loop without figures (02:503-569).  Per feature group: rows with a label of `group_spec` and finite
     features, a stratified split (or `split = (idx_tr, idx_te)`, positions among the kept rows), the classifier fitted on the
     training rows read in place, and on the test rows: accuracy, `classification_metrics`, the ROC arrays and AUC of
     p_fault = 1 - P(normal) against "not the normal class" (the class named `normal`, else class 0).
     Returns a list of dicts: spec, features, class_names, n_train, n_test, clf, accuracy, metrics, auc, fpr, tpr, thresholds,
-    y_test, y_pred, p_fault, idx_train, idx_test, kept_rows."""
+    y_test, y_pred, p_fault, idx_train, idx_test, kept_rows.
+
+    `unsupervised=True` adds script 02's unsupervised curve to the first group (02:571-596): an isolation forest of 200 trees
+    (anomaly.DeviceIsolationForest, seeded with `random_state`) fitted on the normal training rows, on all training rows when
+    there are not more than 10 normal ones, and the ROC and AUC of `anomaly_score` = -score_samples of the test rows read in
+    place: keys auc_unsup, fpr_unsup, tpr_unsup, thresholds_unsup, anomaly_score, iforest.  `unsupervised=<a fitted or imported
+    forest>` scores with that forest instead of fitting one."""
     label_map, class_names = build_label_mapper(parse_group_spec(group_spec))
     normal = class_names.index("normal") if "normal" in class_names else 0
     out = []
@@ -840,6 +848,28 @@ def evaluate_feature_groups(results, feature_groups=FEATURE_GROUPS, group_spec=D
         out.append({"spec": spec, "features": fidx, "class_names": class_names, "n_train": len(idx_tr), "n_test": len(idx_te), "clf": clf,
                     "accuracy": m["accuracy"], "metrics": m, "auc": area, "fpr": r["fpr"], "tpr": r["tpr"], "thresholds": r["thresholds"],
                     "y_test": yte_h, "y_pred": y_pred, "p_fault": pf, "idx_train": idx_tr, "idx_test": idx_te, "kept_rows": kept})
+        if unsupervised is not False and unsupervised is not None and len(out) == 1:
+            from .anomaly import DeviceIsolationForest
+            forest = unsupervised
+            if unsupervised is True:
+                is_normal = _as_numpy(y_tr).astype(np.int64) == normal
+                if _is_tensor(r_tr):
+                    import torch
+                    sel = torch.from_numpy(is_normal).to(r_tr.device)
+                else:
+                    sel = is_normal
+                r_fit = r_tr[sel] if int(is_normal.sum()) > 10 else r_tr
+                forest = DeviceIsolationForest(n_estimators=200, contamination="auto", random_state=random_state, backend=be)
+                forest.fit(results, columns=fidx, row_index=r_fit)
+            saved, forest.backend = forest.backend, be
+            try:
+                score = -forest.score_samples(results, columns=fidx, row_index=r_te)
+            finally:
+                forest.backend = saved
+            ru = roc_counts(truth, score, pos_label=True, backend=be)
+            area_u = ru["U2"] / (2 * ru["n_pos"] * ru["n_neg"]) if ru["n_pos"] and ru["n_neg"] else float("nan")
+            out[0].update(auc_unsup=area_u, fpr_unsup=ru["fpr"], tpr_unsup=ru["tpr"], thresholds_unsup=ru["thresholds"], anomaly_score=score,
+                          iforest=forest)
     return out
 
 
