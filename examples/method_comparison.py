@@ -1,6 +1,6 @@
 """Script 05's question on the device: is the mixture with label-posterior mapping better than plain clustering?  A synthetic
 results array with twelve fault segments (two residual columns drift per fault class), the fault rows split once, and GMM,
-logistic regression, k-means and Ward clustering fitted on the training rows and judged on the test rows by accuracy and
+logistic regression, k-means and Ward clustering and, through `device_extras`, the linear SVC of script 05's Sup_SVM fitted on the training rows and judged on the test rows by accuracy and
 macro precision / recall / F1.  A user's own method rides along as a callable.  Then the recording is replayed in chunks
 through the online diagnoser of the k-means model.  Nothing leaves the GPU but the printed numbers; `--host` runs the
 float64 numpy backend instead.
@@ -57,9 +57,11 @@ def main():
         results, backend = torch.from_numpy(results).cuda(), "device"
     X, y, names = comparison.load_data_for_fault_4class(results, backend=backend)
     print("fault rows: %d x %d features, classes %s" % (X.shape[0], X.shape[1], names))
-    r = comparison.compare_methods(X, y, methods=comparison.METHODS + ("NearestMean",), extra={"NearestMean": nearest_class_mean}, backend=backend)
+    methods = comparison.METHODS + ("Sup_SVM", "NearestMean")
+    extra = {**comparison.device_extras(backend), "NearestMean": nearest_class_mean}      # Sup_SVM: the package's linear SVC (svm.py)
+    r = comparison.compare_methods(X, y, methods=methods, extra=extra, backend=backend)
     print("%-12s %9s %10s %9s %9s" % ("method", "accuracy", "precision", "recall", "F1"))
-    for name in comparison.METHODS + ("NearestMean",):
+    for name in methods:
         m = r[name]
         print("%-12s %9.4f %10.4f %9.4f %9.4f" % (name, m["accuracy"], m["macro_precision"], m["macro_recall"], m["macro_f1"]))
     try:

@@ -772,6 +772,97 @@ int pinn_if_fit(const double* d_arr, long long ld, long long n_arr_rows, const i
 
 int pinn_abi_version(void);
 
+/* ---- Script 05's Sup_SVM: one-vs-one linear SVC, interior point on the dual (pinn_svm.hip) --------------------------------
+ * Rows are read in place as in the modules above (array, leading dimension, column list, optional gather list); d_y holds
+ * the class index 0..n_classes-1 of every row position.  Limits: n_feat <= PINN_SVM_MAX_FEAT, 2 <= n_classes <=
+ * PINN_SVM_MAX_CLASSES (28 pairs).  Outside: PINN_E_ARG, sizes 0.
+ *
+ * Pairs (a, b), a < b, in the order (0,1), (0,2), ..., (C-2,C-1).  The state block, in 8-byte words:
+ *   header       PINN_SVM_ST_HEADER words: [.._ITER] (the largest iteration count of a pair), [.._CONVERGED] (every pair has),
+ *                [.._STATUS] (the pairs' status words ORed: 0, PINN_SVM_NAN, PINN_SVM_SINGULAR, PINN_SVM_RANGE: a gather index
+ *                outside the array or a class index outside [0, n_classes)), [.._C], [.._D], [.._P], [.._N]
+ *   pair blocks  [P][PINN_SVM_PAIR_WORDS]: integers [PINN_SVM_P_ITER], [.._CONVERGED], [.._STATUS], [.._PHASE] (0: fresh,
+ *                1: alpha and w set, 2: iterating, 3: a step waits to be applied), [.._A], [.._B]; doubles [.._M] (rows of the
+ *                pair), [.._KA], [.._KB] (the starting alpha as a fraction of the bound, per side), [.._MU], [.._THETA],
+ *                [.._SIGMU], [.._GAP] (primal - dual at the point), [.._PRIMAL], [.._DUAL], [.._THETA_AFF], [.._COMPL],
+ *                [.._TALPHA], [.._SUMALPHA], [.._W .. + n_feat) (positive for class a), [.._BETA] (the intercept),
+ *                [.._DAFF .. + n_feat + 1), [.._DIR .. + n_feat + 1) and [.._FIX .. + n_feat + 1) (predictor and final
+ *                direction of (w, beta), and the refinement of the latter), [.._RW .. + n_feat) (w - V'alpha at the point)
+ *   mean [D], scale [D], bound [C] (C x class weight: the upper bound of alpha of a row of that class)
+ *   alpha, s, z  [n][C - 1] each: slot j of a row of class k belongs to its j-th other class in increasing order
+ * The caller zeroes the block and fills [.._A], [.._B], [.._M], [.._KA], [.._KB], mean, scale and bound.  Once a pair's
+ * CONVERGED or STATUS is set every later launch skips it.
+ *
+ * A row pass sums per pair, in this order: the upper triangle of sum u u' / d (u = (z-scores, 1), entry (i <= j) at
+ * j (j + 1) / 2 + i), sum g t u / d [D + 1], sum alpha t u [D + 1] (the last is t'alpha), sum s alpha + z (c - alpha),
+ * sum alpha, sum c max(0, 1 - t f).  pinn_svm_pass leaves them at the start of the workspace, [P][that many]. */
+#define PINN_SVM_MAX_FEAT 8
+#define PINN_SVM_MAX_CLASSES 8
+#define PINN_SVM_NAN 1
+#define PINN_SVM_SINGULAR 2
+#define PINN_SVM_RANGE 4
+#define PINN_SVM_ST_HEADER 16
+#define PINN_SVM_ST_ITER 0
+#define PINN_SVM_ST_CONVERGED 1
+#define PINN_SVM_ST_STATUS 2
+#define PINN_SVM_ST_C 3
+#define PINN_SVM_ST_D 4
+#define PINN_SVM_ST_P 5
+#define PINN_SVM_ST_N 6
+#define PINN_SVM_PAIR_WORDS 80
+#define PINN_SVM_P_ITER 0
+#define PINN_SVM_P_CONVERGED 1
+#define PINN_SVM_P_STATUS 2
+#define PINN_SVM_P_PHASE 3
+#define PINN_SVM_P_A 4
+#define PINN_SVM_P_B 5
+#define PINN_SVM_P_M 6
+#define PINN_SVM_P_KA 7
+#define PINN_SVM_P_KB 8
+#define PINN_SVM_P_MU 9
+#define PINN_SVM_P_THETA 10
+#define PINN_SVM_P_SIGMU 11
+#define PINN_SVM_P_GAP 12
+#define PINN_SVM_P_PRIMAL 13
+#define PINN_SVM_P_DUAL 14
+#define PINN_SVM_P_THETA_AFF 15
+#define PINN_SVM_P_COMPL 16
+#define PINN_SVM_P_TALPHA 17
+#define PINN_SVM_P_SUMALPHA 18
+#define PINN_SVM_P_W 20
+#define PINN_SVM_P_BETA 28
+#define PINN_SVM_P_DAFF 30
+#define PINN_SVM_P_DIR 40
+#define PINN_SVM_P_FIX 50
+#define PINN_SVM_P_RW 60
+
+size_t pinn_svm_state_bytes(long long n_rows, int n_classes, int n_feat);        /* 0 for sizes outside the limits */
+size_t pinn_svm_workspace_bytes(long long n_rows, int n_classes, int n_feat);
+
+/* One row pass at the state's point (alpha, s, z, w, beta as they stand; nothing is written to the state): the sums
+ * above, at the start of the workspace.  For tests and tools. */
+int pinn_svm_pass(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                  const long long* d_row_index, long long n, const long long* d_y, int n_classes, const double* d_state,
+                  void* d_ws, size_t ws_bytes, void* stream);
+
+/* Queues n_iter interior-point iterations of every pair (init != 0: the starting point first), six launches each, without
+ * a host synchronisation.  A pair converges when primal - dual <= gap_tol max(1, primal), |t'alpha| <= 1e-12 sum alpha
+ * and max |w - V'alpha| <= 1e-13 sum alpha.
+ * After the call the state is consistent: alpha, w, beta and the gap belong to the same point.
+ * An iteration starts from what the last one left in the workspace (the pairs' Cholesky factors and the predictor's
+ * right-hand sides, behind the sums): a call with init == 0 must be given the workspace of the call before it, unchanged,
+ * and the same rows, d_y and gap_tol.  The workspace of a call with init != 0 may hold anything. */
+int pinn_svm_ipm(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                 const long long* d_row_index, long long n, const long long* d_y, int n_classes, int init, int n_iter,
+                 double gap_tol, double* d_state, void* d_ws, size_t ws_bytes, void* stream);
+
+/* One launch: z-scores, the P pairwise values w.z + b [n][P], the votes [n][C] (a where the value is > 0, else b) and the
+ * prediction [n] (the first maximum of the votes; -1 for a gather index outside the array).  Every output may be NULL.
+ * d_model: mean [D], scale [D], W [P][D], b [P]. */
+int pinn_svm_decision(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                      const long long* d_row_index, long long n, int n_classes, const double* d_model, double* d_decision,
+                      long long* d_votes, long long* d_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

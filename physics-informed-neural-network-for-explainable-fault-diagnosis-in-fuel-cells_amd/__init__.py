@@ -14,7 +14,9 @@ fault diagnosis: `fit_gmm_and_get_probabilities`, `extract_X_y`, the spec parser
 `parse_features` and `parse_group_spec` are script 02's variants and stay in the submodule); and the rest of script 05, the method comparison:
 `fit_kmeans_posterior`, `fit_agglomerative_posterior`, `fit_gmm_and_get_predictions`, `load_data_for_fault_4class`, with
 `DeviceKMeans`, `DeviceWard`, `compare_methods` and `ClusterDiagnoser` (comparison); and script 02's unsupervised detector, the
-isolation forest: `DeviceIsolationForest` and `AnomalyMonitor` (anomaly).
+isolation forest: `DeviceIsolationForest` and `AnomalyMonitor` (anomaly); and script 05's Sup_SVM, a one-vs-one linear SVC solved
+by interior point: `run_supervised_svm_rbf`, with `DeviceLinearSVC`, `build_svm_classifier` and `SVMDiagnoser` (svm), reached
+from `compare_methods` through `device_extras` (comparison).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -42,6 +44,8 @@ _LAZY = {
     "load_data_for_fault_4class": "comparison", "cluster_class_map": "comparison", "assign_clusters": "comparison",
     "CLASS_NAMES_EN": "comparison", "N_CLASSES": "comparison",
     "DeviceIsolationForest": "anomaly", "AnomalyMonitor": "anomaly",
+    "DeviceLinearSVC": "svm", "run_supervised_svm_rbf": "svm", "build_svm_classifier": "svm", "SVMDiagnoser": "svm",
+    "device_extras": "comparison",
 }
 
 

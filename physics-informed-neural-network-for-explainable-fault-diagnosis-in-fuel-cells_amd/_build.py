@@ -38,6 +38,8 @@ SOURCES = [
     ("pinn_cluster.hip", ["-ffp-contract=off"]),
     # isolation forest: float64 sums of host-computed leaf values in tree order; the host backend states the same arithmetic
     ("pinn_iforest.hip", ["-ffp-contract=off"]),
+    # linear SVC by interior point: float64, every operation rounded on its own, as the clustering baselines
+    ("pinn_svm.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

@@ -93,6 +93,13 @@ IF_MAX_TREES, IF_MAX_SAMPLES, IF_MAX_FEAT, IF_MAX_NODES, IF_MAX_LEAF_VALUES, IF_
 IF_MAGIC, IF_HEADER = 0x49464f52, 16
 IF_H_MAGIC, IF_H_TREES, IF_H_NODES, IF_H_FEAT, IF_H_LEAF_VALUES, IF_H_TOTAL_NODES, IF_H_GROUPS, IF_H_DEN = range(8)
 
+# pinn_svm.hip: limits, status and the 8-byte words of the state header and of a pair's block
+SVM_MAX_FEAT, SVM_MAX_CLASSES, SVM_NAN, SVM_SINGULAR, SVM_RANGE, SVM_ST_HEADER, SVM_PAIR_WORDS = 8, 8, 1, 2, 4, 16, 80
+SVM_ST_ITER, SVM_ST_CONVERGED, SVM_ST_STATUS, SVM_ST_C, SVM_ST_D, SVM_ST_P, SVM_ST_N = range(7)
+(SVM_P_ITER, SVM_P_CONVERGED, SVM_P_STATUS, SVM_P_PHASE, SVM_P_A, SVM_P_B, SVM_P_M, SVM_P_KA, SVM_P_KB, SVM_P_MU, SVM_P_THETA, SVM_P_SIGMU,
+ SVM_P_GAP, SVM_P_PRIMAL, SVM_P_DUAL, SVM_P_THETA_AFF, SVM_P_COMPL, SVM_P_TALPHA, SVM_P_SUMALPHA) = range(19)
+SVM_P_W, SVM_P_BETA, SVM_P_DAFF, SVM_P_DIR, SVM_P_FIX, SVM_P_RW = 20, 28, 30, 40, 50, 60
+
 
 class PinnError(RuntimeError):
     pass
@@ -209,6 +216,14 @@ _SIGS = {
                               c_void_p, c_void_p, c_int, c_void_p]),
     "pinn_if_fit": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, c_int, ctypes.c_ulonglong,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_svm_state_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_svm_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_svm_pass": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p,
+                              c_size_t, c_void_p]),
+    "pinn_svm_ipm": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_int, c_int, c_int,
+                             ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_svm_decision": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -4,9 +4,10 @@ Script 05 supports the claim that the Gaussian mixture with label-posterior mapp
 six methods on one stratified split of the fault rows and compares accuracy and macro precision / recall / F1.  Here:
 `GMM` (diagnosis.fit_gmm_and_get_probabilities), `Sup_LR` (detection.build_classifier), and the two clustering baselines
 with a well-defined answer: `KMeans` (k-means, 05:346-393) and `Agglo` (Ward agglomerative clustering with the nearest
-cluster mean, 05:398-450), both with P(class | cluster) from the training labels.  `Sup_SVM` (libsvm's SMO stopped at 1e-3
-with one-vs-one voting) and `Spectral` (ARPACK eigenvectors of a kNN graph, then ten random k-means restarts) have no
-reproducible target and are not built: `compare_methods` takes callables for them.
+cluster mean, 05:398-450), both with P(class | cluster) from the training labels.  `Sup_SVM` (05:323-341, a linear SVC) is
+not one of the built-in four: libsvm's iterate stopped at 1e-3 is no target, but the optimum of its problem is, and svm.py
+solves that; `device_extras()` hands it to `compare_methods` as `extra`.  `Spectral` (ARPACK eigenvectors of a kNN graph, then
+ten random k-means restarts) has no reproducible target and is not built: `compare_methods` takes a callable for it.
 
 The helpers keep script 05's names, arguments and defaults: `fit_kmeans_posterior`, `fit_agglomerative_posterior`,
 `fit_gmm_and_get_predictions`, `run_supervised_lr`, `compute_macro_metrics`, `load_data_for_fault_4class`,
@@ -33,7 +34,7 @@ CLASS_NAMES_EN = ["Flooding", "Oxygen starvation", "Membrane drying", "Hydrogen 
 N_CLASSES = 4
 MAX_CLUSTERS, MAX_FEAT, MAX_CLASSES = 32, 8, 16
 METHODS = ("GMM", "Sup_LR", "KMeans", "Agglo")
-NOT_BUILT = {"Sup_SVM": "libsvm's SMO is stopped at 1e-3 and votes one-vs-one: its predictions near the margin are not a reproducible target",
+NOT_BUILT = {"Sup_SVM": "it is not one of the built-in methods; comparison.device_extras() returns the package's linear SVC (svm.py) for it",
              "Spectral": "ARPACK eigenvectors of a kNN graph followed by ten random k-means restarts have no reproducible target"}
 _HDR = 16                                # 8-byte words of a device state header (include/pinn_hip.h)
 
@@ -621,7 +622,7 @@ def compare_methods(X, y, methods=METHODS, split=None, extra=None, n_classes=N_C
 
     Built in: "GMM" (5 n_classes components), "Sup_LR", "KMeans" (5 n_classes clusters), "Agglo" (4 n_classes clusters), the
     counts of 05:648-662.  `extra` maps a name to a callable (X_tr, y_tr, X_te) -> y_pred, which takes precedence; that is
-    the way to run "Sup_SVM" or "Spectral" from scikit-learn, which raise NotImplementedError without one.
+    the way to run "Sup_SVM" (`extra=device_extras()`) or "Spectral" (from scikit-learn), which raise NotImplementedError without one.
     `method_args` maps a built-in name to further keyword arguments of its function.
     Returns {name: {"y_pred", "confusion_matrix", "accuracy", "macro_precision", "macro_recall", "macro_f1"}}, in the order
     of `methods`; "y_test", "idx_train" and "idx_test" sit next to the names under the key "split"."""
@@ -657,6 +658,13 @@ def compare_methods(X, y, methods=METHODS, split=None, extra=None, n_classes=N_C
         m = classification_metrics(y_te, y_pred, C)
         out[name] = {"y_pred": y_pred, **m}
     return out
+
+
+def device_extras(backend="auto", **svc_args):
+    """{"Sup_SVM": callable} for `compare_methods(..., methods=METHODS + ("Sup_SVM",), extra=device_extras())`: script 05's
+    run_supervised_svm_rbf (svm.py).  `svc_args`: further DeviceLinearSVC arguments."""
+    from .svm import run_supervised_svm_rbf
+    return {"Sup_SVM": lambda X_tr, y_tr, X_te: run_supervised_svm_rbf(X_tr, y_tr, X_te, backend=backend, **svc_args)}
 
 
 class ClusterDiagnoser:
