@@ -863,6 +863,86 @@ int pinn_svm_decision(const double* d_arr, long long ld, long long n_arr_rows, c
                       const long long* d_row_index, long long n, int n_classes, const double* d_model, double* d_decision,
                       long long* d_votes, long long* d_pred, void* stream);
 
+/* ---- Exact t-SNE: the two-dimensional embeddings of scripts 02 and 03 (pinn_tsne.hip) ------------------------------------
+ * Rows are read in place as in the modules above (array, leading dimension, column list, optional gather list).  Limits:
+ * n_feat <= PINN_TSNE_MAX_FEAT, 2 <= n <= PINN_TSNE_MAX_ROWS (the workspace holds P as n x n float64: 8 n^2 bytes, 8 GiB at
+ * the limit, 968 MB at the reference's 1.1e4 rows).  Outside: PINN_E_ARG, sizes 0.
+ *
+ * Workspace, every part at a multiple of 256 bytes: P [n][n]; the per-row sums of the last pair pass [n][PINN_TSNE_ROW_SUMS]
+ * = (Z_i, A_ix, A_iy, R_ix, R_iy, sum_j P log P, sum_j P log(1 + d^2), sum_j P) with w = 1 / (1 + d^2), d = |y_i - y_j|,
+ * Z_i = sum_j w, A_i = sum_j P w (y_i - y_j), R_i = sum_j w^2 (y_i - y_j), j != i; the gradient [n][2] =
+ * 4 (alpha A_i - R_i / Z); PINN_TSNE_SCALARS doubles: [.._SC_PSUM] (the sum of p + p^T that the affinities were divided by),
+ * [.._SC_Z], [.._SC_KL] = alpha (sum P log P + log(alpha) sum P + sum P log(1 + d^2) + sum P log Z), [.._SC_SUMP],
+ * [.._SC_PLOGP], [.._SC_PLOGQ], [.._SC_GNORM] (of the gradient; in a descent iteration of gains x gradient).  The three sums
+ * with log are formed only where the error is wanted: always in pinn_tsne_kl_grad, in a descent iteration every 50th
+ * and the last of a phase (scikit-learn's compute_error); elsewhere they keep what the last such pass left.
+ *
+ * State block, in 8-byte words: PINN_TSNE_ST_HEADER header words, Y [n][2], update [n][2], gains [n][2].  Header: integers
+ * [.._ITER] (the iteration that runs next), [.._DONE], [.._STATUS] (0 or PINN_TSNE_NAN), [.._N], [.._PHASE] (0: early
+ * exaggeration, momentum 0.5, iterations 0..249; 1: momentum 0.8, up to max_iter), [.._BEST_ITER], [.._LAST] (the last
+ * iteration that ran: n_iter_), [.._STOP] and [.._STOP1] (why the run / the first phase ended: PINN_TSNE_STOP_*); doubles
+ * [.._BEST_ERROR], [.._ERROR] (the last KL computed), [.._GNORM], [.._Z]. */
+#define PINN_TSNE_MAX_FEAT 8
+#define PINN_TSNE_MAX_ROWS 32768
+#define PINN_TSNE_NAN 1
+#define PINN_TSNE_NOT_CONVERGED 2
+#define PINN_TSNE_DUPLICATES 4
+#define PINN_TSNE_ROW_SUMS 8
+#define PINN_TSNE_SCALARS 32
+#define PINN_TSNE_SC_PSUM 0
+#define PINN_TSNE_SC_Z 1
+#define PINN_TSNE_SC_KL 2
+#define PINN_TSNE_SC_SUMP 3
+#define PINN_TSNE_SC_PLOGP 4
+#define PINN_TSNE_SC_PLOGQ 5
+#define PINN_TSNE_SC_GNORM 6
+#define PINN_TSNE_ST_HEADER 16
+#define PINN_TSNE_ST_ITER 0
+#define PINN_TSNE_ST_DONE 1
+#define PINN_TSNE_ST_STATUS 2
+#define PINN_TSNE_ST_N 3
+#define PINN_TSNE_ST_PHASE 4
+#define PINN_TSNE_ST_BEST_ERROR 5
+#define PINN_TSNE_ST_BEST_ITER 6
+#define PINN_TSNE_ST_ERROR 7
+#define PINN_TSNE_ST_GNORM 8
+#define PINN_TSNE_ST_LAST 9
+#define PINN_TSNE_ST_STOP 10
+#define PINN_TSNE_ST_STOP1 11
+#define PINN_TSNE_ST_Z 12
+#define PINN_TSNE_STOP_MAX_ITER 1
+#define PINN_TSNE_STOP_NO_PROGRESS 2
+#define PINN_TSNE_STOP_GRAD_NORM 3
+
+size_t pinn_tsne_state_bytes(long long n_rows);          /* 0 for sizes outside the limits */
+size_t pinn_tsne_workspace_bytes(long long n_rows);
+
+/* Joint probabilities of the rows into the workspace's P.  Per row i the root beta_i of H_i(beta) = log(perplexity), H_i
+ * the entropy in nats of p_{j|i} ~ exp(-beta |x_i - x_j|^2): Newton steps inside a bracket until |H - log perplexity| <=
+ * 1e-12 or 200 steps; then P_ij = max((p_{j|i} + p_{i|j}) / S, 2.220446049250313e-16), diagonal 0, symmetric bit for bit.
+ * d_beta [n], d_entropy [n] (H_i at beta_i), d_status [n]: 0, PINN_TSNE_NAN (this row or any other is not finite, or a
+ * gather index lies outside the array; the row of P is 0), PINN_TSNE_NOT_CONVERGED, or PINN_TSNE_DUPLICATES (no error: the
+ * m nearest rows lie at exactly the same distance and log m >= log perplexity, so H > log perplexity for every beta; the row
+ * gets the limit beta -> infinity, p = 1 / m on those rows, d_beta = infinity, d_entropy = log m).  0 < perplexity < n. */
+int pinn_tsne_affinities(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                         const long long* d_row_index, long long n, double perplexity, double* d_beta, double* d_entropy,
+                         long long* d_status, void* d_ws, size_t ws_bytes, void* stream);
+
+/* One pair pass and reduction at the embedding d_Y [n][2] with the workspace's P and exaggeration alpha: per-row sums,
+ * gradient and scalars are left in the workspace.  Nothing else is written.  For tests and timing. */
+int pinn_tsne_kl_grad(long long n, const double* d_Y, double exaggeration, void* d_ws, size_t ws_bytes, void* stream);
+
+/* Queues n_iter iterations (two launches each) without a host synchronisation: scikit-learn 1.7's _gradient_descent
+ * (gains += 0.2 where update x gradient < 0, else x 0.8, floor 0.01; update = momentum update - learning_rate gains gradient;
+ * Y += update) under the schedule of its _tsne: the checks every 50th iteration (best error, n_iter_without_progress - 250
+ * in the first phase -, min_grad_norm), the change of phase after iteration 249 or an earlier stop with update and gains
+ * reset; with max_iter == 250 the run ends with the first phase when that ran to its end.  Once DONE or STATUS is set the
+ * remaining iterations do nothing.  init != 0: the header, update and gains are set first and Y is the caller's; init == 0
+ * continues from the block as it stands (the caller may have written any consistent state).  max_iter >= 250. */
+int pinn_tsne_descend(long long n, int init, int n_iter, int max_iter, double early_exaggeration, double learning_rate,
+                      int n_iter_without_progress, double min_grad_norm, double* d_state, void* d_ws, size_t ws_bytes,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,9 @@ fault diagnosis: `fit_gmm_and_get_probabilities`, `extract_X_y`, the spec parser
 `DeviceKMeans`, `DeviceWard`, `compare_methods` and `ClusterDiagnoser` (comparison); and script 02's unsupervised detector, the
 isolation forest: `DeviceIsolationForest` and `AnomalyMonitor` (anomaly); and script 05's Sup_SVM, a one-vs-one linear SVC solved
 by interior point: `run_supervised_svm_rbf`, with `DeviceLinearSVC`, `build_svm_classifier` and `SVMDiagnoser` (svm), reached
-from `compare_methods` through `device_extras` (comparison).
+from `compare_methods` through `device_extras` (comparison); and the t-SNE embeddings of scripts 02 and 03, the exact method:
+`DeviceTSNE`, `joint_probabilities`, `kl_and_gradient`, `trustworthiness`, `tsne_of_test_samples`, `scatter_by_features`,
+`TSNE_PARAMS` (embedding).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -46,6 +48,8 @@ _LAZY = {
     "DeviceIsolationForest": "anomaly", "AnomalyMonitor": "anomaly",
     "DeviceLinearSVC": "svm", "run_supervised_svm_rbf": "svm", "build_svm_classifier": "svm", "SVMDiagnoser": "svm",
     "device_extras": "comparison",
+    "DeviceTSNE": "embedding", "joint_probabilities": "embedding", "kl_and_gradient": "embedding", "trustworthiness": "embedding",
+    "tsne_of_test_samples": "embedding", "scatter_by_features": "embedding", "TSNE_PARAMS": "embedding",
 }
 
 

@@ -100,6 +100,13 @@ SVM_ST_ITER, SVM_ST_CONVERGED, SVM_ST_STATUS, SVM_ST_C, SVM_ST_D, SVM_ST_P, SVM_
  SVM_P_GAP, SVM_P_PRIMAL, SVM_P_DUAL, SVM_P_THETA_AFF, SVM_P_COMPL, SVM_P_TALPHA, SVM_P_SUMALPHA) = range(19)
 SVM_P_W, SVM_P_BETA, SVM_P_DAFF, SVM_P_DIR, SVM_P_FIX, SVM_P_RW = 20, 28, 30, 40, 50, 60
 
+# pinn_tsne.hip: limits, status, per-row sums, workspace scalars and the 8-byte words of the state header
+TSNE_MAX_FEAT, TSNE_MAX_ROWS, TSNE_NAN, TSNE_NOT_CONVERGED, TSNE_ROW_SUMS, TSNE_SCALARS, TSNE_ST_HEADER = 8, 32768, 1, 2, 8, 32, 16
+TSNE_SC_PSUM, TSNE_SC_Z, TSNE_SC_KL, TSNE_SC_SUMP, TSNE_SC_PLOGP, TSNE_SC_PLOGQ, TSNE_SC_GNORM = range(7)
+(TSNE_ST_ITER, TSNE_ST_DONE, TSNE_ST_STATUS, TSNE_ST_N, TSNE_ST_PHASE, TSNE_ST_BEST_ERROR, TSNE_ST_BEST_ITER, TSNE_ST_ERROR, TSNE_ST_GNORM,
+ TSNE_ST_LAST, TSNE_ST_STOP, TSNE_ST_STOP1, TSNE_ST_Z) = range(13)
+TSNE_STOP_MAX_ITER, TSNE_STOP_NO_PROGRESS, TSNE_STOP_GRAD_NORM, TSNE_DUPLICATES = 1, 2, 3, 4
+
 
 class PinnError(RuntimeError):
     pass
@@ -224,6 +231,13 @@ _SIGS = {
                              ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_svm_decision": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p]),
+    "pinn_tsne_state_bytes": (c_size_t, [c_ll]),
+    "pinn_tsne_workspace_bytes": (c_size_t, [c_ll]),
+    "pinn_tsne_affinities": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, ctypes.c_double, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_tsne_kl_grad": (c_int, [c_ll, c_void_p, ctypes.c_double, c_void_p, c_size_t, c_void_p]),
+    "pinn_tsne_descend": (c_int, [c_ll, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p,
+                                  c_size_t, c_void_p]),
 }
 
 _lib = None
