@@ -119,6 +119,10 @@ class PinnRangeError(PinnError):
 E_RANGE = -4
 
 
+# the head of every entry point that reads rows of the results array in place (_device._DevRows.head()):
+# array, leading dimension, rows of the array, columns, their number, gather index or NULL, rows to read
+_ROWS = [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll]
+
 _SIGS = {
     "pinn_abi_version": (c_int, []),
     "pinn_residuals_workspace_bytes": (c_size_t, []),
@@ -183,58 +187,40 @@ _SIGS = {
                                     c_void_p]),
     "pinn_gmm_state_bytes": (c_size_t, [c_int, c_int]),
     "pinn_gmm_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
-    "pinn_gmm_mstep_init": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
-                                    ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pinn_gmm_em": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, ctypes.c_double,
-                            ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pinn_gmm_kmeans": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, c_void_p, c_void_p,
-                                c_void_p, c_size_t, c_void_p]),
-    "pinn_gmm_label_map": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
-                                   c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pinn_gmm_posterior": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
-                                   c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_gmm_mstep_init": (c_int, _ROWS + [c_int, c_void_p, c_void_p, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_em": (c_int, _ROWS + [c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_kmeans": (c_int, _ROWS + [c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_label_map": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_posterior": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_lr_state_bytes": (c_size_t, [c_int, c_int]),
     "pinn_lr_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
-    "pinn_lr_scaler": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_int, c_int, c_void_p,
-                               c_void_p, c_size_t, c_void_p]),
-    "pinn_lr_pass": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p,
-                             c_size_t, c_void_p]),
-    "pinn_lr_newton": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_int, c_int,
-                               ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pinn_lr_posterior": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_int, c_void_p,
-                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_lr_scaler": (c_int, _ROWS + [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_lr_pass": (c_int, _ROWS + [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_lr_newton": (c_int, _ROWS + [c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_lr_posterior": (c_int, _ROWS + [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_lr_roc_workspace_bytes": (c_size_t, [c_ll]),
     "pinn_lr_roc": (c_int, [c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_size_t, c_void_p]),
     "pinn_km_state_bytes": (c_size_t, [c_ll, c_int, c_int]),
     "pinn_km_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
-    "pinn_km_lloyd": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, c_int, ctypes.c_double,
-                              c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pinn_cluster_means": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_km_lloyd": (c_int, _ROWS + [c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_cluster_means": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_ward_state_bytes": (c_size_t, [c_ll, c_int]),
     "pinn_ward_workspace_bytes": (c_size_t, [c_ll, c_int]),
-    "pinn_ward_tree": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, c_void_p, c_void_p,
-                               c_size_t, c_void_p]),
-    "pinn_cluster_assign": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
-                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_ward_tree": (c_int, _ROWS + [c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_cluster_assign": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_if_forest_bytes": (c_size_t, [c_int, c_int]),
-    "pinn_if_score": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, ctypes.c_double, c_void_p,
-                              c_void_p, c_void_p, c_int, c_void_p]),
-    "pinn_if_fit": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_int, c_int, ctypes.c_ulonglong,
-                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_if_score": (c_int, _ROWS + [c_void_p, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "pinn_if_fit": (c_int, _ROWS + [c_int, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
     "pinn_svm_state_bytes": (c_size_t, [c_ll, c_int, c_int]),
     "pinn_svm_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
-    "pinn_svm_pass": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p,
-                              c_size_t, c_void_p]),
-    "pinn_svm_ipm": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_int, c_int, c_int,
-                             ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pinn_svm_decision": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_int, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_void_p]),
+    "pinn_svm_pass": (c_int, _ROWS + [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_svm_ipm": (c_int, _ROWS + [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_svm_decision": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_tsne_state_bytes": (c_size_t, [c_ll]),
     "pinn_tsne_workspace_bytes": (c_size_t, [c_ll]),
-    "pinn_tsne_affinities": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, ctypes.c_double, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_tsne_affinities": (c_int, _ROWS + [ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_tsne_kl_grad": (c_int, [c_ll, c_void_p, ctypes.c_double, c_void_p, c_size_t, c_void_p]),
     "pinn_tsne_descend": (c_int, [c_ll, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p,
                                   c_size_t, c_void_p]),

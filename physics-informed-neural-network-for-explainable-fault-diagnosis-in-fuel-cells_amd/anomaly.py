@@ -19,13 +19,13 @@ left.  Both backends run the same state machine on the same draws and give the s
 Two backends as in detection.py: "device" reads the rows in place (`columns=`, `row_index=`), "host" is numpy.
 Also here: `AnomalyMonitor` (online use, next to detection.FaultDetector).  Importing this module needs numpy only.
 """
+import functools
 import warnings
 
 import numpy as np
 
 from .detection import FEAT_GRP1, parse_features
-from .diagnosis import _DevRows
-from .risk import _as_numpy, _is_tensor, _pick_backend, _ptr, _torch_lib
+from ._device import _DevRows, _as_numpy, _is_tensor, _pick_backend, _torch_lib, call, columns_of
 
 # include/pinn_hip.h: PINN_IF_*
 MAX_TREES, MAX_SAMPLES, MAX_FEAT, MAX_NODES, MAX_LEAF_VALUES, LDS_NODES = 1024, 1024, 8, 2047, 16384, 4096
@@ -316,11 +316,7 @@ def _as_tree(t):
     return out
 
 
-def _rows(torch, X, columns, row_index):
-    D = len(columns) if columns is not None else (int(X.shape[1]) if len(X.shape) == 2 else 1)
-    if D > MAX_FEAT:
-        _check_limits(D=D)
-    return _DevRows(torch, X, columns, row_index)
+_rows = functools.partial(_DevRows.within, on_excess=lambda D: _check_limits(D=D))
 
 
 # ---------------------------------------------------------------------------------------------- the estimator
@@ -455,9 +451,7 @@ class DeviceIsolationForest:
             threshold = torch.empty(T * M, dtype=torch.float64, device=rows.dev)
             count, status = torch.empty(T, **i32), torch.empty(T, **i32)
             samples = torch.empty(T * m, dtype=torch.int64, device=rows.dev)
-            _lib.check(lib.pinn_if_fit(*rows.head(), T, m, max_depth_of(m), self.seed_, _ptr(feature), _ptr(threshold), _ptr(left),
-                                       _ptr(right), _ptr(n_node), _ptr(count), _ptr(samples), _ptr(status),
-                                       torch.cuda.current_stream().cuda_stream), "pinn_if_fit")
+            call("pinn_if_fit", *rows.head(), T, m, max_depth_of(m), self.seed_, feature, threshold, left, right, n_node, count, samples, status)
             count, status = count.cpu().numpy(), status.cpu().numpy()                # the one host read of a fit
             if status.any():
                 raise ValueError("the training rows hold values that are not finite or lie outside the array")
@@ -496,8 +490,7 @@ class DeviceIsolationForest:
             out = {"sum": torch.empty(n, dtype=torch.float64, device=rows.dev) if "sum" in want else None,
                    "score": torch.empty(n, dtype=torch.float64, device=rows.dev) if "score" in want else None,
                    "pred": torch.empty(n, dtype=torch.int64, device=rows.dev) if "pred" in want else None}
-            _lib.check(lib.pinn_if_score(*rows.head(), _ptr(block), float(self.offset_), _ptr(out["sum"]), _ptr(out["score"]),
-                                         _ptr(out["pred"]), int(variant), torch.cuda.current_stream().cuda_stream), "pinn_if_score")
+            call("pinn_if_score", *rows.head(), block, float(self.offset_), out["sum"], out["score"], out["pred"], int(variant))
         if not _is_tensor(X):
             return {k: out[k].cpu().numpy() for k in want}
         return {k: out[k] for k in want}
@@ -529,7 +522,7 @@ class AnomalyMonitor:
         self.forest, self.backend = forest, backend
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            self.columns = parse_features(features) if isinstance(features, str) else [int(c) for c in features]
+            self.columns = columns_of(features, parse_features)
         self.n_seen = 0
 
     def update(self, rows):

@@ -20,15 +20,15 @@ without a host synchronisation between them).  Ward runs on cluster means and si
 n (n - 1) / 2 distances.  "host": float64 numpy, the same state machines step for step, for machines without a GPU and as
 the referee of the device tests.  Importing this module needs numpy only; scikit-learn is never imported.
 """
+import functools
 import heapq
 
 import numpy as np
 
 from .detection import compute_macro_metrics, run_supervised_lr, stratified_split  # noqa: F401
-from .diagnosis import (DEFAULT_FEATURES, DEFAULT_GROUP_SPEC, RANDOM_STATE, REQUIRED_MAX_INDEX, TEST_SIZE, _DevRows, _host_rows,
-                        build_label_mapper, classification_metrics, extract_X_y, fit_gmm_and_get_probabilities, parse_features,
-                        parse_group_spec)
-from .risk import _as_numpy, _dev_vec, _is_tensor, _on_gpu, _pick_backend, _ptr, _torch_lib
+from ._device import _DevRows, _as_numpy, _dev_vec, _host_rows, _is_tensor, _on_gpu, _pick_backend, _torch_lib, call, columns_of
+from .diagnosis import (DEFAULT_FEATURES, DEFAULT_GROUP_SPEC, RANDOM_STATE, REQUIRED_MAX_INDEX, TEST_SIZE, build_label_mapper,
+                        classification_metrics, extract_X_y, fit_gmm_and_get_probabilities, parse_features, parse_group_spec)
 
 CLASS_NAMES_EN = ["Flooding", "Oxygen starvation", "Membrane drying", "Hydrogen starvation"]
 N_CLASSES = 4
@@ -215,12 +215,7 @@ def cluster_class_map(labels, y, n_clusters, n_classes):
     return np.where(s > 0, cnt / np.where(s > 0, s, 1.0), 1.0 / C)
 
 
-def _rows(torch, X, columns, row_index):
-    """diagnosis._DevRows, with the feature limit reported as what it is: a size the kernels are not built for."""
-    D = len(columns) if columns is not None else (int(X.shape[1]) if len(X.shape) == 2 else 1)
-    if D > MAX_FEAT:
-        _check_limits(D)
-    return _DevRows(torch, X, columns, row_index)
+_rows = functools.partial(_DevRows.within, on_excess=_check_limits)
 
 
 # ---------------------------------------------------------------------------------------------- assignment (both backends)
@@ -256,9 +251,7 @@ def assign_clusters(X, centres, cluster_class_prob=None, columns=None, row_index
                "dist2": torch.empty(n, dtype=torch.float64, device=rows.dev) if "dist2" in want else None,
                "y_prob": torch.empty(n, C, dtype=torch.float64, device=rows.dev) if "y_prob" in want else None,
                "y_pred": torch.empty(n, dtype=torch.int64, device=rows.dev) if "y_pred" in want else None}
-        _lib.check(lib.pinn_cluster_assign(*rows.head(), K, _ptr(c), _ptr(cm), C, _ptr(out["cluster"]), _ptr(out["dist2"]),
-                                           _ptr(out["y_prob"]), _ptr(out["y_pred"]), torch.cuda.current_stream().cuda_stream),
-                   "pinn_cluster_assign")
+        call("pinn_cluster_assign", *rows.head(), K, c, cm, C, out["cluster"], out["dist2"], out["y_prob"], out["y_pred"])
     if not _is_tensor(X):
         return {k: out[k].cpu().numpy() for k in want}
     return {k: out[k] for k in want}
@@ -299,8 +292,7 @@ def lloyd_iteration(X, centres, columns=None, row_index=None, tol=1e-4, backend=
     rows = _rows(torch, X, columns, row_index)
     with torch.cuda.device(rows.dev):
         st, ws, wb = _km_state(torch, lib, rows, K, c0)
-        _lib.check(lib.pinn_km_lloyd(*rows.head(), K, 1, 1, float(tol), 0, _ptr(st), _ptr(ws), wb, torch.cuda.current_stream().cuda_stream),
-                   "pinn_km_lloyd")
+        call("pinn_km_lloyd", *rows.head(), K, 1, 1, float(tol), 0, st, ws, wb)
         h = _km_header(st)
         if h["status"]:
             raise ValueError("the rows hold values that are not finite")
@@ -423,14 +415,14 @@ class DeviceKMeans:
                 done, init = 0, 1
                 while True:
                     step = min(self.chunk, self.max_iter - done)
-                    _lib.check(lib.pinn_km_lloyd(*rows.head(), K, init, step, self.tol, 0, _ptr(st), _ptr(ws), wb, stream), "pinn_km_lloyd")
+                    call("pinn_km_lloyd", *rows.head(), K, init, step, self.tol, 0, st, ws, wb, stream=stream)
                     done, init = done + step, 0
                     h = _km_header(st)                         # one read of the header per chunk
                     if h["converged"] or h["status"] or done >= self.max_iter:
                         break
                 if h["status"]:
                     raise ValueError("the rows hold values that are not finite (status %d)" % h["status"])
-                _lib.check(lib.pinn_km_lloyd(*rows.head(), K, 0, 0, self.tol, 1, _ptr(st), _ptr(ws), wb, stream), "pinn_km_lloyd")
+                call("pinn_km_lloyd", *rows.head(), K, 0, 0, self.tol, 1, st, ws, wb, stream=stream)
                 h = _km_header(st)
                 if best is None or h["inertia"] < best[1]["inertia"]:
                     best = (st, h)
@@ -521,7 +513,7 @@ class DeviceWard:
             queued, init, limit = 0, 1, 3 * (n - 1)
             while True:
                 step = min(self.chunk, limit - queued)
-                _lib.check(lib.pinn_ward_tree(*rows.head(), init, step, _ptr(st), _ptr(ws), wb, stream), "pinn_ward_tree")
+                call("pinn_ward_tree", *rows.head(), init, step, st, ws, wb, stream=stream)
                 queued, init = queued + step, 0
                 hdr = st[:_HDR].cpu().numpy().view(np.int64)        # one read of the header per chunk
                 if hdr[1] or hdr[2] or queued >= limit:
@@ -538,8 +530,7 @@ class DeviceWard:
                 kws = torch.empty(kwb, dtype=torch.uint8, device=rows.dev)
                 means = torch.zeros(self.n_clusters, D, dtype=torch.float64, device=rows.dev)
                 for _ in range(2):                                # the second pass sums x - mean: exact to rounding at any offset
-                    _lib.check(lib.pinn_cluster_means(*rows.head(), self.n_clusters, _ptr(lab_d), _ptr(means), None, _ptr(kws), kwb, stream),
-                               "pinn_cluster_means")
+                    call("pinn_cluster_means", *rows.head(), self.n_clusters, lab_d, means, None, kws, kwb, stream=stream)
                 self.cluster_means_ = means if _is_tensor(X) else means.cpu().numpy()
         self.labels_ = lab_d if _is_tensor(X) else lab
         self.n_features_in_ = D
@@ -679,7 +670,7 @@ class ClusterDiagnoser:
         if self.centres is None:
             raise NotImplementedError("the device backend assigns rows to at most %d clusters" % MAX_CLUSTERS)
         self.model, self.cluster_class_prob, self.backend = model, cluster_class_prob, backend
-        self.columns = parse_features(features) if isinstance(features, str) else [int(c) for c in features]
+        self.columns = columns_of(features, parse_features)
         self.n_seen = 0
 
     def update(self, rows):

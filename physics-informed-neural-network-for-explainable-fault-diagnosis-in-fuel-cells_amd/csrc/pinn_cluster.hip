@@ -406,16 +406,6 @@ __global__ __launch_bounds__(kT) void cluster_assign_kernel(Rows a, const double
   }
 }
 
-inline int n_blocks(long long n) {
-  const long long tiles = (n + kT - 1) / kT;
-  return (int)(tiles < 1 ? 1 : (tiles > kMaxBlocks ? kMaxBlocks : tiles));
-}
-
-inline int scan_blocks(long long n) {
-  const long long b = (n + kScanThreads - 1) / kScanThreads;
-  return (int)(b < 1 ? 1 : (b > kScanBlocks ? kScanBlocks : b));
-}
-
 struct Ws {
   double *tot, *part;
   long long* part_chg;
@@ -462,8 +452,8 @@ extern "C" int pinn_km_lloyd(const double* d_arr, long long ld, long long n_arr_
   if (ws_bytes < pinn_km_workspace_bytes(n, n_clusters, n_feat)) return PINN_E_WORKSPACE;
   const Ws w = carve(d_ws, n_clusters, n_feat);
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
-  const int K = n_clusters, D = n_feat, G = n_blocks(n);
+  clear_error();
+  const int K = n_clusters, D = n_feat, G = row_blocks(n, kT, kMaxBlocks);
   double* centres = d_state + km_centres();
   double* counts = d_state + km_counts(K, D);
   double* mean = d_state + km_mean(K, D);
@@ -491,8 +481,7 @@ extern "C" int pinn_km_lloyd(const double* d_arr, long long ld, long long n_arr_
     hipLaunchKernelGGL(km_final_kernel, dim3(1), dim3(kFinThreads), 0, st, d_state, centres, counts, K, D, (int)FIN_FINISH, G, n, K, tol, w.part,
                        w.part_chg, w.tot);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_cluster_means(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -507,14 +496,13 @@ extern "C" int pinn_cluster_means(const double* d_arr, long long ld, long long n
   if (ws_bytes < pinn_km_workspace_bytes(n, n_clusters, n_feat)) return PINN_E_WORKSPACE;
   const Ws w = carve(d_ws, n_clusters, n_feat);
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
-  const int G = n_blocks(n);
+  clear_error();
+  const int G = row_blocks(n, kT, kMaxBlocks);
   hipLaunchKernelGGL(km_rows_kernel, dim3(G), dim3(kT), 0, st, a, nullptr, d_centres, (int)LAB_GIVEN, const_cast<long long*>(d_labels), 1, w.part,
                      w.part_chg);
   hipLaunchKernelGGL(km_final_kernel, dim3(1), dim3(kFinThreads), 0, st, nullptr, d_centres, d_counts, n_clusters, n_feat, (int)FIN_LABEL_MEANS, G, n,
                      n_clusters, 0.0, w.part, w.part_chg, w.tot);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" size_t pinn_ward_state_bytes(long long n_rows, int n_feat) {
@@ -540,8 +528,8 @@ extern "C" int pinn_ward_tree(const double* d_arr, long long ld, long long n_arr
   double* part_d = static_cast<double*>(d_ws);
   long long* part_j = reinterpret_cast<long long*>(static_cast<char*>(d_ws) + align256(kScanBlocks * sizeof(double)));
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
-  const int G = scan_blocks(n), D = n_feat;
+  clear_error();
+  const int G = row_blocks(n, kScanThreads, kScanBlocks), D = n_feat;
   if (init) {
     hipLaunchKernelGGL(ward_init_kernel, dim3((unsigned)((n + kScanThreads - 1) / kScanThreads)), dim3(kScanThreads), 0, st, a, d_state);
     hipLaunchKernelGGL(ward_start_kernel, dim3(1), dim3(1), 0, st, d_state, n, D);
@@ -550,8 +538,7 @@ extern "C" int pinn_ward_tree(const double* d_arr, long long ld, long long n_arr
     hipLaunchKernelGGL(ward_scan_kernel, dim3(G), dim3(kScanThreads), 0, st, d_state, n, D, part_d, part_j);
     hipLaunchKernelGGL(ward_decide_kernel, dim3(1), dim3(kScanThreads), 0, st, d_state, n, D, G, part_d, part_j);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_cluster_assign(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -569,9 +556,8 @@ extern "C" int pinn_cluster_assign(const double* d_arr, long long ld, long long 
   if (n == 0) return PINN_OK;
   const long long tiles = (n + kT - 1) / kT;
   if (tiles > 0x7fffffffLL) return PINN_E_ARG;
-  (void)hipGetLastError();
+  clear_error();
   hipLaunchKernelGGL(cluster_assign_kernel, dim3((unsigned)tiles), dim3(kT), 0, (hipStream_t)stream, a, d_centres, d_map, n_classes, d_cluster,
                      d_dist2, d_y_prob, d_y_pred);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }

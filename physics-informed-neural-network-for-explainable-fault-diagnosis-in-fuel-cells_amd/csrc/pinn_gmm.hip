@@ -49,8 +49,6 @@ __device__ __forceinline__ bool stopped(const double* st) {
   return h[PINN_GMM_ST_CONVERGED] != 0 || h[PINN_GMM_ST_STATUS] != 0;
 }
 
-__device__ __forceinline__ int tri(int i, int j) { return j * (j + 1) / 2 + i; }      // i <= j
-
 // parameters of the state in LDS: means, upper-triangular precisions_cholesky (packed by columns), logdet, log weights
 struct Staged {
   double* mu;      // [K][D]
@@ -65,9 +63,8 @@ __device__ __forceinline__ void stage_params(const double* __restrict__ st, int 
   if (density) {
     for (int e = threadIdx.x; e < K * T; e += blockDim.x) {
       const int k = e / T, t = e - k * T;
-      int j = 0;
-      while ((j + 1) * (j + 2) / 2 <= t) ++j;
-      const int i = t - j * (j + 1) / 2;
+      int i, j;
+      untri(t, &i, &j);
       s.U[e] = st[st_chol(K, D) + ((size_t)k * D + i) * D + j];
     }
     for (int k = threadIdx.x; k < K; k += blockDim.x) {
@@ -141,11 +138,7 @@ __global__ __launch_bounds__(kRows) void gmm_rows_kernel(Rows a, const double* _
       } else if (f >= 1 && f <= D) {
         oi[q] = f - 1;
       } else if (f > D) {
-        const int p = f - 1 - D;
-        int j = 0;
-        while ((j + 1) * (j + 2) / 2 <= p) ++j;
-        oi[q] = p - j * (j + 1) / 2;
-        oj[q] = j;
+        untri(f - 1 - D, &oi[q], &oj[q]);
       }
     }
   }
@@ -437,11 +430,6 @@ __global__ __launch_bounds__(kRows) void gmm_posterior_kernel(Rows a, const doub
 
 inline int n_moments(int D) { return 1 + D + D * (D + 1) / 2; }
 
-inline int n_blocks(long long n) {
-  const long long tiles = (n + kRows - 1) / kRows;
-  return (int)(tiles < 1 ? 1 : (tiles > kMaxBlocks ? kMaxBlocks : tiles));
-}
-
 struct Ws {
   double *tot, *part, *part_l;
 };
@@ -459,13 +447,13 @@ inline Ws carve(void* d_ws, int K, int D) {
 
 inline void launch_rows(const Rows& a, const double* st, int src, int out, int n_f, const double* resp, const long long* lab,
                         const long long* cls, long long* lab_out, int force, const Ws& w, hipStream_t s) {
-  hipLaunchKernelGGL(gmm_rows_kernel, dim3((unsigned)n_blocks(a.n)), dim3(kRows), 0, s, a, st, src, out, n_f, resp, lab, cls, lab_out,
+  hipLaunchKernelGGL(gmm_rows_kernel, dim3((unsigned)row_blocks(a.n, kRows, kMaxBlocks)), dim3(kRows), 0, s, a, st, src, out, n_f, resp, lab, cls, lab_out,
                      force, w.part, w.part_l);
 }
 
 inline void launch_final(double* st, const Rows& a, int C, int mode, int n_f, double reg, double tol, const Ws& w, double* map_out,
                          hipStream_t s) {
-  hipLaunchKernelGGL(gmm_final_kernel, dim3(1), dim3(kFinThreads), 0, s, st, a.K, a.D, C, mode, n_f, n_blocks(a.n), a.n, reg, tol,
+  hipLaunchKernelGGL(gmm_final_kernel, dim3(1), dim3(kFinThreads), 0, s, st, a.K, a.D, C, mode, n_f, row_blocks(a.n, kRows, kMaxBlocks), a.n, reg, tol,
                      w.part, w.part_l, w.tot, map_out);
 }
 
@@ -494,7 +482,7 @@ extern "C" size_t pinn_gmm_workspace_bytes(long long n_rows, int n_comp, int n_f
   if (ws_bytes < pinn_gmm_workspace_bytes(n, n_comp, n_feat)) return PINN_E_WORKSPACE;           \
   const Ws w = carve(d_ws, n_comp, n_feat);                                                      \
   hipStream_t st = (hipStream_t)stream;                                                          \
-  (void)hipGetLastError()
+  clear_error()
 
 extern "C" int pinn_gmm_mstep_init(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
                                    const long long* d_row_index, long long n, int n_comp, const double* d_resp,
@@ -511,8 +499,7 @@ extern "C" int pinn_gmm_mstep_init(const double* d_arr, long long ld, long long 
   launch_final(d_state, a, 0, FIN_MEANS, 1 + n_feat, reg_covar, 0.0, w, nullptr, st);
   launch_rows(a, d_state, src, OUT_MOMENTS, F, d_resp, d_labels, nullptr, nullptr, 1, w, st);    // second pass: about the means
   launch_final(d_state, a, 0, FIN_INIT, F, reg_covar, 0.0, w, nullptr, st);
-  e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_gmm_em(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -526,8 +513,7 @@ extern "C" int pinn_gmm_em(const double* d_arr, long long ld, long long n_arr_ro
     launch_rows(a, d_state, SRC_ESTEP, OUT_MOMENTS, F, nullptr, nullptr, nullptr, nullptr, 0, w, st);
     launch_final(d_state, a, 0, FIN_EM, F, reg_covar, tol, w, nullptr, st);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_gmm_kmeans(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -543,8 +529,7 @@ extern "C" int pinn_gmm_kmeans(const double* d_arr, long long ld, long long n_ar
   }
   if (d_labels)                                             // the assignment to the final centres
     launch_rows(a, d_state, SRC_NEAREST, OUT_MOMENTS, F, nullptr, nullptr, nullptr, d_labels, 1, w, st);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_gmm_label_map(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -556,8 +541,7 @@ extern "C" int pinn_gmm_label_map(const double* d_arr, long long ld, long long n
   if (n_classes < 1 || n_classes > kMaxC || !d_map || (n > 0 && !d_class) || misaligned8(d_class) || misaligned8(d_map)) return PINN_E_ARG;
   launch_rows(a, d_state, SRC_ESTEP, OUT_CLASS, n_classes, nullptr, nullptr, d_class, nullptr, 1, w, st);
   launch_final(const_cast<double*>(d_state), a, n_classes, FIN_MAP, n_classes, 0.0, 0.0, w, d_map, st);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_gmm_posterior(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -575,9 +559,8 @@ extern "C" int pinn_gmm_posterior(const double* d_arr, long long ld, long long n
   if (n == 0) return PINN_OK;
   const long long tiles = (n + kRows - 1) / kRows;
   if (tiles > 0x7fffffffLL) return PINN_E_ARG;
-  (void)hipGetLastError();
+  clear_error();
   hipLaunchKernelGGL(gmm_posterior_kernel, dim3((unsigned)tiles), dim3(kRows), 0, (hipStream_t)stream, a, d_state, d_map, n_classes,
                      d_log_prob_norm, d_resp, d_y_prob, d_y_pred);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }

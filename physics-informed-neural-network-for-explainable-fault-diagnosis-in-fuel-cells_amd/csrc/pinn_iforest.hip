@@ -347,12 +347,11 @@ extern "C" int pinn_if_score(const double* d_arr, long long ld, long long n_arr_
   const long long per = (long long)kScoreThreads * (many ? 4 : 1);
   const long long blocks = (n + per - 1) / per;
   if (blocks > 0x7fffffffLL) return PINN_E_ARG;
-  (void)hipGetLastError();
+  clear_error();
   const unsigned long long* f = static_cast<const unsigned long long*>(d_forest);
   if (many) launch_score_d<4>(variant, (unsigned)blocks, (hipStream_t)stream, a, f, offset, d_depth_sum, d_score, d_pred);
   else launch_score_d<1>(variant, (unsigned)blocks, (hipStream_t)stream, a, f, offset, d_depth_sum, d_score, d_pred);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_if_fit(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -371,10 +370,9 @@ extern "C" int pinn_if_fit(const double* d_arr, long long ld, long long n_arr_ro
       ((unsigned long long)d_right & 3) || ((unsigned long long)d_n_node & 3) || ((unsigned long long)d_node_count & 3) ||
       ((unsigned long long)d_status & 3))
     return PINN_E_ARG;
-  (void)hipGetLastError();
+  clear_error();
   hipLaunchKernelGGL(if_fit_kernel, dim3((unsigned)n_trees), dim3(kFitThreads), 0, (hipStream_t)stream, a, max_samples, max_depth,
                      (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), d_feature, d_threshold, d_left, d_right, d_n_node, d_node_count,
                      d_samples, d_status);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }

@@ -15,7 +15,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "../../include/pinn_hip.h"
+#include "pinn_rows.h"
+
+static_assert(PINN_LR_MAX_FEAT == PINN_GMM_MAX_FEAT && PINN_LR_MAX_CLASSES <= PINN_GMM_MAX_COMP,
+              "pinn_rows.h sizes Rows and bounds make_rows by the mixture's limits");
 
 namespace pinn {
 namespace {
@@ -31,14 +34,6 @@ constexpr int kHdr = PINN_LR_ST_HEADER;
 constexpr double kEps = 2.220446049250313e-16;
 
 enum { FIN_SUMS = 0, FIN_NEWTON = 1 };
-
-struct Rows {
-  const double* arr;
-  long long ld, n_arr, n;
-  const long long* ridx;
-  int D, C;
-  int col[kMaxD];
-};
 
 // state block: header, then theta [P] (the point the next pass evaluates), accepted [P], direction [P], gradient [P] of the
 // accepted point, mean [D], scale [D], var [D], class_weight [C], class_count [C] (64-bit integers).
@@ -63,26 +58,6 @@ inline bool in_limits(int C, int D) {
 __device__ __forceinline__ bool stopped(const double* st) {
   const long long* h = reinterpret_cast<const long long*>(st);
   return h[PINN_LR_ST_CONVERGED] != 0 || h[PINN_LR_ST_STATUS] != 0 || h[PINN_LR_ST_ITER] >= h[PINN_LR_ST_MAXITER];
-}
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-__device__ __forceinline__ int tri(int i, int j) { return j * (j + 1) / 2 + i; }      // i <= j
-
-__device__ __forceinline__ void untri(int p, int* i, int* j) {
-  int jj = 0;
-  while ((jj + 1) * (jj + 2) / 2 <= p) ++jj;
-  *j = jj;
-  *i = p - jj * (jj + 1) / 2;
-}
-
-__device__ __forceinline__ bool load_row(const Rows& a, long long j, double x[kMaxD]) {
-  const long long row = a.ridx ? a.ridx[j] : j;
-  const bool ok = row >= 0 && row < a.n_arr;               // a gather index outside the array reads nothing
-  const double* r = a.arr + (ok ? row : 0) * a.ld;
-#pragma unroll
-  for (int i = 0; i < kMaxD; ++i) x[i] = (ok && i < a.D) ? r[a.col[i]] : 0.0;
-  return ok;
 }
 
 // The model of a row, shared by the fit and the posterior: z = (x - mean) / scale into u[0..D), the scores of the R
@@ -119,7 +94,7 @@ __global__ __launch_bounds__(kRows) void lr_rows_kernel(Rows a, const double* __
   __shared__ int s_y[kRows];
   __shared__ double s_th[kMaxP], s_mean[kMaxD], s_scale[kMaxD], s_cw[kMaxC];
   if (!force && stopped(st)) return;
-  const int C = a.C, D = a.D, Cp = C | 1, Up = (D + 1) | 1, t = threadIdx.x, P = n_par(C, D);
+  const int C = a.K, D = a.D, Cp = C | 1, Up = (D + 1) | 1, t = threadIdx.x, P = n_par(C, D);
   for (int e = t; e < P; e += kRows) s_th[e] = st[st_theta() + e];
   if (t < D) { s_mean[t] = st[st_mean(C, D) + t]; s_scale[t] = st[st_scale(C, D) + t]; }
   if (t < C) s_cw[t] = st[st_cw(C, D) + t];
@@ -355,7 +330,7 @@ __global__ __launch_bounds__(kRows) void lr_stats_kernel(Rows a, const double* _
                                                          double* __restrict__ part, long long* __restrict__ cnt) {
   __shared__ double s_x[kRows * (kMaxD + 1)];
   __shared__ int s_y[kRows];
-  const int C = a.C, D = a.D, Dp = D | 1, t = threadIdx.x;
+  const int C = a.K, D = a.D, Dp = D | 1, t = threadIdx.x;
   const double mean = (pass == 1 && t < D) ? st[st_mean(C, D) + t] : 0.0;
   double acc = 0.0;
   long long count = 0;
@@ -439,7 +414,7 @@ __global__ __launch_bounds__(kRows) void lr_posterior_kernel(Rows a, const doubl
                                                              double* __restrict__ pf_out) {
   __shared__ double s_p[kRows * kMaxC];
   __shared__ double s_mean[kMaxD], s_scale[kMaxD], s_W[kMaxC * (kMaxD + 1)];
-  const int C = a.C, D = a.D, Cp = C | 1, R = C == 2 ? 1 : C, t = threadIdx.x;
+  const int C = a.K, D = a.D, Cp = C | 1, R = C == 2 ? 1 : C, t = threadIdx.x;
   if (t < D) { s_mean[t] = model[t]; s_scale[t] = model[D + t]; }
   for (int e = t; e < R * (D + 1); e += kRows) {
     const int r = e / (D + 1), i = e - r * (D + 1);
@@ -596,29 +571,6 @@ __global__ __launch_bounds__(kTile) void roc_emit2_kernel(const long long* __res
   }
 }
 
-inline bool misaligned8(const void* p) { return ((unsigned long long)p & 7) != 0; }
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-inline int n_blocks(long long n) {
-  const long long tiles = (n + kRows - 1) / kRows;
-  return (int)(tiles < 1 ? 1 : (tiles > kMaxBlocks ? kMaxBlocks : tiles));
-}
-
-// checks shared by every entry point that reads rows; fills `a`
-inline int make_rows(const double* d_arr, long long ld, long long n_arr, const int* cols, int n_feat, int n_classes,
-                     const long long* d_row_index, long long n, Rows* a) {
-  if (n < 0 || n_arr < 0 || ld < 1 || !cols || !in_limits(n_classes, n_feat)) return PINN_E_ARG;
-  for (int i = 0; i < n_feat; ++i)
-    if (cols[i] < 0 || cols[i] >= ld) return PINN_E_ARG;
-  if (!d_row_index && n > n_arr) return PINN_E_ARG;
-  if (n > 0 && !d_arr) return PINN_E_ARG;
-  if (misaligned8(d_arr) || misaligned8(d_row_index)) return PINN_E_ARG;
-  a->arr = d_arr; a->ld = ld; a->n_arr = n_arr; a->n = n; a->ridx = d_row_index; a->D = n_feat; a->C = n_classes;
-  for (int i = 0; i < kMaxD; ++i) a->col[i] = i < n_feat ? cols[i] : 0;
-  return PINN_OK;
-}
-
 struct Ws {
   double *tot, *part;
   long long* cnt;
@@ -652,6 +604,7 @@ extern "C" size_t pinn_lr_workspace_bytes(long long n_rows, int n_classes, int n
 }
 
 #define LR_COMMON_CHECKS()                                                                          \
+  if (!in_limits(n_classes, n_feat)) return PINN_E_ARG;                                             \
   Rows a;                                                                                           \
   {                                                                                                 \
     const int rc_ = make_rows(d_arr, ld, n_arr_rows, cols, n_feat, n_classes, d_row_index, n, &a);  \
@@ -662,20 +615,19 @@ extern "C" size_t pinn_lr_workspace_bytes(long long n_rows, int n_classes, int n
   if (ws_bytes < pinn_lr_workspace_bytes(n, n_classes, n_feat)) return PINN_E_WORKSPACE;            \
   const Ws w = carve(d_ws, n_classes, n_feat);                                                      \
   hipStream_t st = (hipStream_t)stream;                                                             \
-  (void)hipGetLastError()
+  clear_error()
 
 extern "C" int pinn_lr_scaler(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
                               const long long* d_row_index, long long n, const long long* d_y, int n_classes, int balanced,
                               double* d_state, void* d_ws, size_t ws_bytes, void* stream) {
   using namespace pinn;
   LR_COMMON_CHECKS();
-  const int nb = n_blocks(n);
+  const int nb = row_blocks(n, kRows, kMaxBlocks);
   for (int pass = 0; pass < 2; ++pass) {
     hipLaunchKernelGGL(lr_stats_kernel, dim3((unsigned)nb), dim3(kRows), 0, st, a, d_state, d_y, pass, w.part, w.cnt);
     hipLaunchKernelGGL(lr_stats_final_kernel, dim3(1), dim3(64), 0, st, d_state, n_classes, n_feat, pass, balanced, nb, w.part, w.cnt);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_lr_pass(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -683,12 +635,11 @@ extern "C" int pinn_lr_pass(const double* d_arr, long long ld, long long n_arr_r
                             const double* d_state, void* d_ws, size_t ws_bytes, void* stream) {
   using namespace pinn;
   LR_COMMON_CHECKS();
-  const int nb = n_blocks(n);
+  const int nb = row_blocks(n, kRows, kMaxBlocks);
   hipLaunchKernelGGL(lr_rows_kernel, dim3((unsigned)nb), dim3(kRows), 0, st, a, d_state, d_y, 1, w.part);
   hipLaunchKernelGGL(lr_final_kernel, dim3(1), dim3(kFinThreads), 0, st, const_cast<double*>(d_state), n_classes, n_feat, FIN_SUMS, nb, n,
                      0.0, 0.0, 1, w.part, w.tot);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_lr_newton(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -698,14 +649,13 @@ extern "C" int pinn_lr_newton(const double* d_arr, long long ld, long long n_arr
   using namespace pinn;
   LR_COMMON_CHECKS();
   if (n_passes < 0 || n_passes > 100000 || !(tol >= 0.0) || !(l2 > 0.0) || !(l2 < INFINITY)) return PINN_E_ARG;
-  const int nb = n_blocks(n);
+  const int nb = row_blocks(n, kRows, kMaxBlocks);
   for (int it = 0; it < n_passes; ++it) {
     hipLaunchKernelGGL(lr_rows_kernel, dim3((unsigned)nb), dim3(kRows), 0, st, a, d_state, d_y, 0, w.part);
     hipLaunchKernelGGL(lr_final_kernel, dim3(1), dim3(kFinThreads), 0, st, d_state, n_classes, n_feat, FIN_NEWTON, nb, n, tol, l2,
                        fit_intercept, w.part, w.tot);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_lr_posterior(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -713,6 +663,7 @@ extern "C" int pinn_lr_posterior(const double* d_arr, long long ld, long long n_
                                  int normal_class, double* d_decision, double* d_proba, long long* d_pred, double* d_p_fault,
                                  void* stream) {
   using namespace pinn;
+  if (!in_limits(n_classes, n_feat)) return PINN_E_ARG;
   Rows a;
   const int rc = make_rows(d_arr, ld, n_arr_rows, cols, n_feat, n_classes, d_row_index, n, &a);
   if (rc != PINN_OK) return rc;
@@ -722,11 +673,10 @@ extern "C" int pinn_lr_posterior(const double* d_arr, long long ld, long long n_
   if (n == 0) return PINN_OK;
   const long long tiles = (n + kRows - 1) / kRows;
   if (tiles > 0x7fffffffLL) return PINN_E_ARG;
-  (void)hipGetLastError();
+  clear_error();
   hipLaunchKernelGGL(lr_posterior_kernel, dim3((unsigned)tiles), dim3(kRows), 0, (hipStream_t)stream, a, d_model, normal_class,
                      d_decision, d_proba, d_pred, d_p_fault);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 // ROC workspace: tile sums (4 arrays), then fps, tps, thresholds and keep flags at the boundaries, [n] each
@@ -759,7 +709,7 @@ extern "C" int pinn_lr_roc(const double* d_score_sorted, const long long* d_pos_
   double* thr = reinterpret_cast<double*>(w); w += nb;
   long long* keep = reinterpret_cast<long long*>(w);
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
+  clear_error();
   hipError_t e = hipMemsetAsync(d_counts, 0, PINN_LR_ROC_COUNTS * sizeof(long long), st);
   if (e != hipSuccess) return (int)e;
   const dim3 grid((unsigned)nt), block(kTile);
@@ -770,6 +720,5 @@ extern "C" int pinn_lr_roc(const double* d_score_sorted, const long long* d_pos_
   hipLaunchKernelGGL(roc_tiles2_kernel, grid, block, 0, st, fps, tps, d_counts + PINN_LR_ROC_M, drop_intermediate, keep, tile_c, tile_d);
   hipLaunchKernelGGL(roc_scan_tiles_kernel, dim3(1), block, 0, st, tile_c, tile_d, nt, d_counts + PINN_LR_ROC_KEPT, d_counts + PINN_LR_ROC_U2);
   hipLaunchKernelGGL(roc_emit2_kernel, grid, block, 0, st, fps, tps, thr, keep, tile_c, n, d_counts, d_fps, d_tps, d_thresholds, d_fpr, d_tpr);
-  e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }

@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "../../include/pinn_hip.h"
+#include "pinn_rows.h"
 
 namespace pinn {
 namespace {
@@ -58,8 +58,6 @@ __device__ __forceinline__ Op combine(const Op& l, const Op& r) {
 __device__ __forceinline__ double apply(const Op& o, double x) { return o.f ? o.b : o.m * x + o.b; }
 
 __device__ __forceinline__ int pidx(int i) { return i + (i >> 3); }
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // np.clip: NaN stays NaN (fmin / fmax would return the bound)
 __device__ __forceinline__ double clip_nan(double x, double lo, double hi) {
@@ -501,10 +499,6 @@ __global__ __launch_bounds__(kThreads) void stats_final_kernel(StatsDev a, const
   }
 }
 
-inline bool misaligned8(const void* p) { return ((unsigned long long)p & 7) != 0; }
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline long long n_tiles_of(long long n) { return (n + kTile - 1) / kTile; }
 
 }  // namespace
@@ -537,14 +531,13 @@ extern "C" int pinn_rf_stats(const double* d_arr, long long ld, long long n_rows
   double* part = static_cast<double*>(d_ws);
   long long* cpart = reinterpret_cast<long long*>(part + (size_t)kStatBlocks * PINN_RF_MAX_COLS);
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
+  clear_error();
   for (int pass = 0; pass < 2; ++pass) {
     a.pass = pass;
     hipLaunchKernelGGL(stats_partial_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, a, d_arr, ld, n_rows, d_mu, part, cpart);
     hipLaunchKernelGGL(stats_final_kernel, dim3(1), dim3(kThreads), 0, st, a, part, cpart, (int)blocks, d_mu, d_sigma, d_count);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" size_t pinn_rf_workspace_bytes(long long n_rows, long long n_segments) {
@@ -593,7 +586,7 @@ extern "C" int pinn_rf_series(const double* d_arr, long long ld, long long n_arr
   const double l_max = 1.0 / (1.0 + exp(-a.k * (a.c_max - a.c0)));
   a.denom = (l_max - a.l0) != 0.0 ? (l_max - a.l0) : 1e-6;
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
+  clear_error();
   if (n <= kTile) {
     hipLaunchKernelGGL(rf_single_kernel, dim3(1), dim3(kThreads), 0, st, a, d_arr, ld, n_arr_rows, d_mu, d_sigma, d_row_index, n,
                        d_seg_start, ns, d_carry_in, d_S_layers, d_S_tot, d_C, d_RF_inst, d_RF_smooth, d_carry_out);
@@ -619,8 +612,7 @@ extern "C" int pinn_rf_series(const double* d_arr, long long ld, long long n_arr
     hipLaunchKernelGGL(rf_carry_kernel, dim3(1), block, 0, st, agg_r, tiles, ent_r);
     hipLaunchKernelGGL(rf_pass3_kernel, grid, block, 0, st, a, RF, n, d_seg_start, ns, d_carry_in, ent_r, d_RF_smooth, d_carry_out);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_rf_first_alarm(const double* d_series, long long stride, long long n_src_rows, const long long* d_row_index,
@@ -637,12 +629,11 @@ extern "C" int pinn_rf_first_alarm(const double* d_series, long long stride, lon
   const long long blocks = (n + kThreads - 1) / kThreads;
   if (blocks > 0x7fffffffLL || (ns + kThreads - 1) / kThreads > 0x7fffffffLL) return PINN_E_ARG;
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
+  clear_error();
   unsigned long long* out = reinterpret_cast<unsigned long long*>(d_first);
   hipLaunchKernelGGL(alarm_init_kernel, dim3((unsigned)((ns + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, out, ns);
   if (n > 0)
     hipLaunchKernelGGL(alarm_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, d_series, stride, n_src_rows, d_row_index, n,
                        d_seg_start, ns, mode == PINN_RF_BELOW ? 1 : 0, relative ? 1 : 0, threshold, out);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }

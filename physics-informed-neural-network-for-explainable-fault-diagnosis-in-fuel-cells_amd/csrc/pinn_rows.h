@@ -1,4 +1,5 @@
-// Rows of a float64 array read in place: what pinn_gmm.hip and pinn_cluster.hip share.  Position j reads row ridx[j]
+// What the analysis kernels (risk, gmm, lr, cluster, iforest, svm, tsne) share: rows of a float64 array read in place, the
+// packed upper triangle, the workgroup count of a row pass and the status of a launch.  Position j reads row ridx[j]
 // (NULL: row j) of a row-major array with leading dimension ld, columns col[D]; an index outside the array reads nothing.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,9 +30,34 @@ __device__ __forceinline__ bool load_row(const Rows& a, long long j, double x[kR
 
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
+// packed upper triangle, column by column: (i, j), i <= j, sits at j (j + 1) / 2 + i
+__device__ __forceinline__ int tri(int i, int j) { return j * (j + 1) / 2 + i; }
+
+__device__ __forceinline__ void untri(int p, int* i, int* j) {
+  int jj = 0;
+  while ((jj + 1) * (jj + 2) / 2 <= p) ++jj;
+  *j = jj;
+  *i = p - jj * (jj + 1) / 2;
+}
+
 inline bool misaligned8(const void* p) { return ((unsigned long long)p & 7) != 0; }
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// workgroups of a row pass over n rows: one per tile, at least 1, at most max_blocks.  It is also the number of partial
+// sums per output, so it fixes the order of every sum.
+inline int row_blocks(long long n, int tile, int max_blocks) {
+  const long long tiles = (n + tile - 1) / tile;
+  return (int)(tiles < 1 ? 1 : (tiles > max_blocks ? max_blocks : tiles));
+}
+
+// status of an entry point's launches: clear the sticky error before the first, read it after the last
+inline void clear_error() { (void)hipGetLastError(); }
+
+inline int launch_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PINN_OK : (int)e;
+}
 
 // checks shared by every entry point that reads rows; fills `a`
 inline int make_rows(const double* d_arr, long long ld, long long n_arr, const int* cols, int n_feat, int n_comp,

@@ -66,13 +66,6 @@ __device__ __forceinline__ bool pair_stopped(const double* pb) {
   return h[PINN_SVM_P_CONVERGED] != 0 || h[PINN_SVM_P_STATUS] != 0;
 }
 
-__device__ __forceinline__ void untri(int p, int* i, int* j) {      // p = j (j + 1) / 2 + i, i <= j
-  int jj = 0;
-  while ((jj + 1) * (jj + 2) / 2 <= p) ++jj;
-  *j = jj;
-  *i = p - jj * (jj + 1) / 2;
-}
-
 // the largest step that keeps v + step dv >= 0
 __device__ __forceinline__ double boundary(double v, double dv) { return dv < 0.0 ? -v / dv : INFINITY; }
 
@@ -515,11 +508,6 @@ __global__ __launch_bounds__(kRows) void svm_decision_kernel(Rows a, const doubl
   if (pred_out) pred_out[j] = ok ? best : -1;
 }
 
-inline int n_blocks(long long n) {
-  const long long tiles = (n + kRows - 1) / kRows;
-  return (int)(tiles < 1 ? 1 : (tiles > kMaxBlocks ? kMaxBlocks : tiles));
-}
-
 struct Ws {
   double *tot, *scratch, *part, *pmin, *pbad, *dal, *ds, *dz;
 };
@@ -576,8 +564,8 @@ extern "C" size_t pinn_svm_workspace_bytes(long long n_rows, int n_classes, int 
   Ws w;                                                                                             \
   carve(d_ws, n, n_classes, n_feat, &w);                                                            \
   hipStream_t st = (hipStream_t)stream;                                                             \
-  const int nb = n_blocks(n);                                                                       \
-  (void)hipGetLastError()
+  const int nb = row_blocks(n, kRows, kMaxBlocks);                                                  \
+  clear_error()
 
 extern "C" int pinn_svm_pass(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
                              const long long* d_row_index, long long n, const long long* d_y, int n_classes,
@@ -586,8 +574,7 @@ extern "C" int pinn_svm_pass(const double* d_arr, long long ld, long long n_arr_
   SVM_COMMON_CHECKS();
   const Pass k = {const_cast<double*>(d_state), d_y, w.dal, w.ds, w.dz, w.part, w.pmin, w.pbad, MODE_SUMS};
   launch_pass<PASS_A>(a, k, nb, n_classes, n_feat, MODE_SUMS, 0.0, w, st);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_svm_ipm(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -606,8 +593,7 @@ extern "C" int pinn_svm_ipm(const double* d_arr, long long ld, long long n_arr_r
     launch_pass<PASS_C>(a, k, nb, n_classes, n_feat, MODE_RUN, gap_tol, w, st);
     launch_pass<PASS_A>(a, k, nb, n_classes, n_feat, MODE_RUN, gap_tol, w, st);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_svm_decision(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
@@ -622,8 +608,7 @@ extern "C" int pinn_svm_decision(const double* d_arr, long long ld, long long n_
   if (n == 0) return PINN_OK;
   const long long tiles = (n + kRows - 1) / kRows;
   if (tiles > 0x7fffffffLL) return PINN_E_ARG;
-  (void)hipGetLastError();
+  clear_error();
   hipLaunchKernelGGL(svm_decision_kernel, dim3((unsigned)tiles), dim3(kRows), 0, (hipStream_t)stream, a, d_model, d_decision, d_votes, d_pred);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }

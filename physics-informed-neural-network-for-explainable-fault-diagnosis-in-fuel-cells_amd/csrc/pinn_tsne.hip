@@ -405,13 +405,12 @@ extern "C" int pinn_tsne_affinities(const double* d_arr, long long ld, long long
   double* rows_out = reinterpret_cast<double*>(w + ws_rows_off(n));
   double* scal = reinterpret_cast<double*>(w + ws_scal_off(n));
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
+  clear_error();
   const unsigned tiles = (unsigned)((n + kSymTile - 1) / kSymTile);
   hipLaunchKernelGGL(tsne_cond_kernel, dim3((unsigned)n), dim3(kAffThreads), 0, st, a, log(perplexity), P, rows_out, d_beta, d_entropy, d_status);
   hipLaunchKernelGGL(tsne_psum_kernel, dim3(1), dim3(kFinThreads), 0, st, rows_out, n, scal);
   hipLaunchKernelGGL(tsne_sym_kernel, dim3(tiles, tiles), dim3(kSymThreads), 0, st, P, n, scal);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_tsne_kl_grad(long long n, const double* d_Y, double exaggeration, void* d_ws, size_t ws_bytes, void* stream) {
@@ -424,13 +423,12 @@ extern "C" int pinn_tsne_kl_grad(long long n, const double* d_Y, double exaggera
   double* grad = reinterpret_cast<double*>(w + ws_grad_off(n));
   double* scal = reinterpret_cast<double*>(w + ws_scal_off(n));
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
+  clear_error();
   const unsigned G = (unsigned)((n + kPairRows - 1) / kPairRows);
   hipLaunchKernelGGL(tsne_pair_kernel, dim3(G), dim3(kPairThreads), 0, st, P, d_Y, n, (const double*)nullptr, 0, rows_out);
   hipLaunchKernelGGL(tsne_finish_kernel, dim3(1), dim3(kFinThreads), 0, st, (int)FIN_EVAL, n, (double*)nullptr, const_cast<double*>(d_Y), rows_out, grad, scal,
                      exaggeration, 0, 1.0, 0.0, 0, 0.0);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_tsne_descend(long long n, int init, int n_iter, int max_iter, double early_exaggeration, double learning_rate,
@@ -448,7 +446,7 @@ extern "C" int pinn_tsne_descend(long long n, int init, int n_iter, int max_iter
   double* grad = reinterpret_cast<double*>(w + ws_grad_off(n));
   double* scal = reinterpret_cast<double*>(w + ws_scal_off(n));
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
+  clear_error();
   const unsigned G = (unsigned)((n + kPairRows - 1) / kPairRows);
   if (init) hipLaunchKernelGGL(tsne_init_kernel, dim3(1), dim3(kFinThreads), 0, st, d_state, n);
   for (int it = 0; it < n_iter; ++it) {
@@ -456,6 +454,5 @@ extern "C" int pinn_tsne_descend(long long n, int init, int n_iter, int max_iter
     hipLaunchKernelGGL(tsne_finish_kernel, dim3(1), dim3(kFinThreads), 0, st, (int)FIN_STEP, n, d_state, d_state + kHdr, rows_out, grad, scal, 1.0, max_iter,
                        early_exaggeration, learning_rate, n_iter_without_progress, min_grad_norm);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }

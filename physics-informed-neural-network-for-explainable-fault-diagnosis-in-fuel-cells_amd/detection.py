@@ -19,15 +19,17 @@ predict_proba = softmax([-d, d]), as scikit-learn reports a two-class multinomia
 Two backends, as in risk.py and diagnosis.py.  "device": the HIP kernels of csrc/pinn_lr.hip.  "host": float64 numpy.
 Importing this module needs numpy only; scikit-learn is never imported.
 """
+import functools
 import re
 import warnings
 
 import numpy as np
 
 from . import diagnosis as _dg
-from .diagnosis import (_DevRows, _host_rows, build_label_mapper, classification_metrics, extract_X_y,  # noqa: F401
-                        list_available_features, normalize_feature_spec)
-from .risk import FAULT_ALIASES, INDEX, _as_numpy, _dev_vec, _is_tensor, _on_gpu, _pick_backend, _ptr, _torch_lib
+from ._device import _DevRows, _as_numpy, _dev_vec, _host_rows, _is_tensor, _on_gpu, _pick_backend, _torch_lib, call, columns_of
+from .diagnosis import (build_label_mapper, classification_metrics, extract_X_y, list_available_features,  # noqa: F401
+                        normalize_feature_spec)
+from .risk import FAULT_ALIASES, INDEX
 
 FEAT_GRP1 = "epi,res"
 FEAT_GRP2 = "x0,x3,x4,x5"
@@ -260,8 +262,7 @@ class DeviceStandardScaler:
             yz = torch.zeros(rows.n, dtype=torch.int64, device=rows.dev)
             wb = lib.pinn_lr_workspace_bytes(rows.n, 2, rows.D)
             ws = torch.empty(wb, dtype=torch.uint8, device=rows.dev)
-            _lib.check(lib.pinn_lr_scaler(*rows.head(), _ptr(yz), 2, 0, _ptr(st), _ptr(ws), wb, torch.cuda.current_stream().cuda_stream),
-                       "pinn_lr_scaler")
+            call("pinn_lr_scaler", *rows.head(), yz, 2, 0, st, ws, wb)
             o = _offsets(2, rows.D)
             stats = [st[o[k]:o[k] + rows.D].clone() for k in ("mean", "var", "scale")]
         if not _is_tensor(X):
@@ -301,11 +302,7 @@ def n_pass_sums(C, D):
     return 1 + C * (D + 1) + (C * (C + 1) // 2) * ((D + 1) * (D + 2) // 2)
 
 
-def _rows(torch, X, columns, row_index):
-    D = len(columns) if columns is not None else (X.shape[1] if len(X.shape) == 2 else 0)
-    if D > MAX_FEAT:
-        _check_limits(2, D)
-    return _DevRows(torch, X, columns, row_index)
+_rows = functools.partial(_DevRows.within, on_excess=lambda D: _check_limits(2, D))
 
 
 def _check_limits(C, D):
@@ -442,8 +439,8 @@ class DeviceLogisticRegression:
             st = torch.from_numpy(s0).to(rows.dev)
             wb = lib.pinn_lr_workspace_bytes(rows.n, C, D)
             ws = torch.empty(wb, dtype=torch.uint8, device=rows.dev)
-            head = rows.head() + (_ptr(yi), C)
-            _lib.check(lib.pinn_lr_scaler(*head, int(balanced), _ptr(st), _ptr(ws), wb, stream), "pinn_lr_scaler")
+            head = rows.head() + (yi, C)
+            call("pinn_lr_scaler", *head, int(balanced), st, ws, wb, stream=stream)
             if fit_scaler is not None:
                 stats = [st[o[k]:o[k] + D].clone() for k in ("mean", "var", "scale")]
                 fit_scaler._set(*(stats if _is_tensor(X) else [s.cpu().numpy() for s in stats]), rows.n)
@@ -454,8 +451,7 @@ class DeviceLogisticRegression:
             self._state, self._ws = st, ws
             # every pass is a pair of launches; the block is read once per chunk of `chunk` passes
             while True:
-                _lib.check(lib.pinn_lr_newton(*head, self.chunk, self.tol, l2, int(self.fit_intercept), _ptr(st), _ptr(ws), wb, stream),
-                           "pinn_lr_newton")
+                call("pinn_lr_newton", *head, self.chunk, self.tol, l2, int(self.fit_intercept), st, ws, wb, stream=stream)
                 s = st.cpu().numpy()
                 hdr = s[:_HDR].view(np.int64)
                 if trace is not None:
@@ -503,12 +499,12 @@ class DeviceLogisticRegression:
             st = torch.from_numpy(s0).to(rows.dev)
             wb = lib.pinn_lr_workspace_bytes(rows.n, C, D)
             ws = torch.empty(wb, dtype=torch.uint8, device=rows.dev)
-            head = rows.head() + (_ptr(yi), C)
-            _lib.check(lib.pinn_lr_scaler(*head, int(balanced), _ptr(st), _ptr(ws), wb, stream), "pinn_lr_scaler")
+            head = rows.head() + (yi, C)
+            call("pinn_lr_scaler", *head, int(balanced), st, ws, wb, stream=stream)
             mean, scale = self._scaler_stats(scaler, D)
             st[o["mean"]:o["mean"] + D] = torch.from_numpy(mean).to(rows.dev)
             st[o["scale"]:o["scale"] + D] = torch.from_numpy(scale).to(rows.dev)
-            _lib.check(lib.pinn_lr_pass(*head, _ptr(st), _ptr(ws), wb, stream), "pinn_lr_pass")
+            call("pinn_lr_pass", *head, st, ws, wb, stream=stream)
             out = ws[:n_pass_sums(C, D) * 8].view(torch.float64).clone()
         return out if _is_tensor(X) else out.cpu().numpy()
 
@@ -550,9 +546,7 @@ class DeviceLogisticRegression:
                    "proba": torch.empty(n, C, **f64) if "proba" in want else None,
                    "pred": torch.empty(n, dtype=torch.int64, device=rows.dev) if "pred" in want else None,
                    "p_fault": torch.empty(n, **f64) if "p_fault" in want else None}
-            _lib.check(lib.pinn_lr_posterior(*rows.head(), C, _ptr(model), int(normal_class), _ptr(out["decision"]), _ptr(out["proba"]),
-                                             _ptr(out["pred"]), _ptr(out["p_fault"]), torch.cuda.current_stream().cuda_stream),
-                       "pinn_lr_posterior")
+            call("pinn_lr_posterior", *rows.head(), C, model, int(normal_class), out["decision"], out["proba"], out["pred"], out["p_fault"])
         if not _is_tensor(X):
             return {k: out[k].cpu().numpy() for k in want}
         return {k: out[k] for k in want}
@@ -707,8 +701,7 @@ def roc_counts(y_true, y_score, pos_label=None, drop_intermediate=True, backend=
         i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
         bufs = [torch.empty(n + 1, **i64), torch.empty(n + 1, **i64), torch.empty(n + 1, **f64), torch.empty(n + 1, **f64),
                 torch.empty(n + 1, **f64)] if curve else [None] * 5
-        _lib.check(lib.pinn_lr_roc(_ptr(s_sorted), _ptr(pos_sorted), n, int(bool(drop_intermediate)), _ptr(counts), *[_ptr(b) for b in bufs],
-                                   _ptr(ws), wb, torch.cuda.current_stream().cuda_stream), "pinn_lr_roc")
+        call("pinn_lr_roc", s_sorted, pos_sorted, n, int(bool(drop_intermediate)), counts, *bufs, ws, wb)
         c = counts.cpu().numpy()
     out = {"n_pos": int(c[0]), "n_neg": int(c[1]), "n_distinct": int(c[2]), "U2": int(c[4])}
     if not curve:
@@ -883,7 +876,7 @@ class FaultDetector:
         self.pipeline, self.normal_class, self.backend = pipeline, int(normal_class), backend
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            self.columns = parse_features(features) if isinstance(features, str) else [int(c) for c in features]
+            self.columns = columns_of(features, parse_features)
         self.n_seen = 0
 
     def update(self, rows):

@@ -12,13 +12,13 @@ pass plus a one-workgroup M-step, iterations run without a host synchronisation 
 numpy with scikit-learn's formulas, for machines without a GPU and as the referee of the device tests.  Importing this
 module needs numpy only; scikit-learn is never imported.
 """
-import ctypes
 import re
 
 import numpy as np
 
-from .risk import (AUTO_DEVICE_ROWS, FAULT_ALIASES, INDEX, _as_numpy, _dev_f64_rows, _dev_vec, _gpu_present, _is_tensor,  # noqa: F401
-                   _on_gpu, _pick_backend, _ptr, _torch_lib)
+from ._device import (_DevRows, _as_numpy, _dev_f64_rows, _dev_vec, _host_rows, _is_tensor, _on_gpu, _pick_backend, _torch_lib,  # noqa: F401
+                      call, columns_of)
+from .risk import FAULT_ALIASES, INDEX
 
 DEFAULT_GROUP_SPEC = "flooding:1,2,3,|oxygen_starvation:4,5,6,|membrane_drying:7,8,9,|hydrogen_starvation:10,11,12"
 DEFAULT_FEATURES = "pV,pT,pH,pO"
@@ -162,17 +162,6 @@ def classification_metrics(y_true, y_pred, n_classes):
 
 
 # ---------------------------------------------------------------------------------------------- host backend
-def _host_rows(X, columns=None, row_index=None):
-    a = _as_numpy(X)
-    if a.ndim != 2:
-        raise ValueError("X must be a 2-D array")
-    if row_index is not None:
-        a = a[_as_numpy(row_index, np.int64)]
-    if columns is not None:
-        a = a[:, list(columns)]
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
 def _host_factor(cov):
     """precisions_cholesky (upper triangular, cov = L L^T, U = L^-T) of every covariance; ValueError when one is not
     positive definite."""
@@ -269,31 +258,6 @@ def _upper_factor(P):
 
 
 # ---------------------------------------------------------------------------------------------- device backend
-class _DevRows:
-    """Rows of a float64 device array read in place: column list and optional gather list."""
-
-    def __init__(self, torch, X, columns=None, row_index=None):
-        self.arr = _dev_f64_rows(torch, X)
-        self.dev = self.arr.device
-        cols = list(range(self.arr.shape[1])) if columns is None else [int(c) for c in columns]
-        if not 1 <= len(cols) <= MAX_FEAT:
-            raise ValueError("the device backend takes 1 to %d features, got %d" % (MAX_FEAT, len(cols)))
-        if cols and (min(cols) < 0 or max(cols) >= self.arr.shape[1]):
-            raise ValueError("X has %d columns, column %d is asked for" % (self.arr.shape[1], max(cols)))
-        self.cols, self.D = cols, len(cols)
-        self.c_cols = (ctypes.c_int * self.D)(*cols)
-        self.ridx = _dev_vec(torch, row_index, torch.int64, self.dev)
-        self.n = self.arr.shape[0] if self.ridx is None else self.ridx.numel()
-        self.ld = self.arr.stride(0) if self.arr.shape[0] > 1 else max(self.arr.shape[1], 1)
-
-    def head(self):
-        return (_ptr(self.arr), self.ld, self.arr.shape[0], self.c_cols, self.D, _ptr(self.ridx), self.n)
-
-    def packed(self, torch):
-        a = self.arr if self.ridx is None else self.arr[self.ridx]
-        return a[:, self.cols].contiguous()
-
-
 def _state_words(K, D):
     return _HDR + K * (2 + D + 2 * D * D)
 
@@ -480,8 +444,7 @@ class DeviceGMM:
             elif not self._given():
                 lab = self._device_own_labels(torch, _lib, lib, rows, ws, wb, stream)
             if resp is not None or lab is not None:
-                _lib.check(lib.pinn_gmm_mstep_init(*rows.head(), K, _ptr(resp), _ptr(lab), self.reg_covar, _ptr(self._state),
-                                                   _ptr(ws), wb, stream), "pinn_gmm_mstep_init")
+                call("pinn_gmm_mstep_init", *rows.head(), K, resp, lab, self.reg_covar, self._state, ws, wb, stream=stream)
                 if self.resp_init is None and self.labels_init is None and (self.weights_init is not None or self.means_init is not None):
                     p = self._read_state(D)
                     w = p["weights"] if self.weights_init is None else _as_numpy(self.weights_init)
@@ -517,7 +480,7 @@ class DeviceGMM:
         centres = Xp[torch.tensor(picks, device=rows.dev)].cpu().numpy()
         km = torch.from_numpy(_pack_state(K, D, None, centres, None, None)).to(rows.dev)
         lab = torch.empty(n, dtype=torch.int64, device=rows.dev)
-        _lib.check(lib.pinn_gmm_kmeans(*rows.head(), K, self.kmeans_iter, _ptr(km), _ptr(lab), _ptr(ws), wb, stream), "pinn_gmm_kmeans")
+        call("pinn_gmm_kmeans", *rows.head(), K, self.kmeans_iter, km, lab, ws, wb, stream=stream)
         self.kmeans_centres_ = km[_HDR + K:_HDR + K + K * D].reshape(K, D)
         return lab
 
@@ -527,8 +490,7 @@ class DeviceGMM:
         while True:
             step = min(self.em_chunk, n_iters - done)
             if step > 0:
-                _lib.check(lib.pinn_gmm_em(*rows.head(), K, step, self.tol, self.reg_covar, _ptr(self._state), _ptr(ws), wb, stream),
-                           "pinn_gmm_em")
+                call("pinn_gmm_em", *rows.head(), K, step, self.tol, self.reg_covar, self._state, ws, wb, stream=stream)
                 done += step
             p = self._read_state(D)
             if p["converged"] or done >= n_iters:
@@ -635,9 +597,7 @@ class DeviceGMM:
                    "y_pred": torch.empty(n, dtype=torch.int64, device=rows.dev) if "y_pred" in want else None}
             if (out["y_prob"] is not None or out["y_pred"] is not None) and cm is None:
                 raise ValueError("y_prob and y_pred need comp_fault_prob")
-            _lib.check(lib.pinn_gmm_posterior(*rows.head(), K, _ptr(st), _ptr(cm), C, _ptr(out["log_prob_norm"]), _ptr(out["resp"]),
-                                              _ptr(out["y_prob"]), _ptr(out["y_pred"]), torch.cuda.current_stream().cuda_stream),
-                       "pinn_gmm_posterior")
+            call("pinn_gmm_posterior", *rows.head(), K, st, cm, C, out["log_prob_norm"], out["resp"], out["y_prob"], out["y_pred"])
         if not _is_tensor(X):
             return {k: out[k].cpu().numpy() for k in want}
         return {k: out[k] for k in want}
@@ -680,8 +640,7 @@ class DeviceGMM:
                 raise ValueError("y must hold one class per row")
             ws, wb = self._ws(torch, lib, rows)
             out = torch.empty(K, C, dtype=torch.float64, device=rows.dev)
-            _lib.check(lib.pinn_gmm_label_map(*rows.head(), K, _ptr(st), _ptr(cls), C, _ptr(out), _ptr(ws), wb,
-                                              torch.cuda.current_stream().cuda_stream), "pinn_gmm_label_map")
+            call("pinn_gmm_label_map", *rows.head(), K, st, cls, C, out, ws, wb)
         return out if _is_tensor(X) else out.cpu().numpy()
 
     def diagnose(self, X, comp_fault_prob, columns=None, row_index=None):
@@ -711,7 +670,7 @@ class FaultDiagnoser:
     def __init__(self, gmm, comp_fault_prob, features=DEFAULT_FEATURES, backend="auto"):
         gmm._check_fitted()
         self.gmm, self.comp_fault_prob = gmm, comp_fault_prob
-        self.columns = parse_features(features) if isinstance(features, str) else [int(c) for c in features]
+        self.columns = columns_of(features, parse_features)
         self.backend = backend
         self.n_seen = 0
 

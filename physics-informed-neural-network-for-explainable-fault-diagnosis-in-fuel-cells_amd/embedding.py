@@ -39,10 +39,13 @@ is O(n^2) numpy per iteration, minutes at a few thousand rows.
 AUTO_DEVICE_ROWS = 256 rows when a GPU is present; below that, or without a GPU, the host.  `DeviceTSNE.backend_` says which ran.
 Importing this module needs numpy only; scikit-learn is never imported.
 """
+import functools
+
 import numpy as np
 
-from .diagnosis import _DevRows, _host_rows, extract_X_y
-from .risk import _as_numpy, _dev_vec, _gpu_present, _is_tensor, _on_gpu, _ptr, _torch_lib
+from . import _device
+from ._device import _DevRows, _as_numpy, _dev_vec, _host_rows, _is_tensor, _torch_lib, call
+from .diagnosis import extract_X_y
 
 MAX_FEAT, MAX_ROWS = 8, 32768
 AUTO_DEVICE_ROWS = 256                    # backend="auto" sends a host array of at least this many rows to a present GPU
@@ -57,19 +60,7 @@ _WAVE, _FIN = 64, 1024                    # lanes of the pair pass, threads of t
 _BIG = float(np.finfo(np.float64).max)
 
 
-def _pick_backend(backend, data, n=None):
-    """The rule of backend="auto" for an O(n^2) method: a device tensor stays on the device; a host array of `n` rows (by
-    default its first dimension) goes there from AUTO_DEVICE_ROWS rows on when a GPU is present."""
-    if backend not in ("auto", "device", "host"):
-        raise ValueError("backend must be 'auto', 'device' or 'host'")
-    if backend != "auto":
-        return backend
-    if _on_gpu(data):
-        return "device"
-    if _is_tensor(data):
-        return "host"
-    n = int(_shape(data)[0]) if n is None else int(n)
-    return "device" if n >= AUTO_DEVICE_ROWS and _gpu_present() else "host"
+_pick_backend = functools.partial(_device._pick_backend, threshold=AUTO_DEVICE_ROWS)      # an O(n^2) method: far fewer rows pay
 
 
 def _shape(a):
@@ -313,8 +304,7 @@ def _dev_affinities(torch, _lib, lib, rows, perplexity):
     ws = _DevWork(torch, lib, n, rows.dev)
     beta, ent = torch.empty(n, dtype=torch.float64, device=rows.dev), torch.empty(n, dtype=torch.float64, device=rows.dev)
     status = torch.empty(n, dtype=torch.int64, device=rows.dev)
-    _lib.check(lib.pinn_tsne_affinities(*rows.head(), float(perplexity), _ptr(beta), _ptr(ent), _ptr(status), _ptr(ws.buf), ws.bytes,
-                                        torch.cuda.current_stream().cuda_stream), "pinn_tsne_affinities")
+    call("pinn_tsne_affinities", *rows.head(), float(perplexity), beta, ent, status, ws.buf, ws.bytes)
     return ws, beta, ent, status
 
 
@@ -409,8 +399,7 @@ def kl_and_gradient(P, Y, exaggeration=1.0, backend="auto"):
         ws = _DevWork(torch, lib, n, Pd.device)
         ws.P.copy_(Pd.to(torch.float64))
         Yd = _dev_vec(torch, Y, torch.float64, Pd.device)
-        _lib.check(lib.pinn_tsne_kl_grad(n, _ptr(Yd), alpha, _ptr(ws.buf), ws.bytes, torch.cuda.current_stream().cuda_stream),
-                   "pinn_tsne_kl_grad")
+        call("pinn_tsne_kl_grad", n, Yd, alpha, ws.buf, ws.bytes)
         s = ws.scal.cpu().numpy()
         out = {"grad": ws.grad.clone(), "row_sums": ws.rows.clone()}
     if not _is_tensor(P):
@@ -447,8 +436,7 @@ def descend(P, state, n_iter, *, max_iter=1000, early_exaggeration=12.0, learnin
         left = int(n_iter)
         while left > 0:
             step = min(int(chunk), left)
-            _lib.check(lib.pinn_tsne_descend(n, 0, step, args[0], args[1], args[2], args[3], args[4], _ptr(st), _ptr(ws.buf), ws.bytes,
-                                             torch.cuda.current_stream().cuda_stream), "pinn_tsne_descend")
+            call("pinn_tsne_descend", n, 0, step, args[0], args[1], args[2], args[3], args[4], st, ws.buf, ws.bytes)
             left -= step
         h = _dev_header(st)
         body = st[_HDR:].cpu().numpy().reshape(3, n, 2)
@@ -595,7 +583,7 @@ class DeviceTSNE:
             st[_HDR:_HDR + 2 * n] = Y0.reshape(-1)
             queued, init = 0, 1
             while True:
-                _lib.check(lib.pinn_tsne_descend(n, init, N_ITER_CHECK, *args, _ptr(st), _ptr(ws.buf), ws.bytes, stream), "pinn_tsne_descend")
+                call("pinn_tsne_descend", n, init, N_ITER_CHECK, *args, st, ws.buf, ws.bytes, stream=stream)
                 queued, init = queued + N_ITER_CHECK, 0
                 h = _dev_header(st)                            # one read of the header per chunk
                 if h["done"] or h["status"] or queued >= self.max_iter + N_ITER_CHECK:
@@ -605,7 +593,7 @@ class DeviceTSNE:
             if not h["done"]:
                 raise RuntimeError("the schedule did not end within max_iter = %d iterations (header %r)" % (self.max_iter, h))
             Y = st[_HDR:_HDR + 2 * n].reshape(n, 2).clone()
-            _lib.check(lib.pinn_tsne_kl_grad(n, _ptr(Y), 1.0, _ptr(ws.buf), ws.bytes, stream), "pinn_tsne_kl_grad")
+            call("pinn_tsne_kl_grad", n, Y, 1.0, ws.buf, ws.bytes, stream=stream)
             kl = float(ws.scal[2].item())
         self.embedding_ = Y if _is_tensor(X) else Y.cpu().numpy()
         self.kl_divergence_, self.n_iter_, self.learning_rate_, self.n_features_in_, self.header_ = kl, h["n_iter"], args[2], D, h

@@ -19,6 +19,8 @@ import ctypes
 
 import numpy as np
 
+from ._device import AUTO_DEVICE_ROWS, _as_numpy, _dev_f64_rows, _dev_vec, _is_tensor, _pick_backend, _torch_lib, call  # noqa: F401
+
 # column layout of the results array (results.create_comprehensive_results_array_v2)
 INDEX = {"x0": 0, "x1": 1, "x2": 2, "x3": 3, "x4": 4, "x5": 5, "x6": 6, "x7": 7,
          "y_true": 8, "y_pred": 9, "ale": 10, "epi": 11, "res": 12, "pV": 13, "pT": 14, "pH": 15, "pO": 16, "label": 17}
@@ -60,7 +62,6 @@ RF_CONDITIONS = [
     (405.0, "oxygen_starvation", None), (405.0, "membrane_drying", None), (405.0, "hydrogen_starvation", None),
 ]
 
-AUTO_DEVICE_ROWS = 50000                # backend="auto" sends a host array of at least this many rows to a present GPU
 MAX_COLS, MAX_LAYERS = 8, 4
 
 
@@ -115,40 +116,6 @@ class _Config:
 
 _PARAM_NAMES = ("res_keys", "feature_weights", "layer_config", "layer_weights", "p_layer", "z_safe", "lambda_decay",
                 "k_logistic", "C0_logistic", "C_max", "alpha_smooth", "columns")
-
-
-def _is_tensor(x):
-    return type(x).__module__.split(".")[0] == "torch"
-
-
-def _on_gpu(x):
-    return _is_tensor(x) and x.is_cuda
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except ImportError:
-        return False
-
-
-def _pick_backend(backend, data):
-    if backend not in ("auto", "device", "host"):
-        raise ValueError("backend must be 'auto', 'device' or 'host'")
-    if backend != "auto":
-        return backend
-    if _on_gpu(data):
-        return "device"
-    if not _is_tensor(data) and np.shape(data)[0] >= AUTO_DEVICE_ROWS and _gpu_present():
-        return "device"
-    return "host"
-
-
-def _as_numpy(x, dtype=None):
-    if _is_tensor(x):
-        x = x.detach().cpu().numpy()
-    return np.asarray(x) if dtype is None else np.asarray(x, dtype=dtype)
 
 
 def _fault_labels(fault_name):
@@ -235,38 +202,6 @@ def _host_first(series, threshold, mode):
 
 
 # ---------------------------------------------------------------------------------------------- device backend
-def _torch_lib():
-    import torch
-    from . import _lib
-    if not torch.cuda.is_available():
-        raise _lib.PinnError("the device backend of pinn_amd.risk needs a GPU (backend='host' runs on the CPU)")
-    return torch, _lib, _lib.load()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _dev_f64_rows(torch, data):
-    """A float64 device tensor [N, ld] with unit column stride, without a copy when `data` already is one."""
-    t = data if _is_tensor(data) else torch.from_numpy(np.ascontiguousarray(np.asarray(data, dtype=np.float64)))
-    if t.dim() != 2:
-        raise ValueError("results must be a 2-D array")
-    t = t.detach().to("cuda" if not t.is_cuda else t.device, torch.float64)
-    if t.shape[0] > 0 and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):      # a transposed or expanded view
-        t = t.contiguous()
-    return t
-
-
-def _dev_vec(torch, v, dtype, device):
-    if v is None:
-        return None
-    if _is_tensor(v):
-        return v.detach().to(device, dtype).reshape(-1).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(v).reshape(-1)).astype(
-        np.float64 if dtype == torch.float64 else np.int64)).to(device)
-
-
 def _device_stats(arr, cols, label_col, normal_labels):
     torch, _lib, lib = _torch_lib()
     D = len(cols)
@@ -279,9 +214,7 @@ def _device_stats(arr, cols, label_col, normal_labels):
         c_cols = (ctypes.c_int * D)(*cols)
         c_norm = (ctypes.c_longlong * len(normal_labels))(*[int(v) for v in normal_labels])
         ld = arr.stride(0) if arr.shape[0] > 0 else arr.shape[1]
-        rc = lib.pinn_rf_stats(_ptr(arr), ld, arr.shape[0], c_cols, D, label_col, c_norm, len(normal_labels), _ptr(out[0]),
-                               _ptr(out[1]), _ptr(count), _ptr(ws), ws.numel(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "pinn_rf_stats")
+        call("pinn_rf_stats", arr, ld, arr.shape[0], c_cols, D, label_col, c_norm, len(normal_labels), out[0], out[1], count, ws, ws.numel())
         if int(count[MAX_COLS].item()) == 0:
             raise ValueError("no rows carry a normal label %s" % (tuple(normal_labels),))
     return out[0, :D], out[1, :D]
@@ -317,11 +250,8 @@ def _device_series(arr, mu, sigma, cfg, row_index=None, seg_starts=None, carry_i
         wb = lib.pinn_rf_workspace_bytes(n, n_seg)
         ws = torch.empty(wb, dtype=torch.uint8, device=dev) if wb else None
         ld = arr.stride(0) if arr.shape[0] > 0 else max(arr.shape[1], 1)
-        rc = lib.pinn_rf_series(_ptr(arr), ld, arr.shape[0], ctypes.byref(prm), _ptr(mu_d), _ptr(sg_d), _ptr(ridx), n,
-                                _ptr(seg), 0 if seg is None else n_seg, _ptr(cin), _ptr(layers), _ptr(out["S_tot"]), _ptr(out["C"]),
-                                _ptr(out["RF_inst"]), _ptr(out["RF_smooth"]), _ptr(cout), _ptr(ws), wb,
-                                torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "pinn_rf_series")
+        call("pinn_rf_series", arr, ld, arr.shape[0], ctypes.byref(prm), mu_d, sg_d, ridx, n, seg, 0 if seg is None else n_seg, cin, layers,
+             out["S_tot"], out["C"], out["RF_inst"], out["RF_smooth"], cout, ws, wb)
     res = {k: v for k, v in out.items() if v is not None}
     if layers is not None:
         res["S_layers"] = {name: layers[i] for i, name in enumerate(cfg.layer_names)}
@@ -343,10 +273,8 @@ def _device_first(series, threshold, mode, stride=1, n_src=None, row_index=None,
         n_src = series.numel() if n_src is None else n_src
         n = n_src if ridx is None else ridx.numel()
         first = torch.empty(1 if seg is None else seg.numel(), dtype=torch.int64, device=dev)
-        rc = lib.pinn_rf_first_alarm(_ptr(series), stride, n_src, _ptr(ridx), n, _ptr(seg), 0 if seg is None else seg.numel(),
-                                     _lib.RF_ABOVE if mode == "above" else _lib.RF_BELOW, 1 if relative else 0, float(threshold),
-                                     _ptr(first), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "pinn_rf_first_alarm")
+        call("pinn_rf_first_alarm", series, stride, n_src, ridx, n, seg, 0 if seg is None else seg.numel(),
+             _lib.RF_ABOVE if mode == "above" else _lib.RF_BELOW, 1 if relative else 0, float(threshold), first)
     return first
 
 

@@ -21,9 +21,9 @@ import warnings
 
 import numpy as np
 
+from ._device import _DevRows, _as_numpy, _dev_vec, _host_rows, _is_tensor, _pick_backend, _torch_lib, call, columns_of
 from .detection import DeviceLogisticRegression, DeviceStandardScaler
-from .diagnosis import DEFAULT_FEATURES, _DevRows, _host_rows, parse_features
-from .risk import _as_numpy, _dev_vec, _is_tensor, _pick_backend, _ptr, _torch_lib
+from .diagnosis import DEFAULT_FEATURES, parse_features
 
 # limits, status words and the 8-byte words of the state block: one copy, next to the bindings (include/pinn_hip.h)
 from ._lib import (SVM_MAX_CLASSES as MAX_CLASSES, SVM_MAX_FEAT as MAX_FEAT, SVM_NAN, SVM_P_A as _P_A, SVM_P_B as _P_B, SVM_P_BETA as _P_BETA,
@@ -390,11 +390,11 @@ class DeviceLinearSVC:
             wb = lib.pinn_svm_workspace_bytes(n, C, D)
             ws = torch.empty(wb, dtype=torch.uint8, device=rows.dev)
             stream = torch.cuda.current_stream().cuda_stream
-            head = rows.head() + (_ptr(yi), C)
+            head = rows.head() + (yi, C)
             done, init, limit = 0, 1, self._limit()
             while True:
                 step = min(self.chunk, limit - done)
-                _lib.check(lib.pinn_svm_ipm(*head, init, step, self.gap_tol, _ptr(st), _ptr(ws), wb, stream), "pinn_svm_ipm")
+                call("pinn_svm_ipm", *head, init, step, self.gap_tol, st, ws, wb, stream=stream)
                 done, init = done + step, 0
                 h = st[:_HDR + P * _PW].cpu().numpy()              # one read of the header and the pair blocks per chunk
                 hi = h.view(np.int64)
@@ -452,7 +452,7 @@ class DeviceLinearSVC:
             wb = lib.pinn_svm_workspace_bytes(n, C, D)
             ws = torch.empty(wb, dtype=torch.uint8, device=rows.dev)
             yi = torch.from_numpy(yh).to(rows.dev)
-            _lib.check(lib.pinn_svm_pass(*rows.head(), _ptr(yi), C, _ptr(st), _ptr(ws), wb, torch.cuda.current_stream().cuda_stream), "pinn_svm_pass")
+            call("pinn_svm_pass", *rows.head(), yi, C, st, ws, wb)
             out = ws[:P * n_pass_sums(D) * 8].view(torch.float64).reshape(P, n_pass_sums(D)).clone()
         return out if _is_tensor(X) else out.cpu().numpy()
 
@@ -487,8 +487,7 @@ class DeviceLinearSVC:
             out = {"decision": torch.empty(n, P, dtype=torch.float64, device=rows.dev) if "decision" in want else None,
                    "votes": torch.empty(n, C, dtype=torch.int64, device=rows.dev) if "votes" in want else None,
                    "pred": torch.empty(n, dtype=torch.int64, device=rows.dev) if "pred" in want else None}
-            _lib.check(lib.pinn_svm_decision(*rows.head(), C, _ptr(model), _ptr(out["decision"]), _ptr(out["votes"]), _ptr(out["pred"]),
-                                             torch.cuda.current_stream().cuda_stream), "pinn_svm_decision")
+            call("pinn_svm_decision", *rows.head(), C, model, out["decision"], out["votes"], out["pred"])
         if not _is_tensor(X):
             return {k: out[k].cpu().numpy() for k in want}
         return {k: out[k] for k in want}
@@ -554,7 +553,7 @@ class SVMDiagnoser:
     def __init__(self, pipeline, features=DEFAULT_FEATURES):
         pipeline.named_steps["svc"]._check_fitted()
         self.pipeline = pipeline
-        self.columns = parse_features(features) if isinstance(features, str) else [int(c) for c in features]
+        self.columns = columns_of(features, parse_features)
         self.n_seen = 0
 
     def update(self, rows):

@@ -396,14 +396,14 @@ def test_auto_backend_rule(G, E, monkeypatch):
     assert E.AUTO_DEVICE_ROWS == 256 and E.AUTO_DEVICE_ROWS <= E.MAX_ROWS
     small, large = np.zeros((255, 4)), np.zeros((256, 4))
     for present, want in ((True, "device"), (False, "host")):
-        monkeypatch.setattr(E, "_gpu_present", lambda: present)
+        monkeypatch.setattr(E._device, "_gpu_present", lambda: present)
         assert E._pick_backend("auto", small) == "host" and E._pick_backend("auto", large) == want
         assert E._pick_backend("auto", np.zeros((9000, 22)), 100) == "host"        # rows picked by a gather list count
         assert E._pick_backend("auto", np.zeros((100, 22)), 300) == want
         assert E._pick_backend("host", large) == "host" and E._pick_backend("device", small) == "device"
     with pytest.raises(ValueError):
         E._pick_backend("gpu", large)
-    monkeypatch.setattr(E, "_gpu_present", lambda: False)
+    monkeypatch.setattr(E._device, "_gpu_present", lambda: False)
     m = E.DeviceTSNE(perplexity=20, n_iter=250, init="random", random_state=1).fit(G["X"][:65])
     assert m.backend == "auto" and m.backend_ == "host"
 

@@ -55,8 +55,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="skip the largest size of every group")
     args = ap.parse_args()
     from pinn_amd import _lib, comparison as P
-    from pinn_amd.diagnosis import _DevRows
-    from pinn_amd.risk import _ptr
+    from pinn_amd._device import _DevRows, _ptr
     lib = _lib.load()
     stream = torch.cuda.current_stream().cuda_stream
 

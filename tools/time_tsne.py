@@ -63,8 +63,7 @@ def main():
     args = ap.parse_args()
     import torch
     from pinn_amd import _lib, embedding as E
-    from pinn_amd.diagnosis import _DevRows
-    from pinn_amd.risk import _ptr
+    from pinn_amd._device import _DevRows, _ptr
     if not torch.cuda.is_available():
         sys.exit("time_tsne.py needs a GPU")
     lib = _lib.load()
