@@ -9,17 +9,6 @@ struct PackJobs {
   int n;
 };
 
-static int cu_count_b() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 __global__ __launch_bounds__(256) void pack_bf16_all(const float* __restrict__ params, __bf16* __restrict__ packed, PackJobs jobs) {
   const PackJob j = jobs.j[blockIdx.y];
   const long long n = (long long)j.rows * j.Kp;
@@ -117,7 +106,7 @@ int launch_forward_bf16(const pinn_net_t* net, const FwdArgs& a, bool mc, void* 
   (void)hipGetLastError();
   launch_pack(net, a.params, st);
   const long long n_tiles = (a.n_rows + kTileRows - 1) / kTileRows;
-  const int grid = (int)(n_tiles < 2 * cu_count_b() ? n_tiles : 2 * cu_count_b());
+  const int grid = (int)(n_tiles < 2 * cu_count_cached() ? n_tiles : 2 * cu_count_cached());
   const float* packed = (const float*)net->d_packed;
   const bool bits = a.drop.mode == PINN_DROP_BITS;
 #define PINN_LAUNCH_B(HH, MCC, BB) hipLaunchKernelGGL((mlp_bf16_kernel<HH, MCC, BB>), dim3(grid), dim3(kThreads), 0, st, a, packed)
@@ -504,15 +493,12 @@ static int dispatch_wgrad_b(const WgradArgsB& a, hipStream_t st) {
 
 // chain + weight-gradient launches of one bf16 training step (the fp32 finalize kernel is shared)
 int launch_train_bf16(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
-                      long long n_global, const DropDev& drop, const TrainBuffers& b, unsigned phases, int* grid_out, void* stream) {
+                      long long n_global, const DropDev& drop, const TrainBuffers& b, unsigned phases, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int H = net->hidden, nh = net->n_hidden;
   ParamLayout L{H, nh};
-  const long long n_tiles = (n_rows + kTileRows - 1) / kTileRows;
-  int grid = (int)(n_tiles < 2 * cu_count_b() ? n_tiles : 2 * cu_count_b());
-  if (grid > 1024) grid = 1024;
-  *grid_out = grid;
   if (phases & PINN_PHASE_CHAIN) {
+    const int grid = train_chain_partials(n_rows);
     launch_pack(net, d_params, st);
     TrainArgsB a{};
     a.params = d_params; a.packed = (const float*)net->d_packed; a.x = d_x; a.y = d_y; a.n_rows = n_rows; a.n_global = n_global;
@@ -556,24 +542,26 @@ using namespace pinn;
 
 namespace pinn { size_t wide_scratch_floats(int H); }   // pinn_wide.hip
 
+// the nets whose d_packed the x6 pack kernel fills (shape checked by the caller): they end it with the range record
+static bool has_range_record(const pinn_net_t* net) {
+  if (net_is_wide(net)) return net->precision != PINN_PREC_FP32;
+  return net->precision == PINN_PREC_F32X6 || net->precision == PINN_PREC_F32X6_G6;
+}
+
 extern "C" size_t pinn_packed_bytes(const pinn_net_t* net) {
-  if (!net || net->n_in != 8 || net->n_hidden < 1 || net->n_hidden > 8) return 0;
-  const bool wide = net->hidden == 512 || net->hidden == 1024 || net->hidden == 2048;
-  if (net->hidden != 128 && net->hidden != 256 && !wide) return 0;
+  if (!net || !net_shape_ok(net)) return 0;
   PackLayout K{net->hidden, net->n_hidden};
-  // wide nets: the three copies + the activation scratch of one row chunk (layer-by-layer kernels)
-  // (+ kRangeStatusBytes at the very end of every buffer the x6 pack kernel fills: pinn_net_range_status's record)
-  if (wide) return net->precision != PINN_PREC_FP32 ? (size_t)K.total() * 2 * 5 + pinn::wide_scratch_floats(net->hidden) * 4 + pinn::kRangeStatusBytes : 0;
-  if (net->precision == PINN_PREC_BF16) return (size_t)K.total() * 2;
   // three bf16 copies (hi, mid, lo: backward pass, weight gradients) + two fp16 copies of the forward matrices (scheme X3)
-  if (net->precision == PINN_PREC_F32X6 || net->precision == PINN_PREC_F32X6_G6) return (size_t)K.total() * 2 * 5 + pinn::kRangeStatusBytes;
-  return 0;
+  // + kRangeStatusBytes at the very end of every buffer the x6 pack kernel fills: pinn_net_range_status's record
+  if (has_range_record(net))      // (wide nets: + the activation scratch of one row chunk of the layer-by-layer kernels)
+    return (size_t)K.total() * 2 * 5 + (net_is_wide(net) ? pinn::wide_scratch_floats(net->hidden) * 4 : 0) + pinn::kRangeStatusBytes;
+  return net->precision == PINN_PREC_BF16 ? (size_t)K.total() * 2 : 0;
 }
 
 namespace pinn {
 unsigned* range_status_words(const pinn_net_t* net) {
-  const size_t n = pinn_packed_bytes(net);
-  return (n >= kRangeStatusBytes && net->d_packed) ? (unsigned*)((char*)net->d_packed + n - kRangeStatusBytes) : nullptr;
+  const size_t n = pinn_packed_bytes(net);      // (0: no net, or a shape without kernels)
+  return (n && has_range_record(net) && net->d_packed) ? (unsigned*)((char*)net->d_packed + n - kRangeStatusBytes) : nullptr;
 }
 }  // namespace pinn
 

@@ -203,14 +203,8 @@ static int convert(const Shape& s, const pinn_dropout_t* in, Drop* d) {
   d->mode = in->mode;
   d->row_offset = in->row_offset;
   if (in->mode == PINN_DROP_NONE) return PINN_OK;
-  for (int l = 0; l <= s.k; ++l) {
-    const float p = in->p[l];
-    if (!(p >= 0.0f && p < 1.0f)) return PINN_E_ARG;
-    double t = floor((double)p * 65536.0 + 0.5);
-    if (p > 0.0f && t < 1.0) t = 1.0;
-    d->thr[l] = (unsigned)(t < 0 ? 0 : (t > 65536.0 ? 65536.0 : t));
-    d->scale[l] = 1.0f / (float)(1.0 - (double)p);
-  }
+  for (int l = 0; l <= s.k; ++l)
+    if (!drop_rate(in->p[l], &d->thr[l], &d->scale[l])) return PINN_E_ARG;
   d->seed_lo = (unsigned)(in->seed & 0xFFFFFFFFull);
   d->seed_hi = (unsigned)(in->seed >> 32);
   d->stream = in->stream;

@@ -70,58 +70,6 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_kernel(FwdArgs a) {
   }
 }
 
-static int convert_drop(const pinn_net_t* net, const pinn_dropout_t* in, DropDev* out) {
-  out->mode = PINN_DROP_NONE;
-  out->bits = nullptr; out->words = 0; out->nb = net->hidden / 32;
-  out->seed_lo = out->seed_hi = 0; out->stream = 0; out->row_offset = 0; out->step_counter = nullptr;
-  for (int l = 0; l < kMaxDrop; ++l) { out->thr[l] = 0; out->scale[l] = 1.0f; }
-  if (!in) return PINN_OK;
-  if (in->mode < PINN_DROP_NONE || in->mode > PINN_DROP_BITS) return PINN_E_ARG;
-  out->mode = in->mode;
-  out->row_offset = in->row_offset;
-  if (in->mode == PINN_DROP_NONE) return PINN_OK;
-  for (int l = 0; l <= net->n_hidden; ++l) {
-    const float p = in->p[l];
-    if (!(p >= 0.0f && p < 1.0f)) return PINN_E_ARG;
-    double t = floor((double)p * 65536.0 + 0.5);
-    if (p > 0.0f && t < 1.0) t = 1.0;      // a positive p never rounds to "no dropout"
-    out->thr[l] = (unsigned)(t < 0 ? 0 : (t > 65536.0 ? 65536.0 : t));
-    out->scale[l] = 1.0f / (float)(1.0 - (double)p);
-  }
-  out->seed_lo = (unsigned)(in->seed & 0xFFFFFFFFull);
-  out->seed_hi = (unsigned)(in->seed >> 32);
-  out->stream = in->stream;
-  if (in->mode == PINN_DROP_BITS) {
-    if (!in->d_bits) return PINN_E_ARG;
-    out->bits = in->d_bits;
-    out->words = net->n_hidden * (net->hidden / 32) + net->hidden / 64;
-  }
-  return PINN_OK;
-}
-
-static int check_net(const pinn_net_t* net) {
-  if (!net) return PINN_E_ARG;
-  if (net->n_in != 8) return PINN_E_ARCH;
-  const bool wide = net->hidden == 512 || net->hidden == 1024 || net->hidden == 2048;    // layer-by-layer kernels (pinn_wide.hip)
-  if (net->hidden != 128 && net->hidden != 256 && !wide) return PINN_E_ARCH;
-  if (net->n_hidden < 1 || net->n_hidden > 8) return PINN_E_ARCH;
-  if (net->precision < PINN_PREC_FP32 || net->precision > PINN_PREC_F32X6_G6) return PINN_E_ARG;
-  if (wide && net->precision == PINN_PREC_FP32) return PINN_E_ARCH;                      // split-operand or bf16 arithmetic only
-  if (net->precision != PINN_PREC_FP32 && !net->d_packed) return PINN_E_ARG;
-  return PINN_OK;
-}
-
-static int num_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 int launch_forward_bf16(const pinn_net_t* net, const FwdArgs& a, bool mc, void* stream);   // pinn_bf16.hip
 int launch_forward_x6(const pinn_net_t* net, const FwdArgs& a, bool mc, void* stream);     // pinn_x6.hip
 int launch_forward_wide(const pinn_net_t* net, const FwdArgs& a, bool mc, void* stream);   // pinn_wide.hip
@@ -133,7 +81,7 @@ static int launch(const pinn_net_t* net, const FwdArgs& a, void* stream) {
   if (net->hidden > 256) return launch_forward_wide(net, a, MC, stream);
   if (net->precision == PINN_PREC_BF16) return launch_forward_bf16(net, a, MC, stream);
   if (net->precision >= PINN_PREC_F32X6) return launch_forward_x6(net, a, MC, stream);
-  const int grid = (int)(n_tiles < 2 * num_cus() ? n_tiles : 2 * num_cus());
+  const int grid = (int)(n_tiles < 2 * cu_count_cached() ? n_tiles : 2 * cu_count_cached());
   (void)hipGetLastError();   // drop a stale error left by another HIP user of this thread
   const bool bits = a.drop.mode == PINN_DROP_BITS;
   if (net->hidden == 256) {
@@ -154,8 +102,7 @@ using namespace pinn;
 extern "C" long long pinn_param_count(const pinn_net_t* net) {
   // the shape alone decides (precision / d_packed are not needed to size the parameter buffer)
   if (!net) return PINN_E_ARG;
-  const bool wide = net->hidden == 512 || net->hidden == 1024 || net->hidden == 2048;
-  if (net->n_in != 8 || (net->hidden != 128 && net->hidden != 256 && !wide) || net->n_hidden < 1 || net->n_hidden > 8) return PINN_E_ARCH;
+  if (!net_shape_ok(net)) return PINN_E_ARCH;
   ParamLayout L{net->hidden, net->n_hidden};
   return L.total();
 }
@@ -169,7 +116,7 @@ extern "C" int pinn_mlp_forward(const pinn_net_t* net, const float* d_params, co
   if (!d_x || !d_u || !d_logvar) return PINN_E_ARG;
   FwdArgs a{};
   a.params = d_params; a.x = d_x; a.n_rows = n_rows; a.H = net->hidden; a.nh = net->n_hidden;
-  rc = convert_drop(net, drop, &a.drop);
+  rc = convert_drop(net, drop, false, &a.drop);
   if (rc) return rc;
   a.n_passes = 1; a.o0 = d_u; a.o1 = d_logvar; a.o2 = nullptr;
   return launch<false>(net, a, stream);
@@ -186,7 +133,7 @@ extern "C" int pinn_mc_dropout(const pinn_net_t* net, const float* d_params, con
   if (drop->mode == PINN_DROP_NONE) return PINN_E_ARG;
   FwdArgs a{};
   a.params = d_params; a.x = d_x; a.n_rows = n_rows; a.H = net->hidden; a.nh = net->n_hidden;
-  rc = convert_drop(net, drop, &a.drop);
+  rc = convert_drop(net, drop, false, &a.drop);
   if (rc) return rc;
   a.n_passes = n_passes; a.o0 = d_pred_mean; a.o1 = d_a_u; a.o2 = d_e_u;
   return launch<true>(net, a, stream);

@@ -433,6 +433,68 @@ static inline int cu_count_cached() {
   return cached[dev];
 }
 
+// ---------------------------------------------------------------------------------------
+// host-side decisions every kernel family shares: each is stated here and nowhere else
+// ---------------------------------------------------------------------------------------
+static inline bool net_is_wide(const pinn_net_t* net) {      // layer-by-layer kernels (pinn_wide.hip)
+  return net->hidden == 512 || net->hidden == 1024 || net->hidden == 2048;
+}
+// the shapes the kernels are built for; it alone sizes the parameter buffer (pinn_param_count, pinn_packed_bytes)
+static inline bool net_shape_ok(const pinn_net_t* net) {
+  return net->n_in == 8 && (net->hidden == 128 || net->hidden == 256 || net_is_wide(net)) && net->n_hidden >= 1 && net->n_hidden <= 8;
+}
+static inline int check_net(const pinn_net_t* net) {
+  if (!net) return PINN_E_ARG;
+  if (!net_shape_ok(net)) return PINN_E_ARCH;
+  if (net->precision < PINN_PREC_FP32 || net->precision > PINN_PREC_F32X6_G6) return PINN_E_ARG;
+  if (net_is_wide(net) && net->precision == PINN_PREC_FP32) return PINN_E_ARCH;      // split-operand or bf16 arithmetic only
+  if (net->precision != PINN_PREC_FP32 && !net->d_packed) return PINN_E_ARG;
+  return PINN_OK;
+}
+
+// dropout rate p in [0, 1) -> the 16-bit drop threshold round(65536 p) and the float32 scale 1 / (1 - p); false outside
+static inline bool drop_rate(float p, unsigned* thr, float* scale) {
+  if (!(p >= 0.0f && p < 1.0f)) return false;
+  double t = floor((double)p * 65536.0 + 0.5);
+  if (p > 0.0f && t < 1.0) t = 1.0;      // a positive p never rounds to "no dropout"
+  *thr = (unsigned)(t > 65536.0 ? 65536.0 : t);
+  *scale = 1.0f / (float)(1.0 - (double)p);
+  return true;
+}
+
+// pinn_dropout_t -> DropDev.  train: a training call, which carries d_step_counter (the forward entry points ignore it)
+static inline int convert_drop(const pinn_net_t* net, const pinn_dropout_t* in, bool train, DropDev* out) {
+  out->mode = PINN_DROP_NONE;
+  out->bits = nullptr; out->words = 0; out->nb = net->hidden / 32;
+  out->seed_lo = out->seed_hi = 0; out->stream = 0; out->row_offset = 0; out->step_counter = nullptr;
+  for (int l = 0; l < kMaxDrop; ++l) { out->thr[l] = 0; out->scale[l] = 1.0f; }
+  if (!in) return PINN_OK;
+  if (in->mode < PINN_DROP_NONE || in->mode > PINN_DROP_BITS) return PINN_E_ARG;
+  if (train && in->d_step_counter && net->hidden > 256) return PINN_E_ARCH;      // the layer-by-layer kernels take their pass index by value
+  out->mode = in->mode;
+  out->row_offset = in->row_offset;
+  if (train) out->step_counter = in->d_step_counter;
+  if (in->mode == PINN_DROP_NONE) return PINN_OK;
+  for (int l = 0; l <= net->n_hidden; ++l)
+    if (!drop_rate(in->p[l], &out->thr[l], &out->scale[l])) return PINN_E_ARG;
+  out->seed_lo = (unsigned)(in->seed & 0xFFFFFFFFull);
+  out->seed_hi = (unsigned)(in->seed >> 32);
+  out->stream = in->stream;
+  if (in->mode == PINN_DROP_BITS) {
+    if (!in->d_bits) return PINN_E_ARG;
+    out->bits = in->d_bits;
+    out->words = net->n_hidden * (net->hidden / 32) + net->hidden / 64;
+  }
+  return PINN_OK;
+}
+
+// loss partials of the fused fp32 and bf16 training chains (train_chain_kernel, train_chain_bf16_kernel) = their workgroups
+static inline int train_chain_partials(long long n_rows) {
+  const long long n_tiles = (n_rows + kTileRows - 1) / kTileRows;
+  const int grid = (int)(n_tiles < 2 * cu_count_cached() ? n_tiles : 2 * cu_count_cached());
+  return grid > 1024 ? 1024 : grid;
+}
+
 // Running moments of the MC-dropout passes (01:1486, np.var with ddof = 0): Welford's update on du = u_t - u_eval.
 // The one-pass form E[du^2] - E[du]^2 cancels when the passes nearly coincide (spread << |mean shift|): a row whose
 // passes differed by 1e-4 of their common offset lost all digits of e_u.  k = 1-based pass count, inv_k = 1 / k.
@@ -497,8 +559,7 @@ struct TrainBuffers {
   long long t16;
   int n_slices;
   unsigned* amax;     // PINN_PREC_F32X6: bits of max |d pre-activation| over the whole call (non-negative floats order like unsigned
-                      // integers: atomicMax, order-independent): the wide nets' fp16 weight-gradient kernels' common scale; the range
-                      // record's gradient check (pinn_net_range_status)
+                      // integers: atomicMax, order-independent): the range record's gradient check (pinn_net_range_status)
   // PINN_PREC_F32X6 on the fused nets (packed stash, pinn_x6_core.h):
   unsigned* emax;     // bits of max over rows of max(|du|, |dz|): the forward kernel's atomicMax, zeroed by the pack kernel before it
   void* rowmeta;      // [t16][256 B]: per tile the rows' scales t_r, the two fp16 parts of du_r * norm_r, dz_r (struct RowMeta)

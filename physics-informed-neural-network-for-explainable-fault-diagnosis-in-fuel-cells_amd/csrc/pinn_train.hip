@@ -550,10 +550,19 @@ struct FanOut {
 };
 static FanOut g_fan;
 
+// How the weight-gradient launches of one call are issued.  plan_workspace decides it, once, from the net and the row count; the
+// route fixes the slice count, and the launch site (launch_wgrads) reads both from the Workspace.
+enum WgradRoute {
+  kRouteSerial,     // one launch per layer on the caller's stream
+  kRouteFanOut,     // small row counts: the layers' launches are independent and short -- side by side on up to four streams
+  kRouteMulti       // PINN_PREC_F32X6 at H = 256: every layer in ONE launch of 128 x 128 tiles (wgrad_p_multi_kernel)
+};
+
 struct Workspace {
   long long t16;
   size_t off_stash_h, off_stash_v1, off_stash_v2, off_dpre_h, off_dpre_v1, off_dpre_v2, off_keep, off_du, off_dz, off_loss,
       off_amax, off_rowmeta, off_stash_x, off_slabs;
+  WgradRoute route;      // (the fused bf16 family issues its launches one after the other whatever the route: pinn_bf16.hip)
   int n_slices;
   size_t total;
 };
@@ -579,13 +588,12 @@ static Workspace plan_workspace(const pinn_net_t* net, long long n_rows) {
   w.off_rowmeta = take((size_t)w.t16 * 256);                // struct RowMeta records
   w.off_stash_x = take((size_t)w.t16 * 2048);               // packed input rows (PINN_PREC_F32X6, fused nets)
   const long long t32 = (w.t16 + 1) / 2;
+  const bool one_launch = net->precision == PINN_PREC_F32X6 && H == 256 && nh - 1 + 3 <= kMaxWgradProblems;
+  w.route = (one_launch && w.t16 < kMultiT16) ? kRouteMulti : (w.t16 < kFanOutT16 ? kRouteFanOut : kRouteSerial);
   // slices = workgroups per weight-gradient launch = slabs the reduction adds.  Large row counts: one per CU.  The reference's
   // own sizes (< 32 768 rows) are bound by the slabs instead -- at 1e4 rows 256 slices wrote 67 MB per 256 x 256 layer and the
   // reduction read 180 MB, 100 of the step's 200 us --: 64 slices there, and the five layers' launches run side by side
-  // (fan_out below), 320 workgroups in all
-  // (fan_out below), 320 workgroups in all; PINN_PREC_F32X6 at H = 256 runs them as ONE launch of 128 x 128 tiles
-  // (wgrad_p_multi_kernel): 32 slices, ~450 workgroups
-  const bool one_launch = net->precision == PINN_PREC_F32X6 && H == 256 && nh - 1 + 3 <= kMaxWgradProblems;
+  // (kRouteFanOut), 320 workgroups in all; kRouteMulti: 32 slices, ~450 workgroups
 #ifdef PINN_ABL_MULTI_NS
   constexpr long long kMultiSlices = PINN_ABL_MULTI_NS;
 #else
@@ -599,7 +607,7 @@ static Workspace plan_workspace(const pinn_net_t* net, long long n_rows) {
 #else
   const long long hb = H / 256, wide_slices = hb > 0 && 512 / (hb * hb) > 8 ? 512 / (hb * hb) : 8;
 #endif
-  const long long cap = (one_launch && w.t16 < kMultiT16) ? kMultiSlices : (w.t16 < kFanOutT16 ? 64 : (H > 256 ? wide_slices : (long long)kMaxSlices));
+  const long long cap = w.route == kRouteMulti ? kMultiSlices : (w.route == kRouteFanOut ? 64 : (H > 256 ? wide_slices : (long long)kMaxSlices));
   w.n_slices = (int)(t32 < cap ? (t32 < 1 ? 1 : t32) : cap);
   ParamLayout L{(int)H, (int)nh};
   w.off_slabs = take((size_t)w.n_slices * L.total() * 4);
@@ -615,29 +623,6 @@ static int row_scale_boost(const DropDev& d, int nh) {
     for (int l = 0; l <= nh; ++l) smax = d.scale[l] > smax ? d.scale[l] : smax;
   int c = (int)floor(log2(65504.0 / (8.0 * (double)smax)));
   return c < 0 ? 0 : (c > 12 ? 12 : c);
-}
-
-static int check_net_t(const pinn_net_t* net) {
-  if (!net) return PINN_E_ARG;
-  if (net->n_in != 8) return PINN_E_ARCH;
-  const bool wide = net->hidden == 512 || net->hidden == 1024 || net->hidden == 2048;    // layer-by-layer kernels (pinn_wide.hip)
-  if (net->hidden != 128 && net->hidden != 256 && !wide) return PINN_E_ARCH;
-  if (net->n_hidden < 1 || net->n_hidden > 8) return PINN_E_ARCH;
-  if (net->precision < PINN_PREC_FP32 || net->precision > PINN_PREC_F32X6_G6) return PINN_E_ARG;
-  if (wide && net->precision == PINN_PREC_FP32) return PINN_E_ARCH;
-  if (net->precision != PINN_PREC_FP32 && !net->d_packed) return PINN_E_ARG;
-  return PINN_OK;
-}
-
-static int cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
 }
 
 template <int TI, int TJ, int WI, int WJ, bool QX>
@@ -663,254 +648,278 @@ static int dispatch_wgrad(const WgradArgs& a, hipStream_t st) {
   return PINN_OK;
 }
 
-}  // namespace pinn
-
-namespace pinn {
+// the other families' launchers, and the loss partials their chains write for n_rows rows (one per workgroup of the kernel that
+// computes the loss: each family answers where it picks that kernel; fp32 / bf16: train_chain_partials, pinn_mlp_core.h)
 int launch_train_chain_x6(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
-                          long long n_global, const DropDev& drop, const TrainBuffers& b, unsigned which, int* grid_out,
+                          long long n_global, const DropDev& drop, const TrainBuffers& b, unsigned which,
                           void* stream);   // pinn_x6_train.hip; which: 1 = forward kernel, 2 = backward kernel, 3 = both
-int train_chain_x6_partials(const pinn_net_t* net, long long n_rows);     // pinn_x6_train.hip: the loss partials its forward writes
+int train_chain_x6_partials(const pinn_net_t* net, long long n_rows);     // pinn_x6_train.hip
 int launch_train_chain_wide(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
-                            long long n_global, const DropDev& drop, const TrainBuffers& b, int* grid_out, void* stream);  // pinn_wide.hip
+                            long long n_global, const DropDev& drop, const TrainBuffers& b, void* stream);  // pinn_wide.hip
+int train_chain_wide_partials(const pinn_net_t* net, long long n_rows);   // pinn_wide.hip
 int launch_train_bf16(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
-                      long long n_global, const DropDev& drop, const TrainBuffers& b, unsigned phases, int* grid_out, void* stream);
+                      long long n_global, const DropDev& drop, const TrainBuffers& b, unsigned phases, void* stream);
 int dispatch_wgrad_x6(const WgradArgs& a, int ns, void* stream);   // pinn_x6_wgrad.hip
-int dispatch_wgrad_p(const WgradPArgs& a, void* stream);            // pinn_x6_wgrad.hip: packed operands (PINN_PREC_F32X6, fused nets)
-int dispatch_wgrad_p_multi(const WgradPMulti& m, void* stream);     //   several of them in one launch (small row counts, H = 256)
+int dispatch_wgrad_p(const WgradPArgs& a, void* stream);            // pinn_x6_wgrad.hip: packed operands (PINN_PREC_F32X6)
+int dispatch_wgrad_p_multi(const WgradPMulti& m, void* stream);     //   several of them in one launch (kRouteMulti)
+
+// the two fused families (hidden <= 256) with kernels of their own for the whole step
+static bool fused_x6(const pinn_net_t* net) { return net->precision >= PINN_PREC_F32X6 && net->hidden <= 256; }
+static bool fused_bf16(const pinn_net_t* net) { return net->precision == PINN_PREC_BF16 && net->hidden <= 256; }
+
+static int loss_partials(const pinn_net_t* net, long long n_rows) {
+  if (net->hidden > 256) return train_chain_wide_partials(net, n_rows);
+  if (net->precision >= PINN_PREC_F32X6) return train_chain_x6_partials(net, n_rows);
+  return train_chain_partials(n_rows);
 }
+
+}  // namespace pinn
 
 using namespace pinn;
 
 extern "C" long long pinn_grad_split(const pinn_net_t* net) {
-  if (check_net_t(net) != PINN_OK) return -1;
-  if (net->precision == PINN_PREC_BF16 && net->hidden <= 256) return 0;      // the fused bf16 family launches its weight gradients as one block
+  if (check_net(net) != PINN_OK) return -1;
+  if (fused_bf16(net)) return 0;      // the fused bf16 family launches its weight gradients as one block
   ParamLayout L{net->hidden, net->n_hidden};
   return net->n_hidden >= 2 ? L.w(net->n_hidden - 1) : L.wp();
 }
 
 extern "C" size_t pinn_train_workspace_bytes(const pinn_net_t* net, long long n_rows) {
-  if (check_net_t(net) != PINN_OK || n_rows < 0) return 0;
+  if (check_net(net) != PINN_OK || n_rows < 0) return 0;
   return plan_workspace(net, n_rows).total;
+}
+
+// The phase mask as the launch steps read it.  The forward / backward halves are separate kernels only in the fused x6 path;
+// elsewhere either bit means the chain.  Two-part weight gradients / reduction (pinn_grad_split): the single-part bits mean both
+// parts; a precision whose kernels do not split keeps everything in the "tail".
+static unsigned normalize_phases(const pinn_net_t* net, unsigned phases) {
+  if (!fused_x6(net) && (phases & (PINN_PHASE_CHAIN_FWD | PINN_PHASE_CHAIN_BWD))) phases |= PINN_PHASE_CHAIN;
+  if (phases & PINN_PHASE_WGRAD) phases |= PINN_PHASE_WGRAD_TAIL | PINN_PHASE_WGRAD_HEAD;
+  if (phases & PINN_PHASE_REDUCE) phases |= PINN_PHASE_REDUCE_TAIL | PINN_PHASE_REDUCE_HEAD;
+  if (pinn_grad_split(net) == 0) {
+    phases = (phases & ~(PINN_PHASE_WGRAD | PINN_PHASE_REDUCE)) | ((phases & PINN_PHASE_WGRAD_TAIL) ? PINN_PHASE_WGRAD : 0u) |
+             ((phases & PINN_PHASE_REDUCE_TAIL) ? PINN_PHASE_REDUCE : 0u);
+  }
+  return phases;
+}
+
+// the launchers' view of the workspace
+static TrainBuffers workspace_buffers(const pinn_net_t* net, const Workspace& w, char* base, const DropDev& drop) {
+  TrainBuffers b{};
+  b.stash_h = base + w.off_stash_h; b.stash_v1 = base + w.off_stash_v1; b.stash_v2 = base + w.off_stash_v2;
+  b.dpre_h = base + w.off_dpre_h; b.dpre_v1 = base + w.off_dpre_v1; b.dpre_v2 = base + w.off_dpre_v2;
+  b.keep = (unsigned char*)(base + w.off_keep);
+  b.du = (float*)(base + w.off_du); b.dz = (float*)(base + w.off_dz);
+  b.loss_part = (double*)(base + w.off_loss);
+  b.slabs = (float*)(base + w.off_slabs); b.t16 = w.t16; b.n_slices = w.n_slices;
+  if (net->precision >= PINN_PREC_F32X6 || net->hidden > 256) {      // the split-operand chains (wide nets: also bf16-mixed)
+    b.amax = (unsigned*)(base + w.off_amax); b.emax = b.amax + 1;
+    b.rowmeta = base + w.off_rowmeta; b.qboost = row_scale_boost(drop, net->n_hidden); b.stash_x = base + w.off_stash_x;
+  }
+  return b;
+}
+
+// one training call as its three launch steps see it
+struct TrainCall {
+  const pinn_net_t* net;
+  const float* params; const float* x; const float* y;
+  long long n_rows, n_global;
+  unsigned phases;       // normalize_phases
+  DropDev drop;
+  Workspace w;
+  TrainBuffers b;
+  const unsigned* words; // the workspace's status words (Workspace::off_amax)
+  int n_partials;        // loss_partials: what the chain writes and the reduction sums, in this call or in another
+  hipStream_t st;
+};
+
+// forward + loss + backward chain
+static int launch_chain(const TrainCall& c) {
+  const pinn_net_t* net = c.net;
+  if (fused_bf16(net)) return launch_train_bf16(net, c.params, c.x, c.y, c.n_rows, c.n_global, c.drop, c.b, c.phases & PINN_PHASE_CHAIN, c.st);
+  // split-operand chain on the 16-bit matrix cores (wide nets: also bf16-mixed)
+  if (net->hidden > 256) return launch_train_chain_wide(net, c.params, c.x, c.y, c.n_rows, c.n_global, c.drop, c.b, c.st);
+  if (net->precision >= PINN_PREC_F32X6) {
+    const unsigned which = (c.phases & PINN_PHASE_CHAIN) ? 3u : (((c.phases & PINN_PHASE_CHAIN_FWD) ? 1u : 0u) | ((c.phases & PINN_PHASE_CHAIN_BWD) ? 2u : 0u));
+    return launch_train_chain_x6(net, c.params, c.x, c.y, c.n_rows, c.n_global, c.drop, c.b, which, c.st);
+  }
+  TrainArgs a{};
+  a.params = c.params; a.x = c.x; a.y = c.y; a.n_rows = c.n_rows; a.n_global = c.n_global; a.H = net->hidden; a.nh = net->n_hidden;
+  a.drop = c.drop;
+  a.stash_h = (float*)c.b.stash_h; a.stash_v1 = (float*)c.b.stash_v1; a.stash_v2 = (float*)c.b.stash_v2;
+  a.dpre_h = (float*)c.b.dpre_h; a.dpre_v1 = (float*)c.b.dpre_v1; a.dpre_v2 = (float*)c.b.dpre_v2;
+  a.keep = c.b.keep; a.du = c.b.du; a.dz = c.b.dz; a.loss_part = c.b.loss_part; a.t16 = c.b.t16;
+  const bool bits = a.drop.mode == PINN_DROP_BITS;
+  if (a.H == 256) {
+    if (bits) hipLaunchKernelGGL((train_chain_kernel<256, true>), dim3(c.n_partials), dim3(kThreads), 0, c.st, a);
+    else hipLaunchKernelGGL((train_chain_kernel<256, false>), dim3(c.n_partials), dim3(kThreads), 0, c.st, a);
+  } else {
+    if (bits) hipLaunchKernelGGL((train_chain_kernel<128, true>), dim3(c.n_partials), dim3(kThreads), 0, c.st, a);
+    else hipLaunchKernelGGL((train_chain_kernel<128, false>), dim3(c.n_partials), dim3(kThreads), 0, c.st, a);
+  }
+  return PINN_OK;
+}
+
+// The streams of one call's weight-gradient launches: the caller's, and under kRouteFanOut g_fan's three side streams in turn.
+// Once the fork event is recorded, join() runs on every way out: a side stream left unjoined would invalidate a stream capture.
+struct WgradStreams {
+  hipStream_t st;
+  bool fan;
+  int n_launch = 0;
+  bool used[3] = {false, false, false};
+  hipStream_t pick() {
+    if (!fan) return st;
+    const int k = n_launch++ % 4;
+    if (k == 0) return st;
+    if (!used[k - 1]) { (void)hipStreamWaitEvent(g_fan.side[k - 1], g_fan.fork, 0); used[k - 1] = true; }
+    return g_fan.side[k - 1];
+  }
+  void join() {
+    for (int k = 0; k < 3; ++k)
+      if (used[k]) { (void)hipEventRecord(g_fan.join[k], g_fan.side[k]); (void)hipStreamWaitEvent(st, g_fan.join[k], 0); }
+  }
+};
+
+// tail = the layers whose d pre-activations the backward chain finishes first (last hidden layer, heads); head = the rest
+static bool in_part(const TrainCall& c, int l) {      // hidden layer l >= 1
+  return c.phases & (l == c.net->n_hidden - 1 ? PINN_PHASE_WGRAD_TAIL : PINN_PHASE_WGRAD_HEAD);
+}
+
+// PINN_PREC_F32X6: the chain kernels (fused nets) / layer kernels (wide nets) left every operand as fp16 fragments
+// (pinn_x6_core.h), the row scales in the meta records
+static int launch_wgrads_packed(const TrainCall& c, WgradStreams& s) {
+  const int H = c.net->hidden, nh = c.net->n_hidden;
+  const ParamLayout L{H, nh};
+  const TrainBuffers& b = c.b;
+  const bool multi = c.w.route == kRouteMulti;
+  const bool do_tail = c.phases & PINN_PHASE_WGRAD_TAIL, do_head = c.phases & PINN_PHASE_WGRAD_HEAD;
+  int rc;
+  WgradPMulti mp{};
+  auto issue = [&](const WgradPArgs& pa, int kind) -> int {
+    if (!multi) return dispatch_wgrad_p(pa, (void*)s.pick());
+    mp.p[mp.n] = pa; mp.kind[mp.n] = kind; ++mp.n;
+    return PINN_OK;
+  };
+  WgradPArgs p{};
+  p.meta = b.rowmeta; p.emax = b.emax; p.qboost = b.qboost;
+  p.t16 = b.t16; p.n_slices = b.n_slices; p.slab_stride = L.total(); p.q_log2 = 3;
+  const long long hb = b.t16 * H * 16 * 4;      // bytes per hidden-layer stash
+  if (do_head) {
+    // layer 0: dW0 = d pre_0^T x with the rows as a packed group of their own (8 features of 32, stored as x / 16: any
+    // |x| < 256 survives the row scale in fp16); [H][8] of the [H][32] product is written
+    p.P = (const char*)b.dpre_h; p.Q = (const char*)b.stash_x; p.OUT = H; p.IN = 32; p.dW = b.slabs + L.w0(); p.db = b.slabs + L.b0();
+    p.ldW = 8; p.n_cols = 8; p.q_log2 = -4;
+    if ((rc = issue(p, 0))) return rc;
+    p.ldW = 0; p.n_cols = 0; p.q_log2 = 3;
+  }
+  for (int l = nh - 1; l >= 1; --l) {
+    if (!in_part(c, l)) continue;
+    p.P = (const char*)b.dpre_h + l * hb; p.Q = (const char*)b.stash_h + (l - 1) * hb; p.OUT = H; p.IN = H; p.dW = b.slabs + L.w(l); p.db = b.slabs + L.b(l);
+    if ((rc = issue(p, 1))) return rc;
+  }
+  if (do_tail) {
+    // variance head layer 0 (+ predict weight: dw_p[j] = sum du * h_last[j])
+    p.P = (const char*)b.dpre_v1; p.Q = (const char*)b.stash_h + (nh - 1) * hb; p.OUT = H / 2; p.IN = H; p.dW = b.slabs + L.wv0(); p.db = b.slabs + L.bv0();
+    p.dvq = b.slabs + L.wp();
+    if ((rc = issue(p, 2))) return rc;
+    // variance head layer 1 (+ final weight: dwv2[i] = sum dz * v2[i], fp32 operands)
+    p.P = (const char*)b.dpre_v2; p.Q = (const char*)b.stash_v1; p.OUT = H / 4; p.IN = H / 2; p.dW = b.slabs + L.wv1(); p.db = b.slabs + L.bv1();
+    p.dvq = nullptr; p.s2 = b.dz; p.R = (const float*)b.stash_v2; p.dvr = b.slabs + L.wv2();
+    if ((rc = issue(p, 3))) return rc;
+  }
+  return multi && mp.n > 0 ? dispatch_wgrad_p_multi(mp, (void*)c.st) : PINN_OK;
+}
+
+// every other precision: fp32 operands in the tiled stash.  Operand split of the kernels: 0 = exact fp32 (wgrad_kernel); 3 = three
+// bf16 parts, six products (PINN_PREC_F32X6_G6); 1 = bf16-mixed (wide nets under PINN_PREC_BF16)
+static int launch_wgrads_fp32_stash(const TrainCall& c, WgradStreams& s) {
+  const int H = c.net->hidden, nh = c.net->n_hidden;
+  const ParamLayout L{H, nh};
+  const TrainBuffers& b = c.b;
+  const float* stash_h = (const float*)b.stash_h;
+  const float* dpre_h = (const float*)b.dpre_h;
+  const long long hs = b.t16 * H * 16;   // floats per hidden-layer stash
+  const int ns = c.net->precision == PINN_PREC_F32X6_G6 ? 3 : (c.net->precision == PINN_PREC_BF16 ? 1 : 0);
+  auto wgrad = [&](const WgradArgs& wa) { hipStream_t s_ = s.pick(); return ns ? dispatch_wgrad_x6(wa, ns, (void*)s_) : dispatch_wgrad(wa, s_); };
+  int rc;
+  WgradArgs g{};
+  g.x = c.x; g.n_rows = c.n_rows; g.t16 = b.t16; g.n_slices = b.n_slices; g.slab_stride = L.total();
+  if (c.phases & PINN_PHASE_WGRAD_HEAD) {
+    // layer 0: dW0 = dpre_0 x^T (exact fp32 at every precision)
+    g.P = dpre_h; g.Q = nullptr; g.OUT = H; g.IN = 8; g.dW = b.slabs + L.w0(); g.db = b.slabs + L.b0();
+    if ((rc = dispatch_wgrad(g, s.pick()))) return rc;
+  }
+  for (int l = nh - 1; l >= 1; --l) {
+    if (!in_part(c, l)) continue;
+    g.P = dpre_h + l * hs; g.Q = stash_h + (l - 1) * hs; g.OUT = H; g.IN = H; g.dW = b.slabs + L.w(l); g.db = b.slabs + L.b(l);
+    if ((rc = wgrad(g))) return rc;
+  }
+  if (c.phases & PINN_PHASE_WGRAD_TAIL) {
+    // variance head layer 0 (+ predict weight: dw_p[j] = sum du * h_last[j])
+    g.P = (const float*)b.dpre_v1; g.Q = stash_h + (nh - 1) * hs; g.OUT = H / 2; g.IN = H; g.dW = b.slabs + L.wv0(); g.db = b.slabs + L.bv0();
+    g.s1 = b.du; g.dvq = b.slabs + L.wp();
+    if ((rc = wgrad(g))) return rc;
+    // variance head layer 1 (+ final weight: dwv2[i] = sum dz * v2[i])
+    g.P = (const float*)b.dpre_v2; g.Q = (const float*)b.stash_v1; g.OUT = H / 4; g.IN = H / 2; g.dW = b.slabs + L.wv1(); g.db = b.slabs + L.bv1();
+    g.s1 = nullptr; g.dvq = nullptr; g.s2 = b.dz; g.R = (const float*)b.stash_v2; g.dvr = b.slabs + L.wv2();
+    if ((rc = wgrad(g))) return rc;
+  }
+  return PINN_OK;
+}
+
+// the per-layer weight gradients into the slices' slabs
+static int launch_wgrads(const TrainCall& c) {
+  if (fused_bf16(c.net)) return launch_train_bf16(c.net, c.params, c.x, c.y, c.n_rows, c.n_global, c.drop, c.b, c.phases & PINN_PHASE_WGRAD, c.st);
+  WgradStreams s{c.st, c.w.route == kRouteFanOut && g_fan.init()};
+  if (s.fan && hipEventRecord(g_fan.fork, c.st) != hipSuccess) return (int)hipGetLastError();
+  const int rc = c.net->precision == PINN_PREC_F32X6 ? launch_wgrads_packed(c, s) : launch_wgrads_fp32_stash(c, s);
+  s.join();
+  return rc;
+}
+
+// fixed-order sum of the slabs -> d_grads, of the loss partials -> d_loss; fin: the optimizer step in the same launch
+static void launch_reduce(const TrainCall& c, float* d_grads, double* d_loss, const FinAdam& fin) {
+  const pinn_net_t* net = c.net;
+  const ParamLayout L{net->hidden, net->n_hidden};
+  const long long tot = L.total(), split = pinn_grad_split(net);
+  // (the gradient word of the range record sits behind the pack kernel's words: pack_x6_kernel cleared it for this call)
+  unsigned* rw = net->precision == PINN_PREC_F32X6 ? range_status_words(net) : nullptr;
+  if (rw) rw += kRangePackBlocks * (2 * (net->n_hidden - 1) + 4);
+  const unsigned* amax = fused_bf16(net) ? nullptr : c.words;      // (read next to rw only)
+  auto reduce = [&](long long lo, long long hi, int with_loss) {
+    hipLaunchKernelGGL(grad_finalize_kernel, dim3((unsigned)(((hi - lo) / 4 + kFinGroups - 1) / kFinGroups)), dim3(256), 0, c.st, c.b.slabs, c.b.n_slices, tot,
+                       c.b.loss_part, c.n_partials, L.bp(), L.bv2(), d_grads, d_loss, amax, rw, c.drop.step_counter, lo, hi, with_loss, fin);
+  };
+  const bool both = (c.phases & PINN_PHASE_REDUCE_TAIL) && (c.phases & PINN_PHASE_REDUCE_HEAD);
+  if (both) reduce(0, tot, 1);                               // one launch over the whole vector
+  else if (c.phases & PINN_PHASE_REDUCE_TAIL) reduce(split, tot, 1);
+  else if (split > 0) reduce(0, split, 0);
 }
 
 // fa: the optimizer step in the reduction's launch (pinn_mlp_train_step_dev), or nullptr
 static int train_grads_impl(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y,
                             long long n_rows, long long n_global, const pinn_dropout_t* drop, float* d_grads,
                             double* d_loss, void* d_work, size_t work_bytes, void* stream, unsigned phases, const FinAdam* fa) {
-  int rc = check_net_t(net);
+  int rc = check_net(net);
   if (rc) return rc;
   if (!d_params || !d_x || !d_y || !d_grads || !d_loss || !d_work || n_rows <= 0 || n_global < n_rows) return PINN_E_ARG;
   if (((unsigned long long)d_grads | (unsigned long long)d_work) & 15) return PINN_E_ARG;      // 16-B vector accesses
-  // the forward / backward halves are separate kernels only in the fused x6 path; elsewhere either bit means the chain
-  if (!(net->precision >= PINN_PREC_F32X6 && net->hidden <= 256) && (phases & (PINN_PHASE_CHAIN_FWD | PINN_PHASE_CHAIN_BWD)))
-    phases |= PINN_PHASE_CHAIN;
-  // two-part weight gradients / reduction (pinn_grad_split): the single-part bits mean both parts; a precision whose kernels do
-  // not split keeps everything in the "tail"
-  if (phases & PINN_PHASE_WGRAD) phases |= PINN_PHASE_WGRAD_TAIL | PINN_PHASE_WGRAD_HEAD;
-  if (phases & PINN_PHASE_REDUCE) phases |= PINN_PHASE_REDUCE_TAIL | PINN_PHASE_REDUCE_HEAD;
-  const long long split = pinn_grad_split(net);
-  if (split == 0) {
-    phases = (phases & ~(PINN_PHASE_WGRAD | PINN_PHASE_REDUCE)) | ((phases & PINN_PHASE_WGRAD_TAIL) ? PINN_PHASE_WGRAD : 0u) |
-             ((phases & PINN_PHASE_REDUCE_TAIL) ? PINN_PHASE_REDUCE : 0u);
-  }
-  const Workspace w = plan_workspace(net, n_rows);
-  if (work_bytes < w.total) return PINN_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
+  TrainCall c{};
+  c.net = net; c.params = d_params; c.x = d_x; c.y = d_y; c.n_rows = n_rows; c.n_global = n_global; c.st = (hipStream_t)stream;
+  c.phases = normalize_phases(net, phases);
+  c.w = plan_workspace(net, n_rows);
+  if (work_bytes < c.w.total) return PINN_E_WORKSPACE;
   (void)hipGetLastError();   // drop a stale error left by another HIP user of this thread
-  char* base = (char*)d_work;
-  const int H = net->hidden, nh = net->n_hidden;
-  ParamLayout L{H, nh};
+  if ((rc = convert_drop(net, drop, true, &c.drop))) return rc;
+  c.b = workspace_buffers(net, c.w, (char*)d_work, c.drop);
+  c.words = (const unsigned*)((char*)d_work + c.w.off_amax);
+  c.n_partials = loss_partials(net, n_rows);
   FinAdam fin_adam{};
-  if (fa) { fin_adam = *fa; fin_adam.snap = fa->coeffs ? (const unsigned*)(base + w.off_amax) + 2 : nullptr; }
+  if (fa) { fin_adam = *fa; fin_adam.snap = fa->coeffs ? c.words + 2 : nullptr; }
 
-  TrainArgs a{};
-  a.params = d_params; a.x = d_x; a.y = d_y; a.n_rows = n_rows; a.n_global = n_global; a.H = H; a.nh = nh;
-  // dropout conversion (same rules as the forward entry points)
-  {
-    DropDev& d = a.drop;
-    d.mode = PINN_DROP_NONE; d.bits = nullptr; d.words = 0; d.nb = H / 32; d.seed_lo = d.seed_hi = 0; d.stream = 0; d.row_offset = 0;
-    d.step_counter = nullptr;
-    for (int l = 0; l < kMaxDrop; ++l) { d.thr[l] = 0; d.scale[l] = 1.0f; }
-    if (drop) {
-      if (drop->mode < PINN_DROP_NONE || drop->mode > PINN_DROP_BITS) return PINN_E_ARG;
-      if (drop->d_step_counter && H > 256) return PINN_E_ARCH;      // the layer-by-layer kernels take their pass index by value
-      d.mode = drop->mode; d.row_offset = drop->row_offset; d.step_counter = drop->d_step_counter;
-      if (drop->mode != PINN_DROP_NONE) {
-        for (int l = 0; l <= nh; ++l) {
-          const float p = drop->p[l];
-          if (!(p >= 0.0f && p < 1.0f)) return PINN_E_ARG;
-          double t = floor((double)p * 65536.0 + 0.5);
-    if (p > 0.0f && t < 1.0) t = 1.0;      // a positive p never rounds to "no dropout"
-          d.thr[l] = (unsigned)(t < 0 ? 0 : (t > 65536.0 ? 65536.0 : t));
-          d.scale[l] = 1.0f / (float)(1.0 - (double)p);
-        }
-        d.seed_lo = (unsigned)(drop->seed & 0xFFFFFFFFull); d.seed_hi = (unsigned)(drop->seed >> 32); d.stream = drop->stream;
-        if (drop->mode == PINN_DROP_BITS) {
-          if (!drop->d_bits) return PINN_E_ARG;
-          d.bits = drop->d_bits; d.words = nh * (H / 32) + H / 64;
-        }
-      }
-    }
-  }
-  a.stash_h = (float*)(base + w.off_stash_h); a.stash_v1 = (float*)(base + w.off_stash_v1); a.stash_v2 = (float*)(base + w.off_stash_v2);
-  a.dpre_h = (float*)(base + w.off_dpre_h); a.dpre_v1 = (float*)(base + w.off_dpre_v1); a.dpre_v2 = (float*)(base + w.off_dpre_v2);
-  a.keep = (unsigned char*)(base + w.off_keep);
-  a.du = (float*)(base + w.off_du); a.dz = (float*)(base + w.off_dz);
-  a.loss_part = (double*)(base + w.off_loss);
-  a.t16 = w.t16;
-  const long long n_tiles = (n_rows + kTileRows - 1) / kTileRows;
-  int grid = (int)(n_tiles < 2 * cu_count() ? n_tiles : 2 * cu_count());
-  if (grid > 1024) grid = 1024;
-  if (net->precision == PINN_PREC_BF16 && H <= 256) {
-    TrainBuffers b{};
-    b.stash_h = a.stash_h; b.stash_v1 = a.stash_v1; b.stash_v2 = a.stash_v2;
-    b.dpre_h = a.dpre_h; b.dpre_v1 = a.dpre_v1; b.dpre_v2 = a.dpre_v2;
-    b.keep = a.keep; b.du = a.du; b.dz = a.dz; b.loss_part = a.loss_part;
-    b.slabs = (float*)(base + w.off_slabs); b.t16 = w.t16; b.n_slices = w.n_slices;
-    if ((rc = launch_train_bf16(net, d_params, d_x, d_y, n_rows, n_global, a.drop, b, phases, &grid, stream))) return rc;
-    if (phases & PINN_PHASE_REDUCE)
-      hipLaunchKernelGGL(grad_finalize_kernel, dim3((unsigned)((L.total() / 4 + kFinGroups - 1) / kFinGroups)), dim3(256), 0, st, b.slabs, w.n_slices,
-                         L.total(), a.loss_part, grid, L.bp(), L.bv2(), d_grads, d_loss, (const unsigned*)nullptr, (unsigned*)nullptr, a.drop.step_counter,
-                         0LL, (long long)L.total(), 1, fin_adam);
-    hipError_t eb = hipGetLastError();
-    return eb == hipSuccess ? PINN_OK : (int)eb;
-  }
-  if (net->precision >= PINN_PREC_F32X6 || H > 256) {
-    // split-operand chain on the 16-bit matrix cores (wide nets: also bf16-mixed); the weight-gradient and finalize kernels below are shared
-    if (phases & (PINN_PHASE_CHAIN | PINN_PHASE_CHAIN_FWD | PINN_PHASE_CHAIN_BWD)) {
-      const unsigned which = (phases & PINN_PHASE_CHAIN) ? 3u : (((phases & PINN_PHASE_CHAIN_FWD) ? 1u : 0u) | ((phases & PINN_PHASE_CHAIN_BWD) ? 2u : 0u));
-      TrainBuffers b{};
-      b.stash_h = a.stash_h; b.stash_v1 = a.stash_v1; b.stash_v2 = a.stash_v2;
-      b.dpre_h = a.dpre_h; b.dpre_v1 = a.dpre_v1; b.dpre_v2 = a.dpre_v2;
-      b.keep = a.keep; b.du = a.du; b.dz = a.dz; b.loss_part = a.loss_part;
-      b.slabs = (float*)(base + w.off_slabs); b.t16 = w.t16; b.n_slices = w.n_slices;
-      b.amax = (unsigned*)(base + w.off_amax);
-      b.emax = b.amax + 1; b.rowmeta = base + w.off_rowmeta; b.qboost = row_scale_boost(a.drop, nh); b.stash_x = base + w.off_stash_x;
-      rc = H > 256 ? launch_train_chain_wide(net, d_params, d_x, d_y, n_rows, n_global, a.drop, b, &grid, stream)
-                   : launch_train_chain_x6(net, d_params, d_x, d_y, n_rows, n_global, a.drop, b, which, &grid, stream);
-      if (rc) return rc;
-    } else if (H > 256) {
-      const long long t4 = w.t16 / 4;
-      grid = (int)(t4 < 1024 ? (t4 < 1 ? 1 : t4) : 1024);
-    } else {
-      grid = train_chain_x6_partials(net, n_rows);      // (64-row and quarter tiles write 2x / 4x the 128-row tiles' partials)
-    }
-  } else if (phases & PINN_PHASE_CHAIN) {
-    const bool bits = a.drop.mode == PINN_DROP_BITS;
-    if (H == 256) {
-      if (bits) hipLaunchKernelGGL((train_chain_kernel<256, true>), dim3(grid), dim3(kThreads), 0, st, a);
-      else hipLaunchKernelGGL((train_chain_kernel<256, false>), dim3(grid), dim3(kThreads), 0, st, a);
-    } else {
-      if (bits) hipLaunchKernelGGL((train_chain_kernel<128, true>), dim3(grid), dim3(kThreads), 0, st, a);
-      else hipLaunchKernelGGL((train_chain_kernel<128, false>), dim3(grid), dim3(kThreads), 0, st, a);
-    }
-  }
-
-  float* slabs = (float*)(base + w.off_slabs);
-  const long long tot = L.total();
-  const long long hs = (long long)w.t16 * H * 16;   // floats per hidden-layer stash
-  if (phases & (PINN_PHASE_WGRAD_TAIL | PINN_PHASE_WGRAD_HEAD)) {
-    // tail = the layers whose d pre-activations the backward chain finishes first (last hidden layer, heads); head = the rest
-    const bool do_tail = phases & PINN_PHASE_WGRAD_TAIL, do_head = phases & PINN_PHASE_WGRAD_HEAD;
-    auto in_part = [&](int l) { return l == nh - 1 ? do_tail : do_head; };      // hidden layer l >= 1
-    // small row counts: the launches of the layers are independent and short -- side by side on up to four streams
-    const bool multi = w.t16 < kMultiT16 && net->precision == PINN_PREC_F32X6 && H == 256 && nh - 1 + 3 <= kMaxWgradProblems;
-    const bool fan = !multi && w.t16 < kFanOutT16 && g_fan.init();
-    int n_launch = 0;
-    bool used[3] = {false, false, false};
-    if (fan && hipEventRecord(g_fan.fork, st) != hipSuccess) return (int)hipGetLastError();
-    auto pick = [&]() -> hipStream_t {
-      if (!fan) return st;
-      const int k = n_launch++ % 4;
-      if (k == 0) return st;
-      if (!used[k - 1]) { (void)hipStreamWaitEvent(g_fan.side[k - 1], g_fan.fork, 0); used[k - 1] = true; }
-      return g_fan.side[k - 1];
-    };
-    WgradPMulti mp{};
-    auto issue_p = [&](const WgradPArgs& pa, int kind) -> int {
-      if (!multi) return dispatch_wgrad_p(pa, (void*)pick());
-      mp.p[mp.n] = pa; mp.kind[mp.n] = kind; ++mp.n;
-      return PINN_OK;
-    };
-    WgradArgs g{};
-    g.x = d_x; g.n_rows = n_rows; g.t16 = w.t16; g.n_slices = w.n_slices; g.slab_stride = tot;
-    g.amax = (const unsigned*)(base + w.off_amax);
-    // layer 0: dW0 = dpre_0 x^T
-    g.P = a.dpre_h; g.Q = nullptr; g.OUT = H; g.IN = 8; g.dW = slabs + L.w0(); g.db = slabs + L.b0();
-    g.s1 = nullptr; g.dvq = nullptr; g.s2 = nullptr; g.R = nullptr; g.dvr = nullptr;
-    const bool packed0 = net->precision == PINN_PREC_F32X6;                   // layer 0 from the packed operands too (below)
-    if (do_head && !packed0) { if ((rc = dispatch_wgrad(g, pick()))) return rc; }
-    // every layer but the input one: split-bf16 products on the matrix cores for PINN_PREC_F32X6
-    // operand split of the weight-gradient kernels: 0 = exact fp32 kernels; 3 = three bf16 parts, six products (x6); 4 = two fp16
-    // parts under the common scale the X3 backward kernels measured (PINN_PREC_F32X6); 1 = bf16-mixed (wide nets)
-    if (net->precision == PINN_PREC_F32X6) {
-      // packed stash: the chain kernels (fused nets) / layer kernels (wide nets) left every operand as fp16 fragments
-      // (pinn_x6_core.h), the row scales in the meta records
-      WgradPArgs p{};
-      p.meta = base + w.off_rowmeta; p.emax = (const unsigned*)(base + w.off_amax) + 1; p.qboost = row_scale_boost(a.drop, nh);
-      p.t16 = w.t16; p.n_slices = w.n_slices; p.slab_stride = tot; p.q_log2 = 3;
-      const long long hb = hs * 4;      // bytes per hidden-layer stash
-      if (do_head) {
-        // layer 0: dW0 = d pre_0^T x with the rows as a packed group of their own (8 features of 32, stored as x / 16: any
-        // |x| < 256 survives the row scale in fp16); [H][8] of the [H][32] product is written
-        p.P = (const char*)a.dpre_h; p.Q = (const char*)(base + w.off_stash_x); p.OUT = H; p.IN = 32; p.dW = slabs + L.w0(); p.db = slabs + L.b0();
-        p.ldW = 8; p.n_cols = 8; p.q_log2 = -4;
-        if ((rc = issue_p(p, 0))) return rc;
-        p.ldW = 0; p.n_cols = 0; p.q_log2 = 3;
-      }
-      for (int l = nh - 1; l >= 1; --l) {
-        if (!in_part(l)) continue;
-        p.P = (const char*)a.dpre_h + l * hb; p.Q = (const char*)a.stash_h + (l - 1) * hb; p.OUT = H; p.IN = H; p.dW = slabs + L.w(l); p.db = slabs + L.b(l);
-        if ((rc = issue_p(p, 1))) return rc;
-      }
-      if (do_tail) {
-        // variance head layer 0 (+ predict weight: dw_p[j] = sum du * h_last[j])
-        p.P = (const char*)a.dpre_v1; p.Q = (const char*)a.stash_h + (nh - 1) * hb; p.OUT = H / 2; p.IN = H; p.dW = slabs + L.wv0(); p.db = slabs + L.bv0();
-        p.dvq = slabs + L.wp();
-        if ((rc = issue_p(p, 2))) return rc;
-        // variance head layer 1 (+ final weight: dwv2[i] = sum dz * v2[i], fp32 operands)
-        p.P = (const char*)a.dpre_v2; p.Q = (const char*)a.stash_v1; p.OUT = H / 4; p.IN = H / 2; p.dW = slabs + L.wv1(); p.db = slabs + L.bv1();
-        p.dvq = nullptr; p.s2 = a.dz; p.R = a.stash_v2; p.dvr = slabs + L.wv2();
-        if ((rc = issue_p(p, 3))) return rc;
-      }
-      if (multi && mp.n > 0 && (rc = dispatch_wgrad_p_multi(mp, (void*)st))) return rc;
-    } else {
-    const int ns = net->precision == PINN_PREC_F32X6 ? 4 : (net->precision == PINN_PREC_F32X6_G6 ? 3 : (net->precision == PINN_PREC_BF16 ? 1 : 0));
-    auto wgrad = [&](const WgradArgs& wa) { hipStream_t s_ = pick(); return ns ? dispatch_wgrad_x6(wa, ns, (void*)s_) : dispatch_wgrad(wa, s_); };
-    for (int l = nh - 1; l >= 1; --l) {
-      if (!in_part(l)) continue;
-      g.P = a.dpre_h + l * hs; g.Q = a.stash_h + (l - 1) * hs; g.OUT = H; g.IN = H; g.dW = slabs + L.w(l); g.db = slabs + L.b(l);
-      if ((rc = wgrad(g))) return rc;
-    }
-    if (do_tail) {
-      // variance head layer 0 (+ predict weight: dw_p[j] = sum du * h_last[j])
-      g.P = a.dpre_v1; g.Q = a.stash_h + (nh - 1) * hs; g.OUT = H / 2; g.IN = H; g.dW = slabs + L.wv0(); g.db = slabs + L.bv0();
-      g.s1 = a.du; g.dvq = slabs + L.wp();
-      if ((rc = wgrad(g))) return rc;
-      // variance head layer 1 (+ final weight: dwv2[i] = sum dz * v2[i])
-      g.P = a.dpre_v2; g.Q = a.stash_v1; g.OUT = H / 4; g.IN = H / 2; g.dW = slabs + L.wv1(); g.db = slabs + L.bv1();
-      g.s1 = nullptr; g.dvq = nullptr; g.s2 = a.dz; g.R = a.stash_v2; g.dvr = slabs + L.wv2();
-      if ((rc = wgrad(g))) return rc;
-    }
-    }
-    for (int k = 0; k < 3; ++k)
-      if (used[k]) { (void)hipEventRecord(g_fan.join[k], g_fan.side[k]); (void)hipStreamWaitEvent(st, g_fan.join[k], 0); }
-  }
-
-  if (phases & (PINN_PHASE_REDUCE_TAIL | PINN_PHASE_REDUCE_HEAD)) {
-    // (the gradient word of the range record sits behind the pack kernel's words: pack_x6_kernel cleared it for this call)
-    unsigned* rw = net->precision == PINN_PREC_F32X6 ? range_status_words(net) : nullptr;
-    if (rw) rw += kRangePackBlocks * (2 * (nh - 1) + 4);
-    const bool both = (phases & PINN_PHASE_REDUCE_TAIL) && (phases & PINN_PHASE_REDUCE_HEAD);
-    auto reduce = [&](long long lo, long long hi, int with_loss) {
-      hipLaunchKernelGGL(grad_finalize_kernel, dim3((unsigned)(((hi - lo) / 4 + kFinGroups - 1) / kFinGroups)), dim3(256), 0, st, slabs, w.n_slices, tot,
-                         a.loss_part, grid, L.bp(), L.bv2(), d_grads, d_loss, (const unsigned*)(base + w.off_amax), rw, a.drop.step_counter, lo, hi,
-                         with_loss, fin_adam);
-    };
-    if (both) reduce(0, tot, 1);                               // one launch over the whole vector
-    else if (phases & PINN_PHASE_REDUCE_TAIL) reduce(split, tot, 1);
-    else if (split > 0) reduce(0, split, 0);
-  }
+  if ((c.phases & (PINN_PHASE_CHAIN | PINN_PHASE_CHAIN_FWD | PINN_PHASE_CHAIN_BWD)) && (rc = launch_chain(c))) return rc;
+  if ((c.phases & (PINN_PHASE_WGRAD_TAIL | PINN_PHASE_WGRAD_HEAD)) && (rc = launch_wgrads(c))) return rc;
+  if (c.phases & (PINN_PHASE_REDUCE_TAIL | PINN_PHASE_REDUCE_HEAD)) launch_reduce(c, d_grads, d_loss, fin_adam);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PINN_OK : (int)e;
 }
@@ -929,7 +938,7 @@ extern "C" int pinn_mlp_train_step_dev(const pinn_net_t* net, float* d_params, c
                                        double* d_loss, void* d_work, size_t work_bytes, float* d_m, float* d_v,
                                        const float* d_coeffs, void* stream) {
   if (!net || !drop || !drop->d_step_counter || !d_m || !d_v || !d_coeffs) return PINN_E_ARG;
-  if (!(net->precision >= PINN_PREC_F32X6 && net->hidden <= 256)) return PINN_E_ARCH;      // (the kernels that leave the counter's snapshot)
+  if (!fused_x6(net)) return PINN_E_ARCH;      // (the kernels that leave the counter's snapshot)
   if (((unsigned long long)d_params | (unsigned long long)d_m | (unsigned long long)d_v) & 15) return PINN_E_ARG;
   const FinAdam fa{d_params, d_m, d_v, d_coeffs, nullptr, 0.0f, 1.0f};
   return train_grads_impl(net, d_params, d_x, d_y, n_rows, n_global, drop, d_grads, d_loss, d_work, work_bytes, stream, PINN_PHASE_ALL, &fa);

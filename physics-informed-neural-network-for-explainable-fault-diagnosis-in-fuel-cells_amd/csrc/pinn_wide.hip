@@ -250,7 +250,7 @@ __global__ __launch_bounds__(kThreadsX, 2) void wide_layer_x6_kernel(LayerArgs a
       }
     }
   }
-  if constexpr (kNormRows) {          // the call's largest |d pre-activation|: the fp16 weight-gradient kernels' common scale
+  if constexpr (kNormRows) {          // the call's largest |d pre-activation|: the range record's gradient check
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
     if (lane == 0) atomicMax(a.amax, __float_as_uint(amax));
@@ -590,8 +590,6 @@ size_t wide_scratch_floats(int H) {
   return (size_t)wide::kWideChunk * (2 * (size_t)H + H / 2 + H / 4 + 4);
 }
 
-static int wide_cus() { return cu_count_cached(); }
-
 // forward / MC-dropout of a wide net: chunks of rows through input -> hidden layers -> variance head -> heads
 int launch_forward_wide(const pinn_net_t* net, const FwdArgs& fa, bool mc, void* stream) {
   using namespace wide;
@@ -606,7 +604,7 @@ int launch_forward_wide(const pinn_net_t* net, const FwdArgs& fa, bool mc, void*
   float* bufA = scratch; float* bufB = bufA + (size_t)kWideChunk * H;
   float* v1 = bufB + (size_t)kWideChunk * H; float* v2 = v1 + (size_t)kWideChunk * (H / 2);
   float* accum = v2 + (size_t)kWideChunk * (H / 4);
-  const int cus = wide_cus();
+  const int cus = cu_count_cached();
   const int pk = net->precision == PINN_PREC_F32X6;      // activations between the kernels as packed fragments
   const int n_passes = mc ? fa.n_passes : 0;
   for (long long r0 = 0; r0 < fa.n_rows; r0 += kWideChunk) {
@@ -651,10 +649,17 @@ int launch_forward_wide(const pinn_net_t* net, const FwdArgs& fa, bool mc, void*
   return e == hipSuccess ? PINN_OK : (int)e;
 }
 
+// loss partials of launch_train_chain_wide for n_rows rows = workgroups of wide_loss_kernel: one per four of the stash's
+// 16-row tiles (whole 128-row tiles, as the workspace pads them), 1024 at the most
+int train_chain_wide_partials(const pinn_net_t*, long long n_rows) {
+  const long long t4 = (n_rows + 127) / 128 * 2;
+  return (int)(t4 < 1024 ? (t4 < 1 ? 1 : t4) : 1024);
+}
+
 // chain phase of pinn_mlp_train_grads for a wide net: every layer's activation and d pre-activation to the stash (the
-// layout the weight-gradient kernels read); *grid_out = number of loss partials
+// layout the weight-gradient kernels read)
 int launch_train_chain_wide(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
-                            long long n_global, const DropDev& drop, const TrainBuffers& b, int* grid_out, void* stream) {
+                            long long n_global, const DropDev& drop, const TrainBuffers& b, void* stream) {
   using namespace wide;
   hipStream_t st = (hipStream_t)stream;
   const int H = net->hidden, nh = net->n_hidden;
@@ -663,7 +668,7 @@ int launch_train_chain_wide(const pinn_net_t* net, const float* d_params, const 
   x6::launch_pack_x6(net, d_params, st);
   const char* packed = (const char*)net->d_packed;
   const unsigned copy_bytes = (unsigned)(K.total() * 2);
-  const int cus = wide_cus();
+  const int cus = cu_count_cached();
   const long long tiles = (n_rows + 127) / 128;
   const int grid_l = (int)(tiles < cus ? tiles : cus), grid_s = (int)((tiles * 2 < 4 * cus) ? tiles * 2 : 4 * cus);
   const long long hs = b.t16 * H * 16;            // floats per hidden-layer stash
@@ -688,8 +693,7 @@ int launch_train_chain_wide(const pinn_net_t* net, const float* d_params, const 
   la.bias_off = L.bv1(); la.layer = nh + 1;
   launch_wide_layer<EPI_TANH>(la, grid_l, st, net->precision);
 
-  const long long t4 = b.t16 / 4;
-  const int grid_loss = (int)(t4 < 1024 ? (t4 < 1 ? 1 : t4) : 1024);
+  const int grid_loss = train_chain_wide_partials(net, n_rows);
   const bool x3_grads = net->precision == PINN_PREC_F32X6;          // gradients in scheme X3: the call's largest |d pre| is recorded
   if (x3_grads) {
     hipError_t em = hipMemsetAsync(b.amax, 0, 2 * sizeof(unsigned), st);      // amax and emax (TrainBuffers: consecutive words)
@@ -701,7 +705,6 @@ int launch_train_chain_wide(const pinn_net_t* net, const float* d_params, const 
   if (pk) hipLaunchKernelGGL(wide_rowmeta_kernel, dim3((unsigned)((b.t16 * 16 + 255) / 256)), dim3(256), 0, st, b.du, b.dz, b.emax, b.qboost,
                              (_Float16*)b.rowmeta, b.t16);
   la.du = b.du; la.dz = b.dz; la.amax = b.amax;
-  *grid_out = grid_loss;
 
   // backward: Wv1^T, Wv0^T (+ w_p du), W_l^T for l = nh-1 .. 1
   la.init_w = nullptr; la.init_s = nullptr;

@@ -26,7 +26,6 @@ struct PackJobs6 {
   int with_bf16;         // the three bf16 copies (scheme X6: only PINN_PREC_F32X6_G6's gradient kernels read them)
 };
 
-static int cu_count_x() { return cu_count_cached(); }
 
 // three bf16 copies (hi, mid, lo with w = hi + mid + lo exactly) of every matrix and its transpose,
 // K permuted inside each 32-group (pack_col_x6)
@@ -237,7 +236,7 @@ int launch_forward_x6(const pinn_net_t* net, const FwdArgs& a, bool mc, void* st
   hipStream_t st = (hipStream_t)stream;
   (void)hipGetLastError();
   launch_pack_x6(net, a.params, st, nullptr);
-  const int cus = cu_count_x();
+  const int cus = cu_count_cached();
   const long long t128 = (a.n_rows + 127) / 128;
 #ifdef PINN_DEBUG_HOOKS
   static const bool force8 = getenv("PINN_X6_WAVES8") != nullptr;     // measurement builds only: always the 8-wave kernels

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void train_fwd_x3_kernel(Tra
 
 // backward chain of every row tile: d pre-activations of all layers to the stash, on the transposed copies.
 // S = X3 (PINN_PREC_F32X6): two fp16 parts of per-row-normalised gradients, three MFMAs per product (backward_pass); it also
-// records the call's largest |d pre-activation| (TrainBuffers::amax), the common scale of the fp16 weight-gradient kernels.
+// records the call's largest |d pre-activation| (TrainBuffers::amax) for the range record's gradient check.
 // S = X6 (PINN_PREC_F32X6_G6): three bf16 parts of every operand, six MFMAs.  Against a float64 autograd both leave the
 // gradient tensors as close as torch's own fp32 autograd does (rms error 5e-8 .. 1.2e-7 of a tensor's rms); the
 // golden 3-step Adam trajectory passes with either.
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void train_bwd_kernel(TrainA
     backward_pass<S, H, WAVES>(small, L, pipe, a.drop, a.drop.mode, sx, ring, lane, du, dz, amax, meta);
   }
   if constexpr (S::kActScale != 1.0f) {
-    // the call's common scale for the fp16 weight-gradient kernels: one atomicMax per wave on the float's bits (non-negative
+    // the call's largest |d pre-activation| (pinn_net_range_status): one atomicMax per wave on the float's bits (non-negative
     // floats order like unsigned integers, so the result does not depend on the order of the waves; fmaxf drops NaNs -- a NaN
     // gradient still reaches the stash and, through the operands, the weight gradients)
 #pragma unroll
@@ -612,9 +612,9 @@ static ChainPlan plan_chain(const pinn_net_t* net, long long n_rows) {
 // loss partials of launch_train_chain_x6's forward kernel for n_rows rows (the count a reduction in another call must sum)
 int train_chain_x6_partials(const pinn_net_t* net, long long n_rows) { return x6::plan_chain(net, n_rows).grid_fwd; }
 
-// chain phase of pinn_mlp_train_grads for PINN_PREC_F32X6; *grid_out = forward workgroups (= loss partials)
+// chain phase of pinn_mlp_train_grads for PINN_PREC_F32X6
 int launch_train_chain_x6(const pinn_net_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
-                          long long n_global, const DropDev& drop, const TrainBuffers& b, unsigned which, int* grid_out, void* stream) {
+                          long long n_global, const DropDev& drop, const TrainBuffers& b, unsigned which, void* stream) {
   using namespace x6;
   hipStream_t st = (hipStream_t)stream;
   const bool fast_bwd = net->precision == PINN_PREC_F32X6;           // backward chain in scheme X3 + packed stash (PINN_PREC_F32X6_G6: x6, fp32 stash)
@@ -626,7 +626,6 @@ int launch_train_chain_x6(const pinn_net_t* net, const float* d_params, const fl
   const ChainPlan c = plan_chain(net, n_rows);
   const bool small_n = c.small_n;
   const int grid = c.grid;
-  *grid_out = c.grid_fwd;
   const __bf16* packed = (const __bf16*)net->d_packed;
   const bool bits = drop.mode == PINN_DROP_BITS;
   if (c.quarters) {

@@ -3,7 +3,7 @@ preceded the fp16 gradient kernels ("X3 for the gradients"):
   x6  : 3 bf16 parts, 6 products                                   (PINN_PREC_F32X6_G6)
   x3  : 2 fp16 parts (hi, lo), 3 products, per-row normalisation   (backward_pass<X3>)
   x3s : fp16 hi + SCALED lo' = f16((x - hi) * 2048), third product against the other operand's hi * 2^-11, one power-of-two
-        scale per call                                             (wgrad kernels, kF16S)
+        scale per call                                             (the first fp16 wgrad kernels; removed)
 on synthetic operands with a wide spread over rows and features: h = tanh * dropout, d = gradients.
 usage: python tools/emu_split_schemes.py"""
 import numpy as np
