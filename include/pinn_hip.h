@@ -943,6 +943,96 @@ int pinn_tsne_descend(long long n, int init, int n_iter, int max_iter, double ea
                       int n_iter_without_progress, double min_grad_norm, double* d_state, void* d_ws, size_t ws_bytes,
                       void* stream);
 
+/* ---- Spectral clustering: the `Spectral` baseline of script 05 (05:455-512; pinn_spectral.hip) ---------------------------
+ * The k-nearest-neighbour graph of the rows, its symmetric affinity A = 0.5 (C + C^T) as CSR, the K largest eigenpairs of
+ * S = D^{-1/2} A D^{-1/2} (D = diag(A 1); a row without an edge has S_ii = 1, as scikit-learn's Laplacian gives it the
+ * eigenvalue 0), scikit-learn's embedding D^{-1/2} q_j with its sign rule, and Lloyd's k-means on rows of up to 32 columns.
+ * float64 throughout, every operation rounded on its own; every sum has a fixed order, there are no float atomics and no
+ * workgroup waits on another: the same call gives the same bytes.  Integer atomics only count and hand out slots whose
+ * order is sorted away afterwards.
+ *
+ * Limits: n_feat <= PINN_SP_MAX_FEAT, n_neighbors <= PINN_SP_MAX_NEIGHBORS, n_components <= PINN_SP_MAX_COMPONENTS,
+ * n_clusters <= PINN_SP_MAX_CLUSTERS, n_dim <= PINN_SP_MAX_DIM, 1 <= n <= PINN_SP_MAX_ROWS (the graph search compares all
+ * pairs of rows and keeps 32-bit positions).  Outside: PINN_E_ARG, sizes 0.
+ *
+ * The eigen state and the Lloyd state begin with PINN_CL_ST_HEADER 8-byte words with [PINN_CL_ST_ITER], [.._CONVERGED] and
+ * [.._STATUS] (0 or PINN_SP_NAN) as in the clustering block above: once CONVERGED or STATUS is set, every later queued
+ * launch returns at its first instruction. */
+#define PINN_SP_MAX_FEAT 8
+#define PINN_SP_MAX_NEIGHBORS 32
+#define PINN_SP_MAX_COMPONENTS 32
+#define PINN_SP_MAX_CLUSTERS 32
+#define PINN_SP_MAX_DIM 32
+#define PINN_SP_MAX_ROWS 16777216
+#define PINN_SP_GUARD 16            /* columns of the block beyond n_components */
+#define PINN_SP_MAX_DEGREE 40       /* Chebyshev steps of one filter */
+#define PINN_SP_NAN 1
+#define PINN_SP_BAD_ROW 2           /* pinn_sp_knn: a position read nothing */
+
+/* d_indices [n][n_neighbors] (64-bit) and d_dist2 [n][n_neighbors]: per position the n_neighbors nearest positions by
+ * (sum_i (x_i - y_i)^2 added in column order, position), itself among them when include_self != 0.  Candidates are staged
+ * through LDS in tiles of 128 positions.  A position that reads nothing (gather index outside the array) has no neighbours
+ * (-1, NaN), is nobody's neighbour and sets d_status[0] (one 64-bit word, else 0) to PINN_SP_BAD_ROW; lists that cannot be
+ * filled end in (-1, NaN). */
+int pinn_sp_knn(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                const long long* d_row_index, long long n, int n_neighbors, int include_self, long long* d_indices,
+                double* d_dist2, long long* d_status, void* stream);
+
+/* CSR of A = 0.5 (C + C^T) without its diagonal from the neighbour lists d_knn [n][n_neighbors] (entries outside [0, n) are
+ * skipped): d_indptr [n + 1], d_indices and d_data (0.5 or 1.0) with room for 2 n n_neighbors entries, columns ascending in
+ * every row; d_degree [n] = A 1 and d_dd [n] = sqrt(degree).  Six launches: counts of the transposed lists, a scan, the
+ * fill (slots by integer atomics), the length of every row, a scan, and one workgroup per row that places every entry at
+ * its rank, so the bytes do not depend on the schedule.  A row may be of any length. */
+size_t pinn_sp_affinity_workspace_bytes(long long n, int n_neighbors);
+int pinn_sp_affinity(long long n, int n_neighbors, const long long* d_knn, long long* d_indptr, long long* d_indices,
+                     double* d_data, double* d_degree, double* d_dd, void* d_ws, size_t ws_bytes, void* stream);
+
+/* Eigen state: header; Ritz values [m] descending; column residuals |S q_i - theta_i q_i| [m]; Ritz vectors [n][m];
+ * m = min(n, n_components + PINN_SP_GUARD).  Header: integers [.._N], [.._M], [.._K], [.._MATVEC] (products of S with the
+ * block), [.._DEGREE] (of the last filter); doubles [.._MAXRES] (largest residual of the first K columns), [.._FILT_C],
+ * [.._FILT_E] (centre and half width of the damped interval), [.._TOL]. */
+#define PINN_SP_ST_N 3
+#define PINN_SP_ST_M 4
+#define PINN_SP_ST_K 5
+#define PINN_SP_ST_MATVEC 6
+#define PINN_SP_ST_DEGREE 7
+#define PINN_SP_ST_MAXRES 8
+#define PINN_SP_ST_FILT_C 9
+#define PINN_SP_ST_FILT_E 10
+#define PINN_SP_ST_TOL 11
+
+size_t pinn_sp_eigs_state_bytes(long long n, int n_components);
+size_t pinn_sp_eigs_workspace_bytes(long long n, int n_components);
+
+/* Chebyshev-filtered subspace iteration for the n_components largest eigenpairs of S on the block the caller wrote into
+ * the state's vectors.  init != 0: the header is reset and the block orthonormalised (twice).  n_outer outer iterations are
+ * queued without a host synchronisation, each: S Q (row pass in CSR order); H = Q^T S Q by per-tile partial sums added in
+ * index order; one workgroup diagonalises H (cyclic Jacobi in LDS, round-robin pairs, eigenvalues descending); a row pass
+ * rotates Q and S Q and sums the squared residuals; one workgroup takes the roots and sets CONVERGED when the largest of
+ * the first K is <= tol, else decides the filter: a = max(theta_m, -0.99), c = (a - 1) / 2, e = (a + 1) / 2, degree = the
+ * largest deg <= PINN_SP_MAX_DEGREE with cosh(deg acosh((1 - c) / e)) <= 1e8; PINN_SP_MAX_DEGREE launches of
+ * Y_{j+1} = 2 (S Y_j - c Y_j) / e - Y_{j-1} (Y_1 = (S Y_0 - c Y_0) / e), those beyond the degree returning at once; then
+ * twice: G = Y^T Y, one workgroup scales G to unit diagonal, diagonalises it, floors the eigenvalues at 1e-15 of the largest
+ * and Y <- Y diag(G)^{-1/2} U Lambda^{-1/2}.  The bound 1e8 on the filter's growth makes a rescaling of the block needless.
+ * nnz: entries d_indices and d_data hold (entries of d_indptr beyond it are cut, columns outside [0, n) skipped). */
+int pinn_sp_eigs(long long n, const long long* d_indptr, const long long* d_indices, const double* d_data, long long nnz,
+                 const double* d_dd, int n_components, int init, int n_outer, double tol, double* d_state, void* d_ws,
+                 size_t ws_bytes, void* stream);
+
+/* d_embedding [n][n_components] = q_j[i] / dd[i] (dd = 1 for a row without an edge), columns in descending eigenvalue, every
+ * column with the sign that makes its entry of largest magnitude (the first of equals) positive.  Two launches; workspace
+ * as for pinn_sp_eigs. */
+int pinn_sp_embed(long long n, int n_components, const double* d_dd, const double* d_state, double* d_embedding,
+                  void* d_ws, size_t ws_bytes, void* stream);
+
+/* pinn_km_lloyd on a packed block d_x [n][n_dim]: the same state layout (header words PINN_KM_ST_*, centres [K][n_dim],
+ * counts [K], column means [n_dim], labels [n]), stopping rule, rule for an empty cluster, finishing pass and workspace
+ * head ([K][1 + 2 n_dim] summed terms). */
+size_t pinn_sp_lloyd_state_bytes(long long n, int n_clusters, int n_dim);
+size_t pinn_sp_lloyd_workspace_bytes(long long n, int n_clusters, int n_dim);
+int pinn_sp_lloyd(const double* d_x, long long n, int n_dim, int n_clusters, int init, int n_iters, double tol, int finish,
+                  double* d_state, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

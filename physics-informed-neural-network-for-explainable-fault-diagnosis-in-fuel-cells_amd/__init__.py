@@ -18,7 +18,9 @@ isolation forest: `DeviceIsolationForest` and `AnomalyMonitor` (anomaly); and sc
 by interior point: `run_supervised_svm_rbf`, with `DeviceLinearSVC`, `build_svm_classifier` and `SVMDiagnoser` (svm), reached
 from `compare_methods` through `device_extras` (comparison); and the t-SNE embeddings of scripts 02 and 03, the exact method:
 `DeviceTSNE`, `joint_probabilities`, `kl_and_gradient`, `trustworthiness`, `tsne_of_test_samples`, `scatter_by_features`,
-`TSNE_PARAMS` (embedding).
+`TSNE_PARAMS` (embedding); and script 05's Spectral, spectral clustering of a k-nearest-neighbour graph:
+`fit_spectral_posterior`, with `DeviceSpectralClustering`, `knn_graph`, `knn_affinity` and `spectral_embedding` (spectral),
+reached from `compare_methods` through `spectral_extras` (comparison).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -50,6 +52,8 @@ _LAZY = {
     "device_extras": "comparison",
     "DeviceTSNE": "embedding", "joint_probabilities": "embedding", "kl_and_gradient": "embedding", "trustworthiness": "embedding",
     "tsne_of_test_samples": "embedding", "scatter_by_features": "embedding", "TSNE_PARAMS": "embedding",
+    "DeviceSpectralClustering": "spectral", "fit_spectral_posterior": "spectral", "knn_graph": "spectral", "knn_affinity": "spectral",
+    "spectral_embedding": "spectral", "spectral_extras": "comparison",
 }
 
 

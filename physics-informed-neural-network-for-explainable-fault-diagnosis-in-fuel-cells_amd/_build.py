@@ -42,6 +42,8 @@ SOURCES = [
     ("pinn_svm.hip", ["-ffp-contract=off"]),
     # exact t-SNE: float64, every operation rounded on its own; the host backend states the same sums in the same order
     ("pinn_tsne.hip", ["-ffp-contract=off"]),
+    # spectral clustering: float64, every operation rounded on its own, as the clustering baselines
+    ("pinn_spectral.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

@@ -107,6 +107,11 @@ TSNE_SC_PSUM, TSNE_SC_Z, TSNE_SC_KL, TSNE_SC_SUMP, TSNE_SC_PLOGP, TSNE_SC_PLOGQ,
  TSNE_ST_LAST, TSNE_ST_STOP, TSNE_ST_STOP1, TSNE_ST_Z) = range(13)
 TSNE_STOP_MAX_ITER, TSNE_STOP_NO_PROGRESS, TSNE_STOP_GRAD_NORM, TSNE_DUPLICATES = 1, 2, 3, 4
 
+# pinn_spectral.hip: limits, status and the 8-byte words of the eigen state's header (the Lloyd state has k-means' words)
+SP_MAX_FEAT, SP_MAX_NEIGHBORS, SP_MAX_COMPONENTS, SP_MAX_CLUSTERS, SP_MAX_DIM, SP_MAX_ROWS, SP_GUARD = 8, 32, 32, 32, 32, 1 << 24, 16
+SP_NAN, SP_BAD_ROW = 1, 2
+SP_ST_N, SP_ST_M, SP_ST_K, SP_ST_MATVEC, SP_ST_DEGREE, SP_ST_MAXRES, SP_ST_FILT_C, SP_ST_FILT_E, SP_ST_TOL = range(3, 12)
+
 
 class PinnError(RuntimeError):
     pass
@@ -224,6 +229,17 @@ _SIGS = {
     "pinn_tsne_kl_grad": (c_int, [c_ll, c_void_p, ctypes.c_double, c_void_p, c_size_t, c_void_p]),
     "pinn_tsne_descend": (c_int, [c_ll, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p,
                                   c_size_t, c_void_p]),
+    "pinn_sp_knn": (c_int, _ROWS + [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_sp_affinity_workspace_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_sp_affinity": (c_int, [c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_sp_eigs_state_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_sp_eigs_workspace_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_sp_eigs": (c_int, [c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p,
+                             c_size_t, c_void_p]),
+    "pinn_sp_embed": (c_int, [c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_sp_lloyd_state_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_sp_lloyd_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_sp_lloyd": (c_int, [c_void_p, c_ll, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

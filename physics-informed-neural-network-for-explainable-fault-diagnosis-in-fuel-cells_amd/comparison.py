@@ -6,8 +6,9 @@ six methods on one stratified split of the fault rows and compares accuracy and 
 with a well-defined answer: `KMeans` (k-means, 05:346-393) and `Agglo` (Ward agglomerative clustering with the nearest
 cluster mean, 05:398-450), both with P(class | cluster) from the training labels.  `Sup_SVM` (05:323-341, a linear SVC) is
 not one of the built-in four: libsvm's iterate stopped at 1e-3 is no target, but the optimum of its problem is, and svm.py
-solves that; `device_extras()` hands it to `compare_methods` as `extra`.  `Spectral` (ARPACK eigenvectors of a kNN graph, then
-ten random k-means restarts) has no reproducible target and is not built: `compare_methods` takes a callable for it.
+solves that; `device_extras()` hands it to `compare_methods` as `extra`.  `Spectral` (05:455-512: the eigenvectors of a kNN
+graph, then ten k-means restarts) is not one of the built-in four either: its graph and the subspace of its embedding are
+well-defined targets, spectral.py computes them, and `spectral_extras()` hands it over in the same way.
 
 The helpers keep script 05's names, arguments and defaults: `fit_kmeans_posterior`, `fit_agglomerative_posterior`,
 `fit_gmm_and_get_predictions`, `run_supervised_lr`, `compute_macro_metrics`, `load_data_for_fault_4class`,
@@ -35,7 +36,8 @@ N_CLASSES = 4
 MAX_CLUSTERS, MAX_FEAT, MAX_CLASSES = 32, 8, 16
 METHODS = ("GMM", "Sup_LR", "KMeans", "Agglo")
 NOT_BUILT = {"Sup_SVM": "it is not one of the built-in methods; comparison.device_extras() returns the package's linear SVC (svm.py) for it",
-             "Spectral": "ARPACK eigenvectors of a kNN graph followed by ten random k-means restarts have no reproducible target"}
+             "Spectral": "it is not one of the built-in methods; comparison.spectral_extras() returns the package's spectral clustering "
+                         "(spectral.py) for it"}
 _HDR = 16                                # 8-byte words of a device state header (include/pinn_hip.h)
 
 
@@ -613,7 +615,8 @@ def compare_methods(X, y, methods=METHODS, split=None, extra=None, n_classes=N_C
 
     Built in: "GMM" (5 n_classes components), "Sup_LR", "KMeans" (5 n_classes clusters), "Agglo" (4 n_classes clusters), the
     counts of 05:648-662.  `extra` maps a name to a callable (X_tr, y_tr, X_te) -> y_pred, which takes precedence; that is
-    the way to run "Sup_SVM" (`extra=device_extras()`) or "Spectral" (from scikit-learn), which raise NotImplementedError without one.
+    the way to run "Sup_SVM" (`extra=device_extras()`) and "Spectral" (`extra=spectral_extras()`), which raise NotImplementedError
+    without one; all six methods: `methods=METHODS + ("Sup_SVM", "Spectral"), extra={**device_extras(), **spectral_extras()}`.
     `method_args` maps a built-in name to further keyword arguments of its function.
     Returns {name: {"y_pred", "confusion_matrix", "accuracy", "macro_precision", "macro_recall", "macro_f1"}}, in the order
     of `methods`; "y_test", "idx_train" and "idx_test" sit next to the names under the key "split"."""
@@ -658,8 +661,18 @@ def device_extras(backend="auto", **svc_args):
     return {"Sup_SVM": lambda X_tr, y_tr, X_te: run_supervised_svm_rbf(X_tr, y_tr, X_te, backend=backend, **svc_args)}
 
 
+def spectral_extras(backend="auto", n_classes=N_CLASSES, **sc_args):
+    """{"Spectral": callable} for `compare_methods(..., methods=METHODS + ("Spectral",), extra=spectral_extras())`: script 05's
+    fit_spectral_posterior (spectral.py) on 4 n_classes clusters with random_state = RANDOM_STATE (05:663-670).  `sc_args`:
+    further DeviceSpectralClustering arguments."""
+    from .spectral import fit_spectral_posterior
+    C = int(n_classes)
+    return {"Spectral": lambda X_tr, y_tr, X_te: fit_spectral_posterior(X_tr, y_tr, X_te, n_classes=C, random_state=RANDOM_STATE,
+                                                                         n_clusters=4 * C, backend=backend, **sc_args)}
+
+
 class ClusterDiagnoser:
-    """Class distributions chunk by chunk from a fitted DeviceKMeans or DeviceWard and its P(class | cluster):
+    """Class distributions chunk by chunk from a fitted DeviceKMeans, DeviceWard or DeviceSpectralClustering and its P(class | cluster):
     `update(rows)` takes the next rows of the results array [n, >= 17] (device tensor, or a host array) and returns
     (y_prob, y_pred) for them.  On the device a chunk is one kernel launch that reads the feature columns in place; it can
     run next to diagnosis.FaultDiagnoser on the same chunk."""

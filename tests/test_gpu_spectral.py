@@ -1,0 +1,240 @@
+"""GPU: the device backend of pinn_amd.spectral (csrc/pinn_spectral.hip) against the package's host backend (float64
+numpy, the same steps) and tests/golden/g_spectral.npz.
+
+Gates (from the arithmetic and the fixture, not from what the kernels give): neighbour lists equal and squared
+distances bit-equal to the host's; CSR equal; the eigen stage converged with residuals <= tol, eigenvalues within 1e-12
+of a dense eigvalsh, the projector within the Davis-Kahan bound sqrt(2) |R|_F / gap of a dense eigh, at most 3 x the
+host's outer iterations; one Lloyd iteration on wide rows under the gates of tests/test_gpu_comparison.py; the fixture end to
+end inside the bands of tests/test_spectral_host.py.  Drawn cases are held to the input conditions on the host first, at
+most 3 redraws.  In-place and gathered reads, repeated calls and another chunking are compared byte for byte.  Every
+comparison prints its maxima before it asserts."""
+import numpy as np
+import pytest
+import torch
+
+from test_comparison_host import lloyd_case
+from test_spectral_host import (adjusted_rand, bands, check_abi_limits, check_end_to_end, eigen_case, graph_case, host, orthonormal,
+                                subspace_check)
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def G(golden):
+    g = dict(golden("g_cluster.npz"))
+    g.update({"sp_" + k: v for k, v in golden("g_spectral.npz").items()})
+    return g
+
+
+@pytest.fixture(scope="module")
+def S():
+    from pinn_amd import spectral
+    return spectral
+
+
+@pytest.fixture(scope="module")
+def P():
+    from pinn_amd import comparison
+    return comparison
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+GRAPH_CASES = [(n, D, k) for n in (10, 11, 255, 256, 257, 1025) for D in (1, 4, 8) for k in (1, 10, 32) if k <= n]
+
+
+def same_lists(d, h):
+    """Indices equal and squared distances bit-equal; the unfilled tail is (-1, NaN) in both."""
+    assert np.array_equal(host(d["indices"]), h["indices"])
+    assert host(d["dist2"]).tobytes() == h["dist2"].tobytes()
+
+
+@pytest.mark.parametrize("n,D,k", GRAPH_CASES)
+def test_neighbours_and_affinity_against_the_host(S, n, D, k):
+    X = graph_case(S, n, D, k)
+    h = S.knn_graph(X, k, backend="host")
+    d = S.knn_graph(X, k, backend="device")
+    same_lists(d, h)
+    assert d["status"] == 0 and isinstance(d["indices"], np.ndarray)
+    if k < n:
+        same_lists(S.knn_graph(X, k, include_self=False, backend="device"), S.knn_graph(X, k, include_self=False, backend="host"))
+    # in place through a column list and a gather list: the packed copy's bytes
+    rng = np.random.default_rng(n + D + k)
+    wide = rng.normal(size=(n + 3, D + 3))
+    cols = list(rng.permutation(D + 3)[:D])
+    ridx = rng.permutation(n + 3)[:n]
+    wide[np.ix_(ridx, cols)] = X
+    t = S.knn_graph(dev(wide), k, columns=cols, row_index=dev(ridx), backend="device")
+    assert t["indices"].is_cuda and t["dist2"].is_cuda
+    same_lists(t, h)
+    # the affinity
+    ha = S.knn_affinity(knn=h["indices"], backend="host")
+    da = S.knn_affinity(knn=dev(h["indices"]), backend="device")
+    for key in ("indptr", "indices", "data", "degree"):
+        assert host(da[key]).tobytes() == ha[key].tobytes(), key
+    again = S.knn_affinity(knn=dev(h["indices"]), backend="device")
+    assert all(host(again[key]).tobytes() == host(da[key]).tobytes() for key in da)
+    M = np.zeros((n, n))
+    M[np.repeat(np.arange(n), np.diff(ha["indptr"])), ha["indices"]] = ha["data"]
+    assert np.array_equal(M, M.T)
+    print("n=%d D=%d k=%d: %d entries, longest row %d" % (n, D, k, ha["indptr"][-1], np.diff(ha["indptr"]).max()))
+
+
+def test_a_gather_index_outside_the_array(S):
+    X = graph_case(S, 300, 4, 10)
+    ridx = np.arange(300)
+    ridx[[7, 150]] = [-1, 300]
+    h = S.knn_graph(X, 10, row_index=ridx, backend="host")
+    d = S.knn_graph(dev(X), 10, row_index=dev(ridx), backend="device")
+    same_lists(d, h)
+    assert int(d["status"].item()) == 2 and h["status"] == 2
+    assert np.all(host(d["indices"])[[7, 150]] == -1) and not np.any(np.isin(host(d["indices"]), [7, 150]))
+    ha, da = S.knn_affinity(knn=h["indices"], backend="host"), S.knn_affinity(knn=d["indices"], backend="device")
+    assert all(host(da[key]).tobytes() == ha[key].tobytes() for key in ha) and ha["degree"][7] == 0 and ha["degree"][150] == 0
+
+
+def test_affinity_of_a_hub(S):
+    """300 rows, row 0 in every list: its row of A has >= 200 entries, far more than 2 k."""
+    n, k = 300, 10
+    rng = np.random.default_rng(11)
+    lists = np.zeros((n, k), dtype=np.int64)
+    for i in range(n):                                         # the row itself, row 0, then distinct others
+        head = [0] if i == 0 else [i, 0]
+        lists[i] = head + list(rng.permutation(np.setdiff1d(np.arange(1, n), [i]))[:k - len(head)])
+    ha = S.knn_affinity(knn=lists, backend="host")
+    da = S.knn_affinity(knn=dev(lists), backend="device")
+    again = S.knn_affinity(knn=dev(lists), backend="device")
+    longest = int(np.diff(ha["indptr"]).max())
+    print("hub: row 0 holds %d entries, %d in all" % (np.diff(ha["indptr"])[0], ha["indptr"][-1]))
+    assert np.diff(ha["indptr"])[0] >= 200 and longest == np.diff(ha["indptr"])[0]
+    for key in ("indptr", "indices", "data", "degree"):
+        assert host(da[key]).tobytes() == ha[key].tobytes(), key
+        assert host(again[key]).tobytes() == host(da[key]).tobytes(), key
+    M = np.zeros((n, n))
+    M[np.repeat(np.arange(n), np.diff(ha["indptr"])), host(da["indices"])] = host(da["data"])
+    assert np.array_equal(M, M.T)
+
+
+EIGEN_CASES = [(n, K) for n in (12, 33, 129, 1025, 2049) for K in (1, 4, 16, 32) if K <= n]
+
+
+@pytest.mark.parametrize("n,K", EIGEN_CASES)
+def test_eigen_stage_against_a_dense_eigh(S, n, K):
+    A, lam, vec = eigen_case(n, K)
+    h = S.spectral_embedding(A, K, random_state=n + K, backend="host")
+    d = S.spectral_embedding(A, K, random_state=n + K, backend="device")
+    err = np.abs(d["eigenvalues"] - lam[:K]).max()
+    print("n=%d K=%d: device %d outer iterations and %d products (host %d and %d), residual %.3e, eigenvalues %.3e (gate 1e-12), degree %d"
+          % (n, K, d["n_iter"], d["n_matvec"], h["n_iter"], h["n_matvec"], d["residuals"].max(), err, d["degree"]))
+    assert d["converged"] and d["residuals"].max() <= 1e-10 and err <= 1e-12
+    if n == 12:
+        assert d["n_iter"] == 1                                   # the block is the whole space: one Rayleigh-Ritz step is exact
+    assert d["n_iter"] <= 3 * h["n_iter"]
+    subspace_check(A, orthonormal(d["vectors"]), vec[:, :K], lam[K] if K < n else -np.inf, "n=%d K=%d device against a dense eigh" % (n, K))
+    dd = np.sqrt(A["degree"])
+    top = np.abs(d["embedding"]).argmax(axis=0)
+    assert np.all(d["embedding"][top, np.arange(K)] > 0)
+    e_emb = np.abs(d["embedding"] - d["vectors"] * np.sign((d["embedding"] * d["vectors"]).sum(axis=0)) / np.where(dd > 0, dd, 1.0)[:, None]).max()
+    print("  embedding against vectors / dd: %.3e" % e_emb)
+    assert e_emb <= 1e-15 * max(1.0, np.abs(d["embedding"]).max() * 16)
+    again = S.spectral_embedding(A, K, random_state=n + K, backend="device")
+    other = S.spectral_embedding(A, K, random_state=n + K, backend="device", chunk=1)
+    for key in ("embedding", "vectors", "eigenvalues", "residuals"):
+        assert again[key].tobytes() == d[key].tobytes() and other[key].tobytes() == d[key].tobytes(), key
+    assert other["n_iter"] == d["n_iter"] and other["n_matvec"] == d["n_matvec"]
+
+
+WIDE_CASES = [(n, K, Dm) for n in (1, 127, 128, 129, 2049) for K in (1, 16, 32) for Dm in (1, 16, 32)]
+
+
+@pytest.mark.parametrize("n,K,Dm", WIDE_CASES)
+def test_one_wide_lloyd_iteration_against_the_host(S, P, n, K, Dm):
+    X, c0, h = lloyd_case(P, n, K, Dm)
+    d = S.wide_lloyd_iteration(X, c0, backend="device")
+    assert np.array_equal(d["labels"], h["labels"])
+    err = np.abs(d["sums"] - h["sums"])
+    ratio = (err / np.where(h["abs_sums"] > 0, h["abs_sums"], 1.0)).max()
+    e_c = np.abs(d["centres"] - h["centres"]).max() / max(np.abs(h["centres"]).max(), 1e-300)
+    e_i = abs(d["inertia"] - h["inertia"]) / max(h["inertia"], 1e-300)
+    e_t = abs(d["tol_abs"] - h["tol_abs"]) / max(h["tol_abs"], 1e-300)
+    print("n=%d K=%d D=%d: sums %.3e x sum|terms| (gate 1e-12), centres %.3e, inertia %.3e, tol_abs %.3e (gates 1e-12)" % (n, K, Dm, ratio, e_c, e_i, e_t))
+    assert np.all(err <= 1e-12 * h["abs_sums"])
+    assert e_c <= 1e-12 and e_i <= 1e-12 and e_t <= 1e-12
+    assert abs(d["shift"] - h["shift"]) <= 1e-12 * max(h["shift"], 1e-300) + 1e-24
+
+
+def test_full_lloyd_on_the_fixtures_embedding(G, S, P):
+    E = np.ascontiguousarray(G["sp_sk_embedding"])
+    seeds = P.DeviceKMeans(16, backend="host")._host_seeds(np.random.default_rng(3), E)
+    h = S.wide_lloyd(E, seeds, backend="host")
+    d = S.wide_lloyd(E, seeds, backend="device")
+    t = S.wide_lloyd(dev(E), seeds, backend="device")
+    e_c = np.abs(d["centres"] - h["centres"]).max() / np.abs(h["centres"]).max()
+    print("full Lloyd on [%d, 16]: %d iterations (host %d), inertia %.6e (host %.6e), centres %.3e" % (len(E), d["n_iter"], h["n_iter"], d["inertia"],
+                                                                                                   h["inertia"], e_c))
+    assert np.array_equal(d["labels"], h["labels"]) and d["n_iter"] == h["n_iter"] and d["strict"] == h["strict"]
+    assert abs(d["inertia"] - h["inertia"]) <= 1e-12 * h["inertia"] and e_c <= 1e-12
+    assert t["labels"].is_cuda and host(t["labels"]).tobytes() == d["labels"].tobytes() and host(t["centres"]).tobytes() == d["centres"].tobytes()
+
+
+def test_fixture_end_to_end_on_the_device(G, S, P):
+    g = S.knn_graph(G["X_tr"], 10, backend="device")
+    assert np.array_equal(g["indices"], G["sp_knn_indices"])
+    A = S.knn_affinity(G["X_tr"], 10, backend="device")
+    Ah = S.knn_affinity(G["X_tr"], 10, backend="host")
+    assert all(A[key].tobytes() == Ah[key].tobytes() for key in Ah)
+    e = S.spectral_embedding(A, 16, random_state=0, backend="device")
+    err = np.abs(e["eigenvalues"] - G["sp_eigenvalues"][:16]).max()
+    print("fixture: %d outer iterations, %d products, residual %.3e, eigenvalues %.3e (gate 1e-12)" % (e["n_iter"], e["n_matvec"], e["residuals"].max(), err))
+    assert e["converged"] and err <= 1e-12
+    dd = np.sqrt(Ah["degree"])
+    subspace_check(Ah, orthonormal(e["embedding"] * dd[:, None]), orthonormal(G["sp_sk_embedding"] * dd[:, None]), float(G["sp_eigenvalues"][16]),
+                   "device against scikit-learn's ARPACK embedding", slack=1e-10)
+    r = check_end_to_end(G, S, "device")
+    for a in (r["y_pred"], r["y_prob"], r["model"].labels_, r["model"].embedding_, r["model"].cluster_means_, r["model"].affinity_matrix_["data"]):
+        assert isinstance(a, np.ndarray)
+    t = check_end_to_end(G, S, "device", dev)
+    for a in (t["y_pred"], t["y_prob"], t["cluster_class_prob"], t["model"].labels_, t["model"].embedding_, t["model"].cluster_means_,
+              t["model"].affinity_matrix_["indices"]):
+        assert isinstance(a, torch.Tensor) and a.is_cuda
+    assert host(t["model"].labels_).tobytes() == r["model"].labels_.tobytes() and host(t["model"].embedding_).tobytes() == r["model"].embedding_.tobytes()
+    assert host(t["model"].cluster_means_).tobytes() == r["model"].cluster_means_.tobytes()
+    # the online form: chunks equal one call, byte for byte
+    rng = np.random.default_rng(8)
+    res = rng.normal(0.0, 1.0, (len(G["X_te"]), 22))
+    res[:, 13:17] = G["X_te"]
+    m, cmap = t["model"], t["cluster_class_prob"]
+    one = P.ClusterDiagnoser(m, cmap, backend="device").update(dev(res))
+    dg = P.ClusterDiagnoser(m, cmap, backend="device")
+    parts = [dg.update(dev(res)[a:b]) for a, b in ((0, 1), (1, 130), (130, 131), (131, len(res)))]
+    for i in range(2):
+        assert host(one[i]).tobytes() == np.concatenate([host(p[i]) for p in parts]).tobytes()
+    assert np.array_equal(host(one[1]), host(t["y_pred"]))
+
+
+def test_compare_methods_on_the_device_and_limits(G, S, P):
+    Xa = np.concatenate([G["X_tr"], G["X_te"]])
+    ya = np.concatenate([G["y_tr"], G["y_te"]])
+    n_tr = len(G["y_tr"])
+    split = (np.arange(n_tr), n_tr + np.arange(len(G["y_te"])))
+    r = P.compare_methods(dev(Xa), dev(ya), methods=P.METHODS + ("Sup_SVM", "Spectral"), split=split, backend="device",
+                          extra={**P.device_extras("device"), **P.spectral_extras("device")}, method_args={"KMeans": {"init": G["km_init"]}})
+    assert list(r) == ["split", "GMM", "Sup_LR", "KMeans", "Agglo", "Sup_SVM", "Spectral"]
+    lo, hi, _ = bands(G)
+    print("Spectral through compare_methods on the device: accuracy %.4f (band %.4f .. %.4f)" % (r["Spectral"]["accuracy"], lo, hi))
+    assert lo <= r["Spectral"]["accuracy"] <= hi
+    X9 = np.random.default_rng(1).normal(size=(200, 9))
+    with pytest.raises(NotImplementedError):
+        S.knn_graph(X9, 10, backend="device")
+    with pytest.raises(NotImplementedError):
+        S.knn_graph(X9[:, :4], 33, backend="device")
+    with pytest.raises(NotImplementedError):
+        S.DeviceSpectralClustering(4, n_components=33, backend="device").fit(X9[:, :4])
+    with pytest.raises(NotImplementedError):
+        S.DeviceSpectralClustering(33, backend="device").fit(X9[:, :4])
+    with pytest.raises(NotImplementedError):
+        S.wide_lloyd_iteration(np.zeros((50, 33)), np.zeros((4, 33)), backend="device")
+    from pinn_amd import _lib
+    check_abi_limits(_lib.load())
