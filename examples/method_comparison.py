@@ -1,7 +1,8 @@
 """Script 05's question on the device: is the mixture with label-posterior mapping better than plain clustering?  A synthetic
 results array with twelve fault segments (two residual columns drift per fault class), the fault rows split once, and GMM,
 logistic regression, k-means and Ward clustering and, through `device_extras` and `spectral_extras`, the linear SVC of script
-05's Sup_SVM and the spectral clustering of its Spectral: all six methods of the script, fitted on the training rows and judged
+05's Sup_SVM and the spectral clustering of its Spectral: all six methods of the script, plus, through `kernel_extras`, the
+RBF-kernel SVC that the script names for Sup_SVM (`Sup_SVM_RBF`), fitted on the training rows and judged
 on the test rows by accuracy and macro precision / recall / F1.  A user's own method rides along as a callable.  Then the recording is replayed in chunks
 through the online diagnoser of the k-means model.  Nothing leaves the GPU but the printed numbers; `--host` runs the
 float64 numpy backend instead.
@@ -58,9 +59,11 @@ def main():
         results, backend = torch.from_numpy(results).cuda(), "device"
     X, y, names = comparison.load_data_for_fault_4class(results, backend=backend)
     print("fault rows: %d x %d features, classes %s" % (X.shape[0], X.shape[1], names))
-    methods = comparison.METHODS + ("Sup_SVM", "Spectral", "NearestMean")
-    # Sup_SVM: the package's linear SVC (svm.py); Spectral: its spectral clustering (spectral.py)
-    extra = {**comparison.device_extras(backend), **comparison.spectral_extras(backend), "NearestMean": nearest_class_mean}
+    methods = comparison.METHODS + ("Sup_SVM", "Sup_SVM_RBF", "Spectral", "NearestMean")
+    # Sup_SVM: the package's linear SVC (svm.py), what script 05 runs; Sup_SVM_RBF: the RBF-kernel SVC it names (ksvm.py);
+    # Spectral: its spectral clustering (spectral.py)
+    extra = {**comparison.device_extras(backend), **comparison.kernel_extras(backend), **comparison.spectral_extras(backend),
+             "NearestMean": nearest_class_mean}
     r = comparison.compare_methods(X, y, methods=methods, extra=extra, backend=backend)
     print("%-12s %9s %10s %9s %9s" % ("method", "accuracy", "precision", "recall", "F1"))
     for name in methods:

@@ -1033,6 +1033,80 @@ size_t pinn_sp_lloyd_workspace_bytes(long long n, int n_clusters, int n_dim);
 int pinn_sp_lloyd(const double* d_x, long long n, int n_dim, int n_clusters, int init, int n_iters, double tol, int finish,
                   double* d_state, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- The RBF-kernel SVC that script 05 names: one-vs-one, libsvm's SMO in float64 (pinn_ksvm.hip) -------------------------
+ * Rows are read in place as in the modules above; d_y holds the class index 0..n_classes-1 of every row position.  Limits:
+ * n_feat <= PINN_KSVM_MAX_FEAT, 2 <= n_classes <= PINN_KSVM_MAX_CLASSES (28 pairs).  Outside: PINN_E_ARG, sizes 0.
+ *
+ * A pair (a, b), a < b, in the order (0,1), (0,2), ..., (C-2,C-1), solves min 1/2 al'Q al - e'al, t'al = 0, 0 <= al <= c
+ * over the rows of its two classes in position order, Q_ij = t_i t_j exp(-gamma |z_i - z_j|^2), t = +1 for class a, z the
+ * z-scores (x - mean) / scale, the squared differences added in feature order.  The state block, in 8-byte words:
+ *   header       PINN_KSVM_ST_HEADER words, for the caller's use (the kernels read none of them)
+ *   pair blocks  [P][PINN_KSVM_PAIR_WORDS]: integers [PINN_KSVM_P_ITER], [.._CONVERGED], [.._STATUS] (0, PINN_KSVM_NAN: a row
+ *                of the pair is not finite, PINN_KSVM_RANGE: a gather index outside the array or a class index outside
+ *                [0, n_classes)), [.._A], [.._B], [.._I], [.._J] (the last working set, row positions), [.._NFREE]; doubles
+ *                [.._GMAX], [.._GMIN] (of the last selection), and from pinn_ksvm_finish [.._RHO], [.._PRIMAL], [.._DUAL],
+ *                [.._GAP], [.._SUMALPHA], [.._TALPHA], [.._VIOLATION] (gmax - gmin at the point)
+ *   mean [D], scale [D], bound [C] (C x class weight: the upper bound of alpha of a row of that class)
+ *   alpha, G     [n][C - 1] each: slot j of a row of class k belongs to its j-th other class in increasing order
+ * The caller fills [.._A], [.._B], mean, scale and bound.  Once a pair's CONVERGED or STATUS is set every later launch of
+ * pinn_ksvm_smo leaves the pair alone. */
+#define PINN_KSVM_MAX_FEAT 8
+#define PINN_KSVM_MAX_CLASSES 8
+#define PINN_KSVM_NAN 1
+#define PINN_KSVM_RANGE 4
+#define PINN_KSVM_SV_TILE 128       /* support rows per LDS tile of pinn_ksvm_decision */
+#define PINN_KSVM_ST_HEADER 16
+#define PINN_KSVM_PAIR_WORDS 24
+#define PINN_KSVM_P_ITER 0
+#define PINN_KSVM_P_CONVERGED 1
+#define PINN_KSVM_P_STATUS 2
+#define PINN_KSVM_P_A 3
+#define PINN_KSVM_P_B 4
+#define PINN_KSVM_P_I 5
+#define PINN_KSVM_P_J 6
+#define PINN_KSVM_P_NFREE 7
+#define PINN_KSVM_P_GMAX 8
+#define PINN_KSVM_P_GMIN 9
+#define PINN_KSVM_P_RHO 10
+#define PINN_KSVM_P_PRIMAL 11
+#define PINN_KSVM_P_DUAL 12
+#define PINN_KSVM_P_GAP 13
+#define PINN_KSVM_P_SUMALPHA 14
+#define PINN_KSVM_P_TALPHA 15
+#define PINN_KSVM_P_VIOLATION 16
+
+size_t pinn_ksvm_state_bytes(long long n_rows, int n_classes, int n_feat);       /* 0 for sizes outside the limits */
+size_t pinn_ksvm_workspace_bytes(long long n_rows, int n_classes, int n_feat);
+
+/* Queues n_iters SMO iterations of every pair, two launches each, without a host synchronisation (init != 0: first one
+ * launch that sets alpha = 0, G = -e, the pair blocks' running words and checks the rows).  An iteration: i = the first
+ * maximum of -t G over I_up; it stops the pair (CONVERGED) when gmax - gmin <= tol; j = the first minimum of -b^2 / a over
+ * the rows of I_low with b = gmax + t_j G_j > 0, a = 2 - 2 K_ij (1e-12 where that is not positive); libsvm's clipped update
+ * of (alpha_i, alpha_j); G += t (t_i K_i dalpha_i + t_j K_j dalpha_j).  A status is recorded by the first iteration after
+ * the launch that found it.  d_log: NULL, or [P][n_iters][2] 64-bit words that receive (i, j) of every iteration a pair
+ * did in this call (the others keep what the caller wrote).  A call with init == 0 must be given the workspace of the call
+ * before it, unchanged, and the same rows, d_y, gamma and tol; the workspace of a call with init != 0 may hold anything. */
+int pinn_ksvm_smo(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                  const long long* d_row_index, long long n, const long long* d_y, int n_classes, double gamma, int init,
+                  int n_iters, double tol, double* d_state, long long* d_log, void* d_ws, size_t ws_bytes, void* stream);
+
+/* One launch, a workgroup per pair: libsvm's rho (the mean of t G over the rows with 0 < alpha < c, else the midpoint of the
+ * two bounds), al'Q al = sum alpha (G + 1), primal = 1/2 al'Q al + sum c max(0, -G - t b) with b = -rho, dual = sum alpha -
+ * 1/2 al'Q al, their difference, sum alpha, t'alpha, the number of free rows and gmax - gmin, into the pair blocks.  It reads
+ * the state and d_y alone: no workspace, and of the rows only their number. */
+int pinn_ksvm_finish(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                     const long long* d_row_index, long long n, const long long* d_y, int n_classes, double* d_state,
+                     void* stream);
+
+/* One launch, a thread per row: the P pairwise values sum_s coef[s][slot] K(z, sv_s) - rho[p] [n][P], the terms added in the
+ * order of the support rows, the votes [n][C] (a where the value is > 0, else b) and the prediction [n] (the first maximum
+ * of the votes; -1 for a gather index outside the array).  Every output may be NULL.  d_scaler: NULL or mean [D], scale [D]
+ * of the rows; d_sv [n_sv][D] packed z-scores; d_coef [n_sv][C - 1]: t alpha in the slot layout; d_sv_class [n_sv]. */
+int pinn_ksvm_decision(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                       const long long* d_row_index, long long n, int n_classes, const double* d_scaler, const double* d_sv,
+                       const double* d_coef, const long long* d_sv_class, long long n_sv, const double* d_rho, double gamma,
+                       double* d_decision, long long* d_votes, long long* d_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

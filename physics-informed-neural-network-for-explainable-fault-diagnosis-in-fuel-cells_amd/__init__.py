@@ -20,7 +20,9 @@ from `compare_methods` through `device_extras` (comparison); and the t-SNE embed
 `DeviceTSNE`, `joint_probabilities`, `kl_and_gradient`, `trustworthiness`, `tsne_of_test_samples`, `scatter_by_features`,
 `TSNE_PARAMS` (embedding); and script 05's Spectral, spectral clustering of a k-nearest-neighbour graph:
 `fit_spectral_posterior`, with `DeviceSpectralClustering`, `knn_graph`, `knn_affinity` and `spectral_embedding` (spectral),
-reached from `compare_methods` through `spectral_extras` (comparison).
+reached from `compare_methods` through `spectral_extras` (comparison); and the RBF-kernel SVC that script 05 names for Sup_SVM
+(it runs the linear one), one-vs-one and solved by SMO in float64: `run_supervised_svm_kernel`, with `DeviceKernelSVC`,
+`build_kernel_svm_classifier` and `KernelSVMDiagnoser` (ksvm), reached from `compare_methods` through `kernel_extras` (comparison).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -50,6 +52,8 @@ _LAZY = {
     "DeviceIsolationForest": "anomaly", "AnomalyMonitor": "anomaly",
     "DeviceLinearSVC": "svm", "run_supervised_svm_rbf": "svm", "build_svm_classifier": "svm", "SVMDiagnoser": "svm",
     "device_extras": "comparison",
+    "DeviceKernelSVC": "ksvm", "run_supervised_svm_kernel": "ksvm", "build_kernel_svm_classifier": "ksvm", "KernelSVMDiagnoser": "ksvm",
+    "kernel_extras": "comparison",
     "DeviceTSNE": "embedding", "joint_probabilities": "embedding", "kl_and_gradient": "embedding", "trustworthiness": "embedding",
     "tsne_of_test_samples": "embedding", "scatter_by_features": "embedding", "TSNE_PARAMS": "embedding",
     "DeviceSpectralClustering": "spectral", "fit_spectral_posterior": "spectral", "knn_graph": "spectral", "knn_affinity": "spectral",

@@ -44,6 +44,8 @@ SOURCES = [
     ("pinn_tsne.hip", ["-ffp-contract=off"]),
     # spectral clustering: float64, every operation rounded on its own, as the clustering baselines
     ("pinn_spectral.hip", ["-ffp-contract=off"]),
+    # RBF-kernel SVC by SMO: float64, every operation rounded on its own; the host backend states the same arithmetic
+    ("pinn_ksvm.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

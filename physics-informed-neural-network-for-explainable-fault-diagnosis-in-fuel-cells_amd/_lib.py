@@ -100,6 +100,11 @@ SVM_ST_ITER, SVM_ST_CONVERGED, SVM_ST_STATUS, SVM_ST_C, SVM_ST_D, SVM_ST_P, SVM_
  SVM_P_GAP, SVM_P_PRIMAL, SVM_P_DUAL, SVM_P_THETA_AFF, SVM_P_COMPL, SVM_P_TALPHA, SVM_P_SUMALPHA) = range(19)
 SVM_P_W, SVM_P_BETA, SVM_P_DAFF, SVM_P_DIR, SVM_P_FIX, SVM_P_RW = 20, 28, 30, 40, 50, 60
 
+# pinn_ksvm.hip: limits, status and the 8-byte words of the state header and of a pair's block
+KSVM_MAX_FEAT, KSVM_MAX_CLASSES, KSVM_NAN, KSVM_RANGE, KSVM_SV_TILE, KSVM_ST_HEADER, KSVM_PAIR_WORDS = 8, 8, 1, 4, 128, 16, 24
+(KSVM_P_ITER, KSVM_P_CONVERGED, KSVM_P_STATUS, KSVM_P_A, KSVM_P_B, KSVM_P_I, KSVM_P_J, KSVM_P_NFREE, KSVM_P_GMAX, KSVM_P_GMIN, KSVM_P_RHO,
+ KSVM_P_PRIMAL, KSVM_P_DUAL, KSVM_P_GAP, KSVM_P_SUMALPHA, KSVM_P_TALPHA, KSVM_P_VIOLATION) = range(17)
+
 # pinn_tsne.hip: limits, status, per-row sums, workspace scalars and the 8-byte words of the state header
 TSNE_MAX_FEAT, TSNE_MAX_ROWS, TSNE_NAN, TSNE_NOT_CONVERGED, TSNE_ROW_SUMS, TSNE_SCALARS, TSNE_ST_HEADER = 8, 32768, 1, 2, 8, 32, 16
 TSNE_SC_PSUM, TSNE_SC_Z, TSNE_SC_KL, TSNE_SC_SUMP, TSNE_SC_PLOGP, TSNE_SC_PLOGQ, TSNE_SC_GNORM = range(7)
@@ -223,6 +228,13 @@ _SIGS = {
     "pinn_svm_pass": (c_int, _ROWS + [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_svm_ipm": (c_int, _ROWS + [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_svm_decision": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_ksvm_state_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_ksvm_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_ksvm_smo": (c_int, _ROWS + [c_void_p, c_int, ctypes.c_double, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
+    "pinn_ksvm_finish": (c_int, _ROWS + [c_void_p, c_int, c_void_p, c_void_p]),
+    "pinn_ksvm_decision": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, ctypes.c_double, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
     "pinn_tsne_state_bytes": (c_size_t, [c_ll]),
     "pinn_tsne_workspace_bytes": (c_size_t, [c_ll]),
     "pinn_tsne_affinities": (c_int, _ROWS + [ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

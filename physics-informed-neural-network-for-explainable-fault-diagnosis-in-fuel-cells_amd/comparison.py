@@ -661,6 +661,14 @@ def device_extras(backend="auto", **svc_args):
     return {"Sup_SVM": lambda X_tr, y_tr, X_te: run_supervised_svm_rbf(X_tr, y_tr, X_te, backend=backend, **svc_args)}
 
 
+def kernel_extras(backend="auto", **svc_args):
+    """{"Sup_SVM_RBF": callable} for `compare_methods(..., methods=METHODS + ("Sup_SVM", "Sup_SVM_RBF"),
+    extra={**device_extras(), **kernel_extras()})`: script 05's Sup_SVM with the RBF kernel its name promises
+    (ksvm.run_supervised_svm_kernel).  `svc_args`: further DeviceKernelSVC arguments."""
+    from .ksvm import run_supervised_svm_kernel
+    return {"Sup_SVM_RBF": lambda X_tr, y_tr, X_te: run_supervised_svm_kernel(X_tr, y_tr, X_te, backend=backend, **svc_args)}
+
+
 def spectral_extras(backend="auto", n_classes=N_CLASSES, **sc_args):
     """{"Spectral": callable} for `compare_methods(..., methods=METHODS + ("Spectral",), extra=spectral_extras())`: script 05's
     fit_spectral_posterior (spectral.py) on 4 n_classes clusters with random_state = RANDOM_STATE (05:663-670).  `sc_args`:
