@@ -208,6 +208,130 @@ def mlp_forward(params, x, p_list=None, masks=None, bf16=False):
     return u, logvar
 
 
+def _mm_chunked(a, b, k_chunk):
+    """a [M, K] @ b [K, N] in a's dtype with the K dimension summed in chunks of `k_chunk` (None: one product): every chunk is
+    one product and the partial results are added afterwards, so two values of k_chunk give the same sum in another order."""
+    K = a.shape[1]
+    if k_chunk is None or K <= k_chunk:
+        return a @ b
+    nc = (K + k_chunk - 1) // k_chunk
+    pad = nc * k_chunk - K
+    if pad:
+        a = torch.cat([a, a.new_zeros(a.shape[0], pad)], dim=1)
+        b = torch.cat([b, b.new_zeros(pad, b.shape[1])], dim=0)
+    a3 = a.reshape(a.shape[0], nc, k_chunk).permute(1, 0, 2)
+    b3 = b.reshape(nc, k_chunk, b.shape[1])
+    step = max(1, (1 << 22) // max(1, a.shape[0] * b.shape[1]))       # partials held at once: <= 4 M elements
+    acc = a.new_zeros(a.shape[0], b.shape[1])
+    for c in range(0, nc, step):
+        acc = acc + torch.bmm(a3[c:c + step], b3[c:c + step]).sum(0)
+    return acc
+
+
+def bf16_train_step(params, x, y, p_list=None, masks=None, dtype=torch.float64, n_global=None, k_chunk=None, rounding=True):
+    """One training step (loss sums and every gradient tensor) under the rounding policy of the FUSED bf16/fp32-mixed kernels
+    (pinn_net_t.precision = PINN_PREC_BF16, H in {128, 256}), by a manual backward -- NOT the reference's arithmetic.  The wide
+    nets' bf16 scheme (x6::B1 in csrc/pinn_wide.hip) stashes and contracts through the split-operand machinery and needs a
+    statement of its own; it is not restated here.
+
+    bf(.) below is value -> float32 -> bfloat16, round to nearest; everything else is computed in `dtype` (float64: the
+    referee; float32: the kernels' own accumulator width).  Rounding points, with where the kernels have them (core =
+    csrc/pinn_bf16_core.h, hip = csrc/pinn_bf16.hip):
+
+      forward (= mlp_forward(bf16=True); forward_pass_bf16, core:145-214)
+        layer 0 exact, K = 8 (core:155); every later product bf(h) . bf(W): the activation after dropout goes into the MFMA as a
+        bf16 fragment (core:164-165, 177, 183, 191, 199), the weights are packed to bf16 once per call (hip:20)
+        predict head: dot product on the UNROUNDED last activation (core:166-169, 180)
+        z: dot product on the UNROUNDED v2 (core:203-204, 213)
+      stash: bf(h_l) after dropout (core:172), bf(v1) after dropout (core:194), bf(v2) (core:211)
+      loss, du, dz (train_chain_bf16_kernel, hip:208-231): s = log(softplus(z) + 1e-6), prec = exp(-s), e = y - u,
+        du = -(prec e) / n_global, dz = (-prec e^2 / 2 + 1/2 + 0.01 sign(s)) / n_global . sig / (softplus(z) + 1e-6) with
+        sig = 1 for z > 20, else 1 / (1 + exp(-z)); the 1 / n_global enters HERE, before any rounding (hip:181, 217, 219)
+      backward (hip:233-303)
+        g2 = bf(wv2 dz (1 - v2^2)), v2 unrounded (hip:244, 249; stored hip:254)
+        dv1 = g2 . bf(Wv1) (hip:256)
+        g1 = bf(dv1 s keep (1 - (bf(v1) / s)^2)): the tanh derivative from the ROUNDED stash (hip:261, 266, 269; hip:143-154)
+        dh = wp du + g1 . bf(Wv0) (hip:273-278)
+        per layer l = nh-1 .. 0: gh_l = bf(dh s_l keep (1 - (bf(h_l) / s_l)^2)) (hip:286-297), then dh = gh_l . bf(W_l) (hip:299-302)
+      weight gradients (wgrad_bf16_kernel, hip:368-471; operands hip:522-534)
+        dW_l = gh_l^T bf(h_{l-1}) (hip:402); dW_0 = gh_0^T bf(x): the input is rounded here although layer 0's forward is exact
+        (hip:363); db_l = sum gh_l, of the rounded values (hip:408); dwp = sum du bf(h_last) (hip:432); dWv0 = g1^T bf(h_last);
+        dWv1 = g2^T bf(v1); dwv2 = sum dz bf(v2) (hip:420); dbp = sum du and dbv2 = sum dz, unrounded, with the loss sums
+        (hip:226-227, csrc/pinn_train.hip:510-511)
+
+    params / x / y / masks / p_list as mlp_forward and nll_loss_and_grads; n_global: the divisor of the mean (default: the
+    rows given -- a row shard passes the whole batch's count).  k_chunk: the K dimension of EVERY matrix product and row sum is
+    summed in chunks of that size (None: one product) -- another summation order of the same policy.  rounding=False switches
+    every bf(.) off: the plain backward, which in float64 equals autograd of nll_loss_and_grads.
+
+    Returns (sums, grads, detail): sums = float64 array (sum of 0.5 prec e^2 + 0.5 s, sum |s|, sum e^2) = the kernels'
+    loss[0..2]; grads in param_names order; detail = dict(u, logvar [N, 1], terms) with terms[i] = (g [N, out], inp [N, in]
+    or None for a bias): gradient tensor i is g^T inp, row by row."""
+    nh = (len(params) - 8) // 2
+    N = x.shape[0]
+    n_global = N if n_global is None else n_global
+    P = [p.detach().to(dtype) for p in params]
+    x = x.detach().to(dtype)
+    y = y.detach().to(dtype).reshape(-1, 1)
+    q = (lambda t: t.to(torch.float32).to(torch.bfloat16).to(dtype)) if rounding else (lambda t: t)
+    mm = lambda a, b: _mm_chunked(a, b, k_chunk)
+    lin = F.linear if k_chunk is None else (lambda h, W, b: mm(h, W.t()) + b)
+    drop = masks is not None
+    keep = [torch.as_tensor(np.asarray(m), dtype=torch.float32) for m in masks] if drop else [None] * (nh + 1)
+    scale = [float(dropout_scale(p_list[l])) if drop else 1.0 for l in range(nh + 1)]
+    k = 2 * nh
+    with torch.no_grad():
+        # forward: mlp_forward's statements
+        hs, h = [], x
+        for l in range(nh):
+            a = torch.tanh(lin(h, P[0], P[1])) if l == 0 else torch.tanh(lin(q(h), q(P[2 * l]), P[2 * l + 1]))
+            if drop:
+                a = a * (keep[l] * scale[l])
+            h = a
+            hs.append(h)
+        u = lin(h, P[k], P[k + 1])
+        v1 = torch.tanh(lin(q(h), q(P[k + 2]), P[k + 3]))
+        if drop:
+            v1 = v1 * (keep[nh] * scale[nh])
+        v2 = torch.tanh(lin(q(v1), q(P[k + 4]), P[k + 5]))
+        z = lin(v2, P[k + 6], P[k + 7])
+        # loss and its gradient by (u, z)
+        var = F.softplus(z) + 1e-6
+        s = torch.log(var)
+        prec = torch.exp(-s)
+        e = y - u
+        inv_n = 1.0 / float(n_global)
+        du = -(prec * e) * inv_n
+        ds = (-0.5 * prec * e * e + 0.5 + 0.01 * torch.sign(s)) * inv_n
+        sig = torch.where(z > 20.0, torch.ones_like(z), 1.0 / (1.0 + torch.exp(-z)))
+        dz = ds * sig / var
+        sums = np.array([float((0.5 * prec * e * e + 0.5 * s).double().sum()), float(s.abs().double().sum()),
+                         float((e * e).double().sum())])
+
+        def dact(d, stash, l):       # d pre-activation of a tanh + dropout module from its stashed output
+            a = stash * float(np.float32(1.0) / np.float32(scale[l])) if dtype == torch.float32 else stash / scale[l]
+            g = d * (scale[l] * (1.0 - a * a))
+            return q(g * keep[l] if drop else g)
+
+        # backward chain
+        g2 = q(P[k + 6] * dz * (1.0 - v2 * v2))
+        g1 = dact(mm(g2, q(P[k + 4])), q(v1), nh)
+        dh = P[k] * du + mm(g1, q(P[k + 2]))
+        gh = [None] * nh
+        for l in range(nh - 1, -1, -1):
+            gh[l] = dact(dh, q(hs[l]), l)
+            if l > 0:
+                dh = mm(gh[l], q(P[2 * l]))
+        # weight gradients: g^T inp over the rows
+        terms = []
+        for l in range(nh):
+            terms += [(gh[l], q(x) if l == 0 else q(hs[l - 1])), (gh[l], None)]
+        terms += [(du, q(hs[-1])), (du, None), (g1, q(hs[-1])), (g1, None), (g2, q(v1)), (g2, None), (dz, q(v2)), (dz, None)]
+        ones = x.new_ones(N, 1)
+        grads = [mm(g.t(), ones).reshape(-1) if inp is None else mm(g.t(), inp) for g, inp in terms]
+    return sums, grads, dict(u=u, logvar=s, terms=terms)
+
+
 def aleatoric_loss(gt, pred_y, logvar):
     """01:916-927."""
     precision = torch.exp(-logvar)

@@ -2,7 +2,9 @@
 
 Two checks per kernel: (1) against the oracle run with the SAME rounding policy (bf16 MFMA inputs,
 fp32 everything else) -- tight, only accumulation order differs; (2) against the fp32 oracle (= the
-reference's arithmetic) at the mixed-precision tolerance rtol 2e-2 of SURVEY.md 8(c)."""
+reference's arithmetic) at the mixed-precision tolerance rtol 2e-2 of SURVEY.md 8(c).  For the fused
+nets' training step (1) is the second half of this file: every gradient tensor against a float64
+run of the kernels' own policy, inside a band derived on the CPU (tests/bf16_policy.py)."""
 import ctypes
 
 import numpy as np
@@ -11,6 +13,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import bf16_policy as B
 import pinn_oracle as O
 
 
@@ -128,3 +131,138 @@ def test_model_surface_bf16_end_to_end():
     assert np.abs(yp32 - yp16).max() < 0.05 * np.abs(yp32).max()
     with pytest.raises(ValueError):
         pinn_amd.PhysicsInformedNN(ds[0], ds[1], [8, 256, 256, 256, 1], ds[4], ds[5], p=0.2, logvar=True, precision="fp8")
+
+
+# =======================================================================================
+# The fused kernels against a float64 reference of their OWN rounding policy (O.bf16_train_step), inside a band that
+# test_bf16_policy_host.py derives from that reference and float32 restatements alone (tests/bf16_policy.py).  The gates
+# above, against the reference's fp32 arithmetic, state the 2e-2 mixed-precision contract and have to swallow the whole
+# bf16 rounding error; the ones below do not, so a dropped ragged row, a skipped weight-gradient tile or a wrong keep bit
+# shows.
+# =======================================================================================
+def _cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _dev_inputs(P, x, y, H, nh):
+    import hip_helpers as hh
+    return hh.flat_params(P, H, nh).to(hh.dev()), x.to(hh.dev()).contiguous(), y.reshape(-1).to(hh.dev()).contiguous()
+
+
+def _assert_in_band(label, band, loss, grads, H, nh, ref=None):
+    """Prints every tensor's error / band (max and rms gate), then asserts both <= 1."""
+    import hip_helpers as hh
+    rat = band.ratios(loss.cpu().numpy()[:3], [g.numpy() for g in hh.unflat(grads.cpu(), H, nh)], ref)
+    print("\n%s: error / band (max, rms)  " % label + "  ".join("%s %.3f %.3f" % (n, m, r) for n, m, r in rat))
+    print("%s: worst ratio %.3f" % (label, max(max(m, r) for _, m, r in rat)))
+    bad = [(n, m, r) for n, m, r in rat if not (m <= 1.0 and r <= 1.0)]
+    assert not bad, (label, bad)
+
+
+def _mc(lib, H, nh, fp, x, drop, T):
+    import hip_helpers as hh
+    from pinn_amd import _lib
+    out = torch.empty(3, x.shape[0], device=hh.dev())
+    net = hh.make_net(lib, H, nh, 1)
+    _lib.check(lib.pinn_mc_dropout(ctypes.byref(net), hh.ptr(fp), hh.ptr(x), x.shape[0], ctypes.byref(drop), T, hh.ptr(out[0]),
+                                   hh.ptr(out[1]), hh.ptr(out[2]), hh.stream()), "mc")
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("name", B.CASE_IDS)
+def test_train_grads_bf16_in_policy_band(lib, name):
+    """Loss sums l[0..2] and all 2 nh + 8 gradient tensors of a bf16-mixed training step against the float64 policy reference,
+    inside band_t = 3 E_t + 4 * 2^-8 * R_t for the largest and for the rms error (bf16_policy.py; one p per module, row offset
+    and stream non-zero, poisoned workspace).  The cases: one row; the wave tile (15 / 16 / 17) and workgroup tile (63 / 64 / 65)
+    boundaries; no dropout; 2049 rows (20 empty weight-gradient slices); and 2 CUs 64 + 65 rows, where a workgroup runs a
+    second tile with the weight-slab pipeline carried over and the weight gradients take the serial route with 256 slices."""
+    import hip_helpers as hh
+    c = B.case(name, _cus())
+    fp, xd, yd = _dev_inputs(c.P, c.x, c.y, c.H, c.nh)
+    drop = hh.dropout_struct(c.mode, c.pl, seed=B.SEED, stream_id=B.STREAM, row_offset=B.ROW0)
+    grads, loss = hh.train_grads(lib, c.H, c.nh, fp, xd, yd, drop, precision=1)
+    _assert_in_band("%s (H %d, nh %d, %d rows)" % (name, c.H, c.nh, c.n), c.band, loss, grads, c.H, c.nh)
+
+
+@pytest.mark.parametrize("which", ["g_net128", "drawn65"])
+def test_bf16_injected_masks(lib, which):
+    """PINN_DROP_BITS through mlp_bf16_kernel<.., kBits = true> and train_chain_bf16_kernel<H, true>: the recorded torch masks of
+    g_net128.npz, and 65 drawn rows with one p per module (one row past a workgroup tile: the padding rows read the last mask
+    row).  Forward against mlp_forward(bf16=True) at the forward test's gate, the training step against the policy reference
+    under those masks, inside the band."""
+    import hip_helpers as hh
+    if which == "g_net128":
+        (P, x, y, pl, masks), band = B.golden_case(), B.golden_band()
+    else:
+        P, x, y, pl, masks, band = B.drawn_mask_case()
+    nh = (len(P) - 8) // 2
+    H = P[0].shape[0]
+    bits = hh.pack_mask_bits([masks]).to(hh.dev())
+    drop = hh.dropout_struct(2, pl, bits=bits)
+    fp, xd, yd = _dev_inputs(P, x, y, H, nh)
+    u, lv = hh.forward(lib, H, nh, fp, xd, drop, precision=1)
+    with torch.no_grad():
+        ub, lvb = O.mlp_forward(P, x, pl, masks, bf16=True)
+    np.testing.assert_allclose(u.cpu().numpy(), ub.numpy().reshape(-1), rtol=2e-3, atol=2e-3)
+    np.testing.assert_allclose(lv.cpu().numpy(), lvb.numpy().reshape(-1), rtol=2e-3, atol=2e-3)
+    grads, loss = hh.train_grads(lib, H, nh, fp, xd, yd, drop, precision=1)
+    _assert_in_band("injected masks, " + which, band, loss, grads, H, nh)
+
+
+def test_forward_and_mc_bf16_above_the_grid_cap(lib):
+    """2 CUs 64 + 65 rows of [8, 128, 1]: launch_forward_bf16 caps its grid at 2 CUs workgroups, so one workgroup runs a second
+    (and the ragged last) tile with the slab pipeline carried over.  Forward u / logvar and MC-dropout with T = 4 against the
+    same-policy oracle at the gates of test_forward_bf16 / test_mc_dropout_bf16."""
+    import hip_helpers as hh
+    import regimes as R
+    c = B.case("grid_cap", _cus())
+    T = 4
+    fp, xd, _ = _dev_inputs(c.P, c.x, c.y, c.H, c.nh)
+    drop = hh.dropout_struct(1, c.pl, seed=B.SEED, stream_id=B.STREAM, row_offset=B.ROW0)
+    u, lv = hh.forward(lib, c.H, c.nh, fp, xd, drop, precision=1)
+    o = _mc(lib, c.H, c.nh, fp, xd, drop, T).cpu().numpy()
+    passes = R.philox_masks_passes(c.layers, c.n, c.pl, [B.STREAM + t for t in range(T)], seed=B.SEED, row0=B.ROW0)
+    with torch.no_grad():
+        ue, _ = O.mlp_forward(c.P, c.x, bf16=True)
+        us, lvs = zip(*[O.mlp_forward(c.P, c.x, c.pl, m, bf16=True) for m in passes])
+    us = np.array([t.numpy().reshape(-1) for t in us]); lvs = np.array([t.numpy().reshape(-1) for t in lvs])
+    np.testing.assert_allclose(u.cpu().numpy(), us[0], rtol=2e-3, atol=2e-3)          # pass 0 = the training stream's masks
+    np.testing.assert_allclose(lv.cpu().numpy(), lvs[0], rtol=2e-3, atol=2e-3)
+    np.testing.assert_allclose(o[0], ue.numpy().reshape(-1), rtol=2e-3, atol=2e-3)
+    np.testing.assert_allclose(o[1], np.sqrt(np.exp(lvs.mean(0))), rtol=5e-3)
+    np.testing.assert_allclose(o[2], np.sqrt(us.var(0)), rtol=2e-2, atol=2e-3)
+
+
+def test_bf16_repeatable_and_shard_additive(lib):
+    """Two identical bf16 training calls are bitwise equal; two row shards with n_global = N and their row offsets sum to the full
+    call's gradient and loss sums within band_t (sharding only reorders the slab sums: no wider band is due)."""
+    import hip_helpers as hh
+    c = B.case("mid128")
+    fp, xd, yd = _dev_inputs(c.P, c.x, c.y, c.H, c.nh)
+    mk = lambda off: hh.dropout_struct(1, c.pl, seed=B.SEED, stream_id=B.STREAM, row_offset=B.ROW0 + off)
+    g1, l1 = hh.train_grads(lib, c.H, c.nh, fp, xd, yd, mk(0), precision=1)
+    g2, l2 = hh.train_grads(lib, c.H, c.nh, fp, xd, yd, mk(0), precision=1)
+    assert torch.equal(g1, g2) and torch.equal(l1, l2)
+    cut = 130
+    ga, la = hh.train_grads(lib, c.H, c.nh, fp, xd[:cut].contiguous(), yd[:cut].contiguous(), mk(0), n_global=c.n, precision=1)
+    gb, lb = hh.train_grads(lib, c.H, c.nh, fp, xd[cut:].contiguous(), yd[cut:].contiguous(), mk(cut), n_global=c.n, precision=1)
+    full = (l1.cpu().numpy()[:3], [g.numpy() for g in hh.unflat(g1.cpu(), c.H, c.nh)])
+    _assert_in_band("shards %d + %d against the full call" % (cut, c.n - cut), c.band, la + lb, ga + gb, c.H, c.nh, ref=full)
+    _assert_in_band("shards %d + %d against the reference" % (cut, c.n - cut), c.band, la + lb, ga + gb, c.H, c.nh)
+
+
+def test_mc_dropout_bf16_row_shards_and_eval_forward(lib):
+    """Bitwise: an MC-dropout call equals the concatenation of two row shards with their row offsets, and its o0 equals the eval
+    forward's u."""
+    import hip_helpers as hh
+    c = B.case("mid128")
+    T, cut = 4, 130
+    fp, xd, _ = _dev_inputs(c.P, c.x, c.y, c.H, c.nh)
+    mk = lambda off: hh.dropout_struct(1, c.pl, seed=B.SEED, stream_id=100, row_offset=B.ROW0 + off)
+    full = _mc(lib, c.H, c.nh, fp, xd, mk(0), T)
+    a, b = _mc(lib, c.H, c.nh, fp, xd[:cut].contiguous(), mk(0), T), _mc(lib, c.H, c.nh, fp, xd[cut:].contiguous(), mk(cut), T)
+    assert torch.equal(torch.cat([a, b], dim=1), full)
+    u, _ = hh.forward(lib, c.H, c.nh, fp, xd, None, precision=1)
+    torch.cuda.synchronize()
+    assert torch.equal(full[0], u)
