@@ -57,7 +57,8 @@ SOURCES = [
     ("pinn_optim.hip", []),
     ("pinn_general.hip", []),
 ]
-HEADERS = ["pinn_mlp_core.h", "pinn_bf16_core.h", "pinn_x6_core.h", "pinn_wgrad_args.h", "pinn_rows.h", os.path.join("..", "..", "include", "pinn_hip.h")]
+HEADERS = ["pinn_mlp_core.h", "pinn_bf16_core.h", "pinn_x6_core.h", "pinn_wgrad_args.h", "pinn_rows.h", "pinn_lloyd.h",
+           os.path.join("..", "..", "include", "pinn_hip.h")]
 
 
 class BuildError(RuntimeError):

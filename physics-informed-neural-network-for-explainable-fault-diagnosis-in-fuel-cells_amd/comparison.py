@@ -259,24 +259,76 @@ def assign_clusters(X, centres, cluster_class_prob=None, columns=None, row_index
     return {k: out[k] for k in want}
 
 
-def _km_state(torch, lib, rows, K, centres):
-    """A zeroed k-means state block with `centres` written into it, and the workspace."""
-    _check_limits(rows.D, K)
-    words = lib.pinn_km_state_bytes(rows.n, K, rows.D) // 8
-    st = torch.zeros(words, dtype=torch.float64, device=rows.dev)
-    c = _dev_vec(torch, centres, torch.float64, rows.dev)
-    if c.numel() != K * rows.D:
-        raise ValueError("the centres must be [%d, %d]" % (K, rows.D))
-    st[_HDR:_HDR + K * rows.D] = c
-    wb = lib.pinn_km_workspace_bytes(rows.n, K, rows.D)
-    return st, torch.empty(wb, dtype=torch.uint8, device=rows.dev), wb
-
-
+# ---------------------------------------------------------------------------------------------- Lloyd on the device
 def _km_header(st):
     h = st[:_HDR].cpu().numpy()
     i = h.view(np.int64)
     return {"n_iter": int(i[0]), "converged": bool(i[1]), "status": int(i[2]), "inertia": float(h[5]), "shift": float(h[6]),
             "tol_abs": float(h[7]), "strict": bool(i[8]), "changed": int(i[9]), "done": bool(i[10])}
+
+
+class _Lloyd:
+    """One of the two entry points of the Lloyd state machine (csrc/pinn_lloyd.h) with the rows it runs on: "pinn_km_lloyd"
+    reads rows in place (`head` = rows.head(), up to 8 features), "pinn_sp_lloyd" packed rows (`head` = (E, n, Dm), up to 32
+    columns).  The callers check their limits."""
+    SIZES = {"pinn_km_lloyd": ("pinn_km_state_bytes", "pinn_km_workspace_bytes"),
+             "pinn_sp_lloyd": ("pinn_sp_lloyd_state_bytes", "pinn_sp_lloyd_workspace_bytes")}
+
+    def __init__(self, torch, lib, entry, head, n, D, dev):
+        self.torch, self.entry, self.head, self.n, self.D, self.dev = torch, entry, head, n, D, dev
+        self.state_bytes, self.workspace_bytes = (getattr(lib, name) for name in self.SIZES[entry])
+
+    def state(self, K, centres):
+        """A zeroed state block with `centres` written into it, and the workspace."""
+        torch, D = self.torch, self.D
+        st = torch.zeros(self.state_bytes(self.n, K, D) // 8, dtype=torch.float64, device=self.dev)
+        c = _dev_vec(torch, centres, torch.float64, self.dev)
+        if c.numel() != K * D:
+            raise ValueError("the centres must be [%d, %d]" % (K, D))
+        st[_HDR:_HDR + K * D] = c
+        wb = self.workspace_bytes(self.n, K, D)
+        return st, torch.empty(wb, dtype=torch.uint8, device=self.dev), wb
+
+    def result(self, st, K):
+        """(centres [K, D], labels [n]) copied out of a state block."""
+        D = self.D
+        return st[_HDR:_HDR + K * D].reshape(K, D).clone(), st[_HDR + K * D + K + D:].view(self.torch.int64).clone()
+
+    def run(self, K, centres, max_iter, tol, chunk):
+        """Iterations in chunks until converged, a status or max_iter, then the finishing call: (state, its header)."""
+        stream = self.torch.cuda.current_stream().cuda_stream
+        st, ws, wb = self.state(K, centres)
+        done, init = 0, 1
+        while True:
+            step = min(chunk, max_iter - done)
+            call(self.entry, *self.head, K, init, step, tol, 0, st, ws, wb, stream=stream)
+            done, init = done + step, 0
+            h = _km_header(st)                                 # one read of the header per chunk
+            if h["converged"] or h["status"] or done >= max_iter:
+                break
+        if h["status"]:
+            raise ValueError("the rows hold values that are not finite (status %d)" % h["status"])
+        call(self.entry, *self.head, K, 0, 0, tol, 1, st, ws, wb, stream=stream)
+        return st, _km_header(st)
+
+    def probe(self, K, centres, tol, as_tensor):
+        """One iteration from `centres`: the device dict of lloyd_iteration."""
+        st, ws, wb = self.state(K, centres)
+        call(self.entry, *self.head, K, 1, 1, float(tol), 0, st, ws, wb)
+        h = _km_header(st)
+        if h["status"]:
+            raise ValueError("the rows hold values that are not finite")
+        F = 1 + 2 * self.D
+        new, labels = self.result(st, K)
+        out = {"labels": labels, "sums": ws[:K * F * 8].view(self.torch.float64).reshape(K, F).clone(), "centres": new}
+        if not as_tensor:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+        out.update(shift=h["shift"], inertia=h["inertia"], tol_abs=h["tol_abs"])
+        return out
+
+
+def _narrow(torch, lib, rows):
+    return _Lloyd(torch, lib, "pinn_km_lloyd", rows.head(), rows.n, rows.D, rows.dev)
 
 
 def lloyd_iteration(X, centres, columns=None, row_index=None, tol=1e-4, backend="auto"):
@@ -292,19 +344,9 @@ def lloyd_iteration(X, centres, columns=None, row_index=None, tol=1e-4, backend=
                 "tol_abs": host_tolerance(Xh, tol), "margin": margin}
     torch, _lib, lib = _torch_lib()
     rows = _rows(torch, X, columns, row_index)
+    _check_limits(rows.D, K)
     with torch.cuda.device(rows.dev):
-        st, ws, wb = _km_state(torch, lib, rows, K, c0)
-        call("pinn_km_lloyd", *rows.head(), K, 1, 1, float(tol), 0, st, ws, wb)
-        h = _km_header(st)
-        if h["status"]:
-            raise ValueError("the rows hold values that are not finite")
-        D, F = rows.D, 1 + 2 * rows.D
-        out = {"labels": st[_HDR + K * D + K + D:].view(torch.int64).clone(), "sums": ws[:K * F * 8].view(torch.float64).reshape(K, F).clone(),
-               "centres": st[_HDR:_HDR + K * D].reshape(K, D).clone()}
-    if not _is_tensor(X):
-        out = {k: v.cpu().numpy() for k, v in out.items()}
-    out.update(shift=h["shift"], inertia=h["inertia"], tol_abs=h["tol_abs"])
-    return out
+        return _narrow(torch, lib, rows).probe(K, c0, tol, _is_tensor(X))
 
 
 # ---------------------------------------------------------------------------------------------- k-means
@@ -369,14 +411,14 @@ class DeviceKMeans:
             return int(min(np.searchsorted(c, u * c[-1], side="right"), n - 1))
         return X[self._picks(rng, n, lambda i: _host_d2(X, X[i]), np.minimum, lambda v: float(v.sum()), search)]
 
-    def _device_seeds(self, torch, rng, rows):
-        Xp, n = rows.packed(torch), rows.n
+    def _device_seeds(self, torch, rng, Xp):
+        n = int(Xp.shape[0])
 
         def search(d2, u):
             c = torch.cumsum(d2, dim=0)
             return int(min(int(torch.searchsorted(c, (c[-1] * u).reshape(1), right=True).item()), n - 1))
         picks = self._picks(rng, n, lambda i: ((Xp - Xp[i]) ** 2).sum(dim=1), torch.minimum, lambda v: float(v.sum().item()), search)
-        return Xp[torch.tensor(picks, device=rows.dev)]
+        return Xp[torch.tensor(picks, device=Xp.device)]
 
     def _given_init(self, D):
         c = _as_numpy(self.init, np.float64)
@@ -410,27 +452,14 @@ class DeviceKMeans:
         rng = np.random.default_rng(self.random_state)
         best = None
         with torch.cuda.device(rows.dev):
-            stream = torch.cuda.current_stream().cuda_stream
+            lloyd = _narrow(torch, lib, rows)
             for _ in range(self._runs()):
-                c0 = self._device_seeds(torch, rng, rows) if isinstance(self.init, str) else self._given_init(D)
-                st, ws, wb = _km_state(torch, lib, rows, K, c0)
-                done, init = 0, 1
-                while True:
-                    step = min(self.chunk, self.max_iter - done)
-                    call("pinn_km_lloyd", *rows.head(), K, init, step, self.tol, 0, st, ws, wb, stream=stream)
-                    done, init = done + step, 0
-                    h = _km_header(st)                         # one read of the header per chunk
-                    if h["converged"] or h["status"] or done >= self.max_iter:
-                        break
-                if h["status"]:
-                    raise ValueError("the rows hold values that are not finite (status %d)" % h["status"])
-                call("pinn_km_lloyd", *rows.head(), K, 0, 0, self.tol, 1, st, ws, wb, stream=stream)
-                h = _km_header(st)
+                c0 = self._device_seeds(torch, rng, rows.packed(torch)) if isinstance(self.init, str) else self._given_init(D)
+                st, h = lloyd.run(K, c0, self.max_iter, self.tol, self.chunk)
                 if best is None or h["inertia"] < best[1]["inertia"]:
                     best = (st, h)
             st, h = best
-            centres = st[_HDR:_HDR + K * D].reshape(K, D).clone()
-            labels = st[_HDR + K * D + K + D:].view(torch.int64).clone()
+            centres, labels = lloyd.result(st, K)
         as_tensor = _is_tensor(X)
         self.cluster_centers_ = centres if as_tensor else centres.cpu().numpy()
         self.labels_ = labels if as_tensor else labels.cpu().numpy()

@@ -3,7 +3,7 @@
 //   pinn_sp_affinity   CSR of A = 0.5 (C + C^T) without its diagonal, degrees and their roots
 //   pinn_sp_eigs       the K largest eigenpairs of S = D^{-1/2} A D^{-1/2} by Chebyshev-filtered subspace iteration
 //   pinn_sp_embed      scikit-learn's embedding q_j / dd with its sign rule
-//   pinn_sp_lloyd      the Lloyd state machine of pinn_km_lloyd on packed rows of up to 32 columns
+//   pinn_sp_lloyd      the Lloyd state machine of pinn_lloyd.h on packed rows of up to 32 columns
 // All arithmetic is float64, every operation rounded on its own (built with -ffp-contract=off).
 //
 // The eigen stage works on a block of m = min(n, K + 16) columns.  One outer iteration is a queue of launches: S Q (a
@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "../../include/pinn_hip.h"
+#include "pinn_lloyd.h"
 #include "pinn_rows.h"
 
 namespace pinn {
@@ -36,18 +37,14 @@ constexpr int kGBlocks = 128;                // workgroups of those passes = par
 constexpr int kGOut = (kMaxM * kMaxM + kBT - 1) / kBT;       // outputs per thread of the Gram pass: 9
 constexpr int kROut = (kGR * kMaxM + kBT - 1) / kBT;         // elements per thread of a rotation tile: 6
 constexpr int kSweeps = 30;
-constexpr int kLR = 128;                     // rows per tile of the wide Lloyd pass
 constexpr int kLMaxD = PINN_SP_MAX_DIM, kLMaxK = PINN_SP_MAX_CLUSTERS;
-constexpr int kLOut = (kLMaxK * (1 + 2 * kLMaxD) + kBT - 1) / kBT;   // output sums per thread: 9
-constexpr int kLBlocks = 256;
+constexpr int kLBlocks = 256;                // workgroups of a Lloyd row pass = partial sums per output
 
 static_assert(kMaxD == kRowsMaxD, "pinn_rows.h carries the same limit");
 
 enum { GRAM_H = 0, GRAM_SRC = 1, GRAM_A = 2 };
 enum { JAC_RITZ = 0, JAC_ORTHO = 1 };
 enum { ROT_RITZ = 0, ROT_SRC = 1, ROT_A = 2 };
-enum { LAB_ASSIGN = 0, LAB_WRITE = 1, LAB_GIVEN = 2, LAB_FINISH = 3 };
-enum { FIN_MEAN = 0, FIN_VAR = 1, FIN_LLOYD = 2, FIN_FINISH = 3 };
 
 __host__ __device__ inline int block_cols(long long n, int K) { return (int)(n < (long long)(K + PINN_SP_GUARD) ? n : (long long)(K + PINN_SP_GUARD)); }
 
@@ -56,18 +53,6 @@ __host__ __device__ inline size_t eg_theta() { return kHdr; }
 __host__ __device__ inline size_t eg_res(int m) { return kHdr + (size_t)m; }
 __host__ __device__ inline size_t eg_q(int m) { return kHdr + 2 * (size_t)m; }
 __host__ __device__ inline size_t eg_words(long long n, int m) { return eg_q(m) + (size_t)n * m; }
-
-// Lloyd state, as pinn_cluster.hip's: header, centres [K][D], counts [K], mean [D], labels [n]
-__host__ __device__ inline size_t km_centres() { return kHdr; }
-__host__ __device__ inline size_t km_counts(int K, int D) { return kHdr + (size_t)K * D; }
-__host__ __device__ inline size_t km_mean(int K, int D) { return km_counts(K, D) + (size_t)K; }
-__host__ __device__ inline size_t km_labels(int K, int D) { return km_mean(K, D) + (size_t)D; }
-__host__ __device__ inline size_t km_words(long long n, int K, int D) { return km_labels(K, D) + (size_t)n; }
-
-__device__ __forceinline__ bool stopped(const double* st) {
-  const long long* h = reinterpret_cast<const long long*>(st);
-  return h[PINN_CL_ST_CONVERGED] != 0 || h[PINN_CL_ST_STATUS] != 0;
-}
 
 // ---------------------------------------------------------------------------------------------- neighbour search
 // One thread per position keeps its k best candidates, sorted, in LDS (slot-major: no bank conflicts).  Candidates come in
@@ -583,176 +568,6 @@ __global__ __launch_bounds__(kBT) void embed_write_kernel(long long n, int m, in
   out[e] = sign[j] * embed_value(q, dd, i, m, j);
 }
 
-// ---------------------------------------------------------------------------------------------- Lloyd on wide rows
-// As km_rows_kernel of pinn_cluster.hip, with the tile of packed rows staged through LDS: K x F sums per workgroup,
-// F = 1 + 2 D columns (1, d_i, d_i^2), d = x - the centre of the row's label.
-__global__ __launch_bounds__(kBT) void wl_rows_kernel(const double* __restrict__ X, long long n, int D, int K, const double* __restrict__ st,
-                                                      const double* __restrict__ centres, int mode, long long* __restrict__ labels, int force,
-                                                      double* __restrict__ part, long long* __restrict__ part_chg) {
-  __shared__ double s_x[kLR * (kLMaxD + 1)];
-  __shared__ double s_mu[kLMaxK * kLMaxD];
-  __shared__ int s_lab[kLR];
-  __shared__ long long s_chg[kLR];
-  if (!force && stopped(st)) return;
-  const int Dp = D | 1, F = 1 + 2 * D, KF = K * F, t = threadIdx.x;
-  if (mode == LAB_FINISH) mode = reinterpret_cast<const long long*>(st)[PINN_KM_ST_STRICT] != 0 ? LAB_GIVEN : LAB_WRITE;
-  for (int e = t; e < K * D; e += kBT) s_mu[e] = centres[e];
-
-  int ok_[kLOut], of[kLOut];
-  double acc[kLOut];
-#pragma unroll
-  for (int q = 0; q < kLOut; ++q) {
-    const int o = t + q * kBT;
-    acc[q] = 0.0;
-    ok_[q] = -1; of[q] = 0;
-    if (o < KF) { ok_[q] = o / F; of[q] = o - ok_[q] * F; }
-  }
-
-  long long chg = 0;
-  const long long tiles = (n + kLR - 1) / kLR;
-  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const long long r0 = tile * kLR;
-    const int rows = (int)(n - r0 < (long long)kLR ? n - r0 : (long long)kLR);
-    __syncthreads();
-    for (int e = t; e < kLR * D; e += kBT) {
-      const int r = e / D, c = e - r * D;
-      s_x[r * Dp + c] = r < rows ? X[r0 * D + e] : 0.0;
-    }
-    __syncthreads();
-    if (t < kLR) {
-      int lab = -1;
-      if (t < rows) {
-        const long long j = r0 + t;
-        if (mode == LAB_GIVEN) {
-          const long long l = labels[j];
-          lab = (l >= 0 && l < K) ? (int)l : -1;
-        } else {
-          double bd = INFINITY;
-          lab = 0;
-          for (int k = 0; k < K; ++k) {
-            double d2 = 0.0;
-            for (int i = 0; i < D; ++i) { const double d = s_x[t * Dp + i] - s_mu[k * D + i]; d2 += d * d; }
-            if (d2 < bd) { bd = d2; lab = k; }
-          }
-          if (mode == LAB_WRITE) {
-            chg += labels[j] != (long long)lab;
-            labels[j] = lab;
-          }
-        }
-      }
-      s_lab[t] = lab;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kLOut; ++q) {
-      const int k = ok_[q];
-      if (k >= 0) {
-        const int f = of[q];
-        double s = acc[q];
-        if (f == 0) {
-          for (int rr = 0; rr < kLR; ++rr) s += s_lab[rr] == k ? 1.0 : 0.0;
-        } else if (f <= D) {
-          const double mu = s_mu[k * D + f - 1];
-          for (int rr = 0; rr < kLR; ++rr) s += s_lab[rr] == k ? s_x[rr * Dp + f - 1] - mu : 0.0;
-        } else {
-          const double mu = s_mu[k * D + f - 1 - D];
-          for (int rr = 0; rr < kLR; ++rr) {
-            const double d = s_x[rr * Dp + f - 1 - D] - mu;
-            s += s_lab[rr] == k ? d * d : 0.0;
-          }
-        }
-        acc[q] = s;
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < kLOut; ++q)
-    if (ok_[q] >= 0) part[(size_t)blockIdx.x * KF + t + q * kBT] = acc[q];
-  __syncthreads();
-  if (t < kLR) s_chg[t] = chg;
-  __syncthreads();
-  if (t == 0) {
-    long long s = 0;
-    for (int rr = 0; rr < kLR; ++rr) s += s_chg[rr];
-    part_chg[blockIdx.x] = s;
-  }
-}
-
-// km_final_kernel of pinn_cluster.hip at the wider limits.  One workgroup.
-__global__ __launch_bounds__(kBT) void wl_final_kernel(double* __restrict__ st, double* __restrict__ centres, double* __restrict__ counts, int K, int D,
-                                                       int mode, int n_part, long long n, int K_state, double tol, const double* __restrict__ part,
-                                                       const long long* __restrict__ part_chg, double* __restrict__ tot) {
-  __shared__ double n_mu[kLMaxK * kLMaxD], s_shift[kLMaxK], s_in[kLMaxK];
-  long long* hdr = reinterpret_cast<long long*>(st);
-  if (mode == FIN_LLOYD && stopped(st)) return;
-  const int F = 1 + 2 * D, KF = K * F, t = threadIdx.x;
-  for (int o = t; o < KF; o += kBT) {
-    double s = 0.0;
-    for (int g = 0; g < n_part; ++g) s += part[(size_t)g * KF + o];
-    tot[o] = s;
-  }
-  __syncthreads();
-
-  if (mode == FIN_MEAN) {                                      // K = 1, centre 0: the column means
-    if (t < D) st[km_mean(K_state, D) + t] = tot[0] > 0.0 ? tot[1 + t] / tot[0] : 0.0;
-    return;
-  }
-  if (mode == FIN_VAR) {                                       // K = 1, centre = the means: tol_abs = tol mean_j var_j
-    if (t == 0) {
-      double s = 0.0;
-      for (int i = 0; i < D; ++i) s += tot[0] > 0.0 ? tot[1 + D + i] / tot[0] : 0.0;
-      hdr[PINN_CL_ST_ITER] = 0; hdr[PINN_CL_ST_CONVERGED] = 0; hdr[PINN_CL_ST_STATUS] = 0;
-      hdr[PINN_KM_ST_K] = K_state; hdr[PINN_KM_ST_D] = D; hdr[PINN_KM_ST_N] = n;
-      hdr[PINN_KM_ST_STRICT] = 0; hdr[PINN_KM_ST_CHANGED] = 0; hdr[PINN_KM_ST_DONE] = 0;
-      st[PINN_KM_ST_INERTIA] = INFINITY; st[PINN_KM_ST_SHIFT] = INFINITY;
-      st[PINN_KM_ST_TOL_ABS] = tol * (s / (double)D);
-    }
-    return;
-  }
-  if (t < K) {
-    const double cnt = tot[t * F];
-    double sh = 0.0, in = 0.0;
-    for (int i = 0; i < D; ++i) {
-      const double old = centres[t * D + i];
-      const double nw = (mode != FIN_FINISH && cnt > 0.0) ? old + tot[t * F + 1 + i] / cnt : old;   // an empty cluster keeps its centre
-      n_mu[t * D + i] = nw;
-      sh += (nw - old) * (nw - old);
-      in += tot[t * F + 1 + D + i];
-    }
-    s_shift[t] = sh;
-    s_in[t] = in;
-  }
-  __syncthreads();
-  double shift = 0.0, inertia = 0.0;
-  for (int k = 0; k < K; ++k) { shift += s_shift[k]; inertia += s_in[k]; }
-  if (!(shift == shift) || !(inertia == inertia)) {
-    if (t == 0) hdr[PINN_CL_ST_STATUS] = PINN_SP_NAN;           // the state keeps the last good centres
-    return;
-  }
-  if (t < K) {
-    for (int i = 0; i < D; ++i) centres[t * D + i] = n_mu[t * D + i];
-    counts[t] = tot[t * F];
-  }
-  if (t != 0) return;
-  if (mode == FIN_FINISH) {
-    st[PINN_KM_ST_INERTIA] = inertia;
-    hdr[PINN_KM_ST_DONE] = 1;
-    return;
-  }
-  long long chg = 0;
-  for (int g = 0; g < n_part; ++g) chg += part_chg[g];
-  hdr[PINN_CL_ST_ITER] += 1;
-  hdr[PINN_KM_ST_CHANGED] = chg;
-  st[PINN_KM_ST_INERTIA] = inertia;
-  st[PINN_KM_ST_SHIFT] = shift;
-  if (chg == 0) {
-    hdr[PINN_KM_ST_STRICT] = 1;
-    hdr[PINN_CL_ST_CONVERGED] = 1;
-  } else if (shift <= st[PINN_KM_ST_TOL_ABS]) {
-    hdr[PINN_CL_ST_CONVERGED] = 1;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------- host side
 inline bool rows_ok(long long n) { return n >= 1 && n <= (long long)PINN_SP_MAX_ROWS; }
 inline bool eig_ok(long long n, int K) { return rows_ok(n) && K >= 1 && K <= kMaxK && (long long)K <= n; }
@@ -791,23 +606,6 @@ inline EigWs eig_carve(void* d_ws, long long n, int m) {
   s.part = reinterpret_cast<double*>(w); w += align256((size_t)kGBlocks * m * m * 8);
   s.part_res = reinterpret_cast<double*>(w); w += align256((size_t)kGBlocks * m * 8);
   s.sign = reinterpret_cast<double*>(w);
-  return s;
-}
-
-struct LlWs {
-  double *tot, *part;
-  long long* part_chg;
-};
-
-inline size_t ll_tot_bytes(int K, int D) { return align256((size_t)K * (1 + 2 * D) * sizeof(double)); }
-inline size_t ll_part_bytes(int K, int D) { return align256((size_t)kLBlocks * K * (1 + 2 * D) * sizeof(double)); }
-
-inline LlWs ll_carve(void* d_ws, int K, int D) {
-  char* w = static_cast<char*>(d_ws);
-  LlWs s;
-  s.tot = reinterpret_cast<double*>(w); w += ll_tot_bytes(K, D);
-  s.part = reinterpret_cast<double*>(w); w += ll_part_bytes(K, D);
-  s.part_chg = reinterpret_cast<long long*>(w);
   return s;
 }
 
@@ -944,7 +742,7 @@ extern "C" size_t pinn_sp_lloyd_state_bytes(long long n, int n_clusters, int n_d
 extern "C" size_t pinn_sp_lloyd_workspace_bytes(long long n, int n_clusters, int n_dim) {
   using namespace pinn;
   if (!lloyd_ok(n, n_clusters, n_dim)) return 0;
-  return ll_tot_bytes(n_clusters, n_dim) + ll_part_bytes(n_clusters, n_dim) + align256(kLBlocks * sizeof(long long));
+  return lloyd_workspace_bytes(kLBlocks, n_clusters, n_dim);
 }
 
 extern "C" int pinn_sp_lloyd(const double* d_x, long long n, int n_dim, int n_clusters, int init, int n_iters, double tol, int finish,
@@ -953,34 +751,6 @@ extern "C" int pinn_sp_lloyd(const double* d_x, long long n, int n_dim, int n_cl
   if (!lloyd_ok(n, n_clusters, n_dim) || n_iters < 0 || n_iters > 100000 || !(tol >= 0.0)) return PINN_E_ARG;
   if (!d_x || !d_state || !d_ws || misaligned8(d_x) || misaligned8(d_state) || misaligned8(d_ws)) return PINN_E_ARG;
   if (ws_bytes < pinn_sp_lloyd_workspace_bytes(n, n_clusters, n_dim)) return PINN_E_WORKSPACE;
-  const LlWs w = ll_carve(d_ws, n_clusters, n_dim);
-  hipStream_t st = (hipStream_t)stream;
-  clear_error();
-  const int K = n_clusters, D = n_dim, G = row_blocks(n, kLR, kLBlocks);
-  double* centres = d_state + km_centres();
-  double* counts = d_state + km_counts(K, D);
-  double* mean = d_state + km_mean(K, D);
-  long long* labels = reinterpret_cast<long long*>(d_state + km_labels(K, D));
-  if (init) {
-    hipError_t e = hipMemsetAsync(labels, 0xff, (size_t)n * sizeof(long long), st);        // label -1: the first pass changes every row
-    if (e == hipSuccess) e = hipMemsetAsync(mean, 0, (size_t)D * sizeof(double), st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(wl_rows_kernel, dim3(G), dim3(kBT), 0, st, d_x, n, D, 1, d_state, mean, (int)LAB_ASSIGN, nullptr, 1, w.part, w.part_chg);
-    hipLaunchKernelGGL(wl_final_kernel, dim3(1), dim3(kBT), 0, st, d_state, nullptr, nullptr, 1, D, (int)FIN_MEAN, G, n, K, tol, w.part, w.part_chg,
-                       w.tot);
-    hipLaunchKernelGGL(wl_rows_kernel, dim3(G), dim3(kBT), 0, st, d_x, n, D, 1, d_state, mean, (int)LAB_ASSIGN, nullptr, 1, w.part, w.part_chg);
-    hipLaunchKernelGGL(wl_final_kernel, dim3(1), dim3(kBT), 0, st, d_state, nullptr, nullptr, 1, D, (int)FIN_VAR, G, n, K, tol, w.part, w.part_chg,
-                       w.tot);
-  }
-  for (int it = 0; it < n_iters; ++it) {
-    hipLaunchKernelGGL(wl_rows_kernel, dim3(G), dim3(kBT), 0, st, d_x, n, D, K, d_state, centres, (int)LAB_WRITE, labels, 0, w.part, w.part_chg);
-    hipLaunchKernelGGL(wl_final_kernel, dim3(1), dim3(kBT), 0, st, d_state, centres, counts, K, D, (int)FIN_LLOYD, G, n, K, tol, w.part, w.part_chg,
-                       w.tot);
-  }
-  if (finish) {
-    hipLaunchKernelGGL(wl_rows_kernel, dim3(G), dim3(kBT), 0, st, d_x, n, D, K, d_state, centres, (int)LAB_FINISH, labels, 1, w.part, w.part_chg);
-    hipLaunchKernelGGL(wl_final_kernel, dim3(1), dim3(kBT), 0, st, d_state, centres, counts, K, D, (int)FIN_FINISH, G, n, K, tol, w.part, w.part_chg,
-                       w.tot);
-  }
-  return launch_status();
+  return lloyd_queue<PackedSrc, kLMaxK, kLMaxD, kBT>(PackedSrc{d_x}, n, n_dim, n_clusters, kLBlocks, init, n_iters, tol, finish, d_state, d_ws,
+                                                     (hipStream_t)stream);
 }

@@ -24,13 +24,12 @@ machines without a GPU and as the referee of the device tests.  numpy in -> nump
 out.  Importing this module needs numpy only; neither scipy nor scikit-learn is imported.
 """
 import math
-import types
 import warnings
 
 import numpy as np
 
 from ._device import _DevRows, _as_numpy, _dev_vec, _host_rows, _is_tensor, _on_gpu, _pick_backend, _torch_lib, call
-from .comparison import _HDR, DeviceKMeans, _host_lloyd, _host_step, _posterior_from, host_tolerance
+from .comparison import _HDR, DeviceKMeans, _Lloyd, _host_lloyd, _host_step, _posterior_from, host_tolerance
 
 MAX_FEAT, MAX_NEIGHBORS, MAX_COMPONENTS, MAX_CLUSTERS, MAX_DIM, MAX_ROWS = 8, 32, 32, 32, 32, 1 << 24
 GUARD, MAX_DEGREE, GROWTH = 16, 40, 1e8          # block columns beyond K; Chebyshev steps of a filter; its largest growth
@@ -319,32 +318,18 @@ def spectral_embedding(affinity, n_components, tol=1e-10, max_iter=100, random_s
 
 
 # ---------------------------------------------------------------------------------------------- k-means on wide rows
-def _wide_state(torch, lib, E, K, centres):
-    n, Dm = int(E.shape[0]), int(E.shape[1])
+def _wide(E, K):
+    """(_Lloyd on the packed rows E as a float64 device block, that block's device)."""
+    torch, _lib, lib = _torch_lib()
+    Ed = E if _on_gpu(E) else torch.from_numpy(np.ascontiguousarray(_as_numpy(E, np.float64))).cuda()
+    if Ed.dim() != 2:
+        raise ValueError("the rows must be a 2-D array")
+    Ed = Ed.detach().to(torch.float64).contiguous()
+    n, Dm = int(Ed.shape[0]), int(Ed.shape[1])
     if not (1 <= Dm <= MAX_DIM):
         raise NotImplementedError("the device backend takes rows of up to %d columns, got %d" % (MAX_DIM, Dm))
     _check_limits(n_clusters=K, n=n)
-    st = torch.zeros(lib.pinn_sp_lloyd_state_bytes(n, K, Dm) // 8, dtype=torch.float64, device=E.device)
-    c = _dev_vec(torch, centres, torch.float64, E.device)
-    if c.numel() != K * Dm:
-        raise ValueError("the centres must be [%d, %d]" % (K, Dm))
-    st[_HDR:_HDR + K * Dm] = c
-    wb = lib.pinn_sp_lloyd_workspace_bytes(n, K, Dm)
-    return st, torch.empty(wb, dtype=torch.uint8, device=E.device), wb
-
-
-def _km_header(st):
-    h = st[:_HDR].cpu().numpy()
-    i = h.view(np.int64)
-    return {"n_iter": int(i[0]), "converged": bool(i[1]), "status": int(i[2]), "inertia": float(h[5]), "shift": float(h[6]),
-            "tol_abs": float(h[7]), "strict": bool(i[8])}
-
-
-def _dev_block(torch, E):
-    t = E if _on_gpu(E) else torch.from_numpy(np.ascontiguousarray(_as_numpy(E, np.float64))).cuda()
-    if t.dim() != 2:
-        raise ValueError("the rows must be a 2-D array")
-    return t.detach().to(torch.float64).contiguous()
+    return _Lloyd(torch, lib, "pinn_sp_lloyd", (Ed, n, Dm), n, Dm, Ed.device), torch.cuda.device(Ed.device)
 
 
 def wide_lloyd_iteration(E, centres, tol=KM_TOL, backend="auto"):
@@ -357,22 +342,9 @@ def wide_lloyd_iteration(E, centres, tol=KM_TOL, backend="auto"):
         lab, S, A, new, shift, margin = _host_step(Eh, c0)
         return {"labels": lab, "sums": S, "abs_sums": A, "centres": new, "shift": shift, "inertia": float(S[:, 1 + c0.shape[1]:].sum()),
                 "tol_abs": host_tolerance(Eh, tol), "margin": margin}
-    torch, _lib, lib = _torch_lib()
-    Ed = _dev_block(torch, E)
-    n, Dm = int(Ed.shape[0]), int(Ed.shape[1])
-    with torch.cuda.device(Ed.device):
-        st, ws, wb = _wide_state(torch, lib, Ed, K, c0)
-        call("pinn_sp_lloyd", Ed, n, Dm, K, 1, 1, float(tol), 0, st, ws, wb)
-        h = _km_header(st)
-        if h["status"]:
-            raise ValueError("the rows hold values that are not finite")
-        F = 1 + 2 * Dm
-        out = {"labels": st[_HDR + K * Dm + K + Dm:].view(torch.int64).clone(), "sums": ws[:K * F * 8].view(torch.float64).reshape(K, F).clone(),
-               "centres": st[_HDR:_HDR + K * Dm].reshape(K, Dm).clone()}
-    if not _is_tensor(E):
-        out = {key: v.cpu().numpy() for key, v in out.items()}
-    out.update(shift=h["shift"], inertia=h["inertia"], tol_abs=h["tol_abs"])
-    return out
+    lloyd, device = _wide(E, K)
+    with device:
+        return lloyd.probe(K, c0, tol, _is_tensor(E))
 
 
 def wide_lloyd(E, centres, max_iter=KM_MAX_ITER, tol=KM_TOL, backend="auto", chunk=16):
@@ -384,25 +356,10 @@ def wide_lloyd(E, centres, max_iter=KM_MAX_ITER, tol=KM_TOL, backend="auto", chu
         Eh = np.ascontiguousarray(_as_numpy(E, np.float64))
         cen, lab, inertia, n_iter, strict = _host_lloyd(Eh, c0, int(max_iter), host_tolerance(Eh, tol))
         return {"centres": cen, "labels": lab, "inertia": inertia, "n_iter": n_iter, "strict": strict}
-    torch, _lib, lib = _torch_lib()
-    Ed = _dev_block(torch, E)
-    n, Dm = int(Ed.shape[0]), int(Ed.shape[1])
-    with torch.cuda.device(Ed.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        st, ws, wb = _wide_state(torch, lib, Ed, K, c0)
-        done, init = 0, 1
-        while True:
-            step = min(int(chunk), int(max_iter) - done)
-            call("pinn_sp_lloyd", Ed, n, Dm, K, init, step, float(tol), 0, st, ws, wb, stream=stream)
-            done, init = done + step, 0
-            h = _km_header(st)                                   # one read of the header per chunk
-            if h["converged"] or h["status"] or done >= int(max_iter):
-                break
-        if h["status"]:
-            raise ValueError("the rows hold values that are not finite (status %d)" % h["status"])
-        call("pinn_sp_lloyd", Ed, n, Dm, K, 0, 0, float(tol), 1, st, ws, wb, stream=stream)
-        h = _km_header(st)
-        out = {"centres": st[_HDR:_HDR + K * Dm].reshape(K, Dm).clone(), "labels": st[_HDR + K * Dm + K + Dm:].view(torch.int64).clone()}
+    lloyd, device = _wide(E, K)
+    with device:
+        st, h = lloyd.run(K, c0, int(max_iter), float(tol), int(chunk))
+        out = dict(zip(("centres", "labels"), lloyd.result(st, K)))
     if not _is_tensor(E):
         out = {key: v.cpu().numpy() for key, v in out.items()}
     out.update(inertia=h["inertia"], n_iter=h["n_iter"], strict=h["strict"])
@@ -416,7 +373,7 @@ def _kmeans_restarts(E, n_clusters, n_init, rng, backend):
     for _ in range(int(n_init)):
         if _on_gpu(E):
             import torch
-            c0 = seeder._device_seeds(torch, rng, types.SimpleNamespace(packed=lambda _t: E, n=int(E.shape[0]), dev=E.device))
+            c0 = seeder._device_seeds(torch, rng, E)
         else:
             c0 = seeder._host_seeds(rng, E)
         run = wide_lloyd(E, c0, backend=backend)

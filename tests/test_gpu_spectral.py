@@ -4,7 +4,8 @@ numpy, the same steps) and tests/golden/g_spectral.npz.
 Gates (from the arithmetic and the fixture, not from what the kernels give): neighbour lists equal and squared
 distances bit-equal to the host's; CSR equal; the eigen stage converged with residuals <= tol, eigenvalues within 1e-12
 of a dense eigvalsh, the projector within the Davis-Kahan bound sqrt(2) |R|_F / gap of a dense eigh, at most 3 x the
-host's outer iterations; one Lloyd iteration on wide rows under the gates of tests/test_gpu_comparison.py; the fixture end to
+host's outer iterations; one Lloyd iteration on wide rows under the gates of tests/test_gpu_comparison.py, and
+byte for byte what the narrow entry point gives on data both take (up to 256 tiles); the fixture end to
 end inside the bands of tests/test_spectral_host.py.  Drawn cases are held to the input conditions on the host first, at
 most 3 redraws.  In-place and gathered reads, repeated calls and another chunking are compared byte for byte.  Every
 comparison prints its maxima before it asserts."""
@@ -163,6 +164,19 @@ def test_one_wide_lloyd_iteration_against_the_host(S, P, n, K, Dm):
     assert np.all(err <= 1e-12 * h["abs_sums"])
     assert e_c <= 1e-12 and e_i <= 1e-12 and e_t <= 1e-12
     assert abs(d["shift"] - h["shift"]) <= 1e-12 * max(h["shift"], 1e-300) + 1e-24
+
+
+@pytest.mark.parametrize("n,K,D", [(n, K, D) for n in (1, 129, 2049) for K in (1, 20, 32) for D in (1, 8)])
+def test_narrow_and_wide_lloyd_give_the_same_bytes(S, P, n, K, D):
+    """Data both entry points take: up to 256 tiles (32768 rows) they launch the same number of workgroups, so every sum
+    has one order (csrc/pinn_lloyd.h) and the results are equal, not close.  Above that the caps on workgroups differ."""
+    X, c0, _ = lloyd_case(P, n, K, D)
+    a = P.lloyd_iteration(X, c0, backend="device")
+    b = S.wide_lloyd_iteration(X, c0, backend="device")
+    for key in ("labels", "sums", "centres"):
+        assert a[key].dtype == b[key].dtype and a[key].shape == b[key].shape and a[key].tobytes() == b[key].tobytes(), key
+    for key in ("shift", "inertia", "tol_abs"):
+        assert a[key] == b[key], (key, a[key], b[key])
 
 
 def test_full_lloyd_on_the_fixtures_embedding(G, S, P):

@@ -94,7 +94,7 @@ def main():
         cmap = np.random.default_rng(0).dirichlet(np.ones(C), K)
         for layout, arr, cols in (("packed", torch.from_numpy(X).cuda(), None), ("in_place", torch.from_numpy(full).cuda(), [13, 14, 15, 16])):
             rows = _DevRows(torch, arr, cols)
-            st, ws, wb = P._km_state(torch, lib, rows, K, centres)
+            st, ws, wb = P._narrow(torch, lib, rows).state(K, centres)
             lib.pinn_km_lloyd(*rows.head(), K, 1, 0, 1e-4, 0, _ptr(st), _ptr(ws), wb, stream)
 
             def one():
