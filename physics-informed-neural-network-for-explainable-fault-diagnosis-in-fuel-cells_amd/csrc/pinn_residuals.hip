@@ -202,12 +202,45 @@ __device__ __forceinline__ void row_terms(long long row, const float* __restrict
     }
   }
 
-template <bool kCols>
+// The sums a pass can touch: one stage model's are a contiguous range of the enum, any other flag combination gets all of them.
+// Stated once for everything that reduces sums (the two row-pass kernels, the finalize, the persistent stage kernel): what lies
+// outside the range is exactly 0 and costs no shuffle, no LDS round and no load.
+struct SumRange { int lo, hi; };
+constexpr SumRange live_sums(unsigned flags) {
+  return flags == PINN_RES_V ? SumRange{PINN_S_FV2, PINN_S_YU2 + 1}
+       : flags == PINN_RES_T ? SumRange{PINN_S_FT2, PINN_S_FT_ABS + 1}
+       : flags == PINN_RES_H ? SumRange{PINN_S_FH2, PINN_S_TGTH + 1}
+       : flags == PINN_RES_O ? SumRange{PINN_S_FO2, PINN_S_TGTO + 1}
+                             : SumRange{0, PINN_NSUMS};
+}
+
+// a workgroup's sums of the range kLo..kHi-1: wave64 shuffles -> LDS -> partials[block][PINN_NSUMS] (entries outside the range are
+// not written: residuals_finalize is given the same range and does not read them)
+template <int kLo, int kHi, int kBlock>
+__device__ __forceinline__ void block_partials(const float (&acc)[PINN_NSUMS], double* __restrict__ partials) {
+  __shared__ double red[kBlock / 64][kHi - kLo];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = kLo; s < kHi; ++s) {
+    const double w = wave_sum((double)acc[s]);
+    if (lane == 0) red[wave][s - kLo] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < kHi - kLo) {
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) t += red[w][threadIdx.x];
+    partials[(long long)blockIdx.x * PINN_NSUMS + kLo + threadIdx.x] = t;
+  }
+}
+
+// kFlags: the one stage model of the call as a constant (its terms and sums alone exist), or 0: `flags` at run time, any combination
+template <bool kCols, unsigned kFlags>
 __global__ __launch_bounds__(kThreads) void residuals_kernel(
     const float* __restrict__ x, const float* __restrict__ u, const float* __restrict__ y, AffineDev aff,
-    const float* __restrict__ lambdas, unsigned flags, long long n_rows, float* __restrict__ cols, long long ld,
+    const float* __restrict__ lambdas, unsigned flags_rt, long long n_rows, float* __restrict__ cols, long long ld,
     double* __restrict__ partials) {
-  __shared__ double red[kThreads / 64][PINN_NSUMS];
+  const unsigned flags = kFlags ? kFlags : flags_rt;
   const LamDev L = load_lambdas(lambdas);
   float acc[PINN_NSUMS];
 #pragma unroll
@@ -218,42 +251,35 @@ __global__ __launch_bounds__(kThreads) void residuals_kernel(
     row_terms<kCols>(row, x, u, y, aff, L, flags, cols, ld, acc);
 
   if (partials == nullptr) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < PINN_NSUMS; ++s) {
-    const double w = wave_sum((double)acc[s]);
-    if (lane == 0) red[wave][s] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < PINN_NSUMS) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) t += red[w][threadIdx.x];
-    partials[(long long)blockIdx.x * PINN_NSUMS + threadIdx.x] = t;
-  }
+  block_partials<live_sums(kFlags).lo, live_sums(kFlags).hi, kThreads>(acc, partials);
 }
 
-// fixed-order final reduction: thread (s, j) sums partials j, j+32, ... then lane s adds the 32 j-sums in order
-__global__ __launch_bounds__(1024) void residuals_finalize(const double* __restrict__ partials, int n_blocks,
+// fixed-order final reduction of the sums s_lo..s_hi-1 (live_sums of the pass that wrote the partials): thread (s, j) sums partials
+// j, j+32, ... then lane s adds the 32 j-sums in order.  Every other entry of `sums` is set to 0.
+__global__ __launch_bounds__(1024) void residuals_finalize(const double* __restrict__ partials, int n_blocks, int s_lo, int s_hi,
                                                            double* __restrict__ sums) {
   __shared__ double red[32][PINN_NSUMS + 1];
   const int s = threadIdx.x & 31, j = threadIdx.x >> 5;
-  // all loads first (independent addresses), then the adds in fixed order: not a latency-bound chain
-  double v[kMaxBlocks / 32];
+  if (s >= s_lo && s < s_hi) {
+    // all loads first (independent addresses), then the adds in fixed order: not a latency-bound chain
+    double v[kMaxBlocks / 32];
 #pragma unroll
-  for (int k = 0; k < kMaxBlocks / 32; ++k) {
-    const int b = j + 32 * k;
-    v[k] = b < n_blocks ? partials[(long long)b * PINN_NSUMS + s] : 0.0;
+    for (int k = 0; k < kMaxBlocks / 32; ++k) {
+      const int b = j + 32 * k;
+      v[k] = b < n_blocks ? partials[(long long)b * PINN_NSUMS + s] : 0.0;
+    }
+    double t = 0.0;
+#pragma unroll
+    for (int k = 0; k < kMaxBlocks / 32; ++k) t += v[k];
+    red[j][s] = t;
   }
-  double t = 0.0;
-#pragma unroll
-  for (int k = 0; k < kMaxBlocks / 32; ++k) t += v[k];
-  red[j][s] = t;
   __syncthreads();
   if (threadIdx.x < PINN_NSUMS) {
     double r = 0.0;
+    if (threadIdx.x >= s_lo && threadIdx.x < s_hi) {
 #pragma unroll
-    for (int k = 0; k < 32; ++k) r += red[k][threadIdx.x];
+      for (int k = 0; k < 32; ++k) r += red[k][threadIdx.x];
+    }
     sums[threadIdx.x] = r;
   }
 }
@@ -356,6 +382,8 @@ __global__ void lambda_step_kernel(int stage, const double* __restrict__ sums, d
 constexpr int kStageThreads = 1024;
 constexpr int kLogFloats = PINN_STAGE_LOG_FLOATS;   // [0..1] total / physics loss, [2] lr of the next epoch, [3..19] lambdas, [20..51] sums
 constexpr int kCacheFloats = 6;
+// how many of them a stage model fills (stage_prepare): the rest of a row's slots is never read
+constexpr int cached_floats(unsigned flags) { return (flags & PINN_RES_V) ? 6 : ((flags & PINN_RES_T) ? 4 : 2); }
 
 // Everything of a row that does not depend on the stage's parameters is computed ONCE (the de-normalisation with its
 // float64 divides, powf / expf of the Nernst terms, the flow ratios): 6 floats per row, struct-of-arrays in d_work.
@@ -488,9 +516,7 @@ __global__ __launch_bounds__(kStageThreads) void stage_run_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid < PINN_NLAMBDA) lam_s[tid] = lambdas[tid];
   if (tid < 2 * PINN_NLAMBDA) adam_s[tid] = adam[tid];
-  // the sums this stage reads: a contiguous range of the enum
-  constexpr int s_lo = (kFlags & PINN_RES_V) ? PINN_S_FV2 : ((kFlags & PINN_RES_T) ? PINN_S_FT2 : ((kFlags & PINN_RES_H) ? PINN_S_FH2 : PINN_S_FO2));
-  constexpr int s_hi = 1 + ((kFlags & PINN_RES_V) ? PINN_S_YU2 : ((kFlags & PINN_RES_T) ? PINN_S_FT_ABS : ((kFlags & PINN_RES_H) ? PINN_S_TGTH : PINN_S_TGTO)));
+  constexpr int s_lo = live_sums(kFlags).lo, s_hi = live_sums(kFlags).hi;   // the sums this stage reads
   if (tid < PINN_NSUMS) sums[tid] = 0.0;
   {   // parameter-independent part of every row, once
     const LamDev L0 = load_lambdas(lambdas);
@@ -502,7 +528,7 @@ __global__ __launch_bounds__(kStageThreads) void stage_run_kernel(
     }
   }
   __syncthreads();
-  constexpr int n_cached = (kFlags & PINN_RES_V) ? 6 : ((kFlags & PINN_RES_T) ? 4 : 2);
+  constexpr int n_cached = cached_floats(kFlags);
   const double inv_n = 1.0 / (double)n_rows;
   // thread 0's optimizer state: beta^step as running products (pow() once), the StepLR rate recomputed at its edges
   double b1p = pow(0.9, (double)first_epoch), b2p = pow(0.999, (double)first_epoch);
@@ -584,12 +610,16 @@ __global__ __launch_bounds__(kThreads) void stage_prepare_kernel(const float* __
   }
 }
 
+// One instantiation per stage kind, as the persistent kernel: only that stage's cache columns, terms and sums exist, and only its
+// range of sums is reduced and stored.  (With run-time flags every workgroup shuffled, staged and stored all 32 sums, at most
+// nine of them other than zero: the epilogue, not the 8 - 24 B/row of loads, set the time at 1e6 rows.)  Grid, rows per thread
+// and every order of summation are those of the run-time form, so each sum keeps its bits.
+template <unsigned kFlags>
 __global__ __launch_bounds__(kThreads) void residuals_cached_kernel(const float* __restrict__ cache, AffineDev aff,
-                                                                    const float* __restrict__ lambdas, unsigned flags, long long n_rows,
+                                                                    const float* __restrict__ lambdas, long long n_rows,
                                                                     double* __restrict__ partials) {
-  __shared__ double red[kThreads / 64][PINN_NSUMS];
   const LamDev L = load_lambdas(lambdas);
-  const int n_cached = (flags & PINN_RES_V) ? 6 : ((flags & PINN_RES_T) ? 4 : 2);
+  constexpr int n_cached = cached_floats(kFlags);
   float acc[PINN_NSUMS];
 #pragma unroll
   for (int s = 0; s < PINN_NSUMS; ++s) acc[s] = 0.0f;
@@ -606,21 +636,9 @@ __global__ __launch_bounds__(kThreads) void residuals_cached_kernel(const float*
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q)
-      if (row0 + q * stride < n_rows) stage_terms(c[q], aff, L, flags, acc);
+      if (row0 + q * stride < n_rows) stage_terms(c[q], aff, L, kFlags, acc);
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < PINN_NSUMS; ++s) {
-    const double w = wave_sum((double)acc[s]);
-    if (lane == 0) red[wave][s] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < PINN_NSUMS) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) t += red[w][threadIdx.x];
-    partials[(long long)blockIdx.x * PINN_NSUMS + threadIdx.x] = t;
-  }
+  block_partials<live_sums(kFlags).lo, live_sums(kFlags).hi, kThreads>(acc, partials);
 }
 
 static AffineDev affine_dev(const pinn_affine_t* aff) {
@@ -1064,15 +1082,28 @@ extern "C" int pinn_residuals(const float* d_x, const float* d_u, const float* d
   long long want = (n_rows + kThreads - 1) / kThreads;
   int blocks = (int)(want < 1 ? 1 : (want > kMaxBlocks ? kMaxBlocks : want));
   double* partials = d_sums ? (double*)d_work : nullptr;
+  // the kernel's compile-time flags: the one stage model of a sums-only call, else 0 (run-time flags, all sums).  The instantiation
+  // launched and the range the finalize reads both follow from this one value.
+  const unsigned kf = (!d_cols && one_stage_flag(flags)) ? flags : 0u;
   if (n_rows > 0 || d_sums) {
-    if (d_cols)
-      hipLaunchKernelGGL(residuals_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, d_x, d_u, d_y, a, d_lambda, flags,
-                         n_rows, d_cols, ld, partials);
-    else
-      hipLaunchKernelGGL(residuals_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, d_x, d_u, d_y, a, d_lambda, flags,
-                         n_rows, d_cols, ld, partials);
+#define PINN_RES_LAUNCH(COLS, F)                                                                                                  \
+  hipLaunchKernelGGL((residuals_kernel<COLS, F>), dim3(blocks), dim3(kThreads), 0, st, d_x, d_u, d_y, a, d_lambda, flags, n_rows, \
+                     d_cols, ld, partials)
+    switch (kf) {
+      case PINN_RES_V: PINN_RES_LAUNCH(false, PINN_RES_V); break;
+      case PINN_RES_T: PINN_RES_LAUNCH(false, PINN_RES_T); break;
+      case PINN_RES_H: PINN_RES_LAUNCH(false, PINN_RES_H); break;
+      case PINN_RES_O: PINN_RES_LAUNCH(false, PINN_RES_O); break;
+      default:
+        if (d_cols) PINN_RES_LAUNCH(true, 0u);
+        else PINN_RES_LAUNCH(false, 0u);
+    }
+#undef PINN_RES_LAUNCH
   }
-  if (d_sums) hipLaunchKernelGGL(residuals_finalize, dim3(1), dim3(1024), 0, st, partials, blocks, d_sums);
+  if (d_sums) {
+    const SumRange live = live_sums(kf);
+    hipLaunchKernelGGL(residuals_finalize, dim3(1), dim3(1024), 0, st, partials, blocks, live.lo, live.hi, d_sums);
+  }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PINN_OK : (int)e;
 }
@@ -1138,9 +1169,16 @@ extern "C" int pinn_residuals_cached(const float* d_cache, const pinn_affine_t* 
   (void)hipGetLastError();
   hipStream_t st = (hipStream_t)stream;
   const int blocks = row_blocks((n_rows + 1) / 2);
-  hipLaunchKernelGGL(residuals_cached_kernel, dim3(blocks), dim3(kThreads), 0, st, d_cache, affine_dev(aff), d_lambda, flags, n_rows,
-                     (double*)d_work);
-  hipLaunchKernelGGL(residuals_finalize, dim3(1), dim3(1024), 0, st, (const double*)d_work, blocks, d_sums);
+#define PINN_CACHED_LAUNCH(F)                                                                                                     \
+  hipLaunchKernelGGL((residuals_cached_kernel<F>), dim3(blocks), dim3(kThreads), 0, st, d_cache, affine_dev(aff), d_lambda, n_rows, \
+                     (double*)d_work)
+  if (flags == PINN_RES_V) PINN_CACHED_LAUNCH(PINN_RES_V);
+  else if (flags == PINN_RES_T) PINN_CACHED_LAUNCH(PINN_RES_T);
+  else if (flags == PINN_RES_H) PINN_CACHED_LAUNCH(PINN_RES_H);
+  else PINN_CACHED_LAUNCH(PINN_RES_O);
+#undef PINN_CACHED_LAUNCH
+  const SumRange live = live_sums(flags);
+  hipLaunchKernelGGL(residuals_finalize, dim3(1), dim3(1024), 0, st, (const double*)d_work, blocks, live.lo, live.hi, d_sums);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PINN_OK : (int)e;
 }
