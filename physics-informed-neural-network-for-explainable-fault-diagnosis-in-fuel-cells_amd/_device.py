@@ -1,6 +1,7 @@
 """What the analysis modules (risk, diagnosis, detection, comparison, anomaly, svm, embedding) share on their way to the
 device: the backend="auto" rule, conversions between host arrays and device tensors, the rows of the results array read
 in place (`_DevRows`, the row head of `_lib._ROWS`) with their host twin (`_host_rows`), and the launch itself (`call`).
+What the supervised classifiers share on top of it (class set-up, wanted outputs, the one-vs-one base class) is _classify.py.
 
 Importing this module needs numpy only; torch and the HIP library are loaded when a device path runs.
 """

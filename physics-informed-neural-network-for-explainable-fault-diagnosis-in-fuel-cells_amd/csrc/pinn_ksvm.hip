@@ -23,13 +23,13 @@
 #include <math.h>
 
 #include "../../include/pinn_hip.h"
-#include "pinn_rows.h"
+#include "pinn_ovo.h"
 
 namespace pinn {
 namespace {
 
 constexpr int kT = 256;                      // threads of a workgroup = rows of a tile
-constexpr int kMaxC = PINN_KSVM_MAX_CLASSES, kMaxD = PINN_KSVM_MAX_FEAT, kMaxP = kMaxC * (kMaxC - 1) / 2;
+constexpr int kMaxC = kOvoMaxC, kMaxD = kOvoMaxD, kMaxP = kOvoMaxP;
 constexpr int kMaxBlocks = 1024;             // workgroups per pair = candidate records per pair
 constexpr int kHdr = PINN_KSVM_ST_HEADER, kPW = PINN_KSVM_PAIR_WORDS;
 constexpr int kRecI = 8, kRecJ = 16;         // words of a record
@@ -39,16 +39,8 @@ constexpr double kTau = 1e-12;
 // record words: [0] row position (-1: none), [1] key, [2] alpha, [3] G, [4] c, [5] t, [6] aux (i: the workgroup's min of -tG
 // over I_low; j: K_ij), [7] flags (i: status bits of the rows; j: 1 = stop | status bits << 8)
 
-__host__ __device__ inline int n_pairs(int C) { return C * (C - 1) / 2; }
-__host__ __device__ inline int pair_index(int a, int b, int C) { return a * (2 * C - a - 1) / 2 + (b - a - 1); }      // a < b
-__host__ __device__ inline size_t st_mean(int C) { return kHdr + (size_t)n_pairs(C) * kPW; }
-__host__ __device__ inline size_t st_bound(int C, int D) { return st_mean(C) + 2 * D; }
-__host__ __device__ inline size_t st_alpha(int C, int D) { return st_bound(C, D) + C; }
-__host__ __device__ inline size_t st_words(long long n, int C, int D) { return st_alpha(C, D) + 2 * (size_t)n * (C - 1); }
-
-inline bool in_limits(int C, int D) { return C >= 2 && C <= kMaxC && D >= 1 && D <= kMaxD; }
-
-__device__ __forceinline__ bool finite(double v) { return fabs(v) < INFINITY; }      // false for NaN
+// state block: the prefix of pinn_ovo.h, then alpha and G [n][C - 1]
+__host__ __device__ inline size_t st_words(long long n, int C, int D) { return st_alpha(C, D, kHdr, kPW) + 2 * (size_t)n * (C - 1); }
 
 struct KArgs {
   double* st;               // state block
@@ -153,8 +145,8 @@ __global__ __launch_bounds__(kT) void ksvm_select_kernel(Rows a, KArgs k) {
   const int C = a.K, D = a.D, S1 = C - 1, t = threadIdx.x, p = blockIdx.y, nb = gridDim.x;
   const PairView pv = pair_view(k.st, p, C);
   if (pv.stopped) return;
-  if (t < D) { s_mean[t] = k.st[st_mean(C) + t]; s_scale[t] = k.st[st_mean(C) + D + t]; }
-  if (t < C) s_bound[t] = k.st[st_bound(C, D) + t];
+  if (t < D) { s_mean[t] = k.st[st_mean(C, kHdr, kPW) + t]; s_scale[t] = k.st[st_mean(C, kHdr, kPW) + D + t]; }
+  if (t < C) s_bound[t] = k.st[st_bound(C, D, kHdr, kPW) + t];
   Cand I = no_cand();
   double gmin = INFINITY;
   long long flags = 0;
@@ -177,7 +169,7 @@ __global__ __launch_bounds__(kT) void ksvm_select_kernel(Rows a, KArgs k) {
   }
   double zi[kMaxD], z[kMaxD];
   load_z(a, I.idx, s_mean, s_scale, zi);
-  double* g_al = k.st + st_alpha(C, D);
+  double* g_al = k.st + st_alpha(C, D, kHdr, kPW);
   double* g_G = g_al + (size_t)a.n * S1;
   Cand J = no_cand();
   const long long tiles = (a.n + kT - 1) / kT;
@@ -226,8 +218,8 @@ __global__ __launch_bounds__(kT) void ksvm_update_kernel(Rows a, KArgs k) {
     }
   }
   if (pv.stopped) return;
-  if (t < D) { s_mean[t] = k.st[st_mean(C) + t]; s_scale[t] = k.st[st_mean(C) + D + t]; }
-  if (t < C) s_bound[t] = k.st[st_bound(C, D) + t];
+  if (t < D) { s_mean[t] = k.st[st_mean(C, kHdr, kPW) + t]; s_scale[t] = k.st[st_mean(C, kHdr, kPW) + D + t]; }
+  if (t < C) s_bound[t] = k.st[st_bound(C, D, kHdr, kPW) + t];
   __syncthreads();
   Cand I = no_cand(), J = no_cand();
   double ai = 0.0, aj = 0.0, di = 0.0, dj = 0.0;
@@ -278,7 +270,7 @@ __global__ __launch_bounds__(kT) void ksvm_update_kernel(Rows a, KArgs k) {
     di = ai - I.al; dj = aj - J.al;
     load_z(a, J.idx, s_mean, s_scale, zj);
   }
-  double* g_al = k.st + st_alpha(C, D);
+  double* g_al = k.st + st_alpha(C, D, kHdr, kPW);
   double* g_G = g_al + (size_t)a.n * S1;
   Cand N = no_cand();
   double gmin = INFINITY;
@@ -367,9 +359,9 @@ __global__ __launch_bounds__(kT) void ksvm_finish_kernel(Rows a, KArgs k) {
   long long* pi = reinterpret_cast<long long*>(pb);
   const int ca = (int)pi[PINN_KSVM_P_A], cb = (int)pi[PINN_KSVM_P_B];
   if (ca < 0 || ca >= cb || cb >= C) return;
-  if (t < C) s_bound[t] = k.st[st_bound(C, D) + t];
+  if (t < C) s_bound[t] = k.st[st_bound(C, D, kHdr, kPW) + t];
   __syncthreads();
-  const double* g_al = k.st + st_alpha(C, D);
+  const double* g_al = k.st + st_alpha(C, D, kHdr, kPW);
   const double* g_G = g_al + (size_t)a.n * S1;
   double n_free = 0.0, s_free = 0.0, ub = INFINITY, nlb = INFINITY, s_al = 0.0, s_aq = 0.0, s_ta = 0.0, ngmax = INFINITY, gmin = INFINITY;
   for (long long j = t; j < a.n; j += kT) {
@@ -412,8 +404,6 @@ __global__ __launch_bounds__(kT) void ksvm_finish_kernel(Rows a, KArgs k) {
 }
 
 // ---- decision of given rows: one thread per row; the support rows pass through LDS in tiles of kSvTile
-constexpr int q8(int a, int b) { return a * (2 * kMaxC - a - 1) / 2 + (b - a - 1); }
-
 template <int KC>
 __device__ __forceinline__ void add_support(double acc[kMaxP], const double* cf, double K, int C) {
 #pragma unroll
@@ -470,31 +460,7 @@ __global__ __launch_bounds__(kSvTile) void ksvm_decision_kernel(Rows a, const do
     }
   }
   if (j >= a.n) return;
-  const int P = n_pairs(C);
-  int votes[kMaxC];
-#pragma unroll
-  for (int c = 0; c < kMaxC; ++c) votes[c] = 0;
-#pragma unroll
-  for (int ca = 0; ca < kMaxC; ++ca)
-#pragma unroll
-    for (int cb = ca + 1; cb < kMaxC; ++cb) {
-      if (cb >= C) continue;
-      const int p = pair_index(ca, cb, C);
-      double v = acc[q8(ca, cb)] - rho[p];
-      if (!ok) v = quiet_nan();
-      if (dec_out) dec_out[j * P + p] = v;
-      if (v > 0.0) votes[ca] += 1; else votes[cb] += 1;
-    }
-  int best = 0, bv = votes[0];
-#pragma unroll
-  for (int c = 1; c < kMaxC; ++c)
-    if (c < C && votes[c] > bv) { bv = votes[c]; best = c; }          // the first maximum
-  if (votes_out) {
-#pragma unroll
-    for (int c = 0; c < kMaxC; ++c)
-      if (c < C) votes_out[j * C + c] = ok ? votes[c] : 0;
-  }
-  if (pred_out) pred_out[j] = ok ? best : -1;
+  ovo_decide([&](int ca, int cb, int p) { return acc[q8(ca, cb)] - rho[p]; }, ok, C, j, dec_out, votes_out, pred_out);
 }
 
 struct Ws {

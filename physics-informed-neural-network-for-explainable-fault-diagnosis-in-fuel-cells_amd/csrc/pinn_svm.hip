@@ -26,13 +26,13 @@
 #include <math.h>
 
 #include "../../include/pinn_hip.h"
-#include "pinn_rows.h"
+#include "pinn_ovo.h"
 
 namespace pinn {
 namespace {
 
 constexpr int kRows = 128;                  // rows per tile = threads per workgroup of a row pass
-constexpr int kMaxC = PINN_SVM_MAX_CLASSES, kMaxD = PINN_SVM_MAX_FEAT, kMaxP = kMaxC * (kMaxC - 1) / 2, kMaxSlots = kMaxC - 1;
+constexpr int kMaxC = kOvoMaxC, kMaxD = kOvoMaxD, kMaxP = kOvoMaxP, kMaxSlots = kMaxC - 1;
 constexpr int kD1 = kMaxD + 1;              // (z, 1)
 constexpr int kTerms = 6;                   // per row and slot in LDS
 constexpr int kMaxSums = kD1 * (kD1 + 1) / 2 + 2 * kD1 + 3;
@@ -45,21 +45,11 @@ constexpr double kStartSlack = 1.0, kStepToBoundary = 0.995, kMuFloor = 0.1;
 enum { PASS_A = 0, PASS_B = 1, PASS_C = 2 };
 enum { MODE_RUN = 0, MODE_SUMS = 1 };
 
-__host__ __device__ inline int n_pairs(int C) { return C * (C - 1) / 2; }
 __host__ __device__ inline int n_tri(int D) { return (D + 1) * (D + 2) / 2; }
 __host__ __device__ inline int n_sums_a(int D) { return n_tri(D) + 2 * (D + 1) + 3; }
 __host__ __device__ inline int n_sums_b(int D) { return 2 + 2 * (D + 1); }
-__host__ __device__ inline int pair_index(int a, int b, int C) { return a * (2 * C - a - 1) / 2 + (b - a - 1); }      // a < b
-// state block: header, pair blocks [P][kPW], mean [D], scale [D], bound [C] (C x class weight), alpha, s, z [n][C - 1]
-__host__ __device__ inline size_t st_mean(int C) { return kHdr + (size_t)n_pairs(C) * kPW; }
-__host__ __device__ inline size_t st_scale(int C, int D) { return st_mean(C) + D; }
-__host__ __device__ inline size_t st_bound(int C, int D) { return st_mean(C) + 2 * D; }
-__host__ __device__ inline size_t st_alpha(int C, int D) { return st_bound(C, D) + C; }
-__host__ __device__ inline size_t st_words(long long n, int C, int D) { return st_alpha(C, D) + 3 * (size_t)n * (C - 1); }
-
-inline bool in_limits(int C, int D) { return C >= 2 && C <= kMaxC && D >= 1 && D <= kMaxD; }
-
-__device__ __forceinline__ bool finite(double v) { return fabs(v) < INFINITY; }      // false for NaN
+// state block: the prefix of pinn_ovo.h, then alpha, s, z [n][C - 1]
+__host__ __device__ inline size_t st_words(long long n, int C, int D) { return st_alpha(C, D, kHdr, kPW) + 3 * (size_t)n * (C - 1); }
 
 __device__ __forceinline__ bool pair_stopped(const double* pb) {
   const long long* h = reinterpret_cast<const long long*>(pb);
@@ -112,15 +102,15 @@ __global__ __launch_bounds__(kRows) void svm_rows_kernel(Rows a, Pass k) {
     s_ka[t] = pb[PINN_SVM_P_KA];
     s_kb[t] = pb[PINN_SVM_P_KB];
   }
-  if (t < D) { s_mean[t] = k.st[st_mean(C) + t]; s_scale[t] = k.st[st_scale(C, D) + t]; }
-  if (t < C) s_bound[t] = k.st[st_bound(C, D) + t];
+  if (t < D) { s_mean[t] = k.st[st_mean(C, kHdr, kPW) + t]; s_scale[t] = k.st[st_mean(C, kHdr, kPW) + D + t]; }
+  if (t < C) s_bound[t] = k.st[st_bound(C, D, kHdr, kPW) + t];
   __syncthreads();
   if (!s_any) {                              // every pair has stopped
     if (t == 0) k.pbad[blockIdx.x] = 0.0;
     return;
   }
 
-  double* g_al = k.st + st_alpha(C, D);
+  double* g_al = k.st + st_alpha(C, D, kHdr, kPW);
   double* g_s = g_al + (size_t)a.n * S1;
   double* g_z = g_s + (size_t)a.n * S1;
   double acc[kMaxOut];
@@ -489,23 +479,12 @@ __global__ __launch_bounds__(kRows) void svm_decision_kernel(Rows a, const doubl
   double x[kRowsMaxD], u[kMaxD];
   const bool ok = load_row(a, j, x);
   for (int i = 0; i < D; ++i) u[i] = (x[i] - s_mean[i]) / s_scale[i];
-  int votes[kMaxC];
-  for (int c = 0; c < C; ++c) votes[c] = 0;
-  int p = 0;
-  for (int ca = 0; ca < C; ++ca)
-    for (int cb = ca + 1; cb < C; ++cb, ++p) {
-      double v = 0.0;
-      for (int i = 0; i < D; ++i) v += s_W[p * D + i] * u[i];
-      v += s_b[p];
-      if (!ok) v = quiet_nan();
-      if (dec_out) dec_out[j * P + p] = v;
-      votes[v > 0.0 ? ca : cb] += 1;
-    }
-  int best = 0;
-  for (int c = 1; c < C; ++c) best = votes[c] > votes[best] ? c : best;       // the first maximum
-  if (votes_out)
-    for (int c = 0; c < C; ++c) votes_out[j * C + c] = ok ? votes[c] : 0;
-  if (pred_out) pred_out[j] = ok ? best : -1;
+  const auto value = [&](int, int, int p) {
+    double v = 0.0;
+    for (int i = 0; i < D; ++i) v += s_W[p * D + i] * u[i];
+    return v + s_b[p];
+  };
+  ovo_decide(value, ok, C, j, dec_out, votes_out, pred_out);
 }
 
 struct Ws {

@@ -26,6 +26,7 @@ import warnings
 import numpy as np
 
 from . import diagnosis as _dg
+from ._classify import dev_classes, host_classes, labels_of, scaler_stats, wanted_outputs
 from ._device import _DevRows, _as_numpy, _dev_vec, _host_rows, _is_tensor, _on_gpu, _pick_backend, _torch_lib, call, columns_of
 from .diagnosis import (build_label_mapper, classification_metrics, extract_X_y, list_available_features,  # noqa: F401
                         normalize_feature_spec)
@@ -305,6 +306,10 @@ def n_pass_sums(C, D):
 _rows = functools.partial(_DevRows.within, on_excess=lambda D: _check_limits(2, D))
 
 
+def _too_few(classes):
+    return "this solver needs samples of at least 2 classes in the data, but the data contains only one class: %r" % (classes[0],)
+
+
 def _check_limits(C, D):
     if not limits_ok(C, D):
         raise NotImplementedError("the device backend is built for 2..%d classes, 1..%d features and at most %d Hessian sums "
@@ -372,15 +377,6 @@ class DeviceLogisticRegression:
         self.n_features_in_ = D1 - 1
         self._model = None
 
-    @staticmethod
-    def _scaler_stats(scaler, D):
-        if scaler is None:
-            return np.zeros(D), np.ones(D)
-        mean, scale = _as_numpy(scaler.mean_, np.float64).reshape(-1), _as_numpy(scaler.scale_, np.float64).reshape(-1)
-        if mean.size != D:
-            raise ValueError("the scaler was fitted on %d features, got %d" % (mean.size, D))
-        return mean, scale
-
     # ---- fit
     def fit(self, X, y, sample_weight=None, columns=None, row_index=None, scaler=None, fit_scaler=None, trace=None):
         """`scaler`: a fitted DeviceStandardScaler whose statistics standardise the rows; `fit_scaler`: an unfitted one that
@@ -392,17 +388,11 @@ class DeviceLogisticRegression:
         l2 = 1.0 / self.C
         if _pick_backend(self.backend, X) == "host":
             Xh = _host_rows(X, columns, row_index)
-            yh = _as_numpy(y).reshape(-1)
-            if yh.shape[0] != Xh.shape[0]:
-                raise ValueError("y must hold one class per row")
-            classes, yi = np.unique(yh, return_inverse=True)
+            classes, yi, count = host_classes(y, Xh.shape[0], _too_few)
             C, D = len(classes), Xh.shape[1]
-            if C < 2:
-                raise ValueError("this solver needs samples of at least 2 classes in the data, but the data contains only one class: %r" % (classes[0],))
             if fit_scaler is not None:
                 scaler = fit_scaler.fit(Xh)
-            mean, scale = self._scaler_stats(scaler, D)
-            count = np.bincount(yi, minlength=C)
+            mean, scale = scaler_stats(scaler, D)
             cw = len(yi) / (C * count) if balanced else np.ones(C)
             theta, n_iter, conv, passes, gmax, F = _host_newton(Xh, yi, C, mean, scale, cw, self._theta0(C, D), l2, self.tol, self.max_iter,
                                                                  self.fit_intercept, trace)
@@ -410,23 +400,13 @@ class DeviceLogisticRegression:
             return self
         return self._fit_device(X, y, columns, row_index, scaler, fit_scaler, balanced, l2, trace)
 
-    def _dev_classes(self, torch, y, rows):
-        yt = _dev_vec(torch, y, torch.int64, rows.dev)
-        if yt.numel() != rows.n:
-            raise ValueError("y must hold one class per row")
-        classes = torch.unique(yt)
-        if classes.numel() < 2:
-            raise ValueError("this solver needs samples of at least 2 classes in the data, but the data contains only one class: %r"
-                             % (int(classes[0]),))
-        return classes, torch.searchsorted(classes, yt).contiguous()
-
     def _fit_device(self, X, y, columns, row_index, scaler, fit_scaler, balanced, l2, trace):
         torch, _lib, lib = _torch_lib()
         rows = _rows(torch, X, columns, row_index)
         if rows.n < 1:
             raise ValueError("X holds no rows")
         with torch.cuda.device(rows.dev):
-            classes, yi = self._dev_classes(torch, y, rows)
+            classes, yi, _ = dev_classes(torch, y, rows, _too_few)
             C, D = int(classes.numel()), rows.D
             _check_limits(C, D)
             stream = torch.cuda.current_stream().cuda_stream
@@ -445,7 +425,7 @@ class DeviceLogisticRegression:
                 stats = [st[o[k]:o[k] + D].clone() for k in ("mean", "var", "scale")]
                 fit_scaler._set(*(stats if _is_tensor(X) else [s.cpu().numpy() for s in stats]), rows.n)
             else:                                        # a given scaler, or none: its statistics replace the pass's
-                mean, scale = self._scaler_stats(scaler, D)
+                mean, scale = scaler_stats(scaler, D)
                 st[o["mean"]:o["mean"] + D] = torch.from_numpy(mean).to(rows.dev)
                 st[o["scale"]:o["scale"] + D] = torch.from_numpy(scale).to(rows.dev)
             self._state, self._ws = st, ws
@@ -480,7 +460,7 @@ class DeviceLogisticRegression:
         if _pick_backend(self.backend, X) == "host":
             Xh = _host_rows(X, columns, row_index)
             yi = _as_numpy(y).astype(np.int64).reshape(-1)
-            mean, scale = self._scaler_stats(scaler, D)
+            mean, scale = scaler_stats(scaler, D)
             count = np.bincount(yi[(yi >= 0) & (yi < C)], minlength=C)
             with np.errstate(divide="ignore"):
                 cw = np.where(count > 0, count.sum() / (C * np.maximum(count, 1)), 0.0) if balanced else np.ones(C)
@@ -501,7 +481,7 @@ class DeviceLogisticRegression:
             ws = torch.empty(wb, dtype=torch.uint8, device=rows.dev)
             head = rows.head() + (yi, C)
             call("pinn_lr_scaler", *head, int(balanced), st, ws, wb, stream=stream)
-            mean, scale = self._scaler_stats(scaler, D)
+            mean, scale = scaler_stats(scaler, D)
             st[o["mean"]:o["mean"] + D] = torch.from_numpy(mean).to(rows.dev)
             st[o["scale"]:o["scale"] + D] = torch.from_numpy(scale).to(rows.dev)
             call("pinn_lr_pass", *head, st, ws, wb, stream=stream)
@@ -513,7 +493,7 @@ class DeviceLogisticRegression:
         key = (str(dev), id(scaler))
         if self._model is None or self._model[0] != key:
             D = self.n_features_in_
-            mean, scale = self._scaler_stats(scaler, D)
+            mean, scale = scaler_stats(scaler, D)
             m = np.concatenate([mean, scale, _as_numpy(self.coef_, np.float64).reshape(-1), _as_numpy(self.intercept_, np.float64).reshape(-1)])
             self._model = (key, torch.from_numpy(m).to(dev))
         return self._model[1]
@@ -528,7 +508,7 @@ class DeviceLogisticRegression:
             Xh = _host_rows(X, columns, row_index)
             if Xh.shape[1] != D:
                 raise ValueError("the model was fitted on %d features, got %d" % (D, Xh.shape[1]))
-            mean, scale = self._scaler_stats(scaler, D)
+            mean, scale = scaler_stats(scaler, D)
             s = _scores(Xh, mean, scale, _as_numpy(self.coef_, np.float64), _as_numpy(self.intercept_, np.float64))
             p = _softmax(s)[0]
             out = {"decision": s[:, 1] if C == 2 else s, "proba": p, "pred": s.argmax(axis=1), "p_fault": 1.0 - p[:, int(normal_class)]}
@@ -539,25 +519,16 @@ class DeviceLogisticRegression:
         if rows.D != D:
             raise ValueError("the model was fitted on %d features, got %d" % (D, rows.D))
         with torch.cuda.device(rows.dev):
-            model = self._device_model(torch, rows.dev, scaler)
-            n = rows.n
-            f64 = dict(dtype=torch.float64, device=rows.dev)
-            out = {"decision": (torch.empty(n, **f64) if C == 2 else torch.empty(n, C, **f64)) if "decision" in want else None,
-                   "proba": torch.empty(n, C, **f64) if "proba" in want else None,
-                   "pred": torch.empty(n, dtype=torch.int64, device=rows.dev) if "pred" in want else None,
-                   "p_fault": torch.empty(n, **f64) if "p_fault" in want else None}
-            call("pinn_lr_posterior", *rows.head(), C, model, int(normal_class), out["decision"], out["proba"], out["pred"], out["p_fault"])
-        if not _is_tensor(X):
-            return {k: out[k].cpu().numpy() for k in want}
-        return {k: out[k] for k in want}
+            model, n, f64 = self._device_model(torch, rows.dev, scaler), rows.n, torch.float64
+            spec = {"decision": ((n,) if C == 2 else (n, C), f64), "proba": ((n, C), f64), "pred": ((n,), torch.int64), "p_fault": ((n,), f64)}
+            return wanted_outputs(torch, X, rows.dev, spec, want, self._launch_posterior, rows, C, model, int(normal_class))
+
+    @staticmethod
+    def _launch_posterior(rows, C, model, normal_class, out):
+        call("pinn_lr_posterior", *rows.head(), C, model, normal_class, out["decision"], out["proba"], out["pred"], out["p_fault"])
 
     def _labels(self, pred):
-        cls = self.classes_
-        if _is_tensor(pred):
-            import torch
-            c = cls if _is_tensor(cls) else torch.from_numpy(np.asarray(cls))
-            return c.to(pred.device)[pred]
-        return _as_numpy(cls)[pred]
+        return labels_of(self.classes_, pred)
 
     def decision_function(self, X, columns=None, row_index=None, scaler=None):
         return self._posterior(X, columns, row_index, scaler, want=("decision",))["decision"]

@@ -24,10 +24,10 @@ import warnings
 
 import numpy as np
 
-from ._device import _DevRows, _as_numpy, _dev_vec, _host_rows, _is_tensor, _pick_backend, _torch_lib, call, columns_of
-from .detection import DeviceLogisticRegression, DeviceStandardScaler
-from .diagnosis import DEFAULT_FEATURES, parse_features
-from .svm import DeviceLinearSVC, SVCPipeline, ovr_decision_function, pairs_of, slot_of
+from ._classify import OneVsOneSVC, pairs_of, scaler_stats, slot_of
+from ._device import _is_tensor, _pick_backend, _torch_lib, call
+from .detection import DeviceStandardScaler
+from .svm import SVCPipeline, SVMDiagnoser
 
 # limits, status words and the 8-byte words of the state block: one copy, next to the bindings (include/pinn_hip.h)
 from ._lib import (KSVM_MAX_CLASSES as MAX_CLASSES, KSVM_MAX_FEAT as MAX_FEAT, KSVM_NAN, KSVM_P_A as _P_A, KSVM_P_B as _P_B,
@@ -163,12 +163,10 @@ def _certificate(t, c, al, G):
             "t_alpha": float(np.sum(t * al)), "n_free": int(free.sum()), "violation": float(viol)}
 
 
-def _host_decision(Zx, sv, coef, sv_cls, rho, gamma, C):
-    """(values [n, P], votes [n, C], prediction [n]): the terms of a value added in the order of the support rows; a vote for
-    a where the value is > 0, else for b; the first maximum."""
-    pairs = pairs_of(C)
-    index = {ab: p for p, ab in enumerate(pairs)}
-    acc = np.zeros((Zx.shape[0], len(pairs)))
+def _host_values(Zx, sv, coef, sv_cls, rho, gamma, C):
+    """Pairwise values [n, P]: the terms of a value added in the order of the support rows."""
+    index = {ab: p for p, ab in enumerate(pairs_of(C))}
+    acc = np.zeros((Zx.shape[0], len(index)))
     for s in range(sv.shape[0]):
         K = _kernel_column(Zx, sv[s], gamma)
         k = int(sv_cls[s])
@@ -176,13 +174,7 @@ def _host_decision(Zx, sv, coef, sv_cls, rho, gamma, C):
             if o != k:
                 p = index[(min(o, k), max(o, k))]
                 acc[:, p] = acc[:, p] + coef[s, slot_of(k, o)] * K
-    dec = acc - rho[None, :]
-    votes = np.zeros((Zx.shape[0], C), dtype=np.int64)
-    for p, (a, b) in enumerate(pairs):
-        won = dec[:, p] > 0
-        votes[:, a] += won
-        votes[:, b] += ~won
-    return dec, votes, votes.argmax(axis=1).astype(np.int64)
+    return acc - rho[None, :]
 
 
 def scale_gamma(Z):
@@ -194,7 +186,7 @@ def scale_gamma(Z):
 
 
 # ---------------------------------------------------------------------------------------------- the classifier
-class DeviceKernelSVC:
+class DeviceKernelSVC(OneVsOneSVC):
     """One-vs-one RBF-kernel SVC with scikit-learn's SVC arguments; `kernel="rbf"` only.
 
     `tol` is libsvm's stopping rule, the largest violation gmax - gmin of a pair, and a real parameter here (DeviceLinearSVC
@@ -220,40 +212,22 @@ class DeviceKernelSVC:
             raise NotImplementedError("kernel=%r: only 'rbf' is implemented (svm.DeviceLinearSVC has 'linear')" % (kernel,))
         if probability:
             raise NotImplementedError("probability=True is not implemented")
-        if break_ties:
-            raise NotImplementedError("break_ties=True is not implemented")
-        if decision_function_shape not in ("ovr", "ovo"):
-            raise ValueError("decision_function_shape must be 'ovr' or 'ovo'")
-        if backend not in ("auto", "device", "host"):
-            raise ValueError("backend must be 'auto', 'device' or 'host'")
-        if not (isinstance(class_weight, dict) or class_weight in (None, "balanced")):
-            raise ValueError("class_weight must be None, 'balanced' or a dict")
+        super().__init__(C, class_weight, max_iter, decision_function_shape, break_ties, random_state, backend, chunk, "tol", tol)
         if isinstance(gamma, str):
             if gamma not in ("scale", "auto"):
                 raise ValueError("gamma must be 'scale', 'auto' or a positive number")
         elif not (float(gamma) > 0 and np.isfinite(float(gamma))):
             raise ValueError("gamma must be 'scale', 'auto' or a positive number")
-        if not C > 0 or not np.isfinite(C) or not tol > 0 or int(chunk) < 1 or (int(max_iter) < 1 and int(max_iter) != -1):
-            raise ValueError("C > 0, tol > 0, chunk >= 1 and max_iter >= 1 (or -1) are required")
-        self.C, self.kernel, self.gamma, self.class_weight, self.tol, self.max_iter = float(C), kernel, gamma, class_weight, float(tol), int(max_iter)
-        self.decision_function_shape, self.shrinking, self.probability = decision_function_shape, shrinking, False
-        self.break_ties, self.random_state, self.backend, self.chunk = False, random_state, backend, int(chunk)
-        self._model = None
+        self.kernel, self.gamma, self.tol, self.shrinking, self.probability = kernel, gamma, float(tol), shrinking, False
 
-    def _check_fitted(self):
-        if not hasattr(self, "dual_coef_"):
-            raise RuntimeError("this DeviceKernelSVC is not fitted yet")
+    _FITTED, _NOT_FINITE, _LAYOUT = "dual_coef_", "the kernel SVC failed: %s" % _STATUS_TEXT[KSVM_NAN], (_HDR, _PW, _P_A, _P_B, 0)
+    _check_limits = staticmethod(_check_limits)
 
     def _limit(self, count):
         if self.max_iter != -1:
             return self.max_iter
         top = np.sort(np.asarray(count))[-2:].sum()
         return ITER_PER_ROW * int(top)
-
-    _weights = DeviceLinearSVC._weights
-    _scaler_stats = staticmethod(DeviceLogisticRegression._scaler_stats)
-    _labels = DeviceLogisticRegression._labels
-    pair_alpha = DeviceLinearSVC.pair_alpha
 
     def _gamma_of(self, Z):
         if self.gamma == "auto":
@@ -325,42 +299,6 @@ class DeviceKernelSVC:
         first = yi[idx] == a
         return idx, np.where(first, 1.0, -1.0), self.C * cw[yi[idx]], np.where(first, slot_of(a, b), slot_of(b, a))
 
-    def _host_setup(self, X, y, columns, row_index, scaler):
-        Xh = _host_rows(X, columns, row_index)
-        yh = _as_numpy(y).reshape(-1)
-        if yh.shape[0] != Xh.shape[0]:
-            raise ValueError("y must hold one class per row")
-        classes, yi = np.unique(yh, return_inverse=True)
-        C, D = len(classes), Xh.shape[1]
-        if C < 2:
-            raise ValueError("the number of classes has to be greater than one; got %d class" % C)
-        _check_limits(D, C)
-        mean, scale = self._scaler_stats(scaler, D)
-        count = np.bincount(yi, minlength=C)
-        cw = self._weights(classes, count)
-        if not np.isfinite(Xh).all():
-            raise ValueError("the kernel SVC failed: %s" % _STATUS_TEXT[KSVM_NAN])
-        return (Xh - mean) / scale, yi, classes, cw, count
-
-    def _dev_setup(self, torch, X, y, columns, row_index, scaler):
-        rows = _DevRows.within(torch, X, columns, row_index, lambda D: _check_limits(D, 2))
-        if rows.n < 1:
-            raise ValueError("X holds no rows")
-        yt = _dev_vec(torch, y, torch.int64, rows.dev)
-        if yt.numel() != rows.n:
-            raise ValueError("y must hold one class per row")
-        classes = torch.unique(yt)
-        C, D = int(classes.numel()), rows.D
-        if C < 2:
-            raise ValueError("the number of classes has to be greater than one; got %d class" % C)
-        _check_limits(D, C)
-        yi = torch.searchsorted(classes, yt).contiguous()
-        count = torch.bincount(yi, minlength=C).cpu().numpy()
-        cls_h = classes.cpu().numpy()
-        cw = self._weights(cls_h, count)
-        mean, scale = self._scaler_stats(scaler, D)
-        return rows, yi, classes, cls_h, count, cw, mean, scale
-
     def _dev_gamma(self, torch, Zp):
         """gamma from the packed z-scores [n, D] on the device: two-pass float64 sums."""
         if self.gamma == "auto":
@@ -370,18 +308,6 @@ class DeviceKernelSVC:
         mean = Zp.sum() / Zp.numel()
         var = float((((Zp - mean) ** 2).sum() / Zp.numel()).item())
         return 1.0 / (Zp.shape[1] * var) if var > 0 and np.isfinite(var) else 1.0
-
-    @staticmethod
-    def _state0(n, C, D, bound, mean, scale):
-        pairs = pairs_of(C)
-        s0 = np.zeros(_HDR + len(pairs) * _PW + 2 * D + C)
-        hi = s0.view(np.int64)
-        hi[0:4] = C, D, len(pairs), n
-        for p, (a, b) in enumerate(pairs):
-            hi[_HDR + p * _PW + _P_A], hi[_HDR + p * _PW + _P_B] = a, b
-        o = _HDR + len(pairs) * _PW
-        s0[o:o + D], s0[o + D:o + 2 * D], s0[o + 2 * D:o + 2 * D + C] = mean, scale, bound
-        return s0
 
     def _dev_state(self, torch, lib, rows, C, cw, mean, scale):
         n, D = rows.n, rows.D
@@ -490,53 +416,18 @@ class DeviceKernelSVC:
         if self._model is None or self._model[0] != key:
             stats = None
             if scaler is not None:
-                stats = torch.from_numpy(np.concatenate(self._scaler_stats(scaler, self.n_features_in_))).to(dev)
+                stats = torch.from_numpy(np.concatenate(scaler_stats(scaler, self.n_features_in_))).to(dev)
             self._model = (key, stats, torch.from_numpy(self._sv).to(dev), torch.from_numpy(self._coef).to(dev),
                            torch.from_numpy(self._sv_cls).to(dev), torch.from_numpy(self._rho).to(dev))
         return self._model[1:]
 
-    def _decide(self, X, columns=None, row_index=None, scaler=None, want=("pred",)):
-        """dict with the wanted of "decision" [n, P], "votes" [n, C] and "pred" (class indices)."""
-        self._check_fitted()
-        C, D = len(self.class_weight_), self.n_features_in_
-        if _pick_backend(self.backend, X) == "host":
-            Xh = _host_rows(X, columns, row_index)
-            if Xh.shape[1] != D:
-                raise ValueError("the model was fitted on %d features, got %d" % (D, Xh.shape[1]))
-            mean, scale = self._scaler_stats(scaler, D)
-            dec, votes, pred = _host_decision((Xh - mean) / scale, self._sv, self._coef, self._sv_cls, self._rho, self._gamma, C)
-            out = {"decision": dec, "votes": votes, "pred": pred}
-            return {k: out[k] for k in want}
-        torch, _lib, lib = _torch_lib()
-        rows = _DevRows(torch, X, columns, row_index)
-        if rows.D != D:
-            raise ValueError("the model was fitted on %d features, got %d" % (D, rows.D))
-        with torch.cuda.device(rows.dev):
-            stats, sv, coef, sv_cls, rho = self._device_model(torch, rows.dev, scaler)
-            n, P = rows.n, C * (C - 1) // 2
-            out = {"decision": torch.empty(n, P, dtype=torch.float64, device=rows.dev) if "decision" in want else None,
-                   "votes": torch.empty(n, C, dtype=torch.int64, device=rows.dev) if "votes" in want else None,
-                   "pred": torch.empty(n, dtype=torch.int64, device=rows.dev) if "pred" in want else None}
-            call("pinn_ksvm_decision", *rows.head(), C, stats, sv, coef, sv_cls, sv.shape[0], rho, self._gamma,
-                 out["decision"], out["votes"], out["pred"])
-        if not _is_tensor(X):
-            return {k: out[k].cpu().numpy() for k in want}
-        return {k: out[k] for k in want}
+    def _host_values(self, Z):
+        return _host_values(Z, self._sv, self._coef, self._sv_cls, self._rho, self._gamma, len(self.class_weight_))
 
-    def decision_function(self, X, columns=None, row_index=None, scaler=None, shape=None):
-        """[n, P] pairwise values for "ovo"; for "ovr" [n, C], scikit-learn's transform of votes and confidences ([n] for two
-        classes, as scikit-learn: the negated value, positive for the second class).  `shape` overrides the constructor's."""
-        shape = self.decision_function_shape if shape is None else shape
-        if shape not in ("ovr", "ovo"):
-            raise ValueError("shape must be 'ovr' or 'ovo'")
-        dec = self._decide(X, columns, row_index, scaler, want=("decision",))["decision"]
-        C = len(self.class_weight_)
-        if C == 2:
-            return -dec[:, 0]
-        return dec if shape == "ovo" else ovr_decision_function(dec, C)
-
-    def predict(self, X, columns=None, row_index=None, scaler=None):
-        return self._labels(self._decide(X, columns, row_index, scaler, want=("pred",))["pred"])
+    def _launch_decision(self, torch, rows, scaler, C, out):
+        stats, sv, coef, sv_cls, rho = self._device_model(torch, rows.dev, scaler)
+        call("pinn_ksvm_decision", *rows.head(), C, stats, sv, coef, sv_cls, sv.shape[0], rho, self._gamma,
+             out["decision"], out["votes"], out["pred"])
 
 
 def build_kernel_svm_classifier(backend="auto", **svc_args):
@@ -552,18 +443,5 @@ def run_supervised_svm_kernel(X_tr, y_tr, X_te, C=0.05, gamma="scale", backend="
     return build_kernel_svm_classifier(backend, C=C, gamma=gamma, **svc_args).fit(X_tr, y_tr).predict(X_te)
 
 
-class KernelSVMDiagnoser:
-    """Predicted classes chunk by chunk from a fitted pipeline (build_kernel_svm_classifier), the online form next to
-    svm.SVMDiagnoser: `update(rows)` takes the next rows of the results array [n, >= 17] (device tensor, or a host array) and
-    returns y_pred for them.  On the device a chunk is one kernel launch that reads the feature columns in place."""
-
-    def __init__(self, pipeline, features=DEFAULT_FEATURES):
-        pipeline.named_steps["svc"]._check_fitted()
-        self.pipeline = pipeline
-        self.columns = columns_of(features, parse_features)
-        self.n_seen = 0
-
-    def update(self, rows):
-        y_pred = self.pipeline.predict(rows, columns=self.columns)
-        self.n_seen += int(rows.shape[0])
-        return y_pred
+class KernelSVMDiagnoser(SVMDiagnoser):
+    """svm.SVMDiagnoser on a fitted pipeline of build_kernel_svm_classifier: predicted classes chunk by chunk."""

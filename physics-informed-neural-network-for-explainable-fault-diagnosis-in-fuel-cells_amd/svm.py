@@ -21,15 +21,16 @@ import warnings
 
 import numpy as np
 
-from ._device import _DevRows, _as_numpy, _dev_vec, _host_rows, _is_tensor, _pick_backend, _torch_lib, call, columns_of
-from .detection import DeviceLogisticRegression, DeviceStandardScaler
+from ._classify import OneVsOneSVC, ovr_decision_function, pairs_of, scaler_stats, slot_of  # noqa: F401
+from ._device import _DevRows, _as_numpy, _host_rows, _is_tensor, _pick_backend, _torch_lib, call, columns_of
+from .detection import DeviceStandardScaler
 from .diagnosis import DEFAULT_FEATURES, parse_features
 
 # limits, status words and the 8-byte words of the state block: one copy, next to the bindings (include/pinn_hip.h)
 from ._lib import (SVM_MAX_CLASSES as MAX_CLASSES, SVM_MAX_FEAT as MAX_FEAT, SVM_NAN, SVM_P_A as _P_A, SVM_P_B as _P_B, SVM_P_BETA as _P_BETA,
                    SVM_P_CONVERGED as _P_CONV, SVM_P_GAP as _P_GAP, SVM_P_ITER as _P_ITER, SVM_P_KA as _P_KA, SVM_P_KB as _P_KB,
-                   SVM_P_M as _P_M, SVM_P_W as _P_W, SVM_PAIR_WORDS as _PW, SVM_RANGE, SVM_SINGULAR, SVM_ST_C, SVM_ST_CONVERGED, SVM_ST_D,
-                   SVM_ST_HEADER as _HDR, SVM_ST_N, SVM_ST_P, SVM_ST_STATUS)
+                   SVM_P_M as _P_M, SVM_P_W as _P_W, SVM_PAIR_WORDS as _PW, SVM_RANGE, SVM_SINGULAR, SVM_ST_C, SVM_ST_CONVERGED,
+                   SVM_ST_HEADER as _HDR, SVM_ST_STATUS)
 
 START_SLACK = 1.0                        # s and z start at max(+-(t f - 1), 0) + this
 STEP_TO_BOUNDARY = 0.995
@@ -44,20 +45,10 @@ def _check_limits(D, C):
         raise NotImplementedError("the linear SVC takes 1..%d features and 2..%d classes, got %d and %d" % (MAX_FEAT, MAX_CLASSES, D, C))
 
 
-def pairs_of(C):
-    """[(a, b)] with a < b in scikit-learn's order."""
-    return [(a, b) for a in range(C) for b in range(a + 1, C)]
-
-
 def n_pass_sums(D):
     """Sums of one row pass per pair: the upper triangle of sum u u' / d (u = (z, 1)), sum g t u / d, sum alpha t u (the last
     is t'alpha), then the sum of s alpha + z (c - alpha), sum alpha and the hinge sum."""
     return (D + 1) * (D + 2) // 2 + 2 * (D + 1) + 3
-
-
-def slot_of(k, other):
-    """The slot of class `other` in a row of class k: the other classes in increasing order."""
-    return other if other < k else other - 1
 
 
 # ---------------------------------------------------------------------------------------------- host backend
@@ -169,17 +160,6 @@ def _host_ipm(Z, t, c, gap_tol, max_iter, trace=None):
     return al, w, beta, it, gap, primal, conv
 
 
-def _host_decision(Z, coef, intercept, C):
-    """(values [n, P], votes [n, C], prediction [n]): a vote for a where the value is > 0, else for b; the first maximum."""
-    dec = np.stack([_dot_in_order(Z, coef[p]) + intercept[p] for p in range(coef.shape[0])], axis=1) if coef.shape[0] else np.zeros((len(Z), 0))
-    votes = np.zeros((Z.shape[0], C), dtype=np.int64)
-    for p, (a, b) in enumerate(pairs_of(C)):
-        pos = dec[:, p] > 0
-        votes[:, a] += pos
-        votes[:, b] += ~pos
-    return dec, votes, votes.argmax(axis=1).astype(np.int64)
-
-
 def _dot_in_order(Z, w):
     """sum_i w_i z_i of every row, products added in feature order as the kernel does."""
     v = np.zeros(Z.shape[0])
@@ -188,27 +168,8 @@ def _dot_in_order(Z, w):
     return v
 
 
-def ovr_decision_function(dec_ovo, C):
-    """scikit-learn's _ovr_decision_function as SVC calls it: per class the votes (a where the value is >= 0) plus the summed
-    confidences squashed into (-1/3, 1/3).  numpy or torch."""
-    cols = []
-    for k in range(C):
-        v = 0.0 * dec_ovo[:, 0]
-        conf = 0.0 * dec_ovo[:, 0]
-        for p, (a, b) in enumerate(pairs_of(C)):
-            if a == k:
-                v, conf = v + (dec_ovo[:, p] >= 0) * 1.0, conf + dec_ovo[:, p]
-            elif b == k:
-                v, conf = v + (dec_ovo[:, p] < 0) * 1.0, conf - dec_ovo[:, p]
-        cols.append(v + conf / (3.0 * (abs(conf) + 1.0)))
-    if _is_tensor(dec_ovo):
-        import torch
-        return torch.stack(cols, dim=1)
-    return np.stack(cols, axis=1)
-
-
 # ---------------------------------------------------------------------------------------------- the classifier
-class DeviceLinearSVC:
+class DeviceLinearSVC(OneVsOneSVC):
     """One-vs-one linear SVC with scikit-learn's SVC arguments and defaults; `kernel="linear"` only.  `tol` is accepted for
     compatibility: the solver stops when primal - dual <= gap_tol max(1, primal) of every pair.
 
@@ -225,39 +186,14 @@ class DeviceLinearSVC:
                  random_state=None, gap_tol=1e-11, backend="auto", chunk=8):
         if kernel != "linear":
             raise NotImplementedError("kernel=%r: only 'linear' is implemented" % (kernel,))
-        if break_ties:
-            raise NotImplementedError("break_ties=True is not implemented")
-        if decision_function_shape not in ("ovr", "ovo"):
-            raise ValueError("decision_function_shape must be 'ovr' or 'ovo'")
-        if backend not in ("auto", "device", "host"):
-            raise ValueError("backend must be 'auto', 'device' or 'host'")
-        if not (isinstance(class_weight, dict) or class_weight in (None, "balanced")):
-            raise ValueError("class_weight must be None, 'balanced' or a dict")
-        if not C > 0 or not np.isfinite(C) or not gap_tol > 0 or int(chunk) < 1 or (int(max_iter) < 1 and int(max_iter) != -1):
-            raise ValueError("C > 0, gap_tol > 0, chunk >= 1 and max_iter >= 1 (or -1) are required")
-        self.C, self.kernel, self.class_weight, self.tol, self.max_iter = float(C), kernel, class_weight, float(tol), int(max_iter)
-        self.decision_function_shape, self.break_ties, self.random_state = decision_function_shape, bool(break_ties), random_state
-        self.gap_tol, self.backend, self.chunk = float(gap_tol), backend, int(chunk)
-        self._model = None
+        super().__init__(C, class_weight, max_iter, decision_function_shape, break_ties, random_state, backend, chunk, "gap_tol", gap_tol)
+        self.kernel, self.tol, self.gap_tol = kernel, float(tol), float(gap_tol)
 
-    def _check_fitted(self):
-        if not hasattr(self, "coef_"):
-            raise RuntimeError("this DeviceLinearSVC is not fitted yet")
+    _FITTED, _NOT_FINITE, _LAYOUT = "coef_", _STATUS_TEXT[SVM_NAN], (_HDR, _PW, _P_A, _P_B, SVM_ST_C)
+    _check_limits = staticmethod(_check_limits)
 
     def _limit(self):
         return 500 if self.max_iter == -1 else self.max_iter      # no limit in scikit-learn; 10 to 200 iterations are taken
-
-    def _weights(self, classes, count):
-        C, n = len(classes), int(count.sum())
-        if (count < 1).any():
-            raise ValueError("a class without rows cannot be fitted")
-        if self.class_weight is None:
-            return np.ones(C)
-        if isinstance(self.class_weight, dict):
-            return np.array([float(self.class_weight.get(k.item() if hasattr(k, "item") else k, 1.0)) for k in classes])
-        return n / (C * count.astype(np.float64))
-
-    _scaler_stats = staticmethod(DeviceLogisticRegression._scaler_stats)
 
     def _publish(self, classes, cw, coef, icpt, n_iter, gap, conv, alpha, yi, as_tensor, dev=None):
         C = len(cw)
@@ -280,23 +216,6 @@ class DeviceLinearSVC:
         self.n_support_ = np.bincount(y_h[sup], minlength=C).astype(np.int64)
         self._model = None
 
-    def pair_alpha(self, a, b):
-        """(row positions, alpha) of the pair of class indices a < b, positions into the rows `fit` was given."""
-        self._check_fitted()
-        a, b = int(a), int(b)
-        if not 0 <= a < b < len(self.class_weight_):
-            raise ValueError("a < b must be class indices")
-        yi, al = self._yi, self.alpha_
-        if _is_tensor(al):
-            import torch
-            ia, ib = torch.nonzero(yi == a).reshape(-1), torch.nonzero(yi == b).reshape(-1)
-            pos, order = torch.sort(torch.cat([ia, ib]))
-            return pos, torch.cat([al[ia, slot_of(a, b)], al[ib, slot_of(b, a)]])[order]
-        ia, ib = np.nonzero(yi == a)[0], np.nonzero(yi == b)[0]
-        pos = np.concatenate([ia, ib])
-        order = np.argsort(pos, kind="stable")
-        return pos[order], np.concatenate([al[ia, slot_of(a, b)], al[ib, slot_of(b, a)]])[order]
-
     # ---- fit
     def fit(self, X, y, sample_weight=None, columns=None, row_index=None, scaler=None, trace=None):
         """`scaler`: a fitted DeviceStandardScaler whose statistics standardise the rows.  `trace`: a list that receives one
@@ -307,20 +226,8 @@ class DeviceLinearSVC:
             if trace is not None:
                 raise NotImplementedError("trace= is kept by the host backend only: the device reads its state once per chunk")
             return self._fit_device(X, y, columns, row_index, scaler)
-        Xh = _host_rows(X, columns, row_index)
-        yh = _as_numpy(y).reshape(-1)
-        if yh.shape[0] != Xh.shape[0]:
-            raise ValueError("y must hold one class per row")
-        classes, yi = np.unique(yh, return_inverse=True)
-        C, D = len(classes), Xh.shape[1]
-        if C < 2:
-            raise ValueError("the number of classes has to be greater than one; got %d class" % C)
-        _check_limits(D, C)
-        mean, scale = self._scaler_stats(scaler, D)
-        cw = self._weights(classes, np.bincount(yi, minlength=C))
-        if not np.isfinite(Xh).all():
-            raise ValueError(_STATUS_TEXT[SVM_NAN])
-        Z = (Xh - mean) / scale
+        Z, yi, classes, cw, _ = self._host_setup(X, y, columns, row_index, scaler)
+        C, D = len(classes), Z.shape[1]
         pairs = pairs_of(C)
         P = len(pairs)
         coef, icpt, n_iter, gap, conv = np.zeros((P, D)), np.zeros(P), np.zeros(P, dtype=np.int64), np.zeros(P), np.zeros(P, dtype=bool)
@@ -337,52 +244,21 @@ class DeviceLinearSVC:
         self._publish(classes, cw, coef, icpt, n_iter, gap, conv, alpha, yi, False)
         return self
 
-    def _dev_setup(self, torch, rows, y):
-        """Class indices, the classes (device and host), their counts and weights."""
-        yt = _dev_vec(torch, y, torch.int64, rows.dev)
-        if yt.numel() != rows.n:
-            raise ValueError("y must hold one class per row")
-        classes = torch.unique(yt)
-        C, D = int(classes.numel()), rows.D
-        if C < 2:
-            raise ValueError("the number of classes has to be greater than one; got %d class" % C)
-        _check_limits(D, C)
-        yi = torch.searchsorted(classes, yt).contiguous()
-        count = torch.bincount(yi, minlength=C).cpu().numpy()
-        cls_h = classes.cpu().numpy()
-        cw = self._weights(cls_h, count)
-        return yi, classes, cls_h, count, cw
-
-    @staticmethod
-    def _state0(n, C, D, count, bound, mean, scale):
-        pairs = pairs_of(C)
-        words = _HDR + len(pairs) * _PW + 2 * D + C
-        s0 = np.zeros(words)
-        hi = s0.view(np.int64)
-        hi[SVM_ST_C], hi[SVM_ST_D], hi[SVM_ST_P], hi[SVM_ST_N] = C, D, len(pairs), n
-        for p, (a, b) in enumerate(pairs):
+    def _state0(self, n, C, D, count, bound, mean, scale):
+        s0 = super()._state0(n, C, D, bound, mean, scale)
+        for p, (a, b) in enumerate(pairs_of(C)):
             o = _HDR + p * _PW
-            hi[o + _P_A], hi[o + _P_B] = a, b
             Ca, Cb = bound[a] * count[a], bound[b] * count[b]
             s0[o + _P_M] = count[a] + count[b]
             s0[o + _P_KA], s0[o + _P_KB] = START_ALPHA * min(Ca, Cb) / Ca, START_ALPHA * min(Ca, Cb) / Cb
-        o = _HDR + len(pairs) * _PW
-        s0[o:o + D], s0[o + D:o + 2 * D], s0[o + 2 * D:o + 2 * D + C] = mean, scale, bound
         return s0
 
     def _fit_device(self, X, y, columns, row_index, scaler):
         torch, _lib, lib = _torch_lib()
-        D = len(columns) if columns is not None else (int(X.shape[1]) if len(X.shape) == 2 else 1)
-        if D > MAX_FEAT:
-            _check_limits(D, 2)
-        rows = _DevRows(torch, X, columns, row_index)
-        if rows.n < 1:
-            raise ValueError("X holds no rows")
+        rows, yi, classes, cls_h, count, cw, mean, scale = self._dev_setup(torch, X, y, columns, row_index, scaler)
         with torch.cuda.device(rows.dev):
-            yi, classes, cls_h, count, cw = self._dev_setup(torch, rows, y)
             C, D, n = len(cw), rows.D, rows.n
             P = C * (C - 1) // 2
-            mean, scale = self._scaler_stats(scaler, D)
             s0 = self._state0(n, C, D, count, self.C * cw, mean, scale)
             words = lib.pinn_svm_state_bytes(n, C, D) // 8
             st = torch.zeros(words, dtype=torch.float64, device=rows.dev)
@@ -424,7 +300,7 @@ class DeviceLinearSVC:
         yh = _as_numpy(y).astype(np.int64).reshape(-1)
         count = np.bincount(yh, minlength=C)
         cw = self._weights(np.arange(C), count)
-        mean, scale = self._scaler_stats(scaler, D)
+        mean, scale = scaler_stats(scaler, D)
         a_h, s_h, z_h = (np.asarray(_as_numpy(v), dtype=np.float64).reshape(len(yh), C - 1) for v in (alpha, s, z))
         if _pick_backend(self.backend, X) == "host":
             Z = (_host_rows(X, columns, row_index) - mean) / scale
@@ -460,54 +336,18 @@ class DeviceLinearSVC:
     def _device_model(self, torch, dev, scaler):
         key = (str(dev), id(scaler))
         if self._model is None or self._model[0] != key:
-            mean, scale = self._scaler_stats(scaler, self.n_features_in_)
+            mean, scale = scaler_stats(scaler, self.n_features_in_)
             m = np.concatenate([mean, scale, self._w.reshape(-1), self._b.reshape(-1)])
             self._model = (key, torch.from_numpy(m).to(dev))
         return self._model[1]
 
-    def _decide(self, X, columns=None, row_index=None, scaler=None, want=("pred",)):
-        """dict with the wanted of "decision" [n, P], "votes" [n, C] and "pred" (class indices)."""
-        self._check_fitted()
-        C, D = len(self.class_weight_), self.n_features_in_
-        if _pick_backend(self.backend, X) == "host":
-            Xh = _host_rows(X, columns, row_index)
-            if Xh.shape[1] != D:
-                raise ValueError("the model was fitted on %d features, got %d" % (D, Xh.shape[1]))
-            mean, scale = self._scaler_stats(scaler, D)
-            dec, votes, pred = _host_decision((Xh - mean) / scale, self._w, self._b, C)
-            out = {"decision": dec, "votes": votes, "pred": pred}
-            return {k: out[k] for k in want}
-        torch, _lib, lib = _torch_lib()
-        rows = _DevRows(torch, X, columns, row_index)
-        if rows.D != D:
-            raise ValueError("the model was fitted on %d features, got %d" % (D, rows.D))
-        with torch.cuda.device(rows.dev):
-            model = self._device_model(torch, rows.dev, scaler)
-            n, P = rows.n, C * (C - 1) // 2
-            out = {"decision": torch.empty(n, P, dtype=torch.float64, device=rows.dev) if "decision" in want else None,
-                   "votes": torch.empty(n, C, dtype=torch.int64, device=rows.dev) if "votes" in want else None,
-                   "pred": torch.empty(n, dtype=torch.int64, device=rows.dev) if "pred" in want else None}
-            call("pinn_svm_decision", *rows.head(), C, model, out["decision"], out["votes"], out["pred"])
-        if not _is_tensor(X):
-            return {k: out[k].cpu().numpy() for k in want}
-        return {k: out[k] for k in want}
+    def _host_values(self, Z):
+        if not self._w.shape[0]:
+            return np.zeros((len(Z), 0))
+        return np.stack([_dot_in_order(Z, self._w[p]) + self._b[p] for p in range(self._w.shape[0])], axis=1)
 
-    _labels = DeviceLogisticRegression._labels
-
-    def decision_function(self, X, columns=None, row_index=None, scaler=None, shape=None):
-        """[n, P] pairwise values for "ovo"; for "ovr" [n, C], scikit-learn's transform of votes and confidences ([n] for two
-        classes, as scikit-learn: the negated value, positive for the second class).  `shape` overrides the constructor's."""
-        shape = self.decision_function_shape if shape is None else shape
-        if shape not in ("ovr", "ovo"):
-            raise ValueError("shape must be 'ovr' or 'ovo'")
-        dec = self._decide(X, columns, row_index, scaler, want=("decision",))["decision"]
-        C = len(self.class_weight_)
-        if C == 2:
-            return -dec[:, 0]
-        return dec if shape == "ovo" else ovr_decision_function(dec, C)
-
-    def predict(self, X, columns=None, row_index=None, scaler=None):
-        return self._labels(self._decide(X, columns, row_index, scaler, want=("pred",))["pred"])
+    def _launch_decision(self, torch, rows, scaler, C, out):
+        call("pinn_svm_decision", *rows.head(), C, self._device_model(torch, rows.dev, scaler), out["decision"], out["votes"], out["pred"])
 
 
 class SVCPipeline:

@@ -36,10 +36,10 @@ def main():
                 rows[cur][m.group(1).strip()] = int(m.group(2))
         for k, r in rows.items():
             name = subprocess.run(["c++filt", k], stdout=subprocess.PIPE).stdout.decode().strip()
-            name = re.sub(r"\(.*$", "", name).replace("void ", "").replace("pinn::x6::", "").replace("pinn::", "")
-            name = name.replace("(anonymous namespace)::", "")
-            print("%-58s VGPR %3d AGPR %3d  VGPR-spill %3d  SGPR-spill %3d  scratch %3d B/lane  waves/SIMD %d  LDS(static) %6d" % (
-                name, r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("VGPRs Spill", -1), r.get("SGPRs Spill", -1),
+            name = re.sub(r"\(.*$", "", name.replace("(anonymous namespace)::", ""))      # before the cut at the argument list's bracket
+            name = name.replace("void ", "").replace("pinn::x6::", "").replace("pinn::", "")
+            print("%-58s VGPR %3d AGPR %3d SGPR %3d  VGPR-spill %3d  SGPR-spill %3d  scratch %3d B/lane  waves/SIMD %d  LDS(static) %6d" % (
+                name, r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("TotalSGPRs", -1), r.get("VGPRs Spill", -1), r.get("SGPRs Spill", -1),
                 r.get("ScratchSize", -1), r.get("Occupancy", -1), r.get("LDS Size", -1)))
 
 
