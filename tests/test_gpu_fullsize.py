@@ -9,6 +9,10 @@ workgroup in the grid-stride loops, 256 live gradient slabs, a 7.7 GB training s
         rows around 558 000 -- where a per-row stash offset would cross 2^32 bytes -- and the ragged tail), with the same
         calls on the windows alone (matching row_offset), and those agree with the oracle at the fp32 tolerance
         (the bf16-mixed family: at its rtol 2e-2 against the fp32 oracle).
+
+(i) and (ii) compare the training kernels with themselves: a row tile that every call skips, counts twice or scales wrongly passes both, and
+one 16-row tile in 1e6 rows is below (ii)'s gate.  test_gpu_wgrad_routes.py holds the same weight-gradient routes and tile walks to a float64
+oracle at the smallest row counts that reach them (up to 163 857 rows).
 """
 import ctypes
 
