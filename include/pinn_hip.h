@@ -440,6 +440,28 @@ int pinn_rf_series(const double* d_arr, long long ld, long long n_arr_rows, cons
                    double* d_S_tot, double* d_C, double* d_RF_inst, double* d_RF_smooth, double* d_carry_out,
                    void* d_ws, size_t ws_bytes, void* stream);
 
+/* Sweep of RF parameter sets (calibration): n_cand candidates over the same positions and segments in two launches.
+ * The candidate table d_cand is [n_cand][PINN_RF_SWEEP_WORDS] float64 in device memory:
+ *   0..7 w[d] | 8..11 beta[l] | 12 p_layer | 13 z_safe | 14 lambda_decay | 15 k_logistic | 16 c0_logistic |
+ *   17 c_max | 18 alpha_smooth | 19 warn threshold | 20 danger threshold | 21..23 reserved, 0
+ * Of `shape`, n_cols, n_layers, col[] and layer_of[] are read; the rest is ignored.  Per (candidate, segment) the result is
+ * that of pinn_rf_series without carry-in on that segment followed by pinn_rf_first_alarm(PINN_RF_ABOVE) at the
+ * candidate's two thresholds: C[first] = 0, RF_smooth[first] = RF_inst[first], NaN never matches and never enters the
+ * peak, a gather index outside the array reads nothing.  Outputs, each [n_cand][n_segments] (n_segments == 0: one segment):
+ * d_first_warn, d_first_danger (position from the segment's start, -1: none), d_n_warn (rows with RF_smooth >= warn),
+ * d_peak (maximum of the non-NaN RF_smooth, NaN if there is none), d_carry_out (may be NULL) [..][2] = (C, RF_smooth) at
+ * the segment's last row.  d_bad [n_cand]: 1 where any of a candidate's 24 words is not finite or its p_layer is 0; such a
+ * candidate gets -1 / 0 / NaN and the call still returns PINN_OK.  n_cand >= 1 and n_cand * n_segments <= 2^31 - 1.  The
+ * workspace holds z = (R - mu) / sigma as [n_cols][n] columns.  Nothing per row is written, no workgroup waits on
+ * another, and two calls give the same bytes. */
+#define PINN_RF_SWEEP_WORDS 24
+size_t pinn_rf_sweep_workspace_bytes(long long n, int n_cols);
+int pinn_rf_sweep(const double* d_arr, long long ld, long long n_arr_rows, const pinn_rf_params_t* shape,
+                  const double* d_mu, const double* d_sigma, const long long* d_row_index, long long n,
+                  const long long* d_seg_start, long long n_segments, const double* d_cand, long long n_cand,
+                  long long* d_first_warn, long long* d_first_danger, long long* d_n_warn, double* d_peak,
+                  double* d_carry_out, int* d_bad, void* d_ws, size_t ws_bytes, void* stream);
+
 /* find_first_alarm_index (04:289-300) per segment: d_first[s] = the first position, counted from the segment's start, whose
  * value is >= (PINN_RF_ABOVE) or <= (PINN_RF_BELOW) the threshold, or -1.  NaN never matches.  Position j reads
  * d_series[row * stride] with row = d_row_index[j] (NULL: j).  relative != 0: the threshold of a segment is the value at

@@ -6,7 +6,7 @@ Public surface mirrors the reference's `01_train_pinn_multiphysics_model.py`:
 `load_data_normal_raw`, `load_data_fault_raw`, `combine_and_normalize_datasets`, `add_noise_to_combined_data` (ingest),
 `plot_model_results_detailed_split` (its statistics; no figure), and `save_checkpoint` / `load_checkpoint`; and the
 stage after the results array, script 04's risk function: `estimate_mu_sigma_normal`, `compute_rf_time_series`,
-`find_first_alarm_index`, `compute_rf_advance_for_condition`, with `rf_advance_for_conditions` and `RiskMonitor` (risk); and script 03's Gaussian-mixture
+`find_first_alarm_index`, `compute_rf_advance_for_condition`, with `rf_advance_for_conditions`, `RiskMonitor` and the calibration of its parameters, `rf_grid`, `rf_sweep`, `calibrate_rf` (risk); and script 03's Gaussian-mixture
 fault diagnosis: `fit_gmm_and_get_probabilities`, `extract_X_y`, the spec parsers, with `DeviceGMM`, `FaultDiagnoser` and
 `classification_metrics` (diagnosis); and script 02's fault detection: `build_classifier`, `explain_coefficients`, with
 `DeviceStandardScaler`, `DeviceLogisticRegression`, `roc_curve`, `auc`, `auc_score`, `stratified_split`,
@@ -38,6 +38,7 @@ _LAZY = {
     "save_checkpoint": "report", "load_checkpoint": "report",
     "estimate_mu_sigma_normal": "risk", "compute_rf_time_series": "risk", "find_first_alarm_index": "risk",
     "compute_rf_advance_for_condition": "risk", "rf_advance_for_conditions": "risk", "rf_series": "risk", "RiskMonitor": "risk",
+    "rf_grid": "risk", "rf_sweep": "risk", "calibrate_rf": "risk", "RFSweep": "risk", "RFCalibration": "risk",
     "DeviceGMM": "diagnosis", "FaultDiagnoser": "diagnosis", "fit_gmm_and_get_probabilities": "diagnosis",
     "classification_metrics": "diagnosis", "extract_X_y": "diagnosis", "parse_features": "diagnosis",
     "parse_group_spec": "diagnosis", "build_label_mapper": "diagnosis", "normalize_feature_spec": "diagnosis",

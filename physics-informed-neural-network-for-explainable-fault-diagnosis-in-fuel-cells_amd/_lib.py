@@ -70,6 +70,7 @@ class RFParams(ctypes.Structure):
 
 
 RF_ABOVE, RF_BELOW, RF_TILE = 0, 1, 2048
+RF_SWEEP_WORDS = 24                     # float64 words of one candidate of pinn_rf_sweep (include/pinn_hip.h)
 
 # pinn_gmm.hip: limits, status and the 8-byte words of the state header
 GMM_MAX_COMP, GMM_MAX_FEAT, GMM_MAX_CLASSES, GMM_SINGULAR, GMM_TILE = 32, 8, 16, 1, 128
@@ -193,6 +194,9 @@ _SIGS = {
     "pinn_rf_workspace_bytes": (c_size_t, [c_ll, c_ll]),
     "pinn_rf_series": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(RFParams), c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_ll,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_rf_sweep_workspace_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_rf_sweep": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(RFParams), c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_ll,
+                              c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_rf_first_alarm": (c_int, [c_void_p, c_ll, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, ctypes.c_double, c_void_p,
                                     c_void_p]),
     "pinn_gmm_state_bytes": (c_size_t, [c_int, c_int]),

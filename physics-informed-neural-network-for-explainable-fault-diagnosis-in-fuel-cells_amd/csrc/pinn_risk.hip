@@ -2,6 +2,7 @@
 //   pinn_rf_stats       mu / sigma of the residual columns over the normal rows      (04:181-197)
 //   pinn_rf_series      S_tot -> decaying integral C -> logistic RF_inst -> smoothed  (04:201-285)
 //   pinn_rf_first_alarm first sample at or past a threshold, per segment              (04:289-300)
+//   pinn_rf_sweep       many parameter sets over the same segments: first alarms, alarm rows and peak per (set, segment)
 // All arithmetic is float64 and separately rounded (built with -ffp-contract=off).
 //
 // The two recurrences  C(t) = lambda C(t-1) + S(t)  and  RF_s(t) = alpha RF(t) + (1-alpha) RF_s(t-1)  are scans over
@@ -114,6 +115,36 @@ __device__ __forceinline__ Op block_exclusive(const Op& mine, Op* s_wave, Op* to
   return combine(pre, prev);
 }
 
+// S_tot of one row from its z-scores (04:240-259); the layer sums go to S_layers[L * n + j] when it is given
+__device__ __forceinline__ double s_of_z(const RiskDev& a, const double z[PINN_RF_MAX_COLS], double* __restrict__ S_layers,
+                                         long long n, long long j) {
+  double term[PINN_RF_MAX_COLS];
+#pragma unroll
+  for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+    term[d] = 0.0;
+    if (d < a.n_cols) {
+      const double t = fabs(z[d]) - a.z_safe;
+      const double at = (t > 0.0 || t != t) ? t : 0.0;        // np.maximum(0, .): NaN propagates
+      term[d] = a.w[d] * (a.p_is_two ? at * at : pow(at, a.p));
+    }
+  }
+  double S = 0.0;
+#pragma unroll
+  for (int L = 0; L < PINN_RF_MAX_LAYERS; ++L) {
+    if (L < a.n_layers) {
+      double acc = 0.0;
+      bool used = false;
+#pragma unroll
+      for (int d = 0; d < PINN_RF_MAX_COLS; ++d)
+        if (d < a.n_cols && a.layer_of[d] == L) { acc = used ? acc + term[d] : term[d]; used = true; }
+      const double Sl = used ? (a.p_is_two ? sqrt(acc) : pow(acc, a.inv_p)) : 0.0;
+      if (S_layers) S_layers[(long long)L * n + j] = Sl;
+      S += a.beta[L] * Sl;
+    }
+  }
+  return S;
+}
+
 // ---- per-row instantaneous intensity S_tot (04:233-259), rows taken striped so that neighbouring lanes read neighbouring rows
 __device__ __forceinline__ void stage_s(const RiskDev& a, const double* __restrict__ arr, long long ld, long long n_arr,
                                         const double* __restrict__ mu, const double* __restrict__ sigma,
@@ -133,32 +164,16 @@ __device__ __forceinline__ void stage_s(const RiskDev& a, const double* __restri
     const long long row = ridx ? ridx[j] : j;
     const bool ok = row >= 0 && row < n_arr;                  // a gather index outside the array reads nothing: the row is NaN
     const double* r = arr + (ok ? row : 0) * ld;
-    double term[PINN_RF_MAX_COLS];
+    double z[PINN_RF_MAX_COLS];
 #pragma unroll
     for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
-      term[d] = 0.0;
+      z[d] = 0.0;
       if (d < a.n_cols) {
         const double R = ok ? r[a.col[d]] : quiet_nan();
-        const double z = (R - m[d]) / sg[d];
-        const double t = fabs(z) - a.z_safe;
-        const double at = (t > 0.0 || t != t) ? t : 0.0;        // np.maximum(0, .): NaN propagates
-        term[d] = a.w[d] * (a.p_is_two ? at * at : pow(at, a.p));
+        z[d] = (R - m[d]) / sg[d];
       }
     }
-    double S = 0.0;
-#pragma unroll
-    for (int L = 0; L < PINN_RF_MAX_LAYERS; ++L) {
-      if (L < a.n_layers) {
-        double acc = 0.0;
-        bool used = false;
-#pragma unroll
-        for (int d = 0; d < PINN_RF_MAX_COLS; ++d)
-          if (d < a.n_cols && a.layer_of[d] == L) { acc = used ? acc + term[d] : term[d]; used = true; }
-        const double Sl = used ? (a.p_is_two ? sqrt(acc) : pow(acc, a.inv_p)) : 0.0;
-        if (S_layers) S_layers[(long long)L * n + j] = Sl;
-        S += a.beta[L] * Sl;
-      }
-    }
+    const double S = s_of_z(a, z, S_layers, n, j);
     if (S_out) S_out[j] = S;
     s_val[pidx(i)] = S;
   }
@@ -499,6 +514,165 @@ __global__ __launch_bounds__(kThreads) void stats_final_kernel(StatsDev a, const
   }
 }
 
+// ---- sweep of parameter sets: z-scores staged once as [D][n] columns, then one workgroup per (candidate, segment)
+struct SweepShape {
+  int n_cols, n_layers;
+  int col[PINN_RF_MAX_COLS], layer_of[PINN_RF_MAX_COLS];
+};
+
+// words of a candidate (include/pinn_hip.h)
+constexpr int kCandP = 12, kCandZSafe = 13, kCandLambda = 14, kCandK = 15, kCandC0 = 16, kCandCMax = 17, kCandAlpha = 18,
+              kCandWarn = 19, kCandDanger = 20;
+constexpr long long kNoPosition = 0x7fffffffffffffffLL;
+
+__device__ __forceinline__ bool finite_word(double x) { return fabs(x) <= 1.7976931348623157e308; }     // false for NaN and +-inf
+
+// z = (R - mu) / sigma of every position and column, the division as in stage_s; column d begins at z + d * zs
+__global__ __launch_bounds__(kThreads) void sweep_stage_kernel(SweepShape sh, const double* __restrict__ arr, long long ld, long long n_arr,
+                                                                const double* __restrict__ mu, const double* __restrict__ sigma,
+                                                                const long long* __restrict__ ridx, long long n,
+                                                                double* __restrict__ z, long long zs) {
+  const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (j >= n) return;
+  const long long row = ridx ? ridx[j] : j;
+  const bool ok = row >= 0 && row < n_arr;                    // a gather index outside the array reads nothing: the row is NaN
+  const double* r = arr + (ok ? row : 0) * ld;
+#pragma unroll
+  for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+    if (d < sh.n_cols) {
+      const double R = ok ? r[sh.col[d]] : quiet_nan();
+      z[(long long)d * zs + j] = (R - mu[d]) / sigma[d];
+    }
+  }
+}
+
+// Workgroup b evaluates candidate b / ns on segment b % ns: it walks the segment tile by tile in order, the values of both
+// recurrences entering a tile held in registers (the workgroup's aggregate applied to the value that entered the tile
+// before, as rf_carry_kernel does between tiles), and writes four words and the carry: nothing per row.  A thread keeps its
+// own first positions, count and maximum over all tiles; they meet once, after the last tile, in lane and wave order.
+__global__ __launch_bounds__(kThreads) void rf_sweep_kernel(SweepShape sh, const double* __restrict__ z, long long zs, long long n,
+                                                             const long long* __restrict__ ss, long long ns,
+                                                             const double* __restrict__ cand, long long* __restrict__ first_warn,
+                                                             long long* __restrict__ first_danger, long long* __restrict__ n_warn,
+                                                             double* __restrict__ peak, double* __restrict__ carry, int* __restrict__ bad) {
+  __shared__ double s_val[kPad];
+  __shared__ Op s_wave[kThreads / 64];
+  __shared__ long long s_int[kThreads / 64][3];
+  __shared__ double s_peak[kThreads / 64];
+  __shared__ RiskDev s_a;
+  __shared__ double s_thr[2];
+  __shared__ int s_bad;
+  const long long b = blockIdx.x;
+  const long long p = b / ns, s = b - p * ns;
+  // the candidate's 24 words are read once, by thread 0, and its RiskDev lives in LDS: every thread reads the same words
+  // from there when it needs them, so none of them has to stay in a vector register across the tile loop
+  if (threadIdx.x == 0) {
+    const double* __restrict__ c = cand + p * PINN_RF_SWEEP_WORDS;
+    bool is_bad = false;
+    for (int q = 0; q < PINN_RF_SWEEP_WORDS; ++q) is_bad = is_bad || !finite_word(c[q]);
+    is_bad = is_bad || c[kCandP] == 0.0;
+    s_bad = is_bad ? 1 : 0;
+    if (s == 0) bad[p] = s_bad;
+    if (is_bad) {
+      first_warn[b] = -1; first_danger[b] = -1; n_warn[b] = 0; peak[b] = quiet_nan();
+      if (carry) { carry[2 * b] = quiet_nan(); carry[2 * b + 1] = quiet_nan(); }
+    } else {
+      RiskDev a;
+      a.n_cols = sh.n_cols; a.n_layers = sh.n_layers; a.p_is_two = c[kCandP] == 2.0; a.pad_ = 0;
+      for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+        const bool in = d < sh.n_cols;
+        a.col[d] = 0;
+        a.layer_of[d] = in ? sh.layer_of[d] : -1;
+        a.w[d] = in ? c[d] : 0.0;
+      }
+      for (int l = 0; l < PINN_RF_MAX_LAYERS; ++l) a.beta[l] = l < sh.n_layers ? c[PINN_RF_MAX_COLS + l] : 0.0;
+      a.p = c[kCandP]; a.inv_p = 1.0 / a.p; a.z_safe = c[kCandZSafe]; a.lambda = c[kCandLambda];
+      a.k = c[kCandK]; a.c0 = c[kCandC0]; a.c_max = c[kCandCMax];
+      a.alpha = c[kCandAlpha]; a.one_minus_alpha = 1.0 - a.alpha;
+      a.l0 = 1.0 / (1.0 + exp(-a.k * (0.0 - a.c0)));                                 // 04:268-270
+      const double l_max = 1.0 / (1.0 + exp(-a.k * (a.c_max - a.c0)));
+      a.denom = (l_max - a.l0) != 0.0 ? (l_max - a.l0) : 1e-6;
+      s_a = a;
+      s_thr[0] = c[kCandWarn];
+      s_thr[1] = c[kCandDanger];
+    }
+  }
+  __syncthreads();
+  if (s_bad) return;                                          // the same for every thread of the workgroup
+  const RiskDev& a = s_a;
+  const double warn = s_thr[0], danger = s_thr[1];
+
+  long long begin = seg_begin(ss, s), next = seg_next(ss, ns, s, n);
+  begin = begin < 0 ? 0 : (begin > n ? n : begin);            // starts are device data: a wrong one must not read past z
+  next = next < begin ? begin : (next > n ? n : next);
+  const long long len = next - begin;
+  const double* __restrict__ zseg = z + begin;
+  double* cout = carry ? carry + 2 * b : nullptr;
+  if (len == 0 && cout && threadIdx.x == 0) { cout[0] = quiet_nan(); cout[1] = quiet_nan(); }
+
+  double enter_c = 0.0, enter_r = 0.0;      // tile 0 begins with the segment start, so these zeros never reach a result
+  long long fw = kNoPosition, fd = kNoPosition, cnt = 0;
+  double pk = quiet_nan();
+  for (long long tile0 = 0; tile0 < len; tile0 += kTile) {
+#pragma unroll 2
+    for (int k = 0; k < kItems; ++k) {
+      const int i = k * kThreads + threadIdx.x;
+      const long long j = tile0 + i;
+      if (j >= len) break;
+      double zr[PINN_RF_MAX_COLS];
+#pragma unroll
+      for (int d = 0; d < PINN_RF_MAX_COLS; ++d) zr[d] = d < sh.n_cols ? zseg[(long long)d * zs + j] : 0.0;
+      s_val[pidx(i)] = s_of_z(a, zr, nullptr, 0, 0);
+    }
+    __syncthreads();
+    double v[kItems], cv[kItems], rf[kItems], rs[kItems];
+    blocked_from_lds(s_val, v);
+    const Op tc = tile_recurrence<0>(a, v, tile0, len, nullptr, 1, nullptr, cout, enter_c, false, s_wave, cv);
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) rf[k] = rf_inst(a, cv[k]);
+    const Op tr = tile_recurrence<1>(a, rf, tile0, len, nullptr, 1, nullptr, cout, enter_r, false, s_wave, rs);
+    enter_c = apply(tc, enter_c);
+    enter_r = apply(tr, enter_r);
+    const long long j0 = tile0 + (long long)threadIdx.x * kItems;
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+      const long long j = j0 + k;
+      if (j < len) {
+        const double x = rs[k];
+        if (x >= warn) { ++cnt; fw = fw < j ? fw : j; }        // NaN never matches
+        if (x >= danger) fd = fd < j ? fd : j;
+        if (x == x && !(pk >= x)) pk = x;                       // and never enters the peak
+      }
+    }
+  }
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const long long ofw = __shfl_down(fw, d, 64), ofd = __shfl_down(fd, d, 64);
+    const double opk = __shfl_down(pk, d, 64);
+    cnt += __shfl_down(cnt, d, 64);
+    fw = fw < ofw ? fw : ofw;
+    fd = fd < ofd ? fd : ofd;
+    if (opk == opk && !(pk >= opk)) pk = opk;
+  }
+  if (lane == 0) { s_int[wave][0] = fw; s_int[wave][1] = fd; s_int[wave][2] = cnt; s_peak[wave] = pk; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kThreads / 64; ++w) {
+      fw = fw < s_int[w][0] ? fw : s_int[w][0];
+      fd = fd < s_int[w][1] ? fd : s_int[w][1];
+      cnt += s_int[w][2];
+      const double opk = s_peak[w];
+      if (opk == opk && !(pk >= opk)) pk = opk;
+    }
+    first_warn[b] = fw == kNoPosition ? -1 : fw;
+    first_danger[b] = fd == kNoPosition ? -1 : fd;
+    n_warn[b] = cnt;
+    peak[b] = pk;
+  }
+}
+
 inline long long n_tiles_of(long long n) { return (n + kTile - 1) / kTile; }
 
 }  // namespace
@@ -612,6 +786,53 @@ extern "C" int pinn_rf_series(const double* d_arr, long long ld, long long n_arr
     hipLaunchKernelGGL(rf_carry_kernel, dim3(1), block, 0, st, agg_r, tiles, ent_r);
     hipLaunchKernelGGL(rf_pass3_kernel, grid, block, 0, st, a, RF, n, d_seg_start, ns, d_carry_in, ent_r, d_RF_smooth, d_carry_out);
   }
+  return launch_status();
+}
+
+extern "C" size_t pinn_rf_sweep_workspace_bytes(long long n, int n_cols) {
+  using namespace pinn;
+  if (n <= 0 || n_cols < 1) return 0;
+  return (size_t)n_cols * align256((size_t)n * sizeof(double));
+}
+
+extern "C" int pinn_rf_sweep(const double* d_arr, long long ld, long long n_arr_rows, const pinn_rf_params_t* shape,
+                             const double* d_mu, const double* d_sigma, const long long* d_row_index, long long n,
+                             const long long* d_seg_start, long long n_segments, const double* d_cand, long long n_cand,
+                             long long* d_first_warn, long long* d_first_danger, long long* d_n_warn, double* d_peak,
+                             double* d_carry_out, int* d_bad, void* d_ws, size_t ws_bytes, void* stream) {
+  using namespace pinn;
+  if (!shape || n < 0 || n_arr_rows < 0 || ld < 1 || n_segments < 0 || (n_segments > 0 && !d_seg_start) || n_cand < 1) return PINN_E_ARG;
+  if (shape->n_cols < 1 || shape->n_cols > PINN_RF_MAX_COLS || shape->n_layers < 0 || shape->n_layers > PINN_RF_MAX_LAYERS) return PINN_E_ARG;
+  for (int d = 0; d < shape->n_cols; ++d)
+    if (shape->col[d] < 0 || shape->col[d] >= ld || shape->layer_of[d] >= shape->n_layers) return PINN_E_ARG;
+  if (d_row_index == nullptr && n > n_arr_rows) return PINN_E_ARG;
+  const long long ns = n_segments > 0 ? n_segments : 1;
+  if (n_cand > 0x7fffffffLL / ns) return PINN_E_ARG;            // one workgroup per (candidate, segment)
+  if (!d_cand || !d_first_warn || !d_first_danger || !d_n_warn || !d_peak || !d_bad) return PINN_E_ARG;
+  if (n > 0 && (!d_arr || !d_mu || !d_sigma || !d_ws)) return PINN_E_ARG;
+  if (misaligned8(d_arr) || misaligned8(d_mu) || misaligned8(d_sigma) || misaligned8(d_row_index) || misaligned8(d_seg_start) ||
+      misaligned8(d_cand) || misaligned8(d_first_warn) || misaligned8(d_first_danger) || misaligned8(d_n_warn) || misaligned8(d_peak) ||
+      misaligned8(d_carry_out) || ((unsigned long long)d_bad & 3) != 0 || misaligned8(d_ws))
+    return PINN_E_ARG;
+  if (ws_bytes < pinn_rf_sweep_workspace_bytes(n, shape->n_cols)) return PINN_E_WORKSPACE;
+  const long long stage_blocks = (n + kThreads - 1) / kThreads;
+  if (stage_blocks > 0x7fffffffLL) return PINN_E_ARG;
+  SweepShape sh;
+  sh.n_cols = shape->n_cols; sh.n_layers = shape->n_layers;
+  for (int d = 0; d < PINN_RF_MAX_COLS; ++d) {
+    const bool in = d < shape->n_cols;
+    sh.col[d] = in ? shape->col[d] : 0;
+    sh.layer_of[d] = in ? shape->layer_of[d] : -1;
+  }
+  double* z = static_cast<double*>(d_ws);
+  const long long zs = (long long)(align256((size_t)n * sizeof(double)) / sizeof(double));
+  hipStream_t st = (hipStream_t)stream;
+  clear_error();
+  if (n > 0)
+    hipLaunchKernelGGL(sweep_stage_kernel, dim3((unsigned)stage_blocks), dim3(kThreads), 0, st, sh, d_arr, ld, n_arr_rows, d_mu, d_sigma,
+                       d_row_index, n, z, zs);
+  hipLaunchKernelGGL(rf_sweep_kernel, dim3((unsigned)(n_cand * ns)), dim3(kThreads), 0, st, sh, z, zs, n, d_seg_start, ns, d_cand,
+                     d_first_warn, d_first_danger, d_n_warn, d_peak, d_carry_out, d_bad);
   return launch_status();
 }
 

@@ -3,7 +3,8 @@
 Public names, argument names and defaults follow script 04, so a call written for it runs here:
 `estimate_mu_sigma_normal`, `compute_rf_time_series`, `find_first_alarm_index`, `compute_rf_advance_for_condition`.
 Added: `rf_series` (gather lists, segments, carried state), `rf_advance_for_conditions` (all conditions in one device
-call) and `RiskMonitor` (online use, chunk by chunk).
+call), `RiskMonitor` (online use, chunk by chunk), and the calibration of the hand-set parameters: `rf_grid`, `rf_sweep`
+(P parameter sets over all conditions and the normal rows in one device call) and `calibrate_rf`.
 
     z = (R - mu) / sigma,  a = max(0, |z| - z_safe)                   per residual column
     S_l = (sum_d w_d a_d^p)^(1/p) per layer,  S_tot = sum_l beta_l S_l
@@ -350,20 +351,11 @@ def _none_if_negative(v):
     return None if v < 0 else v
 
 
-def rf_advance_for_conditions(results, mu, sigma, conditions=None, current_tol=CURRENT_TOL, backend="auto", **params):
-    """Early-warning lead of every (current_target, fault, [index_range]) in `conditions` (default RF_CONDITIONS).
-
-    The rows of a condition (label in the fault's labels, |current - target| <= tol, then the optional relative
-    index_range) form one sub-series.  The device backend concatenates the gather lists and evaluates all sub-series in
-    ONE pinn_rf_series call, one segment per condition; the two alarms are one pinn_rf_first_alarm call each.
-    Returns one dict per condition: n (rows used), idx_v_alarm (first V <= V[0] - 0.1), idx_rf_warn (first RF_smooth >=
-    RF_WARN_THRESHOLD), delta_idx (= idx_v_alarm - idx_rf_warn, positive: RF warns earlier; None unless both fire), and
-    n_total (rows before index_range), v_threshold."""
-    conditions = RF_CONDITIONS if conditions is None else list(conditions)
-    unknown = set(params) - set(_PARAM_NAMES)
-    if unknown:
-        raise TypeError("unknown arguments: %s" % sorted(unknown))
-    cfg = _Config(**params)
+def _condition_rows(results, conditions, current_tol, backend):
+    """The sub-series of every (current_target, fault[, index_range]): rows whose label is one of the fault's and whose
+    current lies within the tolerance of the target, then the optional relative index_range.  Returns (host, arr, out,
+    used): the backend taken, the array on its side, one result dict per condition (n and n_total filled in) and the row
+    lists (numpy on the host, tensors on the device)."""
     parsed = []
     for cond in conditions:
         if len(cond) not in (2, 3):
@@ -397,6 +389,35 @@ def rf_advance_for_conditions(results, mu, sigma, conditions=None, current_tol=C
         a, b = window(total, index_range)
         out.append({"n": b - a, "n_total": total, "idx_v_alarm": None, "idx_rf_warn": None, "delta_idx": None, "v_threshold": None})
         used.append(idx[a:b])
+    return host, arr, out, used
+
+
+def _device_voltage_alarm(arr, ridx, starts):
+    """First V <= V[first] - 0.1 of every segment of the gathered rows (04:389-390) -> (first [n_seg], threshold [n_seg]), device."""
+    ycol = arr[:, INDEX["y_true"]]
+    v_first = _device_first(ycol, -V_ALARM_DROP, "below", stride=arr.stride(0), n_src=arr.shape[0], row_index=ridx,
+                            seg_starts=starts, relative=True)
+    return v_first, ycol[ridx[starts]] - V_ALARM_DROP
+
+
+def rf_advance_for_conditions(results, mu, sigma, conditions=None, current_tol=CURRENT_TOL, backend="auto",
+                              warn_threshold=RF_WARN_THRESHOLD, danger_threshold=RF_DANGER_THRESHOLD, **params):
+    """Early-warning lead of every (current_target, fault, [index_range]) in `conditions` (default RF_CONDITIONS).
+
+    The rows of a condition (label in the fault's labels, |current - target| <= tol, then the optional relative
+    index_range) form one sub-series.  The device backend concatenates the gather lists and evaluates all sub-series in
+    ONE pinn_rf_series call, one segment per condition; the two alarms are one pinn_rf_first_alarm call each.
+    Returns one dict per condition: n (rows used), idx_v_alarm (first V <= V[0] - 0.1), idx_rf_warn (first RF_smooth >=
+    warn_threshold), delta_idx (= idx_v_alarm - idx_rf_warn, positive: RF warns earlier; None unless both fire), and
+    n_total (rows before index_range), v_threshold.  `danger_threshold` is accepted and unused, so that a calibrated
+    parameter set (calibrate_rf's `.params`) replays here as it stands."""
+    conditions = RF_CONDITIONS if conditions is None else list(conditions)
+    unknown = set(params) - set(_PARAM_NAMES)
+    if unknown:
+        raise TypeError("unknown arguments: %s" % sorted(unknown))
+    cfg = _Config(**params)
+    warn_threshold = float(warn_threshold)
+    host, arr, out, used = _condition_rows(results, conditions, current_tol, backend)
     live = [i for i, u in enumerate(used) if u.shape[0] > 0]
     if not live:
         return out
@@ -408,17 +429,15 @@ def rf_advance_for_conditions(results, mu, sigma, conditions=None, current_tol=C
             V = sub[:, INDEX["y_true"]].astype(float)
             thr = float(V[0]) - V_ALARM_DROP
             out[i].update(v_threshold=thr, idx_v_alarm=_host_first(V, thr, "below"),
-                          idx_rf_warn=_host_first(RF_smooth, RF_WARN_THRESHOLD, "above"))
+                          idx_rf_warn=_host_first(RF_smooth, warn_threshold, "above"))
     else:
+        import torch
         ridx = torch.cat([used[i] for i in live])
         lens = [int(used[i].shape[0]) for i in live]
         starts = torch.tensor(np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64), device=arr.device)
         r = _device_series(arr, mu, sigma, cfg, ridx, starts, None, want=("RF_smooth",))
-        rf_first = _device_first(r["RF_smooth"], RF_WARN_THRESHOLD, "above", seg_starts=starts)
-        ycol = arr[:, INDEX["y_true"]]
-        v_first = _device_first(ycol, -V_ALARM_DROP, "below", stride=arr.stride(0), n_src=arr.shape[0], row_index=ridx,
-                                seg_starts=starts, relative=True)
-        v0 = ycol[ridx[starts]] - V_ALARM_DROP
+        rf_first = _device_first(r["RF_smooth"], warn_threshold, "above", seg_starts=starts)
+        v_first, v0 = _device_voltage_alarm(arr, ridx, starts)
         rf_first, v_first, v0 = rf_first.cpu().numpy(), v_first.cpu().numpy(), v0.cpu().numpy()
         for k, i in enumerate(live):
             out[i].update(v_threshold=float(v0[k]), idx_v_alarm=_none_if_negative(v_first[k]), idx_rf_warn=_none_if_negative(rf_first[k]))
@@ -433,11 +452,13 @@ def compute_rf_advance_for_condition(results, mu, sigma, fault_name, current_tar
                                      layer_weights=RF_LAYER_WEIGHTS, p_layer=RF_P_LAYER, z_safe=RF_Z_SAFE,
                                      lambda_decay=RF_LAMBDA_DECAY, k_logistic=RF_K_LOGISTIC, C0_logistic=RF_C0_LOGISTIC,
                                      C_max=RF_C_MAX, alpha_smooth=RF_ALPHA_SMOOTH, V_THRESHOLD=V_THRESHOLD_COND,
-                                     RF_THRESHOLD=RF_THRESHOLD_COND, plot=False, index_range=None, backend="auto"):
+                                     RF_THRESHOLD=RF_THRESHOLD_COND, plot=False, index_range=None, backend="auto",
+                                     warn_threshold=RF_WARN_THRESHOLD):
     """Samples by which the RF warning precedes the voltage alarm for one current plateau and fault class (positive: RF is
     earlier); None when the condition has no rows or one of the two alarms does not fire.  `fault_name`: a class name of
     FAULT_RANGE_MAP, one of the reference's keys, or the labels themselves.  V_THRESHOLD and RF_THRESHOLD are accepted and
-    unused, as in the reference.  No figure is drawn."""
+    unused, as in the reference; `warn_threshold` is the RF warning level (the reference reads its module constant).  No
+    figure is drawn."""
     if plot:
         raise NotImplementedError("plot=True: figures (matplotlib) are out of scope of pinn_amd.risk; pass plot=False")
     _fault_labels(fault_name)             # an unknown name fails before any work
@@ -445,7 +466,8 @@ def compute_rf_advance_for_condition(results, mu, sigma, fault_name, current_tar
     r = rf_advance_for_conditions(results, mu, sigma, [(current_target, fault_name, index_range)], current_tol=current_tol,
                                   backend=backend, res_keys=res_keys, feature_weights=feature_weights, layer_config=layer_config,
                                   layer_weights=layer_weights, p_layer=p_layer, z_safe=z_safe, lambda_decay=lambda_decay,
-                                  k_logistic=k_logistic, C0_logistic=C0_logistic, C_max=C_max, alpha_smooth=alpha_smooth)[0]
+                                  k_logistic=k_logistic, C0_logistic=C0_logistic, C_max=C_max, alpha_smooth=alpha_smooth,
+                                  warn_threshold=warn_threshold)[0]
     if r["n_total"] == 0:
         print("%s no rows match this condition." % tag)
         return None
@@ -459,7 +481,7 @@ def compute_rf_advance_for_condition(results, mu, sigma, fault_name, current_tar
     print(tag)
     print("  sub-series length: %d (matching rows: %d)" % (r["n"], r["n_total"]))
     print("  voltage alarm threshold = V(0) - %.1f = %.4f" % (V_ALARM_DROP, r["v_threshold"]))
-    print("  RF warning threshold = %s" % RF_WARN_THRESHOLD)
+    print("  RF warning threshold = %s" % warn_threshold)
     print("  RF danger threshold = %s" % RF_DANGER_THRESHOLD)
     print("  first voltage alarm (sub-series index): %s" % r["idx_v_alarm"])
     print("  first RF warning (sub-series index): %s" % r["idx_rf_warn"])
@@ -568,3 +590,364 @@ class RiskMonitor:
     @property
     def first_danger(self):
         return self._latched(1)
+
+
+# ---------------------------------------------------------------------------------------------- sweep and calibration
+_STRUCTURAL_NAMES = ("res_keys", "layer_config", "columns")
+_SWEEP_SCALARS = ("p_layer", "z_safe", "lambda_decay", "k_logistic", "C0_logistic", "C_max", "alpha_smooth",
+                  "warn_threshold", "danger_threshold")               # words 12..20 of a candidate, in this order
+_SWEEP_NAMES = ("feature_weights", "layer_weights") + _SWEEP_SCALARS
+_SWEEP_DEFAULTS = {"feature_weights": None, "layer_weights": RF_LAYER_WEIGHTS, "p_layer": RF_P_LAYER, "z_safe": RF_Z_SAFE,
+                   "lambda_decay": RF_LAMBDA_DECAY, "k_logistic": RF_K_LOGISTIC, "C0_logistic": RF_C0_LOGISTIC, "C_max": RF_C_MAX,
+                   "alpha_smooth": RF_ALPHA_SMOOTH, "warn_threshold": RF_WARN_THRESHOLD, "danger_threshold": RF_DANGER_THRESHOLD}
+SWEEP_WORDS = 24                        # float64 words of one candidate (include/pinn_hip.h: PINN_RF_SWEEP_WORDS)
+
+
+def _check_sweep_names(names, what):
+    for name in names:
+        if name in _STRUCTURAL_NAMES:
+            raise ValueError("%s: %r is structure (which columns, which layers), fixed per call and not swept" % (what, name))
+        if name not in _SWEEP_NAMES:
+            raise TypeError("%s: unknown name %r; choose among %s" % (what, name, list(_SWEEP_NAMES)))
+
+
+def rf_grid(**axes):
+    """The Cartesian product of the named axes, e.g. rf_grid(z_safe=[1.5, 2, 3], lambda_decay=[0.99, 1.0]): one array of
+    length P per name, the first axis slowest and the last fastest (itertools.product order).  Axes: the scalar arguments
+    of compute_rf_time_series, warn_threshold, danger_threshold, feature_weights (a list of weight vectors -> [P, D]) and
+    layer_weights (a list of dicts -> an object array of dicts).  Structural names (res_keys, layer_config, columns) and
+    unknown ones raise."""
+    import itertools
+    _check_sweep_names(axes, "rf_grid")
+    values = {k: list(v) for k, v in axes.items()}
+    for k, v in values.items():
+        if not v:
+            raise ValueError("rf_grid: axis %r is empty" % k)
+    combos = list(itertools.product(*values.values())) if values else []
+    out = {}
+    for pos, name in enumerate(values):
+        col = [c[pos] for c in combos]
+        if name == "layer_weights":
+            arr = np.empty(len(col), dtype=object)
+            for i, d in enumerate(col):
+                arr[i] = dict(d)
+            out[name] = arr
+        elif name == "feature_weights":
+            out[name] = np.asarray(col, dtype=float).reshape(len(col), -1)
+        else:
+            out[name] = np.asarray(col, dtype=float)
+    return out
+
+
+def _candidate_table(candidates, fixed):
+    """-> (cfg0, structure, P, table [P, 24] float64).  `cfg0` carries the structure: columns, layers and their names."""
+    _check_sweep_names(candidates, "candidates")
+    unknown = set(fixed) - set(_PARAM_NAMES) - {"warn_threshold", "danger_threshold"}
+    if unknown:
+        raise TypeError("unknown arguments: %s" % sorted(unknown))
+    both = set(candidates) & set(fixed)
+    if both:
+        raise ValueError("%s given both per candidate and fixed" % sorted(both))
+    if not candidates:
+        raise ValueError("candidates is empty: name at least one swept parameter (rf_grid builds the table)")
+    lengths = {k: len(v) for k, v in candidates.items()}
+    P = next(iter(lengths.values()))
+    if P < 1 or any(n != P for n in lengths.values()):
+        raise ValueError("every candidate array needs the same length >= 1, got %s" % lengths)
+    structure = {k: fixed[k] for k in _STRUCTURAL_NAMES if k in fixed}
+    cfg0 = _Config(**structure)
+    D, names = len(cfg0.cols), cfg0.layer_names
+    if D > MAX_COLS or len(names) > MAX_LAYERS:
+        raise ValueError("a sweep takes at most %d residual columns and %d layers" % (MAX_COLS, MAX_LAYERS))
+
+    def column(name):
+        return candidates[name] if name in candidates else fixed.get(name, _SWEEP_DEFAULTS[name])
+
+    table = np.zeros((P, SWEEP_WORDS), dtype=np.float64)
+    fw = column("feature_weights")
+    w = np.ones(D, dtype=float) if fw is None else np.asarray(fw, dtype=float)
+    if w.shape not in ((D,), (P, D)) or ("feature_weights" in candidates and w.shape != (P, D)):
+        raise ValueError("feature_weights must have length %d per candidate, got an array of shape %s" % (D, w.shape))
+    table[:, :D] = w
+    lw = column("layer_weights")
+    if "layer_weights" in candidates:
+        for i in range(P):
+            table[i, MAX_COLS:MAX_COLS + len(names)] = [float(lw[i].get(name, 1.0)) for name in names]
+    else:
+        table[:, MAX_COLS:MAX_COLS + len(names)] = [float(lw.get(name, 1.0)) for name in names]
+    for k, name in enumerate(_SWEEP_SCALARS):
+        table[:, MAX_COLS + MAX_LAYERS + k] = np.asarray(column(name), dtype=float)
+    return cfg0, structure, P, table
+
+
+def _table_params(table, i, cfg0, structure):
+    """Keyword arguments of candidate i: they feed rf_series, rf_advance_for_conditions and RiskMonitor as they stand."""
+    D, names = len(cfg0.cols), cfg0.layer_names
+    row = table[i]
+    out = dict(structure)
+    out["feature_weights"] = row[:D].copy()
+    out["layer_weights"] = {name: float(row[MAX_COLS + k]) for k, name in enumerate(names)}
+    for k, name in enumerate(_SWEEP_SCALARS):
+        out[name] = float(row[MAX_COLS + MAX_LAYERS + k])
+    return out
+
+
+def _table_bad(table):
+    return ~np.isfinite(table).all(axis=1) | (table[:, MAX_COLS + MAX_LAYERS] == 0.0)
+
+
+def _quiet_ranges(quiet, labels_of, n_rows):
+    """Row ranges on which a warning is a false alarm: "normal" -> every maximal run of consecutive rows with a label in
+    NORMAL_LABELS; a list of (start, end); None -> none."""
+    if quiet is None:
+        return []
+    if isinstance(quiet, str):
+        if quiet != "normal":
+            raise ValueError("quiet must be 'normal', a list of (start, end) row ranges, or None")
+        mask = np.isin(labels_of(), list(NORMAL_LABELS))
+        edges = np.flatnonzero(np.diff(np.concatenate([[0], mask.astype(np.int8), [0]])))
+        return [(int(a), int(b)) for a, b in zip(edges[0::2], edges[1::2])]
+    out = []
+    for a, b in quiet:
+        a, b = int(a), int(b)
+        if not 0 <= a < b <= n_rows:
+            raise ValueError("quiet range (%d, %d) does not lie inside the %d rows" % (a, b, n_rows))
+        out.append((a, b))
+    return out
+
+
+def _host_sweep(arr, mu, sigma, cfg0, structure, table, ridx, starts):
+    """The referee: _host_series per candidate over the gathered rows, one restart per segment, then the searches."""
+    P, S, n = table.shape[0], len(starts), len(ridx)
+    bounds = list(starts) + [n]
+    raw = {"first_warn": np.full((P, S), -1, dtype=np.int64), "first_danger": np.full((P, S), -1, dtype=np.int64),
+           "n_warn": np.zeros((P, S), dtype=np.int64), "peak": np.full((P, S), np.nan), "carry": np.full((P, S, 2), np.nan)}
+    bad = _table_bad(table)
+    rows = arr[ridx] if n else np.zeros((0, arr.shape[1]))
+    R = np.stack([rows[:, c].astype(float) for c in cfg0.cols], axis=1) if n else np.zeros((0, len(cfg0.cols)))
+    mu, sigma = _as_numpy(mu, float), _as_numpy(sigma, float)
+    for i in range(P):
+        if bad[i] or n == 0:
+            continue
+        prm = _table_params(table, i, cfg0, structure)
+        warn, danger = prm.pop("warn_threshold"), prm.pop("danger_threshold")
+        with np.errstate(all="ignore"):
+            RF_smooth, carry = _host_series(R, mu, sigma, _Config(**prm), list(starts))[4:6]
+        raw["carry"][i] = carry
+        for s in range(S):
+            seg = RF_smooth[bounds[s]:bounds[s + 1]]
+            hit = seg >= warn
+            fw, fd = _host_first(seg, warn, "above"), _host_first(seg, danger, "above")
+            raw["first_warn"][i, s] = -1 if fw is None else fw
+            raw["first_danger"][i, s] = -1 if fd is None else fd
+            raw["n_warn"][i, s] = int(hit.sum())
+            if not np.isnan(seg).all():
+                raw["peak"][i, s] = np.nanmax(seg)
+    raw["bad"] = bad
+    return raw
+
+
+def _device_sweep(arr, mu, sigma, cfg0, table, ridx, starts):
+    """One pinn_rf_sweep call -> the same dict as _host_sweep, of device tensors."""
+    torch, _lib, lib = _torch_lib()
+    dev = arr.device
+    prm = cfg0.c_struct()
+    if arr.shape[1] <= max(cfg0.cols):
+        raise ValueError("results has %d columns, column %d is needed" % (arr.shape[1], max(cfg0.cols)))
+    P, S, n = table.shape[0], int(starts.numel()), int(ridx.numel())
+    if P * S > 2 ** 31 - 1:
+        raise ValueError("%d candidates x %d segments exceed one launch (2^31 - 1 workgroups): sweep in parts" % (P, S))
+    with torch.cuda.device(dev):
+        mu_d, sg_d = _dev_vec(torch, mu, torch.float64, dev), _dev_vec(torch, sigma, torch.float64, dev)
+        if mu_d.numel() != prm.n_cols or sg_d.numel() != prm.n_cols:
+            raise ValueError("mu and sigma must have one entry per residual key (%d)" % prm.n_cols)
+        cand = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
+        raw = {"first_warn": torch.empty(P, S, dtype=torch.int64, device=dev), "first_danger": torch.empty(P, S, dtype=torch.int64, device=dev),
+               "n_warn": torch.empty(P, S, dtype=torch.int64, device=dev), "peak": torch.empty(P, S, dtype=torch.float64, device=dev),
+               "carry": torch.empty(P, S, 2, dtype=torch.float64, device=dev)}
+        bad = torch.empty(P, dtype=torch.int32, device=dev)
+        wb = lib.pinn_rf_sweep_workspace_bytes(n, prm.n_cols)
+        ws = torch.empty(max(wb, 8), dtype=torch.uint8, device=dev)
+        ld = arr.stride(0) if arr.shape[0] > 0 else max(arr.shape[1], 1)
+        call("pinn_rf_sweep", arr, ld, arr.shape[0], ctypes.byref(prm), mu_d, sg_d, ridx, n, starts, S, cand, P, raw["first_warn"],
+             raw["first_danger"], raw["n_warn"], raw["peak"], raw["carry"], bad, ws, wb)
+    raw["bad"] = bad != 0
+    return raw
+
+
+class RFSweep:
+    """What rf_sweep returns.  Segments are the conditions that have rows (in order), then the quiet ranges; `raw` holds the
+    kernel's outputs per (candidate, segment) as they came (device tensors from the device backend): "first_warn",
+    "first_danger", "n_warn", "peak" [P, S], "carry" [P, S, 2], "bad" [P].  Everything else is numpy, computed from `raw` when
+    first asked for:
+
+      idx_v_alarm [n_cond]        first V <= V[0] - 0.1 of each condition, -1: none (or no rows)
+      idx_rf_warn, idx_rf_danger  [P, n_cond] first RF_smooth >= the candidate's threshold, -1: none
+      delta_idx, fired [P, n_cond] idx_v_alarm - idx_rf_warn where both alarms fire (`fired`), 0 elsewhere
+      n_rows [n_cond], quiet_alarm_rows [P] (rows of the quiet segments with RF_smooth >= warn), quiet_peak [P], bad [P]
+
+    `row_index` and `seg_starts` are the gather list and the segment starts the sweep ran on (rf_series takes them as they
+    stand), `table` the [P, 24] candidate words, `quiet_ranges` the quiet (start, end) row ranges."""
+
+    def __init__(self, raw, idx_v_alarm, n_rows, live, table, cfg0, structure, quiet_ranges, backend, row_index=None, seg_starts=None):
+        self.raw, self.n_rows, self.table, self.backend = raw, np.asarray(n_rows, dtype=np.int64), table, backend
+        self.row_index, self.seg_starts = row_index, seg_starts
+        self.idx_v_alarm = np.asarray(idx_v_alarm, dtype=np.int64)
+        self.quiet_ranges = list(quiet_ranges)
+        self._live, self._cfg0, self._structure, self._np = list(live), cfg0, structure, None
+        self.n_candidates, self.n_conditions = table.shape[0], self.n_rows.shape[0]
+
+    def _host(self):
+        if self._np is None:
+            self._np = {k: _as_numpy(v) for k, v in self.raw.items()}
+        return self._np
+
+    def _per_condition(self, key, fill):
+        a = self._host()[key]
+        out = np.full((self.n_candidates, self.n_conditions), fill, dtype=a.dtype)
+        out[:, self._live] = a[:, :len(self._live)]
+        return out
+
+    @property
+    def idx_rf_warn(self):
+        return self._per_condition("first_warn", -1)
+
+    @property
+    def idx_rf_danger(self):
+        return self._per_condition("first_danger", -1)
+
+    @property
+    def peak(self):
+        """[P, n_cond] maximum of RF_smooth over each condition, NaN where there is none."""
+        return self._per_condition("peak", np.nan)
+
+    @property
+    def fired(self):
+        return (self.idx_v_alarm[None, :] >= 0) & (self.idx_rf_warn >= 0)
+
+    @property
+    def delta_idx(self):
+        return np.where(self.fired, self.idx_v_alarm[None, :] - self.idx_rf_warn, 0)
+
+    @property
+    def quiet_alarm_rows(self):
+        return self._host()["n_warn"][:, len(self._live):].sum(axis=1)
+
+    @property
+    def quiet_peak(self):
+        q = self._host()["peak"][:, len(self._live):]
+        out = np.full(self.n_candidates, np.nan)
+        if q.shape[1]:
+            some = ~np.isnan(q).all(axis=1)
+            out[some] = np.nanmax(q[some], axis=1)
+        return out
+
+    @property
+    def bad(self):
+        return self._host()["bad"].astype(bool)
+
+    def candidate(self, i):
+        """Keyword arguments of candidate i, for RiskMonitor(mu, sigma, **kw) and rf_advance_for_conditions(..., **kw)."""
+        return _table_params(self.table, int(i), self._cfg0, self._structure)
+
+
+def rf_sweep(results, mu, sigma, candidates, conditions=None, quiet="normal", current_tol=CURRENT_TOL, backend="auto", **fixed):
+    """Evaluate P parameter sets over every condition's sub-series and over the quiet rows, where a warning is a false alarm.
+
+    `candidates`: a dict of per-candidate arrays of length P, as rf_grid returns; names it lacks come from `fixed`, or
+    else from the module's defaults.  `fixed` also takes the structure (res_keys, layer_config, columns), the same for all
+    candidates.  Segments: the conditions' sub-series, selected as rf_advance_for_conditions selects them, then the quiet
+    ranges: quiet="normal" -> every maximal run of consecutive rows labelled NORMAL_LABELS, or a list of (start, end), or
+    None.  The device backend stages the z-scores once and runs all candidates in ONE pinn_rf_sweep call (one workgroup per
+    candidate and segment; nothing per row is written); the voltage alarms are one pinn_rf_first_alarm call.  The host
+    backend loops the float64 numpy series per candidate: the referee, and the path of machines without a GPU.
+    Returns an RFSweep."""
+    conditions = RF_CONDITIONS if conditions is None else list(conditions)
+    cfg0, structure, P, table = _candidate_table(dict(candidates), fixed)
+    host, arr, out, used = _condition_rows(results, conditions, current_tol, backend)
+    live = [i for i, u in enumerate(used) if u.shape[0] > 0]
+    n_rows = [o["n"] for o in out]
+    if host:
+        ranges = _quiet_ranges(quiet, lambda: arr[:, INDEX["label"]].astype(int), arr.shape[0])
+        lists = [used[i] for i in live] + [np.arange(a, b, dtype=np.int64) for a, b in ranges]
+        if not lists:
+            raise ValueError("nothing to sweep over: no condition has rows and there are no quiet rows")
+        ridx = np.concatenate(lists).astype(np.int64)
+        starts = np.concatenate([[0], np.cumsum([len(l) for l in lists])[:-1]]).astype(np.int64)
+        raw = _host_sweep(arr, mu, sigma, cfg0, structure, table, ridx, starts)
+        v_first = np.full(len(conditions), -1, dtype=np.int64)
+        for i in live:
+            V = arr[used[i], INDEX["y_true"]].astype(float)
+            f = _host_first(V, float(V[0]) - V_ALARM_DROP, "below")
+            v_first[i] = -1 if f is None else f
+    else:
+        import torch
+        ranges = _quiet_ranges(quiet, lambda: arr[:, INDEX["label"]].long().cpu().numpy(), arr.shape[0])
+        lists = [used[i] for i in live] + [torch.arange(a, b, dtype=torch.int64, device=arr.device) for a, b in ranges]
+        if not lists:
+            raise ValueError("nothing to sweep over: no condition has rows and there are no quiet rows")
+        ridx = torch.cat(lists)
+        starts_h = np.concatenate([[0], np.cumsum([int(l.shape[0]) for l in lists])[:-1]]).astype(np.int64)
+        starts = torch.from_numpy(starts_h).to(arr.device)
+        raw = _device_sweep(arr, mu, sigma, cfg0, table, ridx, starts)
+        v_first = np.full(len(conditions), -1, dtype=np.int64)
+        if live:
+            n_live = sum(int(used[i].shape[0]) for i in live)
+            v_first[live] = _device_voltage_alarm(arr, ridx[:n_live], starts[:len(live)])[0].cpu().numpy()
+    return RFSweep(raw, v_first, n_rows, live, table, cfg0, structure, ranges, "host" if host else "device", ridx, starts)
+
+
+def _calibration_choice(idx_v_alarm, idx_rf_warn, quiet_alarm_rows, bad, max_quiet_alarm_rows=0, require_all=True):
+    """The calibration rule, on integers alone.  idx_v_alarm [n_cond] and idx_rf_warn [P, n_cond] (-1: none),
+    quiet_alarm_rows [P], bad [P].  Over the conditions whose voltage alarm fires: a candidate is feasible if it is not bad,
+    has at most max_quiet_alarm_rows alarm rows on the quiet segments and (require_all) warns on every such condition
+    (otherwise on at least one).  Among the feasible: the largest minimum lead idx_v_alarm - idx_rf_warn over the
+    conditions on which both fire, then the largest sum of leads, then the lowest index.  Returns that index; raises
+    ValueError, naming how many candidates failed which rule, when none is feasible."""
+    iv = np.asarray(idx_v_alarm, dtype=np.int64).reshape(-1)
+    ir = np.asarray(idx_rf_warn, dtype=np.int64)
+    quiet_rows = np.asarray(quiet_alarm_rows, dtype=np.int64).reshape(-1)
+    bad = np.asarray(bad, dtype=bool).reshape(-1)
+    P = ir.shape[0]
+    target = iv >= 0
+    if not target.any():
+        raise ValueError("no condition's voltage alarm fires: there is no lead to calibrate against")
+    warned = ir[:, target] >= 0
+    lead = iv[target][None, :] - ir[:, target]
+    noisy = quiet_rows > int(max_quiet_alarm_rows)
+    silent = ~warned.all(axis=1) if require_all else ~warned.any(axis=1)
+    feasible = ~bad & ~noisy & ~silent
+    if not feasible.any():
+        raise ValueError("no feasible candidate among %d: %d bad, %d with more than %d alarm rows on the quiet segments, "
+                         "%d silent on %s condition whose voltage alarm fires"
+                         % (P, int(bad.sum()), int(noisy.sum()), int(max_quiet_alarm_rows), int(silent.sum()),
+                            "a" if require_all else "every"))
+    big = np.iinfo(np.int64).max
+    worst = np.where(warned, lead, big).min(axis=1)
+    total = np.where(warned, lead, 0).sum(axis=1)
+    best = None
+    for i in np.flatnonzero(feasible):
+        key = (int(worst[i]), int(total[i]))
+        if best is None or key > best[0]:
+            best = (key, int(i))
+    return best[1]
+
+
+class RFCalibration:
+    """What calibrate_rf returns: `index` of the chosen candidate, its keyword arguments `params` (they feed
+    RiskMonitor(mu, sigma, **params) and rf_advance_for_conditions(..., **params)), `table` (the per-condition dicts of
+    rf_advance_for_conditions at these parameters) and the whole `sweep`."""
+
+    def __init__(self, index, params, table, sweep):
+        self.index, self.params, self.table, self.sweep = index, params, table, sweep
+
+
+def calibrate_rf(results, mu, sigma, candidates, conditions=None, quiet="normal", current_tol=CURRENT_TOL, backend="auto",
+                 max_quiet_alarm_rows=0, require_all=True, **fixed):
+    """Choose among `candidates` (see rf_sweep) the parameter set whose RF warning leads the voltage alarm by the most
+    samples in the worst condition while staying silent on the quiet rows: _calibration_choice's rule on rf_sweep's output."""
+    sweep = rf_sweep(results, mu, sigma, candidates, conditions=conditions, quiet=quiet, current_tol=current_tol, backend=backend, **fixed)
+    index = _calibration_choice(sweep.idx_v_alarm, sweep.idx_rf_warn, sweep.quiet_alarm_rows, sweep.bad, max_quiet_alarm_rows, require_all)
+    params = sweep.candidate(index)
+    table = rf_advance_for_conditions(results, mu, sigma, conditions, current_tol=current_tol, backend=backend, **params)
+    return RFCalibration(index, params, table, sweep)
