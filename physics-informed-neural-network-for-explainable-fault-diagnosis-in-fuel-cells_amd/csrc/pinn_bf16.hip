@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_bf16_kernel(FwdArgs a, const 
       forward_pass_bf16<H, false, kBits>(a.params, small, L, pipe, a.drop, c, xa, xb, st, u, z, v2);
       if (valid && lane < 16) {
         a.o0[lrow] = u;
-        a.o1[lrow] = logf(softplus_f32(z) + 1e-6f);
+        a.o1[lrow] = logvar_of(z);
       }
     } else {
       float u_eval = 0.f, mean = 0.f, m2 = 0.f, sl = 0.f;
@@ -87,15 +87,12 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_bf16_kernel(FwdArgs a, const 
           u_eval = u;
         } else {
           welford_update(mean, m2, u - u_eval, 1.0f / (float)(t + 1));      // population variance of the passes: m2 / T
-          sl += logf(softplus_f32(z) + 1e-6f);
+          sl += logvar_of(z);
         }
       }
       if (valid && lane < 16) {
-        const float inv_t = 1.0f / (float)a.n_passes;
-        const float var = m2 * inv_t;
         a.o0[lrow] = u_eval;
-        a.o1[lrow] = expf(0.5f * (sl * inv_t));
-        a.o2[lrow] = sqrtf(var);
+        mc_finish(m2, sl, a.n_passes, a.o1[lrow], a.o2[lrow]);
       }
     }
   }
@@ -126,8 +123,6 @@ int launch_forward_bf16(const pinn_net_t* net, const FwdArgs& a, bool mc, void* 
 // =======================================================================================
 // training: forward + NLL + backward chain (bf16 MFMA inputs, bf16 stash)
 // =======================================================================================
-constexpr int kLossTermsB = 8;
-
 struct TrainArgsB {
   const float* params;
   const float* packed;
@@ -159,7 +154,7 @@ __global__ __launch_bounds__(kThreads, 2) void train_chain_bf16_kernel(TrainArgs
   constexpr int NG4 = (H / 4 + 31) / 32;     // 32-groups of the H/4-wide layer (H = 128: one, half filled by a second block? no: H/4 = 32 -> 1)
   __shared__ __attribute__((aligned(16))) char lds_w[2 * kChunkBytes];
   __shared__ ChunkDesc tab[kMaxChunks];
-  __shared__ double red[4][kLossTermsB];
+  __shared__ double red[4][kLossTerms];
   __shared__ __attribute__((aligned(16))) float small[kMaxSmall];
   ParamLayout L{a.H, a.nh};
   PackLayout K{a.H, a.nh};
@@ -179,7 +174,7 @@ __global__ __launch_bounds__(kThreads, 2) void train_chain_bf16_kernel(TrainArgs
   const bool drop = a.drop.mode != PINN_DROP_NONE;
   const float inv_n = (float)(1.0 / (double)a.n_global);
   const int n_groups = L.nh * NP + NP / 2;
-  float s_nll = 0.f, s_abs = 0.f, s_mse = 0.f, s_du = 0.f, s_dz = 0.f;
+  LossSums sums;
   __bf16* const stash_h = (__bf16*)a.b.stash_h;
   __bf16* const stash_v1 = (__bf16*)a.b.stash_v1;
   __bf16* const stash_v2 = (__bf16*)a.b.stash_v2;
@@ -206,29 +201,9 @@ __global__ __launch_bounds__(kThreads, 2) void train_chain_bf16_kernel(TrainArgs
     forward_pass_bf16<H, true, kBits>(P, small, L, pipe, a.drop, c, xa, xb, st, u, z, v2);
 
     // aleatoric_loss (01:916-927) and its gradient, fp32
-    float du = 0.f, dz = 0.f;
-    {
-      const float sp = softplus_f32(z);
-      const float var = sp + 1e-6f;
-      const float s = logf(var);
-      const float prec = expf(-s);
-      const float e = yv - u;
-      if (valid) {
-        du = -(prec * e) * inv_n;
-        const float sgn = (s > 0.f) ? 1.f : ((s < 0.f) ? -1.f : 0.f);
-        const float ds = (-0.5f * prec * e * e + 0.5f + 0.01f * sgn) * inv_n;
-        const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
-        dz = ds * sig / var;
-        if (kq == 0) {
-          s_nll += 0.5f * prec * e * e + 0.5f * s;
-          s_abs += fabsf(s);
-          s_mse += e * e;
-          s_du += du;
-          s_dz += dz;
-        }
-      }
-      if (lane < 16) { a.b.du[t16 * 16 + lane] = du; a.b.dz[t16 * 16 + lane] = dz; }
-    }
+    float du, dz;
+    loss_row(u, z, yv, inv_n, valid, kq == 0, du, dz, sums);
+    if (lane < 16) { a.b.du[t16 * 16 + lane] = du; a.b.dz[t16 * 16 + lane] = dz; }
 
     // ---------------- backward: variance head
     f32x4 dh[NT];
@@ -303,21 +278,7 @@ __global__ __launch_bounds__(kThreads, 2) void train_chain_bf16_kernel(TrainArgs
     }
   }
 
-  float terms[5] = {s_nll, s_abs, s_mse, s_du, s_dz};
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    double v = (double)terms[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kLossTermsB) {
-    double t = 0.0;
-    if (threadIdx.x < 5)
-      for (int w = 0; w < 4; ++w) t += red[w][threadIdx.x];
-    a.b.loss_part[(long long)blockIdx.x * kLossTermsB + threadIdx.x] = t;
-  }
+  store_loss_partials<4>(sums, red, a.b.loss_part, lane, wave);
 }
 
 // =======================================================================================

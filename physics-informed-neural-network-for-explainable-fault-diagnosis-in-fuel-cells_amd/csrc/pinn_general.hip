@@ -555,7 +555,7 @@ __device__ __forceinline__ float sum16(float s) {
 
 template <int HM>
 __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
-  __shared__ double red[16][5];
+  __shared__ double red[16][kLossSums];
   const int tid = threadIdx.x, g = tid & 15, rr = tid >> 4;
   const long long r = (long long)blockIdx.x * 16 + rr;      // chunk row (every one is allocated)
   const float* hrow = a.h + r * a.ldh;
@@ -570,7 +570,7 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
     if (valid && g == 0) {
       const long long o = HM == kHeadFwd ? a.row0 + r : r;
       a.u[o] = u;
-      a.lv[o] = logf(softplus_f32(z) + 1e-6f);
+      a.lv[o] = logvar_of(z);
     }
     return;
   }
@@ -578,11 +578,7 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
     float du = 0.f, dz = 0.f;
     if (valid) {
       du = a.gu[a.row0 + r];
-      if (a.glv) {
-        const float var = softplus_f32(z) + 1e-6f;
-        const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
-        dz = a.glv[a.row0 + r] * sig / var;
-      }
+      if (a.glv) dz = through_logvar(a.glv[a.row0 + r], softplus_slope(z), var_of(z));
     }
     if (g == 0) {
       a.du[r] = du;
@@ -595,35 +591,19 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
     }
     return;
   }
-  // aleatoric_loss (01:916-927) and its gradient, arithmetic of pinn_train.hip
+  // aleatoric_loss (01:916-927) and its gradient (pinn_loss.h): one row's terms, as doubles, per 16 lanes
   const float inv_n = (float)(1.0 / (double)a.n_global);
-  float du = 0.f, dz = 0.f;
-  double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  {
-    const float yv = a.y[valid ? a.row0 + r : a.row0];
-    const float sp = softplus_f32(z);
-    const float var = sp + 1e-6f;
-    const float s = logf(var);
-    const float prec = expf(-s);
-    const float e = yv - u;
-    if (valid) {
-      du = -(prec * e) * inv_n;
-      const float sgn = (s > 0.f) ? 1.f : ((s < 0.f) ? -1.f : 0.f);
-      const float ds = (-0.5f * prec * e * e + 0.5f + 0.01f * sgn) * inv_n;
-      const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
-      dz = ds * sig / var;
-      t[0] = (double)(0.5f * prec * e * e + 0.5f * s);
-      t[1] = (double)fabsf(s);
-      t[2] = (double)(e * e);
-      t[3] = (double)du;
-      t[4] = (double)dz;
-    }
-  }
+  float du, dz;
+  LossSums row;          // this row's terms alone
+  loss_row(u, z, a.y[valid ? a.row0 + r : a.row0], inv_n, valid, true, du, dz, row);
   if (g == 0) {
     a.du[r] = du;
     a.dz[r] = dz;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) red[rr][q] = t[q];
+    red[rr][kLossNll] = (double)row.nll;
+    red[rr][kLossAbs] = (double)row.abs;
+    red[rr][kLossMse] = (double)row.mse;
+    red[rr][kLossDu] = (double)du;
+    red[rr][kLossDz] = (double)dz;
   }
   // d pre_v2 = w_v2[f] * dz * (1 - v2^2) (zero in the padding and on invalid rows)
   float* drow = a.dpre_v2 + r * a.ld_dpre;
@@ -632,10 +612,10 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
     drow[f] = f < a.hv2 ? a.wv2[f] * dz * (1.0f - v * v) : 0.0f;
   }
   __syncthreads();
-  if (tid < 5) {
+  if (tid < kLossSums) {
     double s = 0.0;
     for (int q = 0; q < 16; ++q) s += red[q][tid];
-    a.loss_part[((a.row0 / 16) + blockIdx.x) * 8 + tid] = s;
+    a.loss_part[((a.row0 / 16) + blockIdx.x) * kLossTerms + tid] = s;
   }
 }
 
@@ -723,9 +703,9 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinArgs a) {
   }
   if (blockIdx.x == 0 && a.loss_part) {
     __shared__ double red[256];
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < kLossOut; ++q) {
       double s = 0.0;
-      for (long long b = threadIdx.x; b < a.n_parts; b += 256) s += a.loss_part[b * 8 + q];
+      for (long long b = threadIdx.x; b < a.n_parts; b += 256) s += a.loss_part[b * kLossTerms + q];
       red[threadIdx.x] = s;
       __syncthreads();
       for (int w = 128; w > 0; w >>= 1) {
@@ -759,10 +739,8 @@ __global__ __launch_bounds__(256) void mc_final_kernel(const float* __restrict__
                                                        float* o2) {
   const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
   if (r >= n_rows) return;
-  const float inv_t = 1.0f / (float)n_passes;
   o0[r] = st[r];
-  o1[r] = expf(0.5f * (st[3 * n_rows + r] * inv_t));
-  o2[r] = sqrtf(st[2 * n_rows + r] * inv_t);
+  mc_finish(st[2 * n_rows + r], st[3 * n_rows + r], n_passes, o1[r], o2[r]);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1066,14 +1044,14 @@ __global__ __launch_bounds__(256) void head2_kernel(Head2Args a) {
   const bool valid = r < a.n_valid;
   float du = 0.f, qz = 0.f, pz = 0.f;
   if (valid) {
-    const float var = softplus_f32(z) + 1e-6f;
-    const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
+    const float var = var_of(z);
+    const float sig = softplus_slope(z);
     const float f1 = sig / var;
     const float f2 = sig * (1.0f - sig) / var - f1 * f1;
     du = a.gu[a.row0 + r];
     if (a.glv) {
       const float glv = a.glv[a.row0 + r];
-      qz = glv * sig / var;               // pinn_gnet_backward's dz
+      qz = through_logvar(glv, sig, var);   // pinn_gnet_backward's dz
       pz = glv * f2 * zd;
     }
     if (g == 0) {

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_kernel(FwdArgs a) {
       forward_pass<H, false, kBits>(a.params, small, L, pipe, a.drop, c, xa, xb, st, u, z, v2);
       if (valid && lane < 16) {
         a.o0[lrow] = u;
-        a.o1[lrow] = logf(softplus_f32(z) + 1e-6f);
+        a.o1[lrow] = logvar_of(z);
       }
     } else {
       // pass -1: eval (dropout off) -> pred_mean (01:1442-1445, 1480); passes 0..T-1 stochastic
@@ -56,15 +56,12 @@ __global__ __launch_bounds__(kThreads, 2) void mlp_kernel(FwdArgs a) {
           u_eval = u;
         } else {
           welford_update(mean, m2, u - u_eval, 1.0f / (float)(t + 1));      // population variance of the passes: m2 / T
-          sl += logf(softplus_f32(z) + 1e-6f);
+          sl += logvar_of(z);
         }
       }
       if (valid && lane < 16) {
-        const float inv_t = 1.0f / (float)a.n_passes;
-        const float var = m2 * inv_t;
         a.o0[lrow] = u_eval;
-        a.o1[lrow] = expf(0.5f * (sl * inv_t));   // sqrt(exp(mean_t logvar_t)), 01:1483
-        a.o2[lrow] = sqrtf(var);                  // population std over passes, 01:1486
+        mc_finish(m2, sl, a.n_passes, a.o1[lrow], a.o2[lrow]);
       }
     }
   }

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pinn_hip.h"
+#include "pinn_loss.h"
 
 namespace pinn {
 
@@ -579,9 +580,6 @@ struct FwdArgs {
   float* o1;             // forward: logvar   | MC: a_u
   float* o2;             //                   | MC: e_u
 };
-
-// logvar = log(softplus(z) + 1e-6), softplus with torch's threshold 20 (01:432-434)
-__device__ __forceinline__ float softplus_f32(float z) { return z > 20.0f ? z : log1pf(expf(z)); }
 
 // ---------------------------------------------------------------------------------------
 // One forward pass of the whole net for this wave's 16 rows -> (u, z); every lane holds them.

@@ -22,7 +22,6 @@ namespace pinn {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kMaxSlices = 256;
-constexpr int kLossTerms = 8;   // nll, |logvar|, (y-u)^2, du, dz, spare...
 
 struct TrainArgs {
   const float* params;
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(kThreads, 2) void train_chain_kernel(TrainArgs a) {
   const bool drop = a.drop.mode != PINN_DROP_NONE;
   const float inv_n = (float)(1.0 / (double)a.n_global);
   const int n_groups = L.nh * NP + NP / 2;
-  float s_nll = 0.f, s_abs = 0.f, s_mse = 0.f, s_du = 0.f, s_dz = 0.f;
+  LossSums sums;
 
   const long long n_tiles = (a.n_rows + kTileRows - 1) / kTileRows;
   const unsigned pass0 = train_pass(a.drop);      // 0, or the device's step counter (replayed graphs)
@@ -104,30 +103,9 @@ __global__ __launch_bounds__(kThreads, 2) void train_chain_kernel(TrainArgs a) {
     forward_pass<H, true, kBits>(P, small, L, pipe, a.drop, c, xa, xb, st, u, z, v2);
 
     // ------------------------------------------------------------------ aleatoric_loss (01:916-927) and its gradient
-    float du = 0.f, dz = 0.f;
-    {
-      const float sp = softplus_f32(z);
-      const float var = sp + 1e-6f;
-      const float s = logf(var);                 // logvar
-      const float prec = expf(-s);               // precision = exp(-logvar), 01:919
-      const float e = yv - u;
-      if (valid) {
-        du = -(prec * e) * inv_n;
-        const float sgn = (s > 0.f) ? 1.f : ((s < 0.f) ? -1.f : 0.f);
-        const float ds = (-0.5f * prec * e * e + 0.5f + 0.01f * sgn) * inv_n;
-        // d logvar / dz = softplus'(z) / (softplus(z) + 1e-6); torch: softplus' = 1 above threshold 20
-        const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
-        dz = ds * sig / var;
-        if (kq == 0) {
-          s_nll += 0.5f * prec * e * e + 0.5f * s;
-          s_abs += fabsf(s);
-          s_mse += e * e;
-          s_du += du;
-          s_dz += dz;
-        }
-      }
-      if (lane < 16) { a.du[t16 * 16 + lane] = du; a.dz[t16 * 16 + lane] = dz; }
-    }
+    float du, dz;
+    loss_row(u, z, yv, inv_n, valid, kq == 0, du, dz, sums);
+    if (lane < 16) { a.du[t16 * 16 + lane] = du; a.dz[t16 * 16 + lane] = dz; }
 
     // ------------------------------------------------------------------ backward: variance head
     f32x4 dh[NT];
@@ -204,21 +182,7 @@ __global__ __launch_bounds__(kThreads, 2) void train_chain_kernel(TrainArgs a) {
   }
 
   // ---------------------------------------------------------------------- loss partial sums of this workgroup
-  float terms[5] = {s_nll, s_abs, s_mse, s_du, s_dz};
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    double v = (double)terms[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kLossTerms) {
-    double t = 0.0;
-    if (threadIdx.x < 5)
-      for (int w = 0; w < 4; ++w) t += red[w][threadIdx.x];
-    a.loss_part[(long long)blockIdx.x * kLossTerms + threadIdx.x] = t;
-  }
+  store_loss_partials<4>(sums, red, a.loss_part, lane, wave);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -506,11 +470,11 @@ __global__ __launch_bounds__(256) void grad_finalize_kernel(const float* __restr
     __syncthreads();
     if (threadIdx.x < kLossTerms) {
       const double t = ((lred[0][threadIdx.x] + lred[1][threadIdx.x]) + lred[2][threadIdx.x]) + lred[3][threadIdx.x];
-      if (threadIdx.x < 4) loss_out[threadIdx.x] = t;    // nll sum, |logvar| sum, (y-u)^2 sum, (sum du)
-      if (threadIdx.x == 3) grads[off_bp] = (float)t;    // d loss / d b_p  = sum du
-      if (threadIdx.x == 4) grads[off_bv2] = (float)t;   // d loss / d bv_2 = sum dz
-      if (ad.p && (threadIdx.x == 3 || threadIdx.x == 4)) {      // (their groups' padding floats have zero gradient: no update)
-        const long long o = threadIdx.x == 3 ? off_bp : off_bv2;
+      if (threadIdx.x < kLossOut) loss_out[threadIdx.x] = t;   // nll sum, |logvar| sum, (y-u)^2 sum, (sum du)
+      if (threadIdx.x == kLossDu) grads[off_bp] = (float)t;    // d loss / d b_p  = sum du
+      if (threadIdx.x == kLossDz) grads[off_bv2] = (float)t;   // d loss / d bv_2 = sum dz
+      if (ad.p && (threadIdx.x == kLossDu || threadIdx.x == kLossDz)) {      // (their groups' padding floats have zero gradient: no update)
+        const long long o = threadIdx.x == kLossDu ? off_bp : off_bv2;
         float pj = ad.p[o], mj = ad.m[o], vj = ad.v[o];
         adam_update(pj, (float)t, mj, vj, step_size, bc2_sqrt);
         ad.p[o] = pj; ad.m[o] = mj; ad.v[o] = vj;

@@ -250,11 +250,7 @@ __global__ __launch_bounds__(kThreadsX, 2) void wide_layer_x6_kernel(LayerArgs a
       }
     }
   }
-  if constexpr (kNormRows) {          // the call's largest |d pre-activation|: the range record's gradient check
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
-    if (lane == 0) atomicMax(a.amax, __float_as_uint(amax));
-  }
+  if constexpr (kNormRows) wave_max_to(a.amax, amax, lane == 0);          // the call's largest |d pre-activation|: the range record's gradient check
 }
 
 // input layer: h0 = dropout(tanh(W0 x + b0)) -> stash; 8 MACs per output, VALU
@@ -389,7 +385,7 @@ __global__ __launch_bounds__(256) void wide_heads_kernel(HeadArgs a) {
       zp = block_dot(vv, a.params + a.wv2_off + t * 16, kq, zp);
     }
     const float u = sum_kq(up) + a.params[a.bp_off], z = sum_kq(zp) + a.params[a.bv2_off];
-    const float lv = logf(softplus_f32(z) + 1e-6f);
+    const float lv = logvar_of(z);
     if (lrow < a.n_rows && lane < 16) {
       if (a.mode == 0) { a.o0[lrow] = u; a.o1[lrow] = lv; }
       else if (a.mode == 1) {
@@ -408,10 +404,7 @@ __global__ __launch_bounds__(256) void wide_heads_kernel(HeadArgs a) {
 __global__ __launch_bounds__(256) void wide_mc_finalize_kernel(const float* accum, long long stride, long long n, int n_passes, float* a_u, float* e_u) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float inv_t = 1.0f / (float)n_passes;
-  const float var = accum[2 * stride + i] * inv_t;          // Welford m2 / T
-  a_u[i] = expf(0.5f * (accum[3 * stride + i] * inv_t));
-  e_u[i] = sqrtf(var);
+  mc_finish(accum[2 * stride + i], accum[3 * stride + i], n_passes, a_u[i], e_u[i]);          // Welford m2, sum of logvar
 }
 
 // heads + aleatoric_loss (01:916-927) + its gradient for the training chain: du, dz per row, loss partial sums per
@@ -423,7 +416,7 @@ struct LossArgs {
   float* dv2;               // [T16][H/4][16]
   const float* y;
   float* du; float* dz;     // [T16 * 16]
-  double* loss_part;        // [grid][8]
+  double* loss_part;        // [grid][kLossTerms]
   long long n_rows, n_global;
   int H;
   long long wp_off, bp_off, wv2_off, bv2_off;
@@ -433,11 +426,11 @@ struct LossArgs {
 };
 __global__ __launch_bounds__(256) void wide_loss_kernel(LossArgs a) {
   float amax = 0.0f, gmax = 0.0f;
-  __shared__ double red[4][8];
+  __shared__ double red[4][kLossTerms];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kq = lane >> 4;
   const long long n_t16 = (a.n_rows + 127) / 128 * 8;
   const float inv_n = (float)(1.0 / (double)a.n_global);
-  float s_nll = 0.f, s_abs = 0.f, s_mse = 0.f, s_du = 0.f, s_dz = 0.f;
+  LossSums sums;
   for (long long t16 = (long long)blockIdx.x * 4 + wave; t16 < n_t16; t16 += (long long)gridDim.x * 4) {
     const long long lrow = t16 * 16 + (lane & 15);
     const bool valid = lrow < a.n_rows;
@@ -450,29 +443,9 @@ __global__ __launch_bounds__(256) void wide_loss_kernel(LossArgs a) {
     }
     const float u = sum_kq(up) + a.params[a.bp_off], z = sum_kq(zp) + a.params[a.bv2_off];
     const float yv = a.y[valid ? lrow : a.n_rows - 1];
-    float du = 0.f, dz = 0.f;
-    {
-      const float sp = softplus_f32(z);
-      const float var = sp + 1e-6f;
-      const float s = logf(var);
-      const float prec = expf(-s);
-      const float e = yv - u;
-      if (valid) {
-        du = -(prec * e) * inv_n;
-        const float sgn = (s > 0.f) ? 1.f : ((s < 0.f) ? -1.f : 0.f);
-        const float ds = (-0.5f * prec * e * e + 0.5f + 0.01f * sgn) * inv_n;
-        const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
-        dz = ds * sig / var;
-        if (kq == 0) {
-          s_nll += 0.5f * prec * e * e + 0.5f * s;
-          s_abs += fabsf(s);
-          s_mse += e * e;
-          s_du += du;
-          s_dz += dz;
-        }
-      }
-      if (lane < 16) { a.du[t16 * 16 + lane] = du; a.dz[t16 * 16 + lane] = dz; }
-    }
+    float du, dz;
+    loss_row(u, z, yv, inv_n, valid, kq == 0, du, dz, sums);
+    if (lane < 16) { a.du[t16 * 16 + lane] = du; a.dz[t16 * 16 + lane] = dz; }
     if (a.packed) {
       // the backward layers' first operand in the row's normalised units (norm = 2^(4 - e), max(|du|, |dz|) = m 2^e), as (hi, lo)
       gmax = fmaxf(gmax, fmaxf(fabsf(du), fabsf(dz)));
@@ -510,31 +483,9 @@ __global__ __launch_bounds__(256) void wide_loss_kernel(LossArgs a) {
       store_block(dp, t, vv);
     }
   }
-  if (a.amax) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
-    if (lane == 0) atomicMax(a.amax, __float_as_uint(amax));
-  }
-  if (a.packed && a.emax) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, off, 64));
-    if (lane == 0) atomicMax(a.emax, __float_as_uint(gmax));
-  }
-  float terms[5] = {s_nll, s_abs, s_mse, s_du, s_dz};
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    double v = (double)terms[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 8) {
-    double t = 0.0;
-    if (threadIdx.x < 5)
-      for (int w = 0; w < 4; ++w) t += red[w][threadIdx.x];
-    a.loss_part[(long long)blockIdx.x * 8 + threadIdx.x] = t;
-  }
+  if (a.amax) wave_max_to(a.amax, amax, lane == 0);
+  if (a.packed && a.emax) wave_max_to(a.emax, gmax, lane == 0);
+  store_loss_partials<4>(sums, red, a.loss_part, lane, wave);
 }
 
 // The packed weight gradients' row records (pinn_x6_core.h RowMeta): per 16-row tile fp16 t_r = 2^(e_r - E + c), the two fp16 parts of

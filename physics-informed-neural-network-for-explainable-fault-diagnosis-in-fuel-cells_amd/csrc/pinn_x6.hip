@@ -179,7 +179,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void mlp_x6_kernel(FwdArgs a
       forward_pass<S, H, kBits, false, WAVES>(w0t, small, L, pipe, a.drop, c, xa, xb, u, z);
       if (valid && lane < 16) {
         a.o0[lrow] = u;
-        a.o1[lrow] = logf(softplus_f32(z) + 1e-6f);
+        a.o1[lrow] = logvar_of(z);
       }
     } else {
       float u_eval = 0.f;
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void mlp_x6_kernel(FwdArgs a
         if (t < 0) {
           u_eval = u;
         } else if (!spare) {
-          const float inv_k = 1.0f / (float)(t / 2 + 1), lv = logf(softplus_f32(z) + 1e-6f);      // k-th pass of its parity
+          const float inv_k = 1.0f / (float)(t / 2 + 1), lv = logvar_of(z);      // k-th pass of its parity
           if (kSplit || !(t & 1)) { welford_update(m_even.mean, m_even.m2, u - u_eval, inv_k); m_even.sl += lv; }
           else { welford_update(m_odd.mean, m_odd.m2, u - u_eval, inv_k); m_odd.sl += lv; }
         }
@@ -212,11 +212,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void mlp_x6_kernel(FwdArgs a
       }
       if (valid && lane < 16 && parity == 0) {
         merge_moments(m_even, m_odd, a.n_passes);
-        const float inv_t = 1.0f / (float)a.n_passes;
-        const float var = m_even.m2 * inv_t;                     // population variance of the passes
         a.o0[lrow] = u_eval;
-        a.o1[lrow] = expf(0.5f * (m_even.sl * inv_t));
-        a.o2[lrow] = sqrtf(var);
+        mc_finish(m_even.m2, m_even.sl, a.n_passes, a.o1[lrow], a.o2[lrow]);
       }
     }
   }

@@ -10,8 +10,6 @@
 namespace pinn {
 namespace x6 {
 
-constexpr int kLossTermsX = 8;   // nll, |logvar|, (y-u)^2, du, dz, spare... (= kLossTerms of pinn_train.hip)
-
 struct TrainArgsX {
   const float* params;
   const float* x;
@@ -32,12 +30,12 @@ template <int H, bool kBits, int WAVES, bool kPack>
 __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void train_fwd_x3_kernel(TrainArgsX a, const __bf16* packed) {
   using S = X3;
   constexpr int kThreadsX = WAVES * 64, kTileRowsX = WAVES * 16;
-  constexpr int kSmallBytes = kMaxSmall * 4, kW0Bytes = 8 * kW0Stride * 4, kRedBytes = 8 * kLossTermsX * 8;
+  constexpr int kSmallBytes = kMaxSmall * 4, kW0Bytes = 8 * kW0Stride * 4, kRedBytes = 8 * kLossTerms * 8;
   constexpr int kSlabAt = (kSmallBytes + kW0Bytes + kRedBytes + 1023) & ~1023;
   __shared__ __attribute__((aligned(1024))) char smem[kSlabAt + 2 * S::Pipe::kSlab];
   float* small = reinterpret_cast<float*>(smem);
   float* w0t = reinterpret_cast<float*>(smem + kSmallBytes);
-  double (*red)[kLossTermsX] = reinterpret_cast<double (*)[kLossTermsX]>(smem + kSmallBytes + kW0Bytes);
+  double (*red)[kLossTerms] = reinterpret_cast<double (*)[kLossTerms]>(smem + kSmallBytes + kW0Bytes);
   char* lds_w = smem + kSlabAt;
   ParamLayout L{a.H, a.nh};
   PackLayout K{a.H, a.nh};
@@ -49,7 +47,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void train_fwd_x3_kernel(Tra
 
   const int lane = threadIdx.x & 63, wave = pipe.wave, kq = lane >> 4;
   const float inv_n = (float)(1.0 / (double)a.n_global);
-  float s_nll = 0.f, s_abs = 0.f, s_mse = 0.f, s_du = 0.f, s_dz = 0.f;
+  LossSums sums;
   float gmax = 0.f;        // kPack: max over this lane's rows of max(|du|, |dz|) -> TrainBuffers::emax (the row scales' reference)
   if (blockIdx.x == 0 && threadIdx.x == 0) *a.b.amax = 0u;      // the backward kernel (next in the stream) takes its atomicMax from 0
 
@@ -87,54 +85,15 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void train_fwd_x3_kernel(Tra
     forward_pass<S, H, kBits, true, WAVES, kPack>(w0t, small, L, pipe, a.drop, c, xa, xb, u, z, &sx);
 
     // ------------------------------------------------------------------ aleatoric_loss (01:916-927) and its gradient
-    float du = 0.f, dz = 0.f;
-    {
-      const float sp = softplus_f32(z);
-      const float var = sp + 1e-6f;
-      const float s = logf(var);                 // logvar
-      const float prec = expf(-s);               // precision = exp(-logvar), 01:919
-      const float e = yv - u;
-      if (valid) {
-        du = -(prec * e) * inv_n;
-        const float sgn = (s > 0.f) ? 1.f : ((s < 0.f) ? -1.f : 0.f);
-        const float ds = (-0.5f * prec * e * e + 0.5f + 0.01f * sgn) * inv_n;
-        // d logvar / dz = softplus'(z) / (softplus(z) + 1e-6); torch: softplus' = 1 above threshold 20
-        const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
-        dz = ds * sig / var;
-        if (kq == 0) {
-          s_nll += 0.5f * prec * e * e + 0.5f * s;
-          s_abs += fabsf(s);
-          s_mse += e * e;
-          s_du += du;
-          s_dz += dz;
-        }
-      }
-      if (lane < 16) { a.b.du[t16 * 16 + lane] = du; a.b.dz[t16 * 16 + lane] = dz; }
-      gmax = fmaxf(gmax, fmaxf(fabsf(du), fabsf(dz)));          // (fmaxf drops a NaN: it reaches the gradients through du, dz themselves)
-    }
+    float du, dz;
+    loss_row(u, z, yv, inv_n, valid, kq == 0, du, dz, sums);
+    if (lane < 16) { a.b.du[t16 * 16 + lane] = du; a.b.dz[t16 * 16 + lane] = dz; }
+    gmax = fmaxf(gmax, fmaxf(fabsf(du), fabsf(dz)));          // (fmaxf drops a NaN: it reaches the gradients through du, dz themselves)
   }
-  if constexpr (kPack) {      // one atomicMax per wave on the float's bits: order-independent, so bitwise reproducible
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, off, 64));
-    if (lane == 0) atomicMax(a.b.emax, __float_as_uint(gmax));
-  }
+  if constexpr (kPack) wave_max_to(a.b.emax, gmax, lane == 0);
 
   // ---------------------------------------------------------------------- loss partial sums of this workgroup
-  float terms[5] = {s_nll, s_abs, s_mse, s_du, s_dz};
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    double v = (double)terms[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kLossTermsX) {
-    double t = 0.0;
-    if (threadIdx.x < 5)
-      for (int w = 0; w < WAVES; ++w) t += red[w][threadIdx.x];
-    a.b.loss_part[(long long)blockIdx.x * kLossTermsX + threadIdx.x] = t;
-  }
+  store_loss_partials<WAVES>(sums, red, a.b.loss_part, lane, wave);
 }
 
 // backward chain of every row tile: d pre-activations of all layers to the stash, on the transposed copies.
@@ -177,14 +136,9 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void train_bwd_kernel(TrainA
     const RowMeta meta{S::kCopies == 2 ? (_Float16*)a.b.rowmeta + t16 * 128 : nullptr, E, a.b.qboost};
     backward_pass<S, H, WAVES>(small, L, pipe, a.drop, a.drop.mode, sx, ring, lane, du, dz, amax, meta);
   }
-  if constexpr (S::kActScale != 1.0f) {
-    // the call's largest |d pre-activation| (pinn_net_range_status): one atomicMax per wave on the float's bits (non-negative
-    // floats order like unsigned integers, so the result does not depend on the order of the waves; fmaxf drops NaNs -- a NaN
-    // gradient still reaches the stash and, through the operands, the weight gradients)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
-    if (lane == 0) atomicMax(a.b.amax, __float_as_uint(amax));
-  }
+  // the call's largest |d pre-activation| (pinn_net_range_status); a NaN gradient is dropped here but still reaches the stash and,
+  // through the operands, the weight gradients
+  if constexpr (S::kActScale != 1.0f) wave_max_to(a.b.amax, amax, lane == 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -367,13 +321,13 @@ __global__ __launch_bounds__(kSmallThreads, 1) void train_fwd_small_kernel(Train
   using Frag = Frag2;
   static_assert(H == 256, "four feature quarters of 64");
   constexpr int NP = H / 32;
-  constexpr int kSmallBytes = kMaxSmall * 4, kW0Bytes = 8 * kW0Stride * 4, kRedBytes = 8 * kLossTermsX * 8;
+  constexpr int kSmallBytes = kMaxSmall * 4, kW0Bytes = 8 * kW0Stride * 4, kRedBytes = 8 * kLossTerms * 8;
   constexpr int kXchBytes = 2 * NP * 2048, kHeadBytes = 2 * 4 * 16 * 2 * 4;
   constexpr int kSlabAt = (kSmallBytes + kW0Bytes + kRedBytes + kXchBytes + kHeadBytes + 1023) & ~1023;
   __shared__ __attribute__((aligned(1024))) char smem[kSlabAt + kQDepth * S::Pipe::kSlab];
   float* small = reinterpret_cast<float*>(smem);
   float* w0t = reinterpret_cast<float*>(smem + kSmallBytes);
-  double (*red)[kLossTermsX] = reinterpret_cast<double (*)[kLossTermsX]>(smem + kSmallBytes + kW0Bytes);
+  double (*red)[kLossTerms] = reinterpret_cast<double (*)[kLossTerms]>(smem + kSmallBytes + kW0Bytes);
   char* xch_lds = smem + kSmallBytes + kW0Bytes + kRedBytes;
   float* head = reinterpret_cast<float*>(xch_lds + kXchBytes);       // [row tile][quarter][row][u, z]
   ParamLayout L{a.H, a.nh};
@@ -396,7 +350,8 @@ __global__ __launch_bounds__(kSmallThreads, 1) void train_fwd_small_kernel(Train
   const int fq = wave & 3, rt = wave >> 2;                           // feature quarter, row tile of the workgroup
   const Xch xch{xch_lds + rt * (NP * 2048), (lane & 15) * 64 + kq * 16};
   const float inv_n = (float)(1.0 / (double)a.n_global);
-  float s_nll = 0.f, s_abs = 0.f, s_mse = 0.f, s_du = 0.f, s_dz = 0.f, gmax = 0.f;
+  LossSums sums;
+  float gmax = 0.f;
   if (blockIdx.x == 0 && threadIdx.x == 0) *a.b.amax = 0u;
   const unsigned pass0 = train_pass(a.drop);
   if (blockIdx.x == 0 && threadIdx.x == 0) a.b.amax[2] = pass0;
@@ -520,51 +475,17 @@ __global__ __launch_bounds__(kSmallThreads, 1) void train_fwd_small_kernel(Train
       const float z = (hp[1] + hp[33]) + small[SL.bv2()];
       const float yv = a.y[srow];
       // ---------------------------------------------------------------- aleatoric_loss (01:916-927) and its gradient
-      float du = 0.f, dz = 0.f;
-      const float sp = softplus_f32(z);
-      const float var = sp + 1e-6f;
-      const float sl = logf(var);                // logvar
-      const float prec = expf(-sl);              // precision = exp(-logvar), 01:919
-      const float e = yv - u;
-      if (valid) {
-        du = -(prec * e) * inv_n;
-        const float sgn = (sl > 0.f) ? 1.f : ((sl < 0.f) ? -1.f : 0.f);
-        const float ds = (-0.5f * prec * e * e + 0.5f + 0.01f * sgn) * inv_n;
-        const float sig = z > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-z));
-        dz = ds * sig / var;
-        if (kq == 0) {
-          s_nll += 0.5f * prec * e * e + 0.5f * sl;
-          s_abs += fabsf(sl);
-          s_mse += e * e;
-          s_du += du;
-          s_dz += dz;
-        }
-      }
+      float du, dz;
+      loss_row(u, z, yv, inv_n, valid, kq == 0, du, dz, sums);
       if (lane < 16) { a.b.du[t16 * 16 + lane] = du; a.b.dz[t16 * 16 + lane] = dz; }
       gmax = fmaxf(gmax, fmaxf(fabsf(du), fabsf(dz)));
     }
     PINN_QS(11);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the slabs requested past the last step: landed before the LDS is released
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, off, 64));
-  if (lane == 0 && fq == 0) atomicMax(a.b.emax, __float_as_uint(gmax));
+  wave_max_to(a.b.emax, gmax, lane == 0 && fq == 0);
 
-  float terms[5] = {s_nll, s_abs, s_mse, s_du, s_dz};
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    double v = (double)terms[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kLossTermsX) {
-    double t = 0.0;
-    if (threadIdx.x < 5)
-      for (int w = 0; w < 8; ++w) t += red[w][threadIdx.x];
-    a.b.loss_part[(long long)blockIdx.x * kLossTermsX + threadIdx.x] = t;
-  }
+  store_loss_partials<8>(sums, red, a.b.loss_part, lane, wave);
   PINN_QS(12);
 }
 
