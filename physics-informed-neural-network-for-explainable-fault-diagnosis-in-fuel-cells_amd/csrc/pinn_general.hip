@@ -929,82 +929,6 @@ static void launch_finalize(const Shape& s, const float* acc, float* grads, cons
   hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)gx), dim3(256), 0, st, f);
 }
 
-// upstream gradients of pinn_gnet_backward: dL/du and dL/dlogvar per row (glv NULL: zero), dL/dx out (gx NULL: not computed)
-struct Upstream { const float* gu; const float* glv; float* gx; };
-
-// recomputing forward + backward of every chunk, fixed-order slab sums -> d_grads.  up == NULL: aleatoric_loss on (x, y), gradients
-// divided by n_global, loss sums -> d_loss (pinn_gnet_train_grads).  up != NULL: the given upstream gradients, raw sums, no loss, and
-// optionally dL/dx (pinn_gnet_backward).
-static int run_train(const Shape& s, const float* d_params, const float* d_x, const float* d_y, long long n_rows, long long n_global,
-                     const Drop& d, const Upstream* up, float* d_grads, double* d_loss, void* d_work, size_t work_bytes, hipStream_t st) {
-  const Layout L = train_layout(s, n_rows, 1);
-  if (!d_work || !al16(d_work)) return PINN_E_ARG;
-  if (work_bytes < L.end) return PINN_E_WORKSPACE;
-  char* base = (char*)d_work;
-  const float* pack = (const float*)(base + L.pack);
-  int rc = launch_pack(s, d_params, (float*)(base + L.pack), st);
-  if (rc) return rc;
-  float* act[kMaxMat];
-  for (int t = 0; t < s.n_mat; ++t) act[t] = s.is_gemm(t) ? (float*)(base + L.act[0][act_index(s, t)]) : nullptr;
-  unsigned* keep = (unsigned*)(base + L.keep);
-  float* dp[2] = {(float*)(base + L.dpre[0][0]), (float*)(base + L.dpre[0][1])};
-  float* du = (float*)(base + L.du);
-  float* dz = (float*)(base + L.dz);
-  float* slabs = (float*)(base + L.slabs);
-  float* acc = (float*)(base + L.acc);
-  double* loss_part = (double*)(base + L.loss);
-  ChunkIO io = train_io(s, act, nullptr, keep);
-  io.in[0] = d_x;
-  const int v0m = s.mat_v0(), v1m = s.mat_v1();
-  const long long nch = n_chunks(n_rows, L.rows);
-  for (long long ch = 0; ch < nch; ++ch) {
-    const long long row0 = ch * L.rows;
-    const long long nv = n_rows - row0 < L.rows ? n_rows - row0 : L.rows;
-    const float* x = d_x + row0 * 8;
-    forward_layers(s, d_params, pack, d, io, row0, nv, L.rows, n_rows, false, st);
-    HeadArgs h = head_args(s, d_params, act[s.k - 1], s.mp[s.k - 1], act[v1m], s.mp[v1m], nv, row0);
-    h.y = d_y; h.n_global = n_global; h.du = du; h.dz = dz; h.dpre_v2 = dp[0]; h.ld_dpre = s.max_wp; h.wd = s.mp[v1m];
-    h.loss_part = loss_part;
-    if (up) {
-      h.gu = up->gu; h.glv = up->glv;
-      hipLaunchKernelGGL(heads_kernel<kHeadGrad>, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, h);
-    } else {
-      hipLaunchKernelGGL(heads_kernel<kHeadTrain>, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, h);
-    }
-    // variance head layer 1, then layer 0 (+ the predict head), then the hidden layers top-down
-    wgrad(s, v1m, L, dp[0], s.max_wp, act[v0m], s.mp[v0m], nv, slabs, st);
-    bwd(s, v1m, L, pack, d, dp[0], dp[1], act[v0m], s.mp[v0m], s.k, keep, nullptr, nullptr, nv, st);
-    wgrad(s, v0m, L, dp[1], s.max_wp, act[s.k - 1], s.mp[s.k - 1], nv, slabs, st);
-    {
-      VecArgs va{};
-      va.h = act[s.k - 1]; va.ldh = s.mp[s.k - 1]; va.hk = s.hk;
-      va.v2 = act[v1m]; va.ldv = s.mp[v1m]; va.hv2 = s.hv2;
-      va.du = du; va.dz = dz; va.K = L.rows; va.slice_rows = L.slice_rows;
-      va.slab = slabs; va.slab_stride = s.gtotal; va.reg_p = s.reg[s.mat_pred()]; va.reg_v2 = s.reg[s.mat_v2()];
-      const int cols = s.hk + 1 + s.hv2 + 1;
-      hipLaunchKernelGGL(vec_grad_kernel, dim3((unsigned)L.slices, (unsigned)((cols + 255) / 256)), dim3(256), 0, st, va);
-    }
-    bwd(s, v0m, L, pack, d, dp[1], dp[0], act[s.k - 1], s.mp[s.k - 1], s.k - 1, keep, d_params + s.woff[s.mat_pred()], du, nv, st);
-    int cur = 0;
-    for (int l = s.k - 1; l >= 0; --l) {
-      if (l == 0) wgrad(s, 0, L, dp[cur], s.max_wp, x, 8, nv, slabs, st);
-      else wgrad(s, l, L, dp[cur], s.max_wp, act[l - 1], s.mp[l - 1], nv, slabs, st);
-      if (l > 0) {
-        bwd(s, l, L, pack, d, dp[cur], dp[cur ^ 1], act[l - 1], s.mp[l - 1], l - 1, keep, nullptr, nullptr, nv, st);
-        cur ^= 1;
-      }
-    }
-    if (up && up->gx)        // dp[cur] is now d pre-activation of hidden layer 0
-      hipLaunchKernelGGL(dx_kernel, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, d_params + s.woff[0], s.w[0], (const float*)dp[cur],
-                         (long long)s.max_wp, nv, row0, up->gx);
-    launch_reduce(s, L, slabs, acc, ch == 0, st);
-    rc = last_error();
-    if (rc) return rc;
-  }
-  launch_finalize(s, acc, d_grads, up ? nullptr : loss_part, nch * (L.rows / 16), d_loss, st);
-  return last_error();
-}
-
 // ---------------------------------------------------------------------------------------
 // double backward (pinn_gnet_backward2): the gradient of S = <v, dL/dx> with respect to g_u, g_lv, x and the parameters.
 //
@@ -1103,89 +1027,137 @@ __global__ __launch_bounds__(256) void vec_grad2_kernel(Vec2Args a) {
   }
 }
 
-struct Second { const float* gu; const float* glv; const float* vx; float* grads; float* gx; float* ggu; float* gglv; };
+// One call of pinn_gnet_train_grads / _train_step, pinn_gnet_backward or pinn_gnet_backward2.  Upstream: gu == NULL: aleatoric_loss on
+// (x, y), gradients divided by n_global, loss sums -> loss; otherwise the given dL/du and dL/dlogvar per row (glv NULL: zero), raw sums,
+// no loss.  vx != NULL: the second stream of the double backward (the section above), with ggu / gglv (each NULL: not written).
+// grads NULL: no weight gradient; gx NULL: no dL/dx (dS/dx)
+struct GradCall {
+  const float* y; long long n_global;
+  const float* gu; const float* glv;
+  const float* vx; float* ggu; float* gglv;
+  float* grads; float* gx; double* loss;
+};
 
-static int run_backward2(const Shape& s, const float* d_params, const float* d_x, long long n_rows, const Drop& d, const Second& o,
-                         void* d_work, size_t work_bytes, hipStream_t st) {
-  const Layout L = train_layout(s, n_rows, 2);
+// the workspace of a chunk.  tan, dq, pz: the second stream's (NULL with one stream); loss_part: one stream only
+struct ChunkBufs {
+  float* act[kMaxMat]; float* tan[kMaxMat]; unsigned* keep;
+  float* dp[2]; float* dq[2]; float* du; float* dz; float* pz; float* slabs; float* acc; double* loss_part;
+};
+
+// heads of a chunk: du, dz (, pz) per row and the d pre-activation(s) below the variance head's second tanh, in dp[0] (, dq[0])
+static void launch_heads(const Shape& s, const Layout& L, const float* params, const GradCall& c, const ChunkBufs& w, long long nv,
+                         long long row0, hipStream_t st) {
+  const int v1m = s.mat_v1();
+  const dim3 grid((unsigned)(L.rows / 16)), blk(256);
+  if (c.vx) {
+    Head2Args h{};
+    h.hd = w.tan[s.k - 1]; h.ldh = s.mp[s.k - 1]; h.hk = s.hk;
+    h.v2 = w.act[v1m]; h.v2d = w.tan[v1m]; h.ldv = s.mp[v1m]; h.hv2 = s.hv2;
+    h.wp = params + s.woff[s.mat_pred()]; h.wv2 = params + s.woff[s.mat_v2()]; h.bv2 = params + s.boff[s.mat_v2()];
+    h.n_valid = nv; h.row0 = row0;
+    h.gu = c.gu; h.glv = c.glv; h.ggu = c.ggu; h.gglv = c.gglv;
+    h.du = w.du; h.qz = w.dz; h.pz = w.pz; h.dp = w.dp[0]; h.dq = w.dq[0]; h.ld_dpre = s.max_wp; h.wd = s.mp[v1m];
+    hipLaunchKernelGGL(head2_kernel, grid, blk, 0, st, h);
+    return;
+  }
+  HeadArgs h = head_args(s, params, w.act[s.k - 1], s.mp[s.k - 1], w.act[v1m], s.mp[v1m], nv, row0);
+  h.y = c.y; h.n_global = c.n_global; h.gu = c.gu; h.glv = c.glv;
+  h.du = w.du; h.dz = w.dz; h.dpre_v2 = w.dp[0]; h.ld_dpre = s.max_wp; h.wd = s.mp[v1m];
+  h.loss_part = w.loss_part;
+  if (c.gu) hipLaunchKernelGGL(heads_kernel<kHeadGrad>, grid, blk, 0, st, h);
+  else hipLaunchKernelGGL(heads_kernel<kHeadTrain>, grid, blk, 0, st, h);
+}
+
+// the two one-row tensors (predict, last variance layer) of a chunk, per slice
+static void launch_vec_grad(const Shape& s, const Layout& L, const ChunkBufs& w, bool paired, hipStream_t st) {
+  const int v1m = s.mat_v1(), cols = s.hk + 1 + s.hv2 + 1;
+  const dim3 grid((unsigned)L.slices, (unsigned)((cols + 255) / 256)), blk(256);
+  if (paired) {
+    Vec2Args va{};
+    va.hd = w.tan[s.k - 1]; va.ldh = s.mp[s.k - 1]; va.hk = s.hk;
+    va.v2 = w.act[v1m]; va.v2d = w.tan[v1m]; va.ldv = s.mp[v1m]; va.hv2 = s.hv2;
+    va.du = w.du; va.qz = w.dz; va.pz = w.pz; va.K = L.rows; va.slice_rows = L.slice_rows;
+    va.slab = w.slabs; va.slab_stride = s.gtotal; va.reg_p = s.reg[s.mat_pred()]; va.reg_v2 = s.reg[s.mat_v2()];
+    hipLaunchKernelGGL(vec_grad2_kernel, grid, blk, 0, st, va);
+  } else {
+    VecArgs va{};
+    va.h = w.act[s.k - 1]; va.ldh = s.mp[s.k - 1]; va.hk = s.hk;
+    va.v2 = w.act[v1m]; va.ldv = s.mp[v1m]; va.hv2 = s.hv2;
+    va.du = w.du; va.dz = w.dz; va.K = L.rows; va.slice_rows = L.slice_rows;
+    va.slab = w.slabs; va.slab_stride = s.gtotal; va.reg_p = s.reg[s.mat_pred()]; va.reg_v2 = s.reg[s.mat_v2()];
+    hipLaunchKernelGGL(vec_grad_kernel, grid, blk, 0, st, va);
+  }
+}
+
+// recomputing forward + backward of every chunk, fixed-order slab sums -> c.grads.  With one stream tan[..], dq[..] and vx are NULL, and
+// the optional arguments of train_io / wgrad / bwd select the single-stream kernels
+static int run_grads(const Shape& s, const float* d_params, const float* d_x, long long n_rows, const pinn_dropout_t* drop,
+                     const GradCall& c, void* d_work, size_t work_bytes, hipStream_t st) {
+  Drop d;
+  int rc = convert(s, drop, &d);
+  if (rc) return rc;
+  (void)hipGetLastError();
+  const bool two = c.vx != nullptr;
+  const Layout L = train_layout(s, n_rows, two ? 2 : 1);
   if (!d_work || !al16(d_work)) return PINN_E_ARG;
   if (work_bytes < L.end) return PINN_E_WORKSPACE;
   char* base = (char*)d_work;
   const float* pack = (const float*)(base + L.pack);
-  int rc = launch_pack(s, d_params, (float*)(base + L.pack), st);
+  rc = launch_pack(s, d_params, (float*)(base + L.pack), st);
   if (rc) return rc;
-  float* act[kMaxMat]; float* tan[kMaxMat];
-  for (int t = 0; t < s.n_mat; ++t) {
-    act[t] = s.is_gemm(t) ? (float*)(base + L.act[0][act_index(s, t)]) : nullptr;
-    tan[t] = s.is_gemm(t) ? (float*)(base + L.act[1][act_index(s, t)]) : nullptr;
-  }
-  unsigned* keep = (unsigned*)(base + L.keep);
-  float* dp[2] = {(float*)(base + L.dpre[0][0]), (float*)(base + L.dpre[0][1])};
-  float* dq[2] = {(float*)(base + L.dpre[1][0]), (float*)(base + L.dpre[1][1])};
-  float* du = (float*)(base + L.du);
-  float* qz = (float*)(base + L.dz);
-  float* pz = (float*)(base + L.pz);
-  float* slabs = (float*)(base + L.slabs);
-  float* acc = (float*)(base + L.acc);
-  ChunkIO io = train_io(s, act, tan, keep);
-  io.in[0] = d_x; io.in2[0] = o.vx;
+  auto f32 = [&](size_t off, bool have = true) { return have ? (float*)(base + off) : nullptr; };
+  ChunkBufs w{};
+  for (int t = 0; t < s.n_mat; ++t)
+    if (s.is_gemm(t)) { w.act[t] = f32(L.act[0][act_index(s, t)]); w.tan[t] = f32(L.act[1][act_index(s, t)], two); }
+  w.keep = (unsigned*)(base + L.keep);
+  for (int b = 0; b < 2; ++b) { w.dp[b] = f32(L.dpre[0][b]); w.dq[b] = f32(L.dpre[1][b], two); }
+  w.du = f32(L.du); w.dz = f32(L.dz); w.pz = f32(L.pz, two);
+  w.slabs = f32(L.slabs); w.acc = f32(L.acc);
+  w.loss_part = two ? nullptr : (double*)(base + L.loss);
+  float* const* act = w.act; float* const* tan = w.tan; float* const* dp = w.dp; float* const* dq = w.dq;
+  ChunkIO io = train_io(s, act, tan, w.keep);
+  io.in[0] = d_x; io.in2[0] = c.vx;
   const int v0m = s.mat_v0(), v1m = s.mat_v1();
-  const bool want_w = o.grads != nullptr, want_back = want_w || o.gx;
-  const dim3 blk(256);
+  const bool want_w = c.grads != nullptr, want_back = want_w || c.gx;
   const long long nch = n_chunks(n_rows, L.rows);
   for (long long ch = 0; ch < nch; ++ch) {
     const long long row0 = ch * L.rows;
     const long long nv = n_rows - row0 < L.rows ? n_rows - row0 : L.rows;
     const float* x = d_x + row0 * 8;
-    const float* vx = o.vx + row0 * 8;
-    forward_layers(s, d_params, pack, d, io, row0, nv, L.rows, n_rows, false, st);      // primal and tangent
-    {
-      Head2Args h{};
-      h.hd = tan[s.k - 1]; h.ldh = s.mp[s.k - 1]; h.hk = s.hk;
-      h.v2 = act[v1m]; h.v2d = tan[v1m]; h.ldv = s.mp[v1m]; h.hv2 = s.hv2;
-      h.wp = d_params + s.woff[s.mat_pred()]; h.wv2 = d_params + s.woff[s.mat_v2()]; h.bv2 = d_params + s.boff[s.mat_v2()];
-      h.n_valid = nv; h.row0 = row0;
-      h.gu = o.gu; h.glv = o.glv; h.ggu = o.ggu; h.gglv = o.gglv;
-      h.du = du; h.qz = qz; h.pz = pz; h.dp = dp[0]; h.dq = dq[0]; h.ld_dpre = s.max_wp; h.wd = s.mp[v1m];
-      hipLaunchKernelGGL(head2_kernel, dim3((unsigned)(L.rows / 16)), blk, 0, st, h);
-    }
+    const float* vx = c.vx ? c.vx + row0 * 8 : nullptr;
+    forward_layers(s, d_params, pack, d, io, row0, nv, L.rows, n_rows, false, st);      // primal (and tangent)
+    launch_heads(s, L, d_params, c, w, nv, row0, st);
     if (want_back) {
-      // variance head layer 1, then layer 0 (+ the predict head on the q stream), then the hidden layers top-down
-      if (want_w) wgrad(s, v1m, L, dp[0], s.max_wp, act[v0m], s.mp[v0m], nv, slabs, st, dq[0], tan[v0m]);
-      bwd(s, v1m, L, pack, d, dp[0], dp[1], act[v0m], s.mp[v0m], s.k, keep, nullptr, nullptr, nv, st, dq[0], dq[1], tan[v0m]);
+      // variance head layer 1, then layer 0 (+ the predict head; on the q stream of two), then the hidden layers top-down
+      if (want_w) wgrad(s, v1m, L, dp[0], s.max_wp, act[v0m], s.mp[v0m], nv, w.slabs, st, dq[0], tan[v0m]);
+      bwd(s, v1m, L, pack, d, dp[0], dp[1], act[v0m], s.mp[v0m], s.k, w.keep, nullptr, nullptr, nv, st, dq[0], dq[1], tan[v0m]);
       if (want_w) {
-        wgrad(s, v0m, L, dp[1], s.max_wp, act[s.k - 1], s.mp[s.k - 1], nv, slabs, st, dq[1], tan[s.k - 1]);
-        Vec2Args va{};
-        va.hd = tan[s.k - 1]; va.ldh = s.mp[s.k - 1]; va.hk = s.hk;
-        va.v2 = act[v1m]; va.v2d = tan[v1m]; va.ldv = s.mp[v1m]; va.hv2 = s.hv2;
-        va.du = du; va.qz = qz; va.pz = pz; va.K = L.rows; va.slice_rows = L.slice_rows;
-        va.slab = slabs; va.slab_stride = s.gtotal; va.reg_p = s.reg[s.mat_pred()]; va.reg_v2 = s.reg[s.mat_v2()];
-        const int cols = s.hk + 1 + s.hv2 + 1;
-        hipLaunchKernelGGL(vec_grad2_kernel, dim3((unsigned)L.slices, (unsigned)((cols + 255) / 256)), blk, 0, st, va);
+        wgrad(s, v0m, L, dp[1], s.max_wp, act[s.k - 1], s.mp[s.k - 1], nv, w.slabs, st, dq[1], tan[s.k - 1]);
+        launch_vec_grad(s, L, w, two, st);
       }
-      bwd(s, v0m, L, pack, d, dp[1], dp[0], act[s.k - 1], s.mp[s.k - 1], s.k - 1, keep, d_params + s.woff[s.mat_pred()], du, nv, st,
+      bwd(s, v0m, L, pack, d, dp[1], dp[0], act[s.k - 1], s.mp[s.k - 1], s.k - 1, w.keep, d_params + s.woff[s.mat_pred()], w.du, nv, st,
           dq[1], dq[0], tan[s.k - 1]);
       int cur = 0;
       for (int l = s.k - 1; l >= 0; --l) {
         if (want_w) {
-          if (l == 0) wgrad(s, 0, L, dp[cur], s.max_wp, x, 8, nv, slabs, st, dq[cur], vx);
-          else wgrad(s, l, L, dp[cur], s.max_wp, act[l - 1], s.mp[l - 1], nv, slabs, st, dq[cur], tan[l - 1]);
+          if (l == 0) wgrad(s, 0, L, dp[cur], s.max_wp, x, 8, nv, w.slabs, st, dq[cur], vx);
+          else wgrad(s, l, L, dp[cur], s.max_wp, act[l - 1], s.mp[l - 1], nv, w.slabs, st, dq[cur], tan[l - 1]);
         }
         if (l > 0) {
-          bwd(s, l, L, pack, d, dp[cur], dp[cur ^ 1], act[l - 1], s.mp[l - 1], l - 1, keep, nullptr, nullptr, nv, st, dq[cur], dq[cur ^ 1],
+          bwd(s, l, L, pack, d, dp[cur], dp[cur ^ 1], act[l - 1], s.mp[l - 1], l - 1, w.keep, nullptr, nullptr, nv, st, dq[cur], dq[cur ^ 1],
               tan[l - 1]);
           cur ^= 1;
         }
       }
-      if (o.gx)        // dS/dx = W_0^T p_0
-        hipLaunchKernelGGL(dx_kernel, dim3((unsigned)(L.rows / 16)), blk, 0, st, d_params + s.woff[0], s.w[0], (const float*)dp[cur],
-                           (long long)s.max_wp, nv, row0, o.gx);
-      if (want_w) launch_reduce(s, L, slabs, acc, ch == 0, st);
+      if (c.gx)        // dp[cur] is now d pre-activation of hidden layer 0 (two streams: p_0, dS/dx = W_0^T p_0)
+        hipLaunchKernelGGL(dx_kernel, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, d_params + s.woff[0], s.w[0], (const float*)dp[cur],
+                           (long long)s.max_wp, nv, row0, c.gx);
+      if (want_w) launch_reduce(s, L, w.slabs, w.acc, ch == 0, st);
     }
     rc = last_error();
     if (rc) return rc;
   }
-  if (want_w) launch_finalize(s, acc, o.grads, nullptr, 0, nullptr, st);
+  if (want_w) launch_finalize(s, w.acc, c.grads, c.gu ? nullptr : w.loss_part, w.loss_part ? nch * (L.rows / 16) : 0, c.loss, st);
   return last_error();
 }
 
@@ -1249,11 +1221,9 @@ extern "C" int pinn_gnet_train_grads(const pinn_gnet_t* net, const float* d_para
     return PINN_E_ARG;
   if (n_rows == 0) return PINN_OK;
   if (!d_x || !al16(d_x) || !d_y) return PINN_E_ARG;
-  Drop d;
-  rc = convert(s, drop, &d);
-  if (rc) return rc;
-  (void)hipGetLastError();
-  return run_train(s, d_params, d_x, d_y, n_rows, n_global, d, nullptr, d_grads, d_loss, d_work, work_bytes, (hipStream_t)stream);
+  GradCall c{};
+  c.y = d_y; c.n_global = n_global; c.grads = d_grads; c.loss = d_loss;
+  return run_grads(s, d_params, d_x, n_rows, drop, c, d_work, work_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pinn_gnet_train_step(const pinn_gnet_t* net, float* d_params, const float* d_x, const float* d_y, long long n_rows,
@@ -1275,12 +1245,9 @@ extern "C" int pinn_gnet_backward(const pinn_gnet_t* net, const float* d_params,
   if (n_rows < 0 || !d_params || !al16(d_params) || !d_grads || !al16(d_grads)) return PINN_E_ARG;
   if (n_rows == 0) return PINN_OK;
   if (!d_x || !al16(d_x) || !d_gu || (d_gx && !al16(d_gx))) return PINN_E_ARG;
-  Drop d;
-  rc = convert(s, drop, &d);
-  if (rc) return rc;
-  (void)hipGetLastError();
-  const Upstream up{d_gu, d_glv, d_gx};
-  return run_train(s, d_params, d_x, nullptr, n_rows, n_rows, d, &up, d_grads, nullptr, d_work, work_bytes, (hipStream_t)stream);
+  GradCall c{};
+  c.n_global = n_rows; c.gu = d_gu; c.glv = d_glv; c.grads = d_grads; c.gx = d_gx;
+  return run_grads(s, d_params, d_x, n_rows, drop, c, d_work, work_bytes, (hipStream_t)stream);
 }
 
 extern "C" size_t pinn_gnet_backward2_workspace_bytes(const pinn_gnet_t* net, long long n_rows) {
@@ -1303,10 +1270,7 @@ extern "C" int pinn_gnet_backward2(const pinn_gnet_t* net, const float* d_params
     return e == hipSuccess ? PINN_OK : (int)e;
   }
   if (!d_x || !al16(d_x) || !d_gu || !d_vx || !al16(d_vx) || (d_gx && !al16(d_gx))) return PINN_E_ARG;
-  Drop d;
-  rc = convert(s, drop, &d);
-  if (rc) return rc;
-  (void)hipGetLastError();
-  const Second o{d_gu, d_glv, d_vx, d_grads, d_gx, d_ggu, d_gglv};
-  return run_backward2(s, d_params, d_x, n_rows, d, o, d_work, work_bytes, (hipStream_t)stream);
+  GradCall c{};
+  c.gu = d_gu; c.glv = d_glv; c.vx = d_vx; c.ggu = d_ggu; c.gglv = d_gglv; c.grads = d_grads; c.gx = d_gx;
+  return run_grads(s, d_params, d_x, n_rows, drop, c, d_work, work_bytes, (hipStream_t)stream);
 }

@@ -1,7 +1,5 @@
 """GPU: the DNN under torch autograd -- pinn_gnet_backward (csrc/pinn_general.hip) against the CPU oracle's autograd, and the
 autograd=True surface of pinn_amd.DNN / PhysicsInformedNN for every kernel family."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -10,8 +8,10 @@ pytestmark = pytest.mark.gpu
 
 import pinn_oracle as O
 from conftest import ScalerFromArrays, load_golden, unpack_mask
+from gnet_helpers import SHAPES, backward, oracle_vjp
+from gnet_helpers import data as _data, dev as _dev, drop as _drop, flat as _flat, model as _model, pack_bits as _pack_bits
+from gnet_helpers import params as _params, philox_masks as _philox_masks, unflat as _unflat, upstream as _upstream, widths as _widths
 
-SHAPES = [[8, 32, 32, 32, 1], [8, 100, 100, 1], [8, 64, 200, 48, 1], [8, 7, 1, 4, 1], [8, 2000, 300, 1], [8, 256, 256, 256, 1]]
 REL = 2e-4          # per tensor: max |err| <= REL * max |ref|  (test_gpu_general._check_grads)
 
 
@@ -19,99 +19,6 @@ REL = 2e-4          # per tensor: max |err| <= REL * max |ref|  (test_gpu_genera
 def lib():
     from pinn_amd import _lib
     return _lib.load()
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _flat(layers, params):
-    from pinn_amd import layout
-    offs, total = layout.general_offsets(layers)
-    f = torch.zeros(total, dtype=torch.float32)
-    for (_, shape, off), p in zip(offs, params):
-        f[off:off + p.numel()] = p.detach().reshape(-1)
-    return f.to(_dev())
-
-
-def _unflat(layers, flat):
-    from pinn_amd import layout
-    offs, _ = layout.general_offsets(layers)
-    flat = flat.cpu()
-    return [flat[off:off + int(np.prod(shape))].reshape(shape) for _, shape, off in offs]
-
-
-def _widths(layers):
-    return list(layers[1:-1]) + [layers[-2] // 2]
-
-
-def _drop(mode, layers, p=0.2, seed=0, stream=0, row_offset=0, bits=None):
-    from pinn_amd import _lib
-    d = _lib.Dropout()
-    d.mode = mode
-    for l in range(len(layers) - 1):
-        d.p[l] = p
-    d.seed, d.stream, d.row_offset = seed, stream, row_offset
-    d.d_bits = bits.data_ptr() if bits is not None else None
-    d.d_step_counter = None
-    return d
-
-
-def _philox_masks(layers, seed, stream, row0, n, p):
-    return [O.philox_keep_mask(seed, stream, row0, n, l, w, p) for l, w in enumerate(_widths(layers))]
-
-
-def _pack_bits(masks):
-    """list over modules of bool [N, w] -> int32 [1, N, words]; module l starts at word sum ceil(w_j / 32)."""
-    parts = []
-    for m in masks:
-        m = np.asarray(m, dtype=np.uint8)
-        m = np.concatenate([m, np.zeros((m.shape[0], (-m.shape[1]) % 32), np.uint8)], axis=1)
-        parts.append(np.packbits(m, axis=-1, bitorder="little"))
-    return torch.from_numpy(np.ascontiguousarray(np.concatenate(parts, axis=-1)).view(np.int32)[None].copy())
-
-
-def _data(n, seed):
-    from pinn_amd import synth
-    return synth.make_dataset(n, (), seed=seed)[0]
-
-
-def backward(lib, layers, fp, x, gu, glv=None, drop=None, want_dx=True):
-    """pinn_gnet_backward -> (flat grads, dx or None) on the host."""
-    from pinn_amd import _lib
-    n = x.shape[0]
-    net = _lib.GNet(layers)
-    wb = lib.pinn_gnet_workspace_bytes(ctypes.byref(net), n, 0)
-    assert wb > 0
-    w = torch.full((wb,), 0xFF, dtype=torch.uint8, device=_dev())        # poisoned: reads of unwritten words show as NaN
-    g = torch.full((fp.numel(),), float("nan"), device=_dev())
-    dx = torch.full((n, 8), float("nan"), device=_dev()) if want_dx else None
-    _lib.check(lib.pinn_gnet_backward(ctypes.byref(net), _ptr(fp), _ptr(x), n, ctypes.byref(drop) if drop else None, _ptr(gu),
-                                      _ptr(glv), _ptr(g), _ptr(dx), _ptr(w), w.numel(), _stream()), "pinn_gnet_backward")
-    torch.cuda.synchronize()
-    return g.cpu(), (dx.cpu() if dx is not None else None)
-
-
-def oracle_vjp(P, x, gu, glv, p_list=None, masks=None):
-    """torch.autograd.grad((u, lv), P + [x], (g_u, g_lv)) of O.mlp_forward, fp32 on the CPU."""
-    P = [p.detach().clone().requires_grad_(True) for p in P]
-    x = x.detach().clone().requires_grad_(True)
-    u, lv = O.mlp_forward(P, x, p_list, masks)
-    outs, gos = [u], [gu.reshape(-1, 1)]
-    if glv is not None:
-        outs.append(lv)
-        gos.append(glv.reshape(-1, 1))
-    g = torch.autograd.grad(outs, P + [x], gos, allow_unused=True)
-    g = [torch.zeros_like(t) if gi is None else gi for gi, t in zip(g, P + [x])]
-    return g[:-1], g[-1]
 
 
 def _close(got, want, what):
@@ -125,11 +32,6 @@ def _check(layers, got_flat, got_dx, want_p, want_dx):
         _close(g, w, (layers, name))
     if want_dx is not None:
         _close(got_dx, want_dx, (layers, "dx"))
-
-
-def _upstream(n, seed):
-    gen = torch.Generator().manual_seed(seed)
-    return torch.randn(n, generator=gen), torch.randn(n, generator=gen)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -204,21 +106,6 @@ def test_backward_deterministic_windows_and_shards(lib):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # the module surface
-def _model(layers, n=700, seed=11, **kw):
-    import pinn_amd
-    from pinn_amd import synth
-    ds = synth.make_dataset(n, (), seed=0)
-    torch.manual_seed(0)
-    m = pinn_amd.PhysicsInformedNN(ds[0], ds[1], layers, ds[4], ds[5], p=0.2, logvar=True, seed=seed, **kw)
-    m.verbose = False
-    return m, ds
-
-
-def _params(dnn):
-    named = dict(dnn.named_parameters())
-    return [named[n] for n in O.param_names(dnn.n_hidden)]
-
-
 def _check_module(dnn, layers, x, gu, glv, masks, p=0.2):
     P = [t.detach().cpu() for t in _params(dnn)]
     wp, wx = oracle_vjp(P, x.detach().cpu(), gu.cpu(), glv.cpu(), [p] * (len(layers) - 1), masks)

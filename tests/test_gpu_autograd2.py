@@ -6,6 +6,7 @@ The referee is always the oracle's mlp_forward in float64 under torch's own doub
 Bound: the project's per-tensor rule, max |err| <= 2e-4 * max |ref| + 1e-6 * max |ref| (test_gpu_general._check_grads, REL of
 test_gpu_autograd.py); torch's own float32 double autograd of the same oracle sits about 40 times inside it."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -14,126 +15,19 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import pinn_oracle as O
+from gnet_helpers import SHAPES, backward2, oracle2
+from gnet_helpers import data as _data, dev as _dev, drop as _drop, flat as _flat, model as _model, pack_bits as _pack_bits
+from gnet_helpers import padding as _padding, params as _params, philox_masks as _philox_masks, ptr as _ptr, stream as _stream
+from gnet_helpers import unflat as _unflat, upstream, widths as _widths
 
-SHAPES = [[8, 32, 32, 32, 1], [8, 100, 100, 1], [8, 64, 200, 48, 1], [8, 7, 1, 4, 1], [8, 2000, 300, 1], [8, 256, 256, 256, 1]]
 REL = 2e-4
+_upstream = functools.partial(upstream, with_v=True)      # g_u, g_lv and v
 
 
 @pytest.fixture(scope="module")
 def lib():
     from pinn_amd import _lib
     return _lib.load()
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _flat(layers, params):
-    from pinn_amd import layout
-    offs, total = layout.general_offsets(layers)
-    f = torch.zeros(total, dtype=torch.float32)
-    for (_, shape, off), p in zip(offs, params):
-        f[off:off + p.numel()] = p.detach().reshape(-1)
-    return f.to(_dev())
-
-
-def _unflat(layers, flat):
-    from pinn_amd import layout
-    offs, _ = layout.general_offsets(layers)
-    flat = flat.cpu()
-    return [flat[off:off + int(np.prod(shape))].reshape(shape) for _, shape, off in offs]
-
-
-def _padding(layers, flat):
-    """The entries of the flat buffer that belong to no tensor."""
-    from pinn_amd import layout
-    offs, total = layout.general_offsets(layers)
-    used = torch.zeros(total, dtype=torch.bool)
-    for _, shape, off in offs:
-        used[off:off + int(np.prod(shape))] = True
-    return flat.cpu()[~used]
-
-
-def _widths(layers):
-    return list(layers[1:-1]) + [layers[-2] // 2]
-
-
-def _drop(mode, layers, p=0.2, seed=0, stream=0, row_offset=0, bits=None):
-    from pinn_amd import _lib
-    d = _lib.Dropout()
-    d.mode = mode
-    for l in range(len(layers) - 1):
-        d.p[l] = p
-    d.seed, d.stream, d.row_offset = seed, stream, row_offset
-    d.d_bits = bits.data_ptr() if bits is not None else None
-    d.d_step_counter = None
-    return d
-
-
-def _philox_masks(layers, seed, stream, row0, n, p):
-    return [O.philox_keep_mask(seed, stream, row0, n, l, w, p) for l, w in enumerate(_widths(layers))]
-
-
-def _pack_bits(masks):
-    """list over modules of bool [N, w] -> int32 [1, N, words]; module l starts at word sum ceil(w_j / 32)."""
-    parts = []
-    for m in masks:
-        m = np.asarray(m, dtype=np.uint8)
-        m = np.concatenate([m, np.zeros((m.shape[0], (-m.shape[1]) % 32), np.uint8)], axis=1)
-        parts.append(np.packbits(m, axis=-1, bitorder="little"))
-    return torch.from_numpy(np.ascontiguousarray(np.concatenate(parts, axis=-1)).view(np.int32)[None].copy())
-
-
-def _data(n, seed):
-    from pinn_amd import synth
-    return synth.make_dataset(n, (), seed=seed)[0]
-
-
-def _upstream(n, seed):
-    gen = torch.Generator().manual_seed(seed)
-    return torch.randn(n, generator=gen), torch.randn(n, generator=gen), torch.randn(n, 8, generator=gen)
-
-
-def backward2(lib, layers, fp, x, gu, glv, vx, drop=None, want=("grads", "gx", "ggu", "gglv")):
-    """pinn_gnet_backward2 -> dict of the requested outputs on the host (poisoned workspace and outputs)."""
-    from pinn_amd import _lib
-    n = x.shape[0]
-    net = _lib.GNet(layers)
-    wb = lib.pinn_gnet_backward2_workspace_bytes(ctypes.byref(net), n)
-    assert wb > 0
-    w = torch.full((wb,), 0xFF, dtype=torch.uint8, device=_dev())        # poisoned: reads of unwritten words show as NaN
-    nan = lambda *s: torch.full(s, float("nan"), device=_dev())
-    out = {"grads": nan(fp.numel()) if "grads" in want else None, "gx": nan(n, 8) if "gx" in want else None,
-           "ggu": nan(n) if "ggu" in want else None, "gglv": nan(n) if "gglv" in want else None}
-    _lib.check(lib.pinn_gnet_backward2(ctypes.byref(net), _ptr(fp), _ptr(x), n, ctypes.byref(drop) if drop else None, _ptr(gu), _ptr(glv),
-                                       _ptr(vx), _ptr(out["grads"]), _ptr(out["gx"]), _ptr(out["ggu"]), _ptr(out["gglv"]), _ptr(w),
-                                       w.numel(), _stream()), "pinn_gnet_backward2")
-    torch.cuda.synchronize()
-    return {k: (v.cpu() if v is not None else None) for k, v in out.items()}
-
-
-def oracle2(P, x, gu, glv, vx, p_list=None, masks=None):
-    """float64: (dS/dparams, dS/dx, dS/dg_u, dS/dg_lv) of S = <v, d(g_u . u + g_lv . lv)/dx> by torch's double autograd."""
-    P = [p.detach().double().clone().requires_grad_(True) for p in P]
-    x = x.detach().double().clone().requires_grad_(True)
-    gu = gu.detach().double().reshape(-1, 1).clone().requires_grad_(True)
-    have_lv = glv is not None
-    glv = (glv.detach().double().reshape(-1, 1).clone() if have_lv else torch.zeros_like(gu)).requires_grad_(True)
-    u, lv = O.mlp_forward(P, x, p_list, masks)
-    dx, = torch.autograd.grad([u, lv], x, [gu, glv], create_graph=True)
-    ins = [gu, glv, x] + P
-    g = torch.autograd.grad(dx, ins, vx.detach().double(), allow_unused=True)
-    g = [torch.zeros_like(t) if gi is None else gi for gi, t in zip(g, ins)]
-    return g[3:], g[2], g[0].reshape(-1), g[1].reshape(-1)
 
 
 def _close(got, want, what):
@@ -261,21 +155,6 @@ def test_backward2_zero_rows_zeroes_grads(lib):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # the module surface
-def _model(layers, n=700, seed=11, **kw):
-    import pinn_amd
-    from pinn_amd import synth
-    ds = synth.make_dataset(n, (), seed=0)
-    torch.manual_seed(0)
-    m = pinn_amd.PhysicsInformedNN(ds[0], ds[1], layers, ds[4], ds[5], p=0.2, logvar=True, seed=seed, **kw)
-    m.verbose = False
-    return m, ds
-
-
-def _params(dnn):
-    named = dict(dnn.named_parameters())
-    return [named[n] for n in O.param_names(dnn.n_hidden)]
-
-
 def _oracle_loss(P, x, y, masks, w, layers, p=0.2):
     """float64 on the CPU: the loss of test 3 under torch's double autograd -> (parameter gradients, x gradient)."""
     P = [t.detach().double().clone().requires_grad_(True) for t in P]

@@ -1,5 +1,6 @@
 """GPU parity of the general (any layers list) exact-fp32 kernels, csrc/pinn_general.hip, through the C ABI and the model surface."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -8,125 +9,19 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import pinn_oracle as O
+from gnet_helpers import SHAPES, data, forward, mc, pack_bits, train_grads
+from gnet_helpers import dev as _dev, drop as _drop, flat as _flat, model as _model, philox_masks as _philox_masks
+from gnet_helpers import unflat as _unflat, widths as _widths
 
 RTOL = ATOL = 1e-5
-SHAPES = [[8, 32, 32, 32, 1], [8, 100, 100, 1], [8, 64, 200, 48, 1], [8, 7, 1, 4, 1], [8, 2000, 300, 1], [8, 256, 256, 256, 1]]
+_pack_bits = functools.partial(pack_bits, passes=True)      # a list over passes
+_data = functools.partial(data, with_y=True)                # (x, y)
 
 
 @pytest.fixture(scope="module")
 def lib():
     from pinn_amd import _lib
     return _lib.load()
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _flat(layers, params):
-    from pinn_amd import layout
-    offs, total = layout.general_offsets(layers)
-    f = torch.zeros(total, dtype=torch.float32)
-    for (_, shape, off), p in zip(offs, params):
-        f[off:off + p.numel()] = p.detach().reshape(-1)
-    return f.to(_dev())
-
-
-def _unflat(layers, flat):
-    from pinn_amd import layout
-    offs, _ = layout.general_offsets(layers)
-    flat = flat.cpu()
-    return [flat[off:off + int(np.prod(shape))].reshape(shape) for _, shape, off in offs]
-
-
-def _widths(layers):
-    return list(layers[1:-1]) + [layers[-2] // 2]
-
-
-def _drop(mode, layers, p=0.2, seed=0, stream=0, row_offset=0, bits=None):
-    from pinn_amd import _lib
-    d = _lib.Dropout()
-    d.mode = mode
-    for l in range(len(layers) - 1):
-        d.p[l] = p
-    d.seed, d.stream, d.row_offset = seed, stream, row_offset
-    d.d_bits = bits.data_ptr() if bits is not None else None
-    d.d_step_counter = None
-    return d
-
-
-def _philox_masks(layers, seed, stream, row0, n, p):
-    return [O.philox_keep_mask(seed, stream, row0, n, l, w, p) for l, w in enumerate(_widths(layers))]
-
-
-def _pack_bits(masks_per_pass):
-    """list over passes of list over modules of bool [N, w] -> int32 [T, N, words]; module l starts at word sum ceil(w_j / 32)."""
-    out = []
-    for masks in masks_per_pass:
-        parts = []
-        for m in masks:
-            m = np.asarray(m, dtype=np.uint8)
-            pad = (-m.shape[1]) % 32
-            m = np.concatenate([m, np.zeros((m.shape[0], pad), np.uint8)], axis=1)
-            parts.append(np.packbits(m, axis=-1, bitorder="little"))
-        out.append(np.ascontiguousarray(np.concatenate(parts, axis=-1)).view(np.int32))
-    return torch.from_numpy(np.stack(out, 0).copy())
-
-
-def _work(lib, layers, n, passes=0):
-    from pinn_amd import _lib
-    wb = lib.pinn_gnet_workspace_bytes(ctypes.byref(_lib.GNet(layers)), n, passes)
-    assert wb > 0
-    return torch.full((wb,), 0xFF, dtype=torch.uint8, device=_dev())        # poisoned: reads of unwritten words show as NaN
-
-
-def forward(lib, layers, fp, x, drop=None):
-    from pinn_amd import _lib
-    n = x.shape[0]
-    u, lv = torch.empty(n, device=_dev()), torch.empty(n, device=_dev())
-    w = _work(lib, layers, n)
-    _lib.check(lib.pinn_gnet_forward(ctypes.byref(_lib.GNet(layers)), _ptr(fp), _ptr(x), n, ctypes.byref(drop) if drop else None,
-                                     _ptr(u), _ptr(lv), _ptr(w), w.numel(), _stream()), "pinn_gnet_forward")
-    torch.cuda.synchronize()
-    return u.cpu(), lv.cpu()
-
-
-def mc(lib, layers, fp, x, drop, T):
-    from pinn_amd import _lib
-    n = x.shape[0]
-    out = torch.empty(3, n, device=_dev())
-    w = _work(lib, layers, n, T)
-    _lib.check(lib.pinn_gnet_mc_dropout(ctypes.byref(_lib.GNet(layers)), _ptr(fp), _ptr(x), n, ctypes.byref(drop), T, _ptr(out[0]),
-                                        _ptr(out[1]), _ptr(out[2]), _ptr(w), w.numel(), _stream()), "pinn_gnet_mc_dropout")
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
-def train_grads(lib, layers, fp, x, y, drop=None, n_global=None):
-    from pinn_amd import _lib
-    n = x.shape[0]
-    w = _work(lib, layers, n)
-    g = torch.full((fp.numel(),), float("nan"), device=_dev())
-    loss = torch.zeros(4, dtype=torch.float64, device=_dev())
-    _lib.check(lib.pinn_gnet_train_grads(ctypes.byref(_lib.GNet(layers)), _ptr(fp), _ptr(x), _ptr(y), n, n_global or n,
-                                         ctypes.byref(drop) if drop else None, _ptr(g), _ptr(loss), _ptr(w), w.numel(), _stream()),
-               "pinn_gnet_train_grads")
-    torch.cuda.synchronize()
-    return g.cpu(), loss.cpu()
-
-
-def _data(n, seed):
-    from pinn_amd import synth
-    ds = synth.make_dataset(n, (), seed=seed)
-    return ds[0], ds[1].reshape(-1)
 
 
 def _check_grads(layers, got, want, rtol):
@@ -189,6 +84,34 @@ def test_grads_vs_oracle_autograd(lib, layers, n):
     _check_grads(layers, g, go, rtol=2e-4)
 
 
+def test_grads_several_chunks(lib):
+    """Training gradients and loss sums across chunk edges.  train_layout keeps 78 keep words + 2 * 2016 (d pre ping-pong) + 2 (du, dz)
+    + 2016 + 320 + 160 + 96 (activations, padded to 32) = 6704 floats per row of [8, 2000, 300, 1], so a chunk is
+    (512 MiB / (4 * 6704)) / 64 * 64 = 19 968 rows and 50 000 rows take three: 19 968 + 19 968 + 10 064.  The loss partials of chunk c
+    start at block 1248 c, and finalize_kernel sums 3 * 1248 of them.  Same oracle and bounds as test_grads_vs_oracle_autograd."""
+    from pinn_amd import _lib
+    layers, n = [8, 2000, 300, 1], 50000
+    assert ((512 << 20) // (4 * 6704)) // 64 * 64 == 19968 and 2 * 19968 < n <= 3 * 19968
+    # one chunk's activations cap the workspace: beyond it only the loss partials grow, 4 B per row
+    net = ctypes.byref(_lib.GNet(layers))
+    wb, wb_half = lib.pinn_gnet_workspace_bytes(net, n, 0), lib.pinn_gnet_workspace_bytes(net, n // 2, 0)
+    assert 0 < wb - wb_half < 0.01 * wb_half, (wb, wb_half)
+    P = O.init_params(layers, seed=4)
+    x, y = _data(n, seed=6)
+    seed, stream, row0 = 5, 3, 17          # test_backward_several_chunks' stream: gnet_helpers.philox_masks draws the masks once
+    g, loss = train_grads(lib, layers, _flat(layers, P), x.to(_dev()), y.to(_dev()), _drop(1, layers, 0.2, seed, stream, row0))
+    lo, mse, go, _, _ = O.nll_loss_and_grads(P, x, y.reshape(-1, 1), [0.2] * 3, _philox_masks(layers, seed, stream, row0, n, 0.2))
+    l = loss.numpy()
+    got_lo, got_mse = (l[0] + 0.01 * l[1]) / n, l[2] / n
+    print("loss %.3f of its bound, mse %.3f" % (abs(got_lo - lo.item()) / (2e-5 * abs(lo.item())),
+                                                abs(got_mse - mse.item()) / (2e-5 * abs(mse.item()))))
+    for name, a, w in zip(O.param_names(len(layers) - 2), _unflat(layers, g), go):
+        print("%-24s %.3f of its bound" % (name, float((a - w).abs().max()) / (2e-4 * float(w.abs().max()) + 1e-6 * float(w.abs().max()))))
+    assert abs(got_lo - lo.item()) <= 2e-5 * abs(lo.item())
+    assert abs(got_mse - mse.item()) <= 2e-5 * abs(mse.item())
+    _check_grads(layers, g, go, rtol=2e-4)
+
+
 def test_grads_deterministic_shard_additive_and_windows(lib):
     layers, N = [8, 64, 200, 48, 1], 1536
     P = O.init_params(layers, seed=3)
@@ -244,16 +167,6 @@ def test_mc_T2000_band_vs_bernoulli(lib):
         se = diff.std(ddof=1) / np.sqrt(NREF)
         assert abs(diff.mean() / se) < 3.0, (name, diff.mean() / se)
         assert abs(col[NREF:].mean() / col[:NREF].mean() - 1) < 0.1
-
-
-def _model(layers, n=2000, seed=11, **kw):
-    import pinn_amd
-    from pinn_amd import synth
-    ds = synth.make_dataset(n, (), seed=0)
-    torch.manual_seed(0)
-    m = pinn_amd.PhysicsInformedNN(ds[0], ds[1], layers, ds[4], ds[5], p=0.2, logvar=True, seed=seed, **kw)
-    m.verbose = False
-    return m, ds
 
 
 def _net_params(m):

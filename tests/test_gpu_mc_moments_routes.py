@@ -19,11 +19,11 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import gnet_helpers as G
 import hip_helpers as hh
 import mc_moments as M
 import pinn_oracle as O
 import regimes as R
-import test_gpu_general as G
 
 SEED, S0, P = M.SEED, M.STREAM, M.P_MC
 
@@ -268,8 +268,8 @@ def test_w2_wide_injected_masks_across_the_chunk_edge(lib):
 # general path
 def _general_case(lib, tag, layers, n, T, seed):
     Pm = O.init_params(layers, seed=seed)
-    fp, xd = G._flat(layers, Pm), _rows(n, seed + 1).to(hh.dev())
-    drop = lambda t: G._drop(1, layers, P, SEED, S0 + t, M.ROW0)
+    fp, xd = G.flat(layers, Pm), _rows(n, seed + 1).to(hh.dev())
+    drop = lambda t: G.drop(1, layers, P, SEED, S0 + t, M.ROW0)
     o = G.mc(lib, layers, fp, xd, drop(0), T)
     ref = _passes(lambda d: G.forward(lib, layers, fp, xd, d), T, drop)
     _hold(tag, o, ref)

@@ -19,12 +19,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import gnet_helpers as G
 import hip_helpers as hh
 import pinn_oracle as O
 import regimes as R
-import test_gpu_autograd as A1
-import test_gpu_autograd2 as A2
-import test_gpu_general as G
 
 REGIME_NAMES = list(R.REGIMES)
 # (precision, layers): exact fp32, f32x6 and f32x6g6 on the fused nets; the wide net on the two split-operand precisions
@@ -188,12 +186,12 @@ def _gdrop(c, stream=R.STREAM):
 
 
 def _general(c):
-    return G._flat(c.layers, c.P), c.x.to(hh.dev()).contiguous(), c.y.reshape(-1).to(hh.dev()).contiguous()
+    return G.flat(c.layers, c.P), c.x.to(hh.dev()).contiguous(), c.y.reshape(-1).to(hh.dev()).contiguous()
 
 
 @functools.lru_cache(maxsize=None)
 def _upstream(n):
-    return A2._upstream(n, n)          # g_u, g_lv [n], v [n, 8]
+    return G.upstream(n, n, with_v=True)          # g_u, g_lv [n], v [n, 8]
 
 
 @functools.lru_cache(maxsize=None)
@@ -217,7 +215,7 @@ def _check_general_train(lib, c, tag):
     g, loss = G.train_grads(lib, c.layers, fp, xd, yd, _gdrop(c))
     lo, mse, go = c.nll64
     _loss(tag, loss, c.n, lo, mse)
-    for name, a, w in zip(O.param_names(c.k), G._unflat(c.layers, g), go):
+    for name, a, w in zip(O.param_names(c.k), G.unflat(c.layers, g), go):
         _tensor(tag + name, a, w)
 
 
@@ -226,10 +224,10 @@ def _check_general_backward(lib, c, tag):
     gu, glv, _ = _upstream(c.n)
     gud, glvd = gu.to(hh.dev()), glv.to(hh.dev())
     for with_lv in (True, False):
-        g, dx = A1.backward(lib, c.layers, fp, xd, gud, glvd if with_lv else None, _gdrop(c))
+        g, dx = G.backward(lib, c.layers, fp, xd, gud, glvd if with_lv else None, _gdrop(c))
         wp, wx = _vjp_ref(c, with_lv)
         t = tag + ("" if with_lv else "no g_lv ")
-        for name, a, w in zip(O.param_names(c.k), G._unflat(c.layers, g), wp):
+        for name, a, w in zip(O.param_names(c.k), G.unflat(c.layers, g), wp):
             if not with_lv and name.startswith("var_layers"):
                 assert float(w.abs().max()) == 0.0 and float(a.abs().max()) == 0.0, (t, name)
             else:
@@ -240,9 +238,18 @@ def _check_general_backward(lib, c, tag):
 def _check_general_backward2(lib, c, tag):
     fp, xd, _ = _general(c)
     gu, glv, vx = _upstream(c.n)
-    got = A2.backward2(lib, c.layers, fp, xd, gu.to(hh.dev()), glv.to(hh.dev()), vx.to(hh.dev()), _gdrop(c))
+    got = G.backward2(lib, c.layers, fp, xd, gu.to(hh.dev()), glv.to(hh.dev()), vx.to(hh.dev()), _gdrop(c))
     assert all(bool(torch.isfinite(v).all()) for v in got.values())
-    A2._check(c.layers, got, A2.oracle2(c.P, c.x, gu, glv, vx, c.pl, c.masks), tag)
+    wp, wx, wgu, wglv = G.oracle2(c.P, c.x, gu, glv, vx, c.pl, c.masks)
+    for name, a, w in zip(O.param_names(c.k), G.unflat(c.layers, got["grads"]), wp):
+        if name == "predict.bias":
+            assert float(w.abs().max()) == 0.0 and float(a.abs().max()) == 0.0, (c.layers, tag, name)      # exactly zero
+        else:
+            _tensor("%s %s %s" % (c.layers, tag, name), a, w)
+    assert float(G.padding(c.layers, got["grads"]).abs().sum()) == 0.0
+    _tensor("%s %s dS/dx" % (c.layers, tag), got["gx"], wx)
+    _tensor("%s %s ud" % (c.layers, tag), got["ggu"], wgu)
+    _tensor("%s %s lvd" % (c.layers, tag), got["gglv"], wglv)
 
 
 GENERAL_IDS = ["x".join(map(str, l)) for l in R.GENERAL_NETS]
