@@ -2,9 +2,11 @@
 (`epi,res` / `x0,x3,x4,x5` / `res` / `y_true`) each fitted with StandardScaler + logistic regression on a tenth of the rows
 and judged by the ROC AUC of 1 - P(normal) on the rest; for the first group also the unsupervised AUC of an isolation forest
 fitted on the normal training rows alone (no fault labels); then the recording replayed in chunks through the online detector
-and the anomaly monitor of the first group.  Nothing leaves the GPU but the printed numbers.
+and the anomaly monitor of the first group.  Nothing leaves the GPU but the printed numbers.  With --inference, after the
+AUCs: each AUC's DeLong interval, the paired DeLong tests between the groups (Holm-adjusted) and the bootstrap interval of
+the difference between the first two groups, all on the same test rows (pinn_amd.rocstat).
 
-    python examples/fault_detection.py [--normal-rows 20000] [--fault-rows 1500] [--five-class]
+    python examples/fault_detection.py [--normal-rows 20000] [--fault-rows 1500] [--five-class] [--inference [--n-boot 2000]]
 """
 import argparse
 import os
@@ -15,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from pinn_amd import anomaly, detection  # noqa: E402
+from pinn_amd import anomaly, detection, rocstat  # noqa: E402
 
 
 def synthetic_results(n_normal, n_fault, seed=0):
@@ -40,11 +42,32 @@ def synthetic_results(n_normal, n_fault, seed=0):
     return a
 
 
+def print_inference(groups, n_boot):
+    """What the list of AUCs leaves open: how sure each is, and which differences exceed the split's noise."""
+    table = rocstat.compare_feature_groups(groups, level=0.95, n_boot=n_boot)
+    names = list(table)
+    print("\n%-14s %8s  %-19s %-19s" % ("features", "AUC", "95% DeLong", "95%% bootstrap (%d)" % n_boot))
+    for name in names:
+        row = table[name]
+        print("%-14s %8.4f  [%.4f, %.4f]    [%.4f, %.4f]" % ((name, row["auc"]) + row["ci"] + row["boot_ci"]))
+    print("paired DeLong tests, p-values after Holm's adjustment over the %d pairs (row minus column):" % (len(names) * (len(names) - 1) // 2))
+    print("%-14s " % "" + " ".join("%17s" % n for n in names))
+    for name in names:
+        print("%-14s " % name + " ".join("%17s" % ("-" if o == name else "%+.4f p=%.1e" % (table[name]["diff"][o], table[name]["p_holm"][o]))
+                                         for o in names))
+    a, b = names[0], names[1]
+    lo, hi = table[a]["boot_diff_ci"][b]
+    print("AUC(%s) - AUC(%s) = %+.4f, 95%% bootstrap interval [%+.4f, %+.4f], DeLong z = %.2f\n"
+          % (a, b, table[a]["diff"][b], lo, hi, table[a]["z"][b]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--normal-rows", type=int, default=20000)
     ap.add_argument("--fault-rows", type=int, default=1500)
     ap.add_argument("--five-class", action="store_true", help="normal and the four fault classes instead of normal / fault")
+    ap.add_argument("--inference", action="store_true", help="intervals of the AUCs and paired tests between the feature groups")
+    ap.add_argument("--n-boot", type=int, default=2000, help="resamples of the paired bootstrap of --inference")
     args = ap.parse_args()
 
     results = torch.from_numpy(synthetic_results(args.normal_rows, args.fault_rows)).cuda()
@@ -55,6 +78,8 @@ def main():
         lr = g["clf"].named_steps["logreg"]
         print("%-14s %8d %8d %6d %9.4f %9.4f %8.4f" % (g["spec"], g["n_train"], g["n_test"], lr.n_iter_, g["accuracy"], g["metrics"]["macro_f1"],
                                                       g["auc"]))
+    if args.inference:
+        print_inference(groups, args.n_boot)
     forest = groups[0]["iforest"]
     print("unsupervised, %s: isolation forest of %d trees on %d rows each, AUC %.4f (supervised %.4f)"
           % (groups[0]["spec"], len(forest.trees_), forest.max_samples_, groups[0]["auc_unsup"], groups[0]["auc"]))

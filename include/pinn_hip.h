@@ -1129,6 +1129,53 @@ int pinn_ksvm_decision(const double* d_arr, long long ld, long long n_arr_rows, 
                        const double* d_coef, const long long* d_sv_class, long long n_sv, const double* d_rho, double gamma,
                        double* d_decision, long long* d_votes, long long* d_pred, void* stream);
 
+/* ---- ROC inference: DeLong's covariance of K AUCs and the stratified paired bootstrap ----------------------------------
+ * Everything is an integer.  With m positives, n negatives and psi = 1, 1/2, 0 for a positive score above, equal to, below
+ * a negative one, a positive row i carries a[i] = 2 #{neg < s_i} + #{neg == s_i} (= 2 n V10) and a negative row j carries
+ * b[j] = 2 #{pos > s_j} + #{pos == s_j} (= 2 m V01); sum a = sum b = U2, the integer of the ROC entry point above.  No
+ * float arithmetic, integer atomics only, no workgroup waits on another: the same call gives the same bytes.
+ * Limits: 1 <= n_scores <= PINN_AUC_MAX_SCORES, 1 <= n < 2^31.  Outside: PINN_E_ARG, sizes 0. */
+#define PINN_AUC_MAX_SCORES 8
+#define PINN_AUC_TILE 256              /* elements of one scan tile */
+#define PINN_AUC_BOOT_LDS_GROUPS 12288 /* a histogram of up to this many groups is held in LDS (48 KiB of a CU's 160 KiB) */
+#define PINN_AUC_DRAW_BOOT 2           /* Philox draw kind of the bootstrap (0 and 1 are the isolation forest's) */
+#define PINN_AUC_POS 0
+#define PINN_AUC_NEG 1
+#define PINN_AUC_GROUPS 2
+#define PINN_AUC_U2 3
+#define PINN_AUC_U2B 4
+#define PINN_AUC_COUNTS 8
+
+/* Five launches for all n_scores classifiers.  Per classifier k: d_score_sorted [k][n] ascending, d_pos_sorted [k][n]
+ * (non-zero = positive) and d_row_sorted [k][n] (the row number of every element) in that order.  Equal scores form a group
+ * (+0.0 == -0.0); groups are numbered from 0 in ascending order.  Out: d_comp [k][n] in row order, a[row] for a positive
+ * row and b[row] for a negative one; d_group [k][n] the row's group number; d_counts [k][PINN_AUC_COUNTS]: positives,
+ * negatives, groups, U2 = sum a, and sum b.  A row number outside [0, n) writes nothing. */
+size_t pinn_auc_components_workspace_bytes(long long n, int n_scores);
+int pinn_auc_components(const double* d_score_sorted, const long long* d_pos_sorted, const long long* d_row_sorted,
+                        long long n, int n_scores, long long* d_counts, long long* d_comp, int* d_group, void* d_ws,
+                        size_t ws_bytes, void* stream);
+
+/* Two launches.  d_comp [n_scores][ld], rows <= ld entries of each read as unsigned 64-bit integers.  Out: d_sums
+ * [n_scores (n_scores + 1) / 2][2], the pair (k, l), k <= l, at l (l + 1) / 2 + k: the low and the high 64-bit word of
+ * sum_i comp[k][i] comp[l][i], exact below 2^128.  Workgroup partials are added in index order by one workgroup. */
+size_t pinn_auc_cross_sums_workspace_bytes(long long rows, int n_scores);
+int pinn_auc_cross_sums(const long long* d_comp, long long ld, long long rows, int n_scores, unsigned long long* d_sums,
+                        void* d_ws, size_t ws_bytes, void* stream);
+
+/* One launch, a workgroup per resample first .. first + n_boot - 1 (below 2^32).  d_group_pos [n_scores][m] and d_group_neg
+ * [n_scores][n]: group numbers of the positive and of the negative rows; groups [n_scores] (a HOST array): the group counts.
+ * Resample r draws n negatives, then m positives, with replacement: draw t of stratum s (0 negatives, 1 positives) takes
+ * the 64 bits (word 2 (t & 1), word 2 (t & 1) + 1 as low, high) of Philox4x32-10 at the counter (t >> 1, r,
+ * PINN_AUC_DRAW_BOOT, s) under the key seed, and its index is the high 64 bits of bits x stratum size.  Per classifier the
+ * negatives are counted by group (integer atomics, in LDS up to PINN_AUC_BOOT_LDS_GROUPS groups, else in the workgroup's
+ * slice of the workspace), the counts are scanned, and d_u2 [n_boot][n_scores] = sum over the positive draws of
+ * 2 below[g] + count[g].  A group number outside [0, groups[k]) adds nothing. */
+size_t pinn_auc_bootstrap_workspace_bytes(long long n_boot, int n_scores, const long long* groups);
+int pinn_auc_bootstrap(const int* d_group_pos, const int* d_group_neg, long long m, long long n, int n_scores,
+                       const long long* groups, unsigned long long seed, long long first, long long n_boot,
+                       long long* d_u2, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,9 @@ from `compare_methods` through `device_extras` (comparison); and the t-SNE embed
 `fit_spectral_posterior`, with `DeviceSpectralClustering`, `knn_graph`, `knn_affinity` and `spectral_embedding` (spectral),
 reached from `compare_methods` through `spectral_extras` (comparison); and the RBF-kernel SVC that script 05 names for Sup_SVM
 (it runs the linear one), one-vs-one and solved by SMO in float64: `run_supervised_svm_kernel`, with `DeviceKernelSVC`,
-`build_kernel_svm_classifier` and `KernelSVMDiagnoser` (ksvm), reached from `compare_methods` through `kernel_extras` (comparison).
+`build_kernel_svm_classifier` and `KernelSVMDiagnoser` (ksvm), reached from `compare_methods` through `kernel_extras` (comparison);
+and what script 02's four AUCs leave open, their intervals and paired tests: `auc_components`, `delong_covariance`, `auc_ci`,
+`delong_test`, `compare_aucs`, `bootstrap_auc`, `compare_feature_groups` (rocstat).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -59,6 +61,8 @@ _LAZY = {
     "tsne_of_test_samples": "embedding", "scatter_by_features": "embedding", "TSNE_PARAMS": "embedding",
     "DeviceSpectralClustering": "spectral", "fit_spectral_posterior": "spectral", "knn_graph": "spectral", "knn_affinity": "spectral",
     "spectral_embedding": "spectral", "spectral_extras": "comparison",
+    "auc_components": "rocstat", "delong_covariance": "rocstat", "auc_ci": "rocstat", "delong_test": "rocstat",
+    "compare_aucs": "rocstat", "bootstrap_auc": "rocstat", "compare_feature_groups": "rocstat",
 }
 
 

@@ -46,6 +46,8 @@ SOURCES = [
     ("pinn_spectral.hip", ["-ffp-contract=off"]),
     # RBF-kernel SVC by SMO: float64, every operation rounded on its own; the host backend states the same arithmetic
     ("pinn_ksvm.hip", ["-ffp-contract=off"]),
+    # ROC inference (DeLong components, 128-bit cross sums, bootstrap): integers only, so no float flag matters
+    ("pinn_rocstat.hip", []),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

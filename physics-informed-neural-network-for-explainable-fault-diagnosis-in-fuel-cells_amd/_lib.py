@@ -118,6 +118,10 @@ SP_MAX_FEAT, SP_MAX_NEIGHBORS, SP_MAX_COMPONENTS, SP_MAX_CLUSTERS, SP_MAX_DIM, S
 SP_NAN, SP_BAD_ROW = 1, 2
 SP_ST_N, SP_ST_M, SP_ST_K, SP_ST_MATVEC, SP_ST_DEGREE, SP_ST_MAXRES, SP_ST_FILT_C, SP_ST_FILT_E, SP_ST_TOL = range(3, 12)
 
+# pinn_rocstat.hip: limits, the scan tile, the LDS / workspace switch of the bootstrap histogram and the 8-byte words of the counts
+AUC_MAX_SCORES, AUC_TILE, AUC_BOOT_LDS_GROUPS, AUC_DRAW_BOOT, AUC_COUNTS = 8, 256, 12288, 2, 8
+AUC_POS, AUC_NEG, AUC_GROUPS, AUC_U2, AUC_U2B = range(5)
+
 
 class PinnError(RuntimeError):
     pass
@@ -256,6 +260,13 @@ _SIGS = {
     "pinn_sp_lloyd_state_bytes": (c_size_t, [c_ll, c_int, c_int]),
     "pinn_sp_lloyd_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
     "pinn_sp_lloyd": (c_int, [c_void_p, c_ll, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_auc_components_workspace_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_auc_components": (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_auc_cross_sums_workspace_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_auc_cross_sums": (c_int, [c_void_p, c_ll, c_ll, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_auc_bootstrap_workspace_bytes": (c_size_t, [c_ll, c_int, ctypes.POINTER(c_ll)]),
+    "pinn_auc_bootstrap": (c_int, [c_void_p, c_void_p, c_ll, c_ll, c_int, ctypes.POINTER(c_ll), ctypes.c_ulonglong, c_ll, c_ll, c_void_p,
+                                   c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None
