@@ -113,7 +113,8 @@ int pinn_lambda_step(int stage, const double* d_sums, long long n_global, float 
 
 /* ---- a whole physics-parameter stage in ONE launch (01:999-1055, 1098-1151, 1191-1274, 1344-1391).
  * n_iters iterations, epochs first_epoch .. first_epoch + n_iters - 1, of: residual pass (exactly one of the PINN_RES_*
- * flags) over all n_rows rows -> gradients of the stage's scalars -> Adam(lr = lr0 * gamma^(epoch / lr_step), the
+ * flags, and the one of `stage`: PINN_RES_V with PINN_STAGE_LAMBDA_PM / _F, PINN_RES_T / _H / _O with PINN_STAGE_THERMAL /
+ * _HYDROGEN / _OXYGEN; any other pair is PINN_E_ARG) over all n_rows rows -> gradients of the stage's scalars -> Adam(lr = lr0 * gamma^(epoch / lr_step), the
  * StepLR schedule) -> clamp; the arithmetic of pinn_residuals + pinn_lambda_step, run by a single persistent
  * workgroup, so an iteration costs no launch.  For one process holding ALL rows (n_global == n_rows) and
  * n_rows <= PINN_STAGE_RUN_MAX_ROWS; larger or sharded series iterate the two calls above.

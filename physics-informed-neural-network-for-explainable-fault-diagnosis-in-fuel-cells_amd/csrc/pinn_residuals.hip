@@ -1129,6 +1129,10 @@ extern "C" int pinn_lambda_stage_run(int stage, unsigned flags, const float* d_x
       n_iters < 0 || first_epoch < 0 || lr_step < 1)
     return PINN_E_ARG;
   if (flags != PINN_RES_V && flags != PINN_RES_T && flags != PINN_RES_H && flags != PINN_RES_O) return PINN_E_ARG;
+  // the stage names the parameters and the loss, the flag the row model: a pair that contradicts itself is refused, not reinterpreted
+  const unsigned stage_flag = stage == PINN_STAGE_THERMAL ? PINN_RES_T : (stage == PINN_STAGE_HYDROGEN ? PINN_RES_H
+                              : (stage == PINN_STAGE_OXYGEN ? PINN_RES_O : PINN_RES_V));
+  if (flags != stage_flag) return PINN_E_ARG;
   if ((flags & PINN_RES_V) && (!d_u || !d_y)) return PINN_E_ARG;
   if (d_log && log_every > 0 && first_epoch % log_every) return PINN_E_ARG;
   if (!d_work) return PINN_E_ARG;

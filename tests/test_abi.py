@@ -114,6 +114,21 @@ def test_null_workspace_and_buffer_pointers_are_argument_errors(lib):
     assert lib.pinn_results_assemble(one, one, ctypes.byref(aff), 0.0, 1.0, 200, None, 0, one, one, one, one, 10, None, 10, None, None) == E_ARG
 
 
+def test_stage_run_refuses_a_stage_that_contradicts_its_flag(lib):
+    """pinn_lambda_stage_run, all 5 x 4 pairs, on the host: with n_iters = 0 a valid call returns PINN_OK before any launch, so the
+    addresses are never dereferenced.  The voltage stages go with PINN_RES_V, every other stage with its own flag."""
+    from pinn_amd import _lib
+    aff = _lib.Affine()
+    one = ctypes.c_void_p(0x1000)
+    own = {_lib.STAGE_LAMBDA_PM: _lib.RES_V, _lib.STAGE_LAMBDA_F: _lib.RES_V, _lib.STAGE_THERMAL: _lib.RES_T, _lib.STAGE_HYDROGEN: _lib.RES_H,
+           _lib.STAGE_OXYGEN: _lib.RES_O}
+    for stage, flag in own.items():
+        for flags in (_lib.RES_V, _lib.RES_T, _lib.RES_H, _lib.RES_O):
+            rc = lib.pinn_lambda_stage_run(stage, flags, one, one, one, ctypes.byref(aff), 10, 1.0, 0.8, 1000, 0, 0, one, one, one, None, 1000, None,
+                                           one, 1 << 20, None)
+            assert rc == (0 if flags == flag else -1), (stage, flags, rc)
+
+
 def test_dropout_struct_is_validated_alike_at_every_entry_point(lib):
     """One pinn_dropout_t, one rule: every entry point that takes the struct rejects the same bad ones with PINN_E_ARG (-1),
     on the host.  Only failing calls, with addresses that are never dereferenced."""
