@@ -7,230 +7,83 @@
 // d loss / d lambda) with wave64 shuffles -> LDS -> one partial per workgroup,
 // finished by a fixed-order second kernel (bitwise reproducible, no float atomics).
 //
-// Compiled with -ffp-contract=off: every float op below is rounded exactly like the
+// This file holds the kernels and the entry points.  The models themselves (the de-normalised row, each model's
+// parameter-independent and parameter-dependent part, its accumulation, the Euler step of net_f_T) and the two reductions
+// (block_sums, sums_finalize) are stated once in pinn_physics.h; the one-pass kernel, the cached stage passes, the persistent
+// stage kernel and both backwards are assembled from those pieces, so they cannot disagree on a formula.
+//
+// Compiled with -ffp-contract=off: every float op here and in pinn_physics.h is rounded exactly like the
 // reference's separate torch ops, so only the transcendental calls can differ (<= 2 ulp).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <type_traits>
 #include "../../include/pinn_hip.h"
+#include "pinn_physics.h"
+#include "pinn_rows.h"
 
 namespace {
 
+using pinn::clear_error;
+using pinn::launch_status;
+
 constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 1024;   // 256 CUs x 4 workgroups; grid-stride beyond
 
-struct AffineDev {
-  double x_min[8];
-  double x_scale[8];
-  double y_min, y_scale;
-  float vn_scale, vn_min;
-};
-
-__device__ __forceinline__ float denorm(float v, double mn, double sc) {
-  // numpy in-place `X -= min_; X /= scale_` on a float32 array with float64 operands
-  float t = (float)((double)v - mn);
-  return (float)((double)t / sc);
-}
-
-// torch.clamp propagates NaN (a NaN parameter or row stays visible, 01:586-610 / 01:1040-1047); fminf / fmaxf return the
-// operand that is not a NaN and would swallow it ("surface NaN")
-__device__ __forceinline__ float clamp_min_t(float x, float lo) { return x != x ? x : fmaxf(x, lo); }
-__device__ __forceinline__ float clamp_t(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// the twelve live physics parameters and the constant P_H2O of 01:745-753
-struct LamDev {
-  float l1, l2, l3, lT1, lT3, lT5, lH1, lH2, lH3, lO1, lO2, lO3, P_H2O;
-};
-__device__ __forceinline__ LamDev load_lambdas(const float* __restrict__ lambdas) {
-  LamDev L;
-  L.l1 = lambdas[PINN_L1]; L.l2 = lambdas[PINN_L2]; L.l3 = lambdas[PINN_L3];
-  L.lT1 = lambdas[PINN_LT1]; L.lT3 = lambdas[PINN_LT3]; L.lT5 = lambdas[PINN_LT5];
-  L.lH1 = lambdas[PINN_LH1]; L.lH2 = lambdas[PINN_LH2]; L.lH3 = lambdas[PINN_LH3];
-  L.lO1 = lambdas[PINN_LO1]; L.lO2 = lambdas[PINN_LO2]; L.lO3 = lambdas[PINN_LO3];
-  // 01:745-753  P_H2O from Tc = 55 (all float32 tensor ops in the reference)
-  const float Tc = 55.0f;
-  const float xw = ((-2.1794f + 0.02953f * Tc) - 9.1837e-5f * (Tc * Tc)) + 1.4454e-7f * ((Tc * Tc) * Tc);
-  L.P_H2O = powf(10.0f, xw);
-  return L;
-}
-
-// every term one row contributes (shared by the one-pass kernel and the persistent stage kernel)
+// every term one row contributes: load -> parameter-independent part -> parameter-dependent part with its sums -> optional columns
 template <bool kCols>
 __device__ __forceinline__ void row_terms(long long row, const float* __restrict__ x, const float* __restrict__ u, const float* __restrict__ y,
                                           const AffineDev& aff, const LamDev& L, unsigned flags, float* __restrict__ cols, long long ld,
                                           float (&acc)[PINN_NSUMS]) {
-  const float l1 = L.l1, l2 = L.l2, l3 = L.l3, lT1 = L.lT1, lT3 = L.lT3, lT5 = L.lT5, lH1 = L.lH1, lH2 = L.lH2, lH3 = L.lH3;
-  const float lO1 = L.lO1, lO2 = L.lO2, lO3 = L.lO3, P_H2O = L.P_H2O;
+  const RowPhys r = load_row(x, row, aff, flags);
+  const float yv = (y != nullptr) ? y[row] : 0.0f;
+  const Current cur = current_of(r.r0);
 
-    const float4 xa = reinterpret_cast<const float4*>(x)[row * 2];
-    const float4 xb = reinterpret_cast<const float4*>(x)[row * 2 + 1];
-    // the float64 divide of the sklearn-exact de-normalisation is the most expensive op of the pass:
-    // only the columns the requested residuals read are de-normalised (flags is wave-uniform)
-    const bool fV = flags & PINN_RES_V, fT = flags & PINN_RES_T, fH = flags & PINN_RES_H, fO = flags & PINN_RES_O;
-    const float r0 = denorm(xa.x, aff.x_min[0], aff.x_scale[0]);                    // I [A]
-    const float r1 = fT ? denorm(xa.y, aff.x_min[1], aff.x_scale[1]) : 0.f;         // coolant flow
-    const float r2 = fT ? denorm(xa.z, aff.x_min[2], aff.x_scale[2]) : 0.f;         // T_in
-    const float r3 = fV ? denorm(xa.w, aff.x_min[3], aff.x_scale[3]) : 0.f;         // P_H2
-    const float r4 = fV ? denorm(xb.x, aff.x_min[4], aff.x_scale[4]) : 0.f;         // P_air
-    const float r5 = (fV || fT) ? denorm(xb.y, aff.x_min[5], aff.x_scale[5]) : 0.f; // T_out
-    const float r6 = fH ? denorm(xb.z, aff.x_min[6], aff.x_scale[6]) : 0.f;         // H2 flow
-    const float r7 = fO ? denorm(xb.w, aff.x_min[7], aff.x_scale[7]) : 0.f;         // air flow
-    const float yv = (y != nullptr) ? y[row] : 0.0f;
-
-    const float i5 = r0 / 270.0f + 1e-5f;        // 01:730, 639, 553
-    const float It = i5 * 270.0f;                // 01:654, 557
-
-    if (flags & PINN_RES_V) {
-      const float un = u[row];
-      const float Tk = r5 + 273.15f;
-      const float P_H2 = r3 / 101.0f + 1.0f;
-      const float P_air = r4 / 101.0f + 1.0f;
-      const float Tk_p = powf(Tk, 1.334f);
-      const float pp_H2 = 0.5f * (P_H2 / expf(1.653f * i5 / Tk_p) - P_H2O);
-      const float pp_O2 = P_air / expf(4.192f * i5 / Tk_p) - P_H2O;
-      const float RT = 8.314f * Tk;
-      const float b = RT / 96485.0f;                         // R*Tk / (2*Alpha*F), 2*Alpha = 1
-      const float V_act = (-b) * logf(i5 / l2);
-      const float V_ohm = -(i5 * l1);
-      const float V_conc = (0.5f * b) * logf(1.0f - i5 / l3);
-      const float E = 220170.0f / 192970.0f - (RT * logf(P_H2O / (pp_H2 * sqrtf(pp_O2)))) / 192970.0f;
-      const float V_est = ((E + V_act) + V_ohm) + V_conc;
-      const float V_out = denorm(un, aff.y_min, aff.y_scale) / 5.0f;   // u detached, 01:734-737
-      const float f = V_est - V_out;
-      const float V_est5 = V_est * 5.0f;
-      // analytic df_V/dlambda
-      const float d1 = -i5;
-      const float d2 = b / l2;
-      const float d3 = 0.5f * b * i5 / (l3 * (l3 - i5));
-      acc[PINN_S_FV2] += f * f;
-      acc[PINN_S_FV_D1] += f * d1;
-      acc[PINN_S_FV_D2] += f * d2;
-      acc[PINN_S_FV_D3] += f * d3;
-      if (y != nullptr) {
-        const float Vn = V_est5 * aff.vn_scale + aff.vn_min;   // 01:1025
-        const float dy = yv - Vn;
-        acc[PINN_S_YV2] += dy * dy;
-        acc[PINN_S_YV_D1] += dy * d1;
-        acc[PINN_S_YV_D2] += dy * d2;
-        acc[PINN_S_YV_D3] += dy * d3;
-        const float du = yv - un;
-        acc[PINN_S_YU2] += du * du;
-      }
-      if (kCols) {
-        cols[PINN_C_FV * ld + row] = f;
-        cols[PINN_C_VACT * ld + row] = V_act;
-        cols[PINN_C_VOHM * ld + row] = V_ohm;
-        cols[PINN_C_VCONC * ld + row] = V_conc;
-        cols[PINN_C_ENERNST * ld + row] = E;
-        cols[PINN_C_VEST5 * ld + row] = V_est5;
-        cols[PINN_C_I * ld + row] = i5;
-        cols[PINN_C_VOUT5 * ld + row] = V_out * 5.0f;
-      }
-    }
-
-    if (flags & PINN_RES_T) {
-      const float i6 = r0 / 270.0f + 1e-6f;     // 01:884
-      const float mc = r1 + 1e-6f;
-      const float It6 = i6 * 270.0f;
-      const float T_pred = ((lT1 * It6 + lT3 * mc) + 0.5f * r2) + lT5;   // 01:905
-      const float f = r5 - T_pred;
-      acc[PINN_S_FT2] += f * f;
-      acc[PINN_S_FT_D1] += f * (-It6);
-      acc[PINN_S_FT_D3] += f * (-mc);
-      acc[PINN_S_FT_D5] += -f;
-      acc[PINN_S_FT_ABS] += fabsf(f);
-      if (kCols) {
-        cols[PINN_C_FT * ld + row] = f;
-        cols[PINN_C_TPRED * ld + row] = T_pred;
-        cols[PINN_C_TOUT * ld + row] = r5;
-      }
-    }
-
-    if (flags & PINN_RES_H) {
-      float Q = ((It / 192970.0f) * 5.0f) * 22.4f;   // 01:660-667
-      Q = Q * 60.0f;
-      Q = clamp_min_t(Q, 1e-8f);
-      const bool lin = It <= lH3;                    // 01:697-701
-      const float tgt = lin ? (lH1 + lH2 * (It / 100.0f)) : (lH1 + lH2 * (lH3 / 100.0f));
-      const float act = (r6 + 1e-6f) / Q;
-      const float f = act - tgt;
-      acc[PINN_S_FH2] += f * f;
-      acc[PINN_S_FH_D1] += -f;
-      acc[PINN_S_FH_D2] += f * (-(lin ? It / 100.0f : lH3 / 100.0f));
-      acc[PINN_S_FH_D3] += f * (-(lin ? 0.0f : lH2 / 100.0f));
-      acc[PINN_S_ACTH] += act;
-      acc[PINN_S_TGTH] += tgt;
-      if (kCols) {
-        cols[PINN_C_FH * ld + row] = f;
-        cols[PINN_C_ACTH * ld + row] = act;
-        cols[PINN_C_TGTH * ld + row] = tgt;
-        cols[PINN_C_ITOT * ld + row] = It;
-      }
-    }
-
-    if (flags & PINN_RES_O) {
-      float Q = ((It * 5.0f) / 385940.0f) * 22.4f;   // 01:564-566
-      Q = Q * 60.0f;
-      Q = clamp_min_t(Q, 1e-8f);
-      const float thr = fabsf(lO3);
-      const bool lin = It <= thr;                    // 01:586-590
-      const float raw = lin ? (lO1 + lO2 * (It / 100.0f)) : (lO1 + lO2 * (thr / 100.0f));
-      const float tgt = clamp_t(raw, 1.05f, 15.0f);
-      const float c = (raw >= 1.05f && raw <= 15.0f) ? 1.0f : 0.0f;   // torch.clamp backward is inclusive
-      const float o2 = (r7 + 1e-6f) * 0.21f;
-      const float act = o2 / Q;
-      const float f = (act - tgt) + clamp_min_t(1.0f - act, 0.0f) * 10.0f;   // 01:606-610
-      const float sgn = (lO3 > 0.0f) ? 1.0f : ((lO3 < 0.0f) ? -1.0f : 0.0f);
-      acc[PINN_S_FO2] += f * f;
-      acc[PINN_S_FO_D1] += f * (-c);
-      acc[PINN_S_FO_D2] += f * (-c * (lin ? It / 100.0f : thr / 100.0f));
-      acc[PINN_S_FO_D3] += f * (-c * (lin ? 0.0f : lO2 * sgn / 100.0f));
-      acc[PINN_S_ACTO] += act;
-      acc[PINN_S_TGTO] += tgt;
-      if (kCols) {
-        cols[PINN_C_FO * ld + row] = f;
-        cols[PINN_C_ACTO * ld + row] = act;
-        cols[PINN_C_TGTO * ld + row] = tgt;
-        cols[PINN_C_QO2 * ld + row] = Q;
-        cols[PINN_C_O2FLOW * ld + row] = o2;
-      }
+  if (flags & PINN_RES_V) {
+    const float un = u[row];
+    const VoltPre p = volt_pre(r, cur.i5, un, aff, L.P_H2O);
+    const VoltTerms t = volt_terms(p, L, y != nullptr, yv, un, aff, acc);
+    if (kCols) {
+      cols[PINN_C_FV * ld + row] = t.f;
+      cols[PINN_C_VACT * ld + row] = t.V_act;
+      cols[PINN_C_VOHM * ld + row] = t.V_ohm;
+      cols[PINN_C_VCONC * ld + row] = t.V_conc;
+      cols[PINN_C_ENERNST * ld + row] = p.E;
+      cols[PINN_C_VEST5 * ld + row] = t.V_est5;
+      cols[PINN_C_I * ld + row] = p.i5;
+      cols[PINN_C_VOUT5 * ld + row] = p.V_out * 5.0f;
     }
   }
 
-// The sums a pass can touch: one stage model's are a contiguous range of the enum, any other flag combination gets all of them.
-// Stated once for everything that reduces sums (the two row-pass kernels, the finalize, the persistent stage kernel): what lies
-// outside the range is exactly 0 and costs no shuffle, no LDS round and no load.
-struct SumRange { int lo, hi; };
-constexpr SumRange live_sums(unsigned flags) {
-  return flags == PINN_RES_V ? SumRange{PINN_S_FV2, PINN_S_YU2 + 1}
-       : flags == PINN_RES_T ? SumRange{PINN_S_FT2, PINN_S_FT_ABS + 1}
-       : flags == PINN_RES_H ? SumRange{PINN_S_FH2, PINN_S_TGTH + 1}
-       : flags == PINN_RES_O ? SumRange{PINN_S_FO2, PINN_S_TGTO + 1}
-                             : SumRange{0, PINN_NSUMS};
-}
-
-// a workgroup's sums of the range kLo..kHi-1: wave64 shuffles -> LDS -> partials[block][PINN_NSUMS] (entries outside the range are
-// not written: residuals_finalize is given the same range and does not read them)
-template <int kLo, int kHi, int kBlock>
-__device__ __forceinline__ void block_partials(const float (&acc)[PINN_NSUMS], double* __restrict__ partials) {
-  __shared__ double red[kBlock / 64][kHi - kLo];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = kLo; s < kHi; ++s) {
-    const double w = wave_sum((double)acc[s]);
-    if (lane == 0) red[wave][s - kLo] = w;
+  if (flags & PINN_RES_T) {
+    const ThermPre p = therm_pre(r);
+    const ThermTerms t = therm_terms(p, L, acc);
+    if (kCols) {
+      cols[PINN_C_FT * ld + row] = t.f;
+      cols[PINN_C_TPRED * ld + row] = t.T_pred;
+      cols[PINN_C_TOUT * ld + row] = p.T_out;
+    }
   }
-  __syncthreads();
-  if (threadIdx.x < kHi - kLo) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) t += red[w][threadIdx.x];
-    partials[(long long)blockIdx.x * PINN_NSUMS + kLo + threadIdx.x] = t;
+
+  if (flags & PINN_RES_H) {
+    const FlowPre p = hydrogen_pre(cur.It, r.r6);
+    const FlowTerms t = hydrogen_terms(p, L, acc);
+    if (kCols) {
+      cols[PINN_C_FH * ld + row] = t.f;
+      cols[PINN_C_ACTH * ld + row] = p.act;
+      cols[PINN_C_TGTH * ld + row] = t.tgt;
+      cols[PINN_C_ITOT * ld + row] = p.It;
+    }
+  }
+
+  if (flags & PINN_RES_O) {
+    const FlowPre p = oxygen_pre(cur.It, r.r7);
+    const FlowTerms t = oxygen_terms(p, L, acc);
+    if (kCols) {
+      cols[PINN_C_FO * ld + row] = t.f;
+      cols[PINN_C_ACTO * ld + row] = p.act;
+      cols[PINN_C_TGTO * ld + row] = t.tgt;
+      cols[PINN_C_QO2 * ld + row] = p.Q;
+      cols[PINN_C_O2FLOW * ld + row] = p.o2;
+    }
   }
 }
 
@@ -251,37 +104,7 @@ __global__ __launch_bounds__(kThreads) void residuals_kernel(
     row_terms<kCols>(row, x, u, y, aff, L, flags, cols, ld, acc);
 
   if (partials == nullptr) return;
-  block_partials<live_sums(kFlags).lo, live_sums(kFlags).hi, kThreads>(acc, partials);
-}
-
-// fixed-order final reduction of the sums s_lo..s_hi-1 (live_sums of the pass that wrote the partials): thread (s, j) sums partials
-// j, j+32, ... then lane s adds the 32 j-sums in order.  Every other entry of `sums` is set to 0.
-__global__ __launch_bounds__(1024) void residuals_finalize(const double* __restrict__ partials, int n_blocks, int s_lo, int s_hi,
-                                                           double* __restrict__ sums) {
-  __shared__ double red[32][PINN_NSUMS + 1];
-  const int s = threadIdx.x & 31, j = threadIdx.x >> 5;
-  if (s >= s_lo && s < s_hi) {
-    // all loads first (independent addresses), then the adds in fixed order: not a latency-bound chain
-    double v[kMaxBlocks / 32];
-#pragma unroll
-    for (int k = 0; k < kMaxBlocks / 32; ++k) {
-      const int b = j + 32 * k;
-      v[k] = b < n_blocks ? partials[(long long)b * PINN_NSUMS + s] : 0.0;
-    }
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < kMaxBlocks / 32; ++k) t += v[k];
-    red[j][s] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < PINN_NSUMS) {
-    double r = 0.0;
-    if (threadIdx.x >= s_lo && threadIdx.x < s_hi) {
-#pragma unroll
-      for (int k = 0; k < 32; ++k) r += red[k][threadIdx.x];
-    }
-    sums[threadIdx.x] = r;
-  }
+  block_sums<live_sums(kFlags).lo, live_sums(kFlags).hi, kThreads>(acc, partials + (long long)blockIdx.x * PINN_NSUMS);
 }
 
 // Adam (torch defaults) + clamp for the <= 5 scalars of a physics stage, one thread.
@@ -387,113 +210,48 @@ constexpr int cached_floats(unsigned flags) { return (flags & PINN_RES_V) ? 6 : 
 
 // Everything of a row that does not depend on the stage's parameters is computed ONCE (the de-normalisation with its
 // float64 divides, powf / expf of the Nernst terms, the flow ratios): 6 floats per row, struct-of-arrays in d_work.
-// Same operations in the same order as row_terms, so the two paths differ only in the order of the row sums.
+// stage_prepare packs the *_pre part of the one stage model, stage_terms unpacks it and runs the *_terms part: the functions
+// row_terms runs back to back, so the two paths differ only in the order of the row sums.
+//   V: i5, b, E, V_out, y, u    T: It6, mc, T_in, T_out    H, O: It, act
 __device__ __forceinline__ void stage_prepare(long long row, const float* __restrict__ x, const float* __restrict__ u, const float* __restrict__ y,
                                               const AffineDev& aff, float P_H2O, unsigned flags, float (&c)[kCacheFloats]) {
-  const float4 xa = reinterpret_cast<const float4*>(x)[row * 2];
-  const float4 xb = reinterpret_cast<const float4*>(x)[row * 2 + 1];
-  const float r0 = denorm(xa.x, aff.x_min[0], aff.x_scale[0]);
-  const float i5 = r0 / 270.0f + 1e-5f;
-  const float It = i5 * 270.0f;
+  const RowPhys r = load_row(x, row, aff, flags);
+  const Current cur = current_of(r.r0);
 #pragma unroll
   for (int k = 0; k < kCacheFloats; ++k) c[k] = 0.0f;
   if (flags & PINN_RES_V) {
-    const float r3 = denorm(xa.w, aff.x_min[3], aff.x_scale[3]), r4 = denorm(xb.x, aff.x_min[4], aff.x_scale[4]);
-    const float r5 = denorm(xb.y, aff.x_min[5], aff.x_scale[5]);
     const float un = u[row];
-    const float Tk = r5 + 273.15f;
-    const float P_H2 = r3 / 101.0f + 1.0f;
-    const float P_air = r4 / 101.0f + 1.0f;
-    const float Tk_p = powf(Tk, 1.334f);
-    const float pp_H2 = 0.5f * (P_H2 / expf(1.653f * i5 / Tk_p) - P_H2O);
-    const float pp_O2 = P_air / expf(4.192f * i5 / Tk_p) - P_H2O;
-    const float RT = 8.314f * Tk;
-    c[0] = i5;
-    c[1] = RT / 96485.0f;
-    c[2] = 220170.0f / 192970.0f - (RT * logf(P_H2O / (pp_H2 * sqrtf(pp_O2)))) / 192970.0f;
-    c[3] = denorm(un, aff.y_min, aff.y_scale) / 5.0f;
+    const VoltPre p = volt_pre(r, cur.i5, un, aff, P_H2O);
+    c[0] = p.i5; c[1] = p.b; c[2] = p.E; c[3] = p.V_out;
     c[4] = y[row];
     c[5] = un;
   } else if (flags & PINN_RES_T) {
-    const float r1 = denorm(xa.y, aff.x_min[1], aff.x_scale[1]), r2 = denorm(xa.z, aff.x_min[2], aff.x_scale[2]);
-    const float r5 = denorm(xb.y, aff.x_min[5], aff.x_scale[5]);
-    const float i6 = r0 / 270.0f + 1e-6f;
-    c[0] = i6 * 270.0f; c[1] = r1 + 1e-6f; c[2] = r2; c[3] = r5;
+    const ThermPre p = therm_pre(r);
+    c[0] = p.It6; c[1] = p.mc; c[2] = p.T_in; c[3] = p.T_out;
   } else if (flags & PINN_RES_H) {
-    const float r6 = denorm(xb.z, aff.x_min[6], aff.x_scale[6]);
-    float Q = ((It / 192970.0f) * 5.0f) * 22.4f;
-    Q = Q * 60.0f;
-    Q = clamp_min_t(Q, 1e-8f);
-    c[0] = It; c[1] = (r6 + 1e-6f) / Q;
+    const FlowPre p = hydrogen_pre(cur.It, r.r6);
+    c[0] = p.It; c[1] = p.act;
   } else {
-    const float r7 = denorm(xb.w, aff.x_min[7], aff.x_scale[7]);
-    float Q = ((It * 5.0f) / 385940.0f) * 22.4f;
-    Q = Q * 60.0f;
-    Q = clamp_min_t(Q, 1e-8f);
-    c[0] = It; c[1] = ((r7 + 1e-6f) * 0.21f) / Q;
+    const FlowPre p = oxygen_pre(cur.It, r.r7);
+    c[0] = p.It; c[1] = p.act;
   }
 }
-// the parameter-dependent rest (row_terms' formulas)
+// the parameter-dependent rest with its sums (the cached passes require y)
 __device__ __forceinline__ void stage_terms(const float (&c)[kCacheFloats], const AffineDev& aff, const LamDev& L, unsigned flags,
                                             float (&acc)[PINN_NSUMS]) {
   if (flags & PINN_RES_V) {
-    const float i5 = c[0], b = c[1], E = c[2], V_out = c[3], yv = c[4], un = c[5];
-    const float V_act = (-b) * logf(i5 / L.l2);
-    const float V_ohm = -(i5 * L.l1);
-    const float V_conc = (0.5f * b) * logf(1.0f - i5 / L.l3);
-    const float V_est = ((E + V_act) + V_ohm) + V_conc;
-    const float f = V_est - V_out;
-    const float V_est5 = V_est * 5.0f;
-    const float d1 = -i5;
-    const float d2 = b / L.l2;
-    const float d3 = 0.5f * b * i5 / (L.l3 * (L.l3 - i5));
-    acc[PINN_S_FV2] += f * f;
-    acc[PINN_S_FV_D1] += f * d1;
-    acc[PINN_S_FV_D2] += f * d2;
-    acc[PINN_S_FV_D3] += f * d3;
-    const float Vn = V_est5 * aff.vn_scale + aff.vn_min;
-    const float dy = yv - Vn;
-    acc[PINN_S_YV2] += dy * dy;
-    acc[PINN_S_YV_D1] += dy * d1;
-    acc[PINN_S_YV_D2] += dy * d2;
-    acc[PINN_S_YV_D3] += dy * d3;
-    const float du = yv - un;
-    acc[PINN_S_YU2] += du * du;
+    VoltPre p;
+    p.i5 = c[0]; p.b = c[1]; p.E = c[2]; p.V_out = c[3];
+    volt_terms(p, L, true, c[4], c[5], aff, acc);
   } else if (flags & PINN_RES_T) {
-    const float It6 = c[0], mc = c[1], r2 = c[2], r5 = c[3];
-    const float T_pred = ((L.lT1 * It6 + L.lT3 * mc) + 0.5f * r2) + L.lT5;
-    const float f = r5 - T_pred;
-    acc[PINN_S_FT2] += f * f;
-    acc[PINN_S_FT_D1] += f * (-It6);
-    acc[PINN_S_FT_D3] += f * (-mc);
-    acc[PINN_S_FT_D5] += -f;
-    acc[PINN_S_FT_ABS] += fabsf(f);
-  } else if (flags & PINN_RES_H) {
-    const float It = c[0], act = c[1];
-    const bool lin = It <= L.lH3;
-    const float tgt = lin ? (L.lH1 + L.lH2 * (It / 100.0f)) : (L.lH1 + L.lH2 * (L.lH3 / 100.0f));
-    const float f = act - tgt;
-    acc[PINN_S_FH2] += f * f;
-    acc[PINN_S_FH_D1] += -f;
-    acc[PINN_S_FH_D2] += f * (-(lin ? It / 100.0f : L.lH3 / 100.0f));
-    acc[PINN_S_FH_D3] += f * (-(lin ? 0.0f : L.lH2 / 100.0f));
-    acc[PINN_S_ACTH] += act;
-    acc[PINN_S_TGTH] += tgt;
+    ThermPre p;
+    p.It6 = c[0]; p.mc = c[1]; p.T_in = c[2]; p.T_out = c[3];
+    therm_terms(p, L, acc);
   } else {
-    const float It = c[0], act = c[1];
-    const float thr = fabsf(L.lO3);
-    const bool lin = It <= thr;
-    const float raw = lin ? (L.lO1 + L.lO2 * (It / 100.0f)) : (L.lO1 + L.lO2 * (thr / 100.0f));
-    const float tgt = clamp_t(raw, 1.05f, 15.0f);
-    const float cl = (raw >= 1.05f && raw <= 15.0f) ? 1.0f : 0.0f;
-    const float f = (act - tgt) + clamp_min_t(1.0f - act, 0.0f) * 10.0f;
-    const float sgn = (L.lO3 > 0.0f) ? 1.0f : ((L.lO3 < 0.0f) ? -1.0f : 0.0f);
-    acc[PINN_S_FO2] += f * f;
-    acc[PINN_S_FO_D1] += f * (-cl);
-    acc[PINN_S_FO_D2] += f * (-cl * (lin ? It / 100.0f : thr / 100.0f));
-    acc[PINN_S_FO_D3] += f * (-cl * (lin ? 0.0f : L.lO2 * sgn / 100.0f));
-    acc[PINN_S_ACTO] += act;
-    acc[PINN_S_TGTO] += tgt;
+    FlowPre p;
+    p.It = c[0]; p.act = c[1]; p.Qp = p.Q = p.o2 = 0.0f;   // (not part of the cache: only columns and the backward read them)
+    if (flags & PINN_RES_H) hydrogen_terms(p, L, acc);
+    else oxygen_terms(p, L, acc);
   }
 }
 
@@ -506,17 +264,15 @@ __global__ __launch_bounds__(kStageThreads) void stage_run_kernel(
     long long n_rows, double lr0, double gamma, int lr_step, int first_epoch, int n_iters, float* __restrict__ lambdas,
     float* __restrict__ adam, float* __restrict__ loss_out, float* __restrict__ log, int log_every, double* __restrict__ sums_out,
     float* __restrict__ work) {
-  __shared__ double red[kStageThreads / 64][PINN_NSUMS];
   __shared__ double sums[PINN_NSUMS];
   __shared__ float lam_s[PINN_NLAMBDA], adam_s[2 * PINN_NLAMBDA], loss_s[2];
   constexpr unsigned flags = kFlags;
   // (the voltage stage has two variants, chosen at run time; the others are fixed by the flags)
   const int stage = kFlags == PINN_RES_T ? PINN_STAGE_THERMAL : (kFlags == PINN_RES_H ? PINN_STAGE_HYDROGEN : (kFlags == PINN_RES_O ? PINN_STAGE_OXYGEN
                     : (stage_rt == PINN_STAGE_LAMBDA_F ? PINN_STAGE_LAMBDA_F : PINN_STAGE_LAMBDA_PM)));
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   if (tid < PINN_NLAMBDA) lam_s[tid] = lambdas[tid];
   if (tid < 2 * PINN_NLAMBDA) adam_s[tid] = adam[tid];
-  constexpr int s_lo = live_sums(kFlags).lo, s_hi = live_sums(kFlags).hi;   // the sums this stage reads
   if (tid < PINN_NSUMS) sums[tid] = 0.0;
   {   // parameter-independent part of every row, once
     const LamDev L0 = load_lambdas(lambdas);
@@ -555,20 +311,7 @@ __global__ __launch_bounds__(kStageThreads) void stage_run_kernel(
       for (int q = 0; q < kTrip; ++q)
         if (row0 + q * kStageThreads < n_rows) stage_terms(c[q], aff, L, flags, acc);
     }
-#pragma unroll
-    for (int s = 0; s < PINN_NSUMS; ++s) {
-      if (s >= s_lo && s < s_hi) {                   // block-uniform
-        const double w = wave_sum((double)acc[s]);
-        if (lane == 0) red[wave][s] = w;
-      }
-    }
-    __syncthreads();
-    if (tid >= s_lo && tid < s_hi) {
-      double t = 0.0;
-#pragma unroll
-      for (int w = 0; w < kStageThreads / 64; ++w) t += red[w][tid];
-      sums[tid] = t;
-    }
+    block_sums<live_sums(kFlags).lo, live_sums(kFlags).hi, kStageThreads>(acc, sums);   // the sums this stage reads; the rest stay 0
     __syncthreads();
     if (tid == 0) {
       if (it > 0 && epoch % lr_step == 0) lr = (float)(lr0 * pow(gamma, (double)(epoch / lr_step)));
@@ -589,7 +332,6 @@ __global__ __launch_bounds__(kStageThreads) void stage_run_kernel(
   if (tid < 2 && loss_out) loss_out[tid] = loss_s[tid];
   if (tid < PINN_NSUMS && sums_out) sums_out[tid] = sums[tid];
 }
-
 
 // ---------------------------------------------------------------------------------------
 // The same split for any row count / several processes: the parameter-independent row cache once per trainer call
@@ -638,7 +380,7 @@ __global__ __launch_bounds__(kThreads) void residuals_cached_kernel(const float*
     for (int q = 0; q < 2; ++q)
       if (row0 + q * stride < n_rows) stage_terms(c[q], aff, L, kFlags, acc);
   }
-  block_partials<live_sums(kFlags).lo, live_sums(kFlags).hi, kThreads>(acc, partials);
+  block_sums<live_sums(kFlags).lo, live_sums(kFlags).hi, kThreads>(acc, partials + (long long)blockIdx.x * PINN_NSUMS);
 }
 
 static AffineDev affine_dev(const pinn_affine_t* aff) {
@@ -647,19 +389,27 @@ static AffineDev affine_dev(const pinn_affine_t* aff) {
   a.y_min = aff->y_min; a.y_scale = aff->y_scale; a.vn_scale = aff->vn_scale; a.vn_min = aff->vn_min;
   return a;
 }
-static int row_blocks(long long n_rows) {
-  const long long want = (n_rows + kThreads - 1) / kThreads;
-  return (int)(want < 1 ? 1 : (want > kMaxBlocks ? kMaxBlocks : want));
-}
+static int row_blocks(long long n_rows) { return pinn::row_blocks(n_rows, kThreads, kMaxBlocks); }
 static bool one_stage_flag(unsigned flags) { return flags == PINN_RES_V || flags == PINN_RES_T || flags == PINN_RES_H || flags == PINN_RES_O; }
 
+// The run-time stage flag as a template argument, written once for every kernel that is instantiated per stage model: calls
+// fn(std::integral_constant<unsigned, F>) for the one-stage flag F and returns true; any other value calls nothing and returns false.
+template <typename Fn>
+static bool with_stage_flag(unsigned flags, Fn&& fn) {
+  switch (flags) {
+    case PINN_RES_V: fn(std::integral_constant<unsigned, PINN_RES_V>{}); return true;
+    case PINN_RES_T: fn(std::integral_constant<unsigned, PINN_RES_T>{}); return true;
+    case PINN_RES_H: fn(std::integral_constant<unsigned, PINN_RES_H>{}); return true;
+    case PINN_RES_O: fn(std::integral_constant<unsigned, PINN_RES_O>{}); return true;
+    default: return false;
+  }
+}
 
 // ---------------------------------------------------------------------------------------
 // net_f_T (01:767-867): the Euler energy balance row t-1 -> t.  Row t reads the de-normalised current, coolant flow,
 // inlet and outlet temperature and the DNN's eval-mode voltage of row t - 1 (a halo of ONE row: under row sharding the
-// caller passes the last row of the previous shard as x_halo / u_halo) and its own outlet temperature:
-//   I = (I/270 + 1e-5) 270;  V_rev = 1.229 - 0.0009 ((T_out + 273.15) - 298.15);  V_cell = denorm(u) / 5
-//   Q_el = (I V_rev - I V_cell) lT4;  Q_cool = (m + 1e-6) 4180 (T_out - T_in) lT1;  Q_rad = 20 * 0.2 (T_out - 25) lT3
+// caller passes the last row of the previous shard as x_halo / u_halo) and its own outlet temperature; the step itself is
+// euler_step of pinn_physics.h, which the backward shares:
 //   T_pred[t] = T_out[t-1] + ((Q_el - Q_cool - Q_rad) / lT2) 0.1;   T_pred[0] = T_out[0] (01:857);   f = T_out - T_pred
 // every float op rounded separately, in the reference's order (this file is built with -ffp-contract=off).
 // 32 B/row + 4 B/row (u) read -- the previous row's line is an L1/L2 hit --, 12 B/row written: HBM-bound.
@@ -677,20 +427,8 @@ __global__ __launch_bounds__(kThreads) void net_f_T_kernel(const float* __restri
       const float4 pa = reinterpret_cast<const float4*>(xp)[0];
       const float4 pb = reinterpret_cast<const float4*>(xp)[1];
       const float un = row > 0 ? u[row - 1] : u_halo[0];
-      const float r0 = denorm(pa.x, aff.x_min[0], aff.x_scale[0]);
-      const float m_cool = denorm(pa.y, aff.x_min[1], aff.x_scale[1]) + 1e-6f;
-      const float T_in = denorm(pa.z, aff.x_min[2], aff.x_scale[2]);
-      const float T_prev = denorm(pb.y, aff.x_min[5], aff.x_scale[5]);
-      const float i5 = r0 / 270.0f + 0.00001f;
-      const float I_tot = i5 * 270.0f;
-      const float Tk = T_prev + 273.15f;
-      const float V_rev = 1.229f - 0.0009f * (Tk - 298.15f);
-      const float V_cell = denorm(un, aff.y_min, aff.y_scale) / 5.0f;
-      const float Q_el = (I_tot * V_rev - I_tot * V_cell) * lT4;
-      const float Q_cool = ((m_cool * 4180.0f) * (T_prev - T_in)) * lT1;
-      const float Q_rad = ((20.0f * 0.2f) * (T_prev - 25.0f)) * lT3;
-      const float dT = ((Q_el - Q_cool) - Q_rad) / lT2;
-      pred = T_prev + dT * 0.1f;
+      const EulerFwd e = euler_step(pa, pb, un, aff, lT1, lT2, lT3, lT4);
+      pred = e.T_prev + e.dT * 0.1f;
     }
     f_out[row] = T_out - pred;
     t_pred[row] = pred;
@@ -700,8 +438,8 @@ __global__ __launch_bounds__(kThreads) void net_f_T_kernel(const float* __restri
 
 // ---------------------------------------------------------------------------------------
 // Vector-Jacobian products of the two passes above (torch autograd's backward of the oracle's restatement of 01:535-914).
-// Nothing is saved between the calls: every row's terms are recomputed from x, u and the parameters with the forward's
-// arithmetic (same denorm / load_lambdas, same -ffp-contract=off), then back-propagated op by op in the order torch's
+// Nothing is saved between the calls: every row's terms are recomputed from x, u and the parameters by the forward's own
+// functions (pinn_physics.h, each called inside the guard of the node that needs it), then back-propagated op by op in the order torch's
 // derivative formulas use: a / b -> (g / b, -g * ((a / b) / b)), log -> g / x, exp -> g * exp(x), pow -> g * p x^(p-1),
 // clamp -> inclusive mask, where -> nothing through the condition, abs -> sign.  A node is visited only when an upstream
 // column that reaches it is present (gmask), so NaN rows (I >= lambda_3: log of a negative number) give NaN exactly where
@@ -726,17 +464,8 @@ __host__ __device__ inline unsigned grad_cols_of(unsigned flags) {
 __device__ __forceinline__ void row_backward(long long row, const float* __restrict__ x, const float* __restrict__ u, const AffineDev& aff,
                                              const LamDev& L, unsigned flags, const float* __restrict__ g, long long ld, unsigned gmask,
                                              double (&acc)[PINN_NLAMBDA], float (&gr)[8], float& gu) {
-  const float4 xa = reinterpret_cast<const float4*>(x)[row * 2];
-  const float4 xb = reinterpret_cast<const float4*>(x)[row * 2 + 1];
   const bool fV = flags & PINN_RES_V, fT = flags & PINN_RES_T, fH = flags & PINN_RES_H, fO = flags & PINN_RES_O;
-  const float r0 = denorm(xa.x, aff.x_min[0], aff.x_scale[0]);
-  const float r1 = fT ? denorm(xa.y, aff.x_min[1], aff.x_scale[1]) : 0.f;
-  const float r2 = fT ? denorm(xa.z, aff.x_min[2], aff.x_scale[2]) : 0.f;
-  const float r3 = fV ? denorm(xa.w, aff.x_min[3], aff.x_scale[3]) : 0.f;
-  const float r4 = fV ? denorm(xb.x, aff.x_min[4], aff.x_scale[4]) : 0.f;
-  const float r5 = (fV || fT) ? denorm(xb.y, aff.x_min[5], aff.x_scale[5]) : 0.f;
-  const float r6 = fH ? denorm(xb.z, aff.x_min[6], aff.x_scale[6]) : 0.f;
-  const float r7 = fO ? denorm(xb.w, aff.x_min[7], aff.x_scale[7]) : 0.f;
+  const RowPhys r = load_row(x, row, aff, flags);
 #pragma unroll
   for (int c = 0; c < 8; ++c) gr[c] = 0.0f;
   gu = 0.0f;
@@ -744,17 +473,17 @@ __device__ __forceinline__ void row_backward(long long row, const float* __restr
   auto G = [&](int c) -> float { return (gmask & PINN_BIT(c)) ? g[(long long)c * ld + row] : 0.0f; };
   auto has = [&](unsigned bits) -> bool { return (gmask & bits) != 0u; };
 
-  const float i5 = r0 / 270.0f + 1e-5f;
-  const float It = i5 * 270.0f;
-  float gi5 = 0.0f;   // d / d i5 of the V, H and O models (T_simple has its own i = I/270 + 1e-6)
+  const Current cur = current_of(r.r0);
+  const float i5 = cur.i5, It = cur.It;
+  float gi5 = 0.0f;  // d / d i5 of the V, H and O models (T_simple has its own i = I/270 + 1e-6)
 
   if (fV) {
     const float gFV = G(PINN_C_FV), gVest = gFV + G(PINN_C_VEST5) * 5.0f;
     const float l1 = L.l1, l2 = L.l2, l3 = L.l3;
     float gi = G(PINN_C_I), gb = 0.0f, gTk = 0.0f;
-    const float Tk = r5 + 273.15f;
-    const float RT = 8.314f * Tk;
-    const float b = RT / 96485.0f;
+    const float Tk = kelvin(r.r5);
+    const ThermalVoltage tv = thermal_voltage(Tk);
+    const float RT = tv.RT, b = tv.b;
     if (has(PINN_BIT(PINN_C_FV) | PINN_BIT(PINN_C_VEST5) | PINN_BIT(PINN_C_VACT))) {      // V_act = (-b) log(i / l2)
       const float gA = gVest + G(PINN_C_VACT);
       const float q = i5 / l2, La = logf(q);
@@ -778,13 +507,8 @@ __device__ __forceinline__ void row_backward(long long row, const float* __restr
     }
     if (has(PINN_BIT(PINN_C_FV) | PINN_BIT(PINN_C_VEST5) | PINN_BIT(PINN_C_ENERNST))) {   // E = c - (RT log(P_H2O / (pp_H2 sqrt(pp_O2)))) / 192970
       const float gE = gVest + G(PINN_C_ENERNST);
-      const float P_H2 = r3 / 101.0f + 1.0f;
-      const float P_air = r4 / 101.0f + 1.0f;
-      const float Tk_p = powf(Tk, 1.334f);
-      const float a1 = 1.653f * i5 / Tk_p, e1 = expf(a1), q1 = P_H2 / e1;
-      const float pp_H2 = 0.5f * (q1 - L.P_H2O);
-      const float a2 = 4.192f * i5 / Tk_p, e2 = expf(a2), q2 = P_air / e2;
-      const float pp_O2 = q2 - L.P_H2O;
+      const Nernst n = nernst_pressures(i5, Tk, r.r3, r.r4, L.P_H2O);
+      const float Tk_p = n.Tk_p, a1 = n.a1, e1 = n.e1, q1 = n.q1, pp_H2 = n.pp_H2, a2 = n.a2, e2 = n.e2, q2 = n.q2, pp_O2 = n.pp_O2;
       const float s = sqrtf(pp_O2), D = pp_H2 * s, z = L.P_H2O / D, LE = logf(z);
       const float gnum = (-gE) / 192970.0f;
       gTk += (gnum * LE) * 8.314f;
@@ -814,11 +538,9 @@ __device__ __forceinline__ void row_backward(long long row, const float* __restr
     gr[5] += gF + G(PINN_C_TOUT);
     if (has(PINN_BIT(PINN_C_FT) | PINN_BIT(PINN_C_TPRED))) {    // T_pred = lT1 I + lT3 (m + 1e-6) + 0.5 T_in + lT5
       const float gP = G(PINN_C_TPRED) - gF;
-      const float i6 = r0 / 270.0f + 1e-6f;
-      const float mc = r1 + 1e-6f;
-      const float It6 = i6 * 270.0f;
-      acc[PINN_LT1] += (double)(gP * It6);
-      acc[PINN_LT3] += (double)(gP * mc);
+      const ThermPre p = therm_pre(r);
+      acc[PINN_LT1] += (double)(gP * p.It6);
+      acc[PINN_LT3] += (double)(gP * p.mc);
       acc[PINN_LT5] += (double)gP;
       gr[0] += ((gP * L.lT1) * 270.0f) / 270.0f;
       gr[1] += gP * L.lT3;
@@ -831,9 +553,8 @@ __device__ __forceinline__ void row_backward(long long row, const float* __restr
     float gIt = G(PINN_C_ITOT);
     if (has(PINN_BIT(PINN_C_FH) | PINN_BIT(PINN_C_ACTH))) {     // act = (h2 + 1e-6) / clamp_min(Q, 1e-8)
       const float ga = gF + G(PINN_C_ACTH);
-      const float Qp = (((It / 192970.0f) * 5.0f) * 22.4f) * 60.0f;
-      const float Q = clamp_min_t(Qp, 1e-8f);
-      const float act = (r6 + 1e-6f) / Q;
+      const FlowPre p = hydrogen_pre(It, r.r6);
+      const float Qp = p.Qp, Q = p.Q, act = p.act;
       gr[6] += ga / Q;
       const float gQ = -ga * (act / Q);
       const float gQp = (Qp >= 1e-8f) ? gQ : 0.0f;
@@ -842,7 +563,7 @@ __device__ __forceinline__ void row_backward(long long row, const float* __restr
     if (has(PINN_BIT(PINN_C_FH) | PINN_BIT(PINN_C_TGTH))) {     // target = where(It <= lH3, lH1 + lH2 It / 100, lH1 + lH2 lH3 / 100)
       const float gt = G(PINN_C_TGTH) - gF;
       acc[PINN_LH1] += (double)gt;
-      if (It <= L.lH3) {
+      if (hydrogen_target(It, L).lin) {
         acc[PINN_LH2] += (double)(gt * (It / 100.0f));
         gIt += (gt * L.lH2) / 100.0f;
       } else {
@@ -858,12 +579,11 @@ __device__ __forceinline__ void row_backward(long long row, const float* __restr
     float gIt = 0.0f;
     const bool pAct = has(PINN_BIT(PINN_C_FO) | PINN_BIT(PINN_C_ACTO));
     if (pAct || has(PINN_BIT(PINN_C_QO2) | PINN_BIT(PINN_C_O2FLOW))) {
-      const float Qp = (((It * 5.0f) / 385940.0f) * 22.4f) * 60.0f;
-      const float Q = clamp_min_t(Qp, 1e-8f);
-      const float o2 = (r7 + 1e-6f) * 0.21f;
+      const FlowPre p = oxygen_pre(It, r.r7);
+      const float Qp = p.Qp, Q = p.Q;
       float gQ = G(PINN_C_QO2), go2 = G(PINN_C_O2FLOW);
       if (pAct) {                                               // f = (act - tgt) + clamp_min(1 - act, 0) 10,  act = o2 / Q
-        const float act = o2 / Q;
+        const float act = p.act;
         float ga = gF + G(PINN_C_ACTO);
         if (gmask & PINN_BIT(PINN_C_FO)) ga -= ((1.0f - act) >= 0.0f) ? gF * 10.0f : 0.0f;
         go2 += ga / Q;
@@ -877,9 +597,9 @@ __device__ __forceinline__ void row_backward(long long row, const float* __restr
     }
     if (has(PINN_BIT(PINN_C_FO) | PINN_BIT(PINN_C_TGTO))) {     // target = clamp(where(It <= |lO3|, ...), 1.05, 15)
       const float gt = G(PINN_C_TGTO) - gF;
-      const float thr = fabsf(L.lO3);
-      const bool lin = It <= thr;
-      const float raw = lin ? (L.lO1 + L.lO2 * (It / 100.0f)) : (L.lO1 + L.lO2 * (thr / 100.0f));
+      const Target tg = oxygen_target(It, L);
+      const float thr = tg.thr, raw = tg.raw;
+      const bool lin = tg.lin;
       const float gw = (raw >= 1.05f && raw <= 15.0f) ? gt : 0.0f;
       acc[PINN_LO1] += (double)gw;
       if (lin) {
@@ -905,28 +625,11 @@ __device__ __forceinline__ void store_gx_row(float* __restrict__ gx, long long r
   reinterpret_cast<float4*>(gx)[row * 2 + 1] = make_float4(o[4], o[5], o[6], o[7]);
 }
 
-// the parameter gradients of one workgroup -> partials[blockIdx.x * PINN_NSUMS + k], k < PINN_NLAMBDA
-__device__ __forceinline__ void block_lambda_partials(const double (&acc)[PINN_NLAMBDA], double (*red)[PINN_NLAMBDA], double* __restrict__ partials) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < PINN_NLAMBDA; ++k) {
-    const double w = wave_sum(acc[k]);
-    if (lane == 0) red[wave][k] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < PINN_NLAMBDA) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) t += red[w][threadIdx.x];
-    partials[(long long)blockIdx.x * PINN_NSUMS + threadIdx.x] = t;
-  }
-}
-
+// (parameter gradients: float64 per thread -> partials[blockIdx.x * PINN_NSUMS + k], k < PINN_NLAMBDA, by block_sums)
 __global__ __launch_bounds__(kThreads) void residuals_backward_kernel(
     const float* __restrict__ x, const float* __restrict__ u, AffineDev aff, const float* __restrict__ lambdas, unsigned flags,
     long long n_rows, const float* __restrict__ g, long long ld, unsigned gmask, float* __restrict__ gu_out, float* __restrict__ gx_out,
     double* __restrict__ partials) {
-  __shared__ double red[kThreads / 64][PINN_NLAMBDA];
   const LamDev L = load_lambdas(lambdas);
   double acc[PINN_NLAMBDA];
 #pragma unroll
@@ -938,30 +641,7 @@ __global__ __launch_bounds__(kThreads) void residuals_backward_kernel(
     if (gx_out != nullptr) store_gx_row(gx_out, row, gr, aff);
     if (gu_out != nullptr) gu_out[row] = gu;
   }
-  block_lambda_partials(acc, red, partials);
-}
-
-// fixed-order final reduction of the parameter-gradient partials (residuals_finalize's order) -> float[PINN_NLAMBDA]
-__global__ __launch_bounds__(1024) void lambda_grad_finalize(const double* __restrict__ partials, int n_blocks, float* __restrict__ glambda) {
-  __shared__ double red[32][PINN_NLAMBDA + 1];
-  const int s = threadIdx.x & 31, j = threadIdx.x >> 5;
-  double v[kMaxBlocks / 32];
-#pragma unroll
-  for (int k = 0; k < kMaxBlocks / 32; ++k) {
-    const int b = j + 32 * k;
-    v[k] = (s < PINN_NLAMBDA && b < n_blocks) ? partials[(long long)b * PINN_NSUMS + s] : 0.0;
-  }
-  double t = 0.0;
-#pragma unroll
-  for (int k = 0; k < kMaxBlocks / 32; ++k) t += v[k];
-  if (s < PINN_NLAMBDA) red[j][s] = t;
-  __syncthreads();
-  if (threadIdx.x < PINN_NLAMBDA) {
-    double r = 0.0;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) r += red[k][threadIdx.x];
-    glambda[threadIdx.x] = (float)r;
-  }
+  block_sums<0, PINN_NLAMBDA, kThreads>(acc, partials + (long long)blockIdx.x * PINN_NSUMS);
 }
 
 // Backward of one Euler step t (net_f_T_kernel's arithmetic) with respect to its predecessor row p = t - 1 (or the halo):
@@ -969,23 +649,8 @@ __global__ __launch_bounds__(1024) void lambda_grad_finalize(const double* __res
 struct EulerGrad { float g0, g1, g2, g5, gu; };
 __device__ __forceinline__ EulerGrad euler_step_backward(float4 pa, float4 pb, float un, float g, const AffineDev& aff, float lT1, float lT2,
                                                          float lT3, float lT4, double (&acc)[PINN_NLAMBDA]) {
-  const float r0 = denorm(pa.x, aff.x_min[0], aff.x_scale[0]);
-  const float m_cool = denorm(pa.y, aff.x_min[1], aff.x_scale[1]) + 1e-6f;
-  const float T_in = denorm(pa.z, aff.x_min[2], aff.x_scale[2]);
-  const float T_prev = denorm(pb.y, aff.x_min[5], aff.x_scale[5]);
-  const float i5 = r0 / 270.0f + 0.00001f;
-  const float I_tot = i5 * 270.0f;
-  const float Tk = T_prev + 273.15f;
-  const float V_rev = 1.229f - 0.0009f * (Tk - 298.15f);
-  const float V_cell = denorm(un, aff.y_min, aff.y_scale) / 5.0f;
-  const float A = I_tot * V_rev - I_tot * V_cell;
-  const float Q_el = A * lT4;
-  const float dTc = T_prev - T_in;
-  const float B = (m_cool * 4180.0f) * dTc;
-  const float Q_cool = B * lT1;
-  const float C = (20.0f * 0.2f) * (T_prev - 25.0f);
-  const float Q_rad = C * lT3;
-  const float dT = ((Q_el - Q_cool) - Q_rad) / lT2;
+  const EulerFwd s = euler_step(pa, pb, un, aff, lT1, lT2, lT3, lT4);
+  const float I_tot = s.I_tot, V_rev = s.V_rev, V_cell = s.V_cell, A = s.A, B = s.B, C = s.C, dTc = s.dTc, m_cool = s.m_cool, dT = s.dT;
   // T_pred = T_prev + dT 0.1
   float gTp = g;
   const float gdT = g * 0.1f;
@@ -1019,7 +684,6 @@ __global__ __launch_bounds__(kThreads) void net_f_T_backward_kernel(
     const float* __restrict__ lambdas, long long n_rows, const float* __restrict__ gf, const float* __restrict__ gpred,
     const float* __restrict__ greal, float* __restrict__ gu_out, float* __restrict__ gx_out, float* __restrict__ gx_halo,
     float* __restrict__ gu_halo, double* __restrict__ partials) {
-  __shared__ double red[kThreads / 64][PINN_NLAMBDA];
   const float lT1 = lambdas[PINN_LT1], lT2 = lambdas[PINN_LT2], lT3 = lambdas[PINN_LT3], lT4 = lambdas[PINN_LT4];
   double acc[PINN_NLAMBDA];
 #pragma unroll
@@ -1059,7 +723,12 @@ __global__ __launch_bounds__(kThreads) void net_f_T_backward_kernel(
     if (gx_halo != nullptr) store_gx_row(gx_halo, 0, hr, aff);
     if (gu_halo != nullptr) gu_halo[0] = hu;
   }
-  block_lambda_partials(acc, red, partials);
+  block_sums<0, PINN_NLAMBDA, kThreads>(acc, partials + (long long)blockIdx.x * PINN_NSUMS);
+}
+
+// the PINN_NLAMBDA parameter gradients of a backward from its workgroups' partials
+static void launch_lambda_grad_finalize(const void* d_work, int blocks, float* d_glambda, hipStream_t st) {
+  hipLaunchKernelGGL(sums_finalize<float>, dim3(1), dim3(1024), 0, st, (const double*)d_work, blocks, 0, PINN_NLAMBDA, d_glambda);
 }
 
 }  // namespace
@@ -1075,48 +744,37 @@ extern "C" int pinn_residuals(const float* d_x, const float* d_u, const float* d
   if (d_sums && !d_work) return PINN_E_ARG;
   if (d_sums && work_bytes < pinn_residuals_workspace_bytes()) return PINN_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();   // drop a stale error left by another HIP user of this thread
-  AffineDev a;
-  for (int c = 0; c < 8; ++c) { a.x_min[c] = aff->x_min[c]; a.x_scale[c] = aff->x_scale[c]; }
-  a.y_min = aff->y_min; a.y_scale = aff->y_scale; a.vn_scale = aff->vn_scale; a.vn_min = aff->vn_min;
-  long long want = (n_rows + kThreads - 1) / kThreads;
-  int blocks = (int)(want < 1 ? 1 : (want > kMaxBlocks ? kMaxBlocks : want));
+  clear_error();   // drop a stale error left by another HIP user of this thread
+  const AffineDev a = affine_dev(aff);
+  const int blocks = row_blocks(n_rows);
   double* partials = d_sums ? (double*)d_work : nullptr;
   // the kernel's compile-time flags: the one stage model of a sums-only call, else 0 (run-time flags, all sums).  The instantiation
   // launched and the range the finalize reads both follow from this one value.
   const unsigned kf = (!d_cols && one_stage_flag(flags)) ? flags : 0u;
   if (n_rows > 0 || d_sums) {
-#define PINN_RES_LAUNCH(COLS, F)                                                                                                  \
-  hipLaunchKernelGGL((residuals_kernel<COLS, F>), dim3(blocks), dim3(kThreads), 0, st, d_x, d_u, d_y, a, d_lambda, flags, n_rows, \
-                     d_cols, ld, partials)
-    switch (kf) {
-      case PINN_RES_V: PINN_RES_LAUNCH(false, PINN_RES_V); break;
-      case PINN_RES_T: PINN_RES_LAUNCH(false, PINN_RES_T); break;
-      case PINN_RES_H: PINN_RES_LAUNCH(false, PINN_RES_H); break;
-      case PINN_RES_O: PINN_RES_LAUNCH(false, PINN_RES_O); break;
-      default:
-        if (d_cols) PINN_RES_LAUNCH(true, 0u);
-        else PINN_RES_LAUNCH(false, 0u);
-    }
-#undef PINN_RES_LAUNCH
+    auto launch = [&](auto cols, auto f) {
+      hipLaunchKernelGGL((residuals_kernel<decltype(cols)::value, decltype(f)::value>), dim3(blocks), dim3(kThreads), 0, st, d_x, d_u, d_y, a,
+                         d_lambda, flags, n_rows, d_cols, ld, partials);
+    };
+    const std::integral_constant<unsigned, 0u> run_time_flags;
+    if (d_cols) launch(std::true_type{}, run_time_flags);
+    else if (!with_stage_flag(kf, [&](auto f) { launch(std::false_type{}, f); })) launch(std::false_type{}, run_time_flags);
   }
   if (d_sums) {
     const SumRange live = live_sums(kf);
-    hipLaunchKernelGGL(residuals_finalize, dim3(1), dim3(1024), 0, st, partials, blocks, live.lo, live.hi, d_sums);
+    hipLaunchKernelGGL(sums_finalize<double>, dim3(1), dim3(1024), 0, st, (const double*)partials, blocks, live.lo, live.hi, d_sums);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_lambda_step(int stage, const double* d_sums, long long n_global, float vn_scale, float lr, int step,
                                 float* d_lambda, float* d_adam, float* d_loss, void* stream) {
   if (stage < 0 || stage > PINN_STAGE_OXYGEN || !d_sums || n_global <= 0 || step < 1 || !d_lambda || !d_adam)
     return PINN_E_ARG;
-  (void)hipGetLastError();
+  clear_error();
   hipLaunchKernelGGL(lambda_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, stage, d_sums, 1.0 / (double)n_global,
                      vn_scale, lr, step, d_lambda, d_adam, d_loss);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" size_t pinn_lambda_stage_workspace_bytes(long long n_rows) { return n_rows > 0 ? (size_t)n_rows * 6 * sizeof(float) : 0; }
@@ -1128,7 +786,7 @@ extern "C" int pinn_lambda_stage_run(int stage, unsigned flags, const float* d_x
   if (stage < 0 || stage > PINN_STAGE_OXYGEN || !d_x || !aff || !d_lambda || !d_adam || n_rows <= 0 || n_rows > PINN_STAGE_RUN_MAX_ROWS ||
       n_iters < 0 || first_epoch < 0 || lr_step < 1)
     return PINN_E_ARG;
-  if (flags != PINN_RES_V && flags != PINN_RES_T && flags != PINN_RES_H && flags != PINN_RES_O) return PINN_E_ARG;
+  if (!one_stage_flag(flags)) return PINN_E_ARG;
   // the stage names the parameters and the loss, the flag the row model: a pair that contradicts itself is refused, not reinterpreted
   const unsigned stage_flag = stage == PINN_STAGE_THERMAL ? PINN_RES_T : (stage == PINN_STAGE_HYDROGEN ? PINN_RES_H
                               : (stage == PINN_STAGE_OXYGEN ? PINN_RES_O : PINN_RES_V));
@@ -1138,31 +796,23 @@ extern "C" int pinn_lambda_stage_run(int stage, unsigned flags, const float* d_x
   if (!d_work) return PINN_E_ARG;
   if (work_bytes < pinn_lambda_stage_workspace_bytes(n_rows)) return PINN_E_WORKSPACE;
   if (n_iters == 0) return PINN_OK;
-  (void)hipGetLastError();
-  AffineDev a;
-  for (int c = 0; c < 8; ++c) { a.x_min[c] = aff->x_min[c]; a.x_scale[c] = aff->x_scale[c]; }
-  a.y_min = aff->y_min; a.y_scale = aff->y_scale; a.vn_scale = aff->vn_scale; a.vn_min = aff->vn_min;
-#define PINN_STAGE_LAUNCH(F)                                                                                                          \
-  hipLaunchKernelGGL((stage_run_kernel<F>), dim3(1), dim3(kStageThreads), 0, (hipStream_t)stream, stage, d_x, d_u, d_y, a, n_rows, lr0, gamma, \
-                     lr_step, first_epoch, n_iters, d_lambda, d_adam, d_loss, d_log, log_every, d_sums, (float*)d_work)
-  if (flags == PINN_RES_V) PINN_STAGE_LAUNCH(PINN_RES_V);
-  else if (flags == PINN_RES_T) PINN_STAGE_LAUNCH(PINN_RES_T);
-  else if (flags == PINN_RES_H) PINN_STAGE_LAUNCH(PINN_RES_H);
-  else PINN_STAGE_LAUNCH(PINN_RES_O);
-#undef PINN_STAGE_LAUNCH
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  clear_error();
+  const AffineDev a = affine_dev(aff);
+  with_stage_flag(flags, [&](auto f) {
+    hipLaunchKernelGGL((stage_run_kernel<decltype(f)::value>), dim3(1), dim3(kStageThreads), 0, (hipStream_t)stream, stage, d_x, d_u, d_y, a,
+                       n_rows, lr0, gamma, lr_step, first_epoch, n_iters, d_lambda, d_adam, d_loss, d_log, log_every, d_sums, (float*)d_work);
+  });
+  return launch_status();
 }
 
 extern "C" int pinn_residuals_prepare(const float* d_x, const float* d_u, const float* d_y, const pinn_affine_t* aff,
                                       const float* d_lambda, unsigned flags, long long n_rows, float* d_cache, void* stream) {
   if (!d_x || !aff || !d_lambda || !d_cache || n_rows <= 0 || !one_stage_flag(flags)) return PINN_E_ARG;
   if ((flags & PINN_RES_V) && (!d_u || !d_y)) return PINN_E_ARG;
-  (void)hipGetLastError();
+  clear_error();
   hipLaunchKernelGGL(stage_prepare_kernel, dim3(row_blocks(n_rows)), dim3(kThreads), 0, (hipStream_t)stream, d_x, d_u, d_y, affine_dev(aff),
                      d_lambda, flags, n_rows, d_cache);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  return launch_status();
 }
 
 extern "C" int pinn_residuals_cached(const float* d_cache, const pinn_affine_t* aff, const float* d_lambda, unsigned flags,
@@ -1170,21 +820,17 @@ extern "C" int pinn_residuals_cached(const float* d_cache, const pinn_affine_t* 
   if (!d_cache || !aff || !d_lambda || !d_sums || n_rows <= 0 || !one_stage_flag(flags)) return PINN_E_ARG;
   if (!d_work) return PINN_E_ARG;
   if (work_bytes < pinn_residuals_workspace_bytes()) return PINN_E_WORKSPACE;
-  (void)hipGetLastError();
+  clear_error();
   hipStream_t st = (hipStream_t)stream;
   const int blocks = row_blocks((n_rows + 1) / 2);
-#define PINN_CACHED_LAUNCH(F)                                                                                                     \
-  hipLaunchKernelGGL((residuals_cached_kernel<F>), dim3(blocks), dim3(kThreads), 0, st, d_cache, affine_dev(aff), d_lambda, n_rows, \
-                     (double*)d_work)
-  if (flags == PINN_RES_V) PINN_CACHED_LAUNCH(PINN_RES_V);
-  else if (flags == PINN_RES_T) PINN_CACHED_LAUNCH(PINN_RES_T);
-  else if (flags == PINN_RES_H) PINN_CACHED_LAUNCH(PINN_RES_H);
-  else PINN_CACHED_LAUNCH(PINN_RES_O);
-#undef PINN_CACHED_LAUNCH
+  const AffineDev a = affine_dev(aff);
+  with_stage_flag(flags, [&](auto f) {
+    hipLaunchKernelGGL((residuals_cached_kernel<decltype(f)::value>), dim3(blocks), dim3(kThreads), 0, st, d_cache, a, d_lambda, n_rows,
+                       (double*)d_work);
+  });
   const SumRange live = live_sums(flags);
-  hipLaunchKernelGGL(residuals_finalize, dim3(1), dim3(1024), 0, st, (const double*)d_work, blocks, live.lo, live.hi, d_sums);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  hipLaunchKernelGGL(sums_finalize<double>, dim3(1), dim3(1024), 0, st, (const double*)d_work, blocks, live.lo, live.hi, d_sums);
+  return launch_status();
 }
 
 extern "C" int pinn_net_f_t(const float* d_x, const float* d_u, const float* d_x_halo, const float* d_u_halo, const pinn_affine_t* aff,
@@ -1193,16 +839,10 @@ extern "C" int pinn_net_f_t(const float* d_x, const float* d_u, const float* d_x
   if (n_rows > 1 && !d_u) return PINN_E_ARG;
   if ((d_x_halo == nullptr) != (d_u_halo == nullptr)) return PINN_E_ARG;
   if (n_rows == 0) return PINN_OK;
-  (void)hipGetLastError();
-  AffineDev a;
-  for (int c = 0; c < 8; ++c) { a.x_min[c] = aff->x_min[c]; a.x_scale[c] = aff->x_scale[c]; }
-  a.y_min = aff->y_min; a.y_scale = aff->y_scale; a.vn_scale = aff->vn_scale; a.vn_min = aff->vn_min;
-  long long want = (n_rows + kThreads - 1) / kThreads;
-  const int blocks = (int)(want > kMaxBlocks ? kMaxBlocks : want);
-  hipLaunchKernelGGL(net_f_T_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, d_x, d_u, d_x_halo, d_u_halo, a, d_lambda, n_rows,
-                     d_f, d_t_pred, d_t_real);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  clear_error();
+  hipLaunchKernelGGL(net_f_T_kernel, dim3(row_blocks(n_rows)), dim3(kThreads), 0, (hipStream_t)stream, d_x, d_u, d_x_halo, d_u_halo,
+                     affine_dev(aff), d_lambda, n_rows, d_f, d_t_pred, d_t_real);
+  return launch_status();
 }
 
 static bool misaligned16(const void* p) { return ((unsigned long long)(size_t)p & 15ull) != 0ull; }
@@ -1218,13 +858,12 @@ extern "C" int pinn_residuals_backward(const float* d_x, const float* d_u, const
   if (!d_work) return PINN_E_ARG;
   if (work_bytes < pinn_residuals_workspace_bytes()) return PINN_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
+  clear_error();
   const int blocks = row_blocks(n_rows);
   hipLaunchKernelGGL(residuals_backward_kernel, dim3(blocks), dim3(kThreads), 0, st, d_x, d_u, affine_dev(aff), d_lambda, flags, n_rows,
                      d_g, ld, gmask, d_gu, d_gx, (double*)d_work);
-  hipLaunchKernelGGL(lambda_grad_finalize, dim3(1), dim3(1024), 0, st, (const double*)d_work, blocks, d_glambda);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  launch_lambda_grad_finalize(d_work, blocks, d_glambda, st);
+  return launch_status();
 }
 
 extern "C" int pinn_net_f_t_backward(const float* d_x, const float* d_u, const float* d_x_halo, const float* d_u_halo,
@@ -1239,11 +878,11 @@ extern "C" int pinn_net_f_t_backward(const float* d_x, const float* d_u, const f
   if (!d_work) return PINN_E_ARG;
   if (work_bytes < pinn_residuals_workspace_bytes()) return PINN_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  (void)hipGetLastError();
+  clear_error();
   const int blocks = row_blocks(n_rows);
   hipLaunchKernelGGL(net_f_T_backward_kernel, dim3(blocks), dim3(kThreads), 0, st, d_x, d_u, d_x_halo, d_u_halo, affine_dev(aff), d_lambda,
                      n_rows, d_gf, d_gt_pred, d_gt_real, d_gu, d_gx, d_gx_halo, d_gu_halo, (double*)d_work);
-  hipLaunchKernelGGL(lambda_grad_finalize, dim3(1), dim3(1024), 0, st, (const double*)d_work, blocks, d_glambda);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PINN_OK : (int)e;
+  launch_lambda_grad_finalize(d_work, blocks, d_glambda, st);
+  return launch_status();
 }
+

@@ -1,7 +1,11 @@
 """The cached physics-stage pass, one kernel instantiation per stage kind (pinn_residuals_prepare + pinn_residuals_cached):
 only the stage's own range of the sums is reduced, every other entry of d_sums is exactly 0, the live ones are
 pinn_residuals' for the same flag, and a call repeats to the byte.  Row counts: a single row, the odd second row of a
-two-row trip (255, 257), many workgroups below the grid cap (65 537) and the cap reached with a second trip (524 291)."""
+two-row trip (255, 257), many workgroups below the grid cap (65 537) and the cap reached with a second trip (524 291).
+
+Where the reduction trees of two passes coincide (one workgroup, one row per thread) their sums are compared to the byte, and so
+are the cache slots and the row pass's columns: the passes are assembled from one text of each model (csrc/pinn_physics.h), and
+these tests are what holds them to it."""
 import ctypes
 import functools
 
@@ -110,6 +114,85 @@ def test_stage_pass_live_and_dead_sums(lib, N, kind):
     # the tolerance of test_residuals_cached_matches_residuals (DESIGN K1c): the two passes differ in the order of the row sums
     np.testing.assert_allclose(a[live], gen[live], rtol=2e-6, atol=1e-6 * max(1.0, np.abs(ref).max()) * 1e-3, err_msg="%s N=%d" % (kind, N))
     np.testing.assert_allclose(a[live], ref[live], rtol=2e-6, atol=1e-6 * max(1.0, np.abs(ref).max()) * 1e-3, err_msg="%s N=%d" % (kind, N))
+
+
+def _residuals(lib, N, kind, lam, with_cols):
+    """d_sums (pre-filled with NaN) and, with_cols, the columns of one pinn_residuals call for the one stage flag."""
+    import hip_helpers as hh
+    from pinn_amd import _lib
+    x, u, y, aff = _rows(N)
+    work, wb = _work(lib)
+    cols = torch.full((_lib.NCOLS, N), float("nan"), device=hh.dev()) if with_cols else None
+    sums = torch.full((_lib.NSUMS,), float("nan"), dtype=torch.float64, device=hh.dev())
+    _lib.check(lib.pinn_residuals(hh.ptr(x), hh.ptr(u), hh.ptr(y), ctypes.byref(aff), hh.ptr(lam), _flag(kind), N,
+                                  hh.ptr(cols) if with_cols else None, N if with_cols else 0, hh.ptr(sums), hh.ptr(work), wb, hh.stream()),
+               "residuals")
+    return sums.cpu().numpy(), (cols.cpu().numpy() if with_cols else None)
+
+
+@pytest.mark.parametrize("kind", ["V", "T", "H", "O"])
+@pytest.mark.parametrize("N", [1, 64, 255, 256])
+def test_stage_pass_one_workgroup_equals_row_pass_to_the_byte(lib, N, kind):
+    """Up to 256 rows the cached pass, the row pass specialised for the stage and the row pass with run-time flags (columns) are
+    each one workgroup in which thread t holds row t alone: the reduction trees coincide, so any difference in a sum is a
+    difference in a formula."""
+    import hip_helpers as hh
+    lam = _lam0().to(hh.dev())
+    work, wb = _work(lib)
+    cached = _cached(lib, N, kind, _prepare(lib, N, kind, lam), lam, work, wb)
+    spec, _ = _residuals(lib, N, kind, lam, False)
+    gen, _ = _residuals(lib, N, kind, lam, True)
+    live = _live(kind)
+    print("N %d %s\n  cached    %s\n  residuals %s\n  + columns %s" % (N, kind, cached[live].tolist(), spec[live].tolist(), gen[live].tolist()))
+    assert np.all(np.isfinite(spec[live])) and spec[live][0] > 0.0
+    assert cached.tobytes() == spec.tobytes(), (kind, N, np.flatnonzero(cached != spec))
+    assert gen.tobytes() == spec.tobytes(), (kind, N, np.flatnonzero(gen != spec))
+
+
+@pytest.mark.parametrize("stage,kind", [("LAMBDA_PM", "V"), ("LAMBDA_F", "V"), ("THERMAL", "T"), ("HYDROGEN", "H"), ("OXYGEN", "O")])
+@pytest.mark.parametrize("N", [1, 64])
+def test_persistent_kernel_sums_equal_row_pass_to_the_byte(lib, N, stage, kind):
+    """One iteration of the persistent stage kernel from the initial parameters: up to 64 rows only wave 0 holds rows (one each)
+    and the other waves add +0.0, so its d_sums are pinn_residuals' for the stage's flag, byte for byte."""
+    import hip_helpers as hh
+    from pinn_amd import _lib
+    x, u, y, aff = _rows(N)
+    lam = _lam0().to(hh.dev())
+    ref, _ = _residuals(lib, N, kind, lam, False)
+    swb = lib.pinn_lambda_stage_workspace_bytes(N)
+    swork = torch.empty(swb, dtype=torch.uint8, device=hh.dev())
+    lam_p, adam_p, loss_p = _lam0().to(hh.dev()), torch.zeros(2 * _lib.NLAMBDA, device=hh.dev()), torch.zeros(2, device=hh.dev())
+    sums = torch.full((_lib.NSUMS,), float("nan"), dtype=torch.float64, device=hh.dev())
+    _lib.check(lib.pinn_lambda_stage_run(getattr(_lib, "STAGE_" + stage), _flag(kind), hh.ptr(x), hh.ptr(u), hh.ptr(y), ctypes.byref(aff), N,
+                                         1e-3, 0.8, 1000, 0, 1, hh.ptr(lam_p), hh.ptr(adam_p), hh.ptr(loss_p), None, 1000, hh.ptr(sums),
+                                         hh.ptr(swork), swb, hh.stream()), "stage_run")
+    got = sums.cpu().numpy()
+    live = _live(kind)
+    print("N %d %s persistent %s\n  residuals %s" % (N, stage, got[live].tolist(), ref[live].tolist()))
+    assert np.all(np.isfinite(ref[live])) and ref[live][0] > 0.0
+    assert got.tobytes() == ref.tobytes(), (stage, N, np.flatnonzero(got != ref))
+
+
+def test_stage_cache_slots_equal_columns_to_the_byte(lib):
+    """What stage_prepare stores is what the row pass writes as columns: i5, E and V_out of the voltage model (VOUT5 is 5 V_out,
+    one float32 product) and T_out of the thermal model, at 257 rows (two workgroups)."""
+    import hip_helpers as hh
+    from pinn_amd import _lib
+    N = 257
+    lam = _lam0().to(hh.dev())
+    cv = _prepare(lib, N, "V", lam).view(6, N).cpu().numpy()
+    _, cols = _residuals(lib, N, "V", lam, True)
+    assert np.all(np.isfinite(cv[:4])) and np.all(np.isfinite(cols[_lib.C["VOUT5"]]))
+    for slot, col, scale in ((0, "I", None), (2, "ENERNST", None), (3, "VOUT5", np.float32(5.0))):
+        want = cv[slot] if scale is None else (cv[slot] * scale).astype(np.float32)
+        bad = np.flatnonzero(want.view(np.uint32) != cols[_lib.C[col]].view(np.uint32))
+        print("V slot %d against column %s: %d of %d rows differ" % (slot, col, bad.size, N))
+        assert bad.size == 0, (col, bad[:8], want[bad[:8]], cols[_lib.C[col]][bad[:8]])
+    ct = _prepare(lib, N, "T", lam).view(6, N).cpu().numpy()
+    _, cols = _residuals(lib, N, "T", lam, True)
+    bad = np.flatnonzero(ct[3].view(np.uint32) != cols[_lib.C["TOUT"]].view(np.uint32))
+    print("T slot 3 against column TOUT: %d of %d rows differ" % (bad.size, N))
+    assert np.all(np.isfinite(ct[3])) and bad.size == 0, (bad[:8], ct[3][bad[:8]])
 
 
 def test_stage_pass_matches_persistent_kernel(lib):

@@ -8,7 +8,7 @@ def pick(sub):
     return [r for r in rows if sub in r["Kernel_Name"]]
 kinds = ["V (lambda_PM)", "V (lambda_F)", "T", "H", "O"]
 total = 0.0
-for name in ("residuals_cached_kernel", "residuals_finalize", "lambda_step_kernel"):
+for name in ("residuals_cached_kernel", "sums_finalize<double>", "lambda_step_kernel"):   # (the finalize was residuals_finalize in traces before profiles/r10)
     k = pick(name)
     assert len(k) % 5 == 0 and len(k) >= 5 * steps, (name, len(k))
     k = k[-5 * steps:]                       # the timed steps: five launches each, in bench.py's stage order
