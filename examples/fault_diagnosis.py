@@ -3,7 +3,11 @@ results array on the device, fit the Gaussian mixture to the physics residual co
 components against the labels, print the confusion matrix of the held-out rows, then replay the recording in chunks
 through the risk monitor and the fault diagnoser side by side.
 
-    python examples/fault_diagnosis.py [--rows 6000] [--fault-rows 600] [--epochs 3000] [--components 20]
+    python examples/fault_diagnosis.py [--rows 6000] [--fault-rows 600] [--epochs 3000] [--components 20] [--select]
+
+With --select the number of components and the seed are not taken from the command line: `selection.select_gmm` fits the
+grid K in {2, 4, 8, 12, 16, 20, 24, 32} x seeds 0-2 in one batch on the training rows, scores every candidate on the
+held-out rows, prints the table and diagnoses with the candidate of the lowest BIC.
 """
 import argparse
 import os
@@ -14,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import pinn_amd  # noqa: E402
-from pinn_amd import diagnosis, risk, synth  # noqa: E402
+from pinn_amd import diagnosis, risk, selection, synth  # noqa: E402
 
 
 def main():
@@ -24,6 +28,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=3000)
     ap.add_argument("--mc-times", type=int, default=32)
     ap.add_argument("--components", type=int, default=20)
+    ap.add_argument("--select", action="store_true", help="choose the components and the seed by BIC over a grid")
     args = ap.parse_args()
 
     ds = synth.make_dataset(args.rows, (args.fault_rows,) * 12, seed=0)
@@ -40,8 +45,15 @@ def main():
     # every fourth kept row is held out (the reference draws a stratified random split with scikit-learn)
     pos = torch.arange(X.shape[0], device=X.device)
     test, train = pos[pos % 4 == 3], pos[pos % 4 != 3]
-    y_prob, y_pred, gmm, comp_fault_prob = diagnosis.fit_gmm_and_get_probabilities(
-        X[train], y[train], X[test], len(class_names), random_state=diagnosis.RANDOM_STATE, n_components=args.components)
+    if args.select:
+        gmm, sweep = selection.select_gmm(X[train], X_val=X[test], criterion="bic")
+        print(sweep.table())
+        print("selected by BIC: %d components, seed %d" % (gmm.n_components, gmm.random_state))
+        comp_fault_prob = gmm.label_map(X[train], y[train], len(class_names))
+        y_prob, y_pred = gmm.diagnose(X[test], comp_fault_prob)
+    else:
+        y_prob, y_pred, gmm, comp_fault_prob = diagnosis.fit_gmm_and_get_probabilities(
+            X[train], y[train], X[test], len(class_names), random_state=diagnosis.RANDOM_STATE, n_components=args.components)
     m = diagnosis.classification_metrics(y[test], y_pred, len(class_names))
     print("mixture: %d components, %d EM iterations, converged %s, lower bound %.4f" % (gmm.n_components, gmm.n_iter_, gmm.converged_,
                                                                                       gmm.lower_bound_))

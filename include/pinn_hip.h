@@ -540,6 +540,56 @@ int pinn_gmm_posterior(const double* d_arr, long long ld, long long n_arr_rows, 
                        int n_classes, double* d_log_prob_norm, double* d_resp, double* d_y_prob, long long* d_y_pred,
                        void* stream);
 
+/* ---- batches of mixtures: model selection over component counts and seeds --------------------------------------
+ * n_batch <= PINN_GMM_MAX_BATCH candidates are seeded, initialised, iterated and scored together over one row set (the row
+ * head above), one tol and one reg_covar.  Candidate c has n_comp[c] components (host array, 1..max_comp, max_comp <= 32).
+ * Its state block starts c * pinn_gmm_batch_state_stride(max_comp, n_feat) bytes into d_state and has exactly the
+ * single-model layout for its own n_comp[c]: the block is a valid d_state of pinn_gmm_posterior / _label_map / _em.  Every
+ * entry point is a fixed number of launches for the whole batch without a host synchronisation; the row passes run on a
+ * grid of (row blocks, candidates), the M-steps with one workgroup per candidate, and both are the single model's code: a
+ * candidate's bytes are those of the single-model calls and do not depend on what else is in the batch.  A candidate
+ * whose CONVERGED or STATUS word is set is skipped by every later launch and keeps its parameters; a covariance that is
+ * not positive definite sets that candidate's STATUS only.  n >= 1.  NULL or misaligned pointers, n_batch outside
+ * 1..PINN_GMM_MAX_BATCH and an n_comp[c] outside 1..max_comp: PINN_E_ARG; a workspace below
+ * pinn_gmm_batch_workspace_bytes(n, n_batch, max_comp, n_feat): PINN_E_WORKSPACE; both before any launch. */
+#define PINN_GMM_MAX_BATCH 1024
+
+size_t pinn_gmm_batch_state_stride(int max_comp, int n_feat);               /* bytes; 0 for sizes outside the limits */
+size_t pinn_gmm_batch_workspace_bytes(long long n_rows, int n_batch, int max_comp, int n_feat);   /* likewise */
+
+/* k-means++ seeds, one workgroup per candidate.  Zeroes the state blocks, writes their headers and the n_comp[c] centres
+ * into the means.  Centre 0 is position d_first[c] (clamped to [0, n)); centre k is the first position whose inclusive
+ * cumulative sum of the squared distance to the nearest centre so far exceeds d_u[c][k - 1] x total, n - 1 when none does
+ * (numpy's searchsorted(side="right") clamped; a zero total picks n - 1).  d_u: [n_batch][max_comp - 1] uniforms in [0, 1)
+ * (may be NULL when max_comp is 1).  The sum has a fixed order (256 contiguous chunks, then the chunk sums).  d_picks (may
+ * be NULL): [n_batch][max_comp] the positions picked. */
+int pinn_gmm_batch_seed(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                        const long long* d_row_index, long long n, int n_batch, const int* n_comp, int max_comp,
+                        const long long* d_first, const double* d_u, double* d_state, long long* d_picks, void* d_ws,
+                        size_t ws_bytes, void* stream);
+
+/* pinn_gmm_kmeans per candidate: n_iters Lloyd iterations, then the assignment to the final centres, d_labels [n_batch][n]. */
+int pinn_gmm_batch_kmeans(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                          const long long* d_row_index, long long n, int n_batch, const int* n_comp, int max_comp, int n_iters,
+                          double* d_state, long long* d_labels, void* d_ws, size_t ws_bytes, void* stream);
+
+/* pinn_gmm_mstep_init per candidate from its labels d_labels [n_batch][n]. */
+int pinn_gmm_batch_mstep_init(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                              const long long* d_row_index, long long n, int n_batch, const int* n_comp, int max_comp,
+                              const long long* d_labels, double reg_covar, double* d_state, void* d_ws, size_t ws_bytes,
+                              void* stream);
+
+/* pinn_gmm_em per candidate: n_iters iterations, two launches each for the whole batch. */
+int pinn_gmm_batch_em(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                      const long long* d_row_index, long long n, int n_batch, const int* n_comp, int max_comp, int n_iters,
+                      double tol, double reg_covar, double* d_state, void* d_ws, size_t ws_bytes, void* stream);
+
+/* d_sum[c] = the sum of log_prob_norm over the row set under candidate c's parameters, in a fixed order (rows of a tile,
+ * tiles of a workgroup, workgroups).  The row set need not be the one the candidates were fitted on. */
+int pinn_gmm_batch_score(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                         const long long* d_row_index, long long n, int n_batch, const int* n_comp, int max_comp,
+                         const double* d_state, double* d_sum, void* d_ws, size_t ws_bytes, void* stream);
+
 /* ---- fault detection: reference script 02 (cited as 02:<line>) ---------------------------------------------------
  * StandardScaler + multinomial logistic regression with an L2 penalty (02:195-207) and the ROC curve / AUC of
  * 1 - P(normal) (02:552-557), float64 throughout.  Rows are read in place as for the mixture above (column list, optional

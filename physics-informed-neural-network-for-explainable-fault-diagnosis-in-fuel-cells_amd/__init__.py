@@ -24,7 +24,8 @@ reached from `compare_methods` through `spectral_extras` (comparison); and the R
 (it runs the linear one), one-vs-one and solved by SMO in float64: `run_supervised_svm_kernel`, with `DeviceKernelSVC`,
 `build_kernel_svm_classifier` and `KernelSVMDiagnoser` (ksvm), reached from `compare_methods` through `kernel_extras` (comparison);
 and what script 02's four AUCs leave open, their intervals and paired tests: `auc_components`, `delong_covariance`, `auc_ci`,
-`delong_test`, `compare_aucs`, `bootstrap_auc`, `compare_feature_groups` (rocstat).
+`delong_test`, `compare_aucs`, `bootstrap_auc`, `compare_feature_groups` (rocstat); and the choice of the mixture's size and
+seed, all candidates fitted and scored in one batch: `gmm_sweep`, `select_gmm`, `GMMSweep` (selection).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -63,6 +64,7 @@ _LAZY = {
     "spectral_embedding": "spectral", "spectral_extras": "comparison",
     "auc_components": "rocstat", "delong_covariance": "rocstat", "auc_ci": "rocstat", "delong_test": "rocstat",
     "compare_aucs": "rocstat", "bootstrap_auc": "rocstat", "compare_feature_groups": "rocstat",
+    "gmm_sweep": "selection", "select_gmm": "selection", "GMMSweep": "selection",
 }
 
 

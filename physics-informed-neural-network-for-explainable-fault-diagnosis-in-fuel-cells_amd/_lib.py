@@ -73,7 +73,7 @@ RF_ABOVE, RF_BELOW, RF_TILE = 0, 1, 2048
 RF_SWEEP_WORDS = 24                     # float64 words of one candidate of pinn_rf_sweep (include/pinn_hip.h)
 
 # pinn_gmm.hip: limits, status and the 8-byte words of the state header
-GMM_MAX_COMP, GMM_MAX_FEAT, GMM_MAX_CLASSES, GMM_SINGULAR, GMM_TILE = 32, 8, 16, 1, 128
+GMM_MAX_COMP, GMM_MAX_FEAT, GMM_MAX_CLASSES, GMM_SINGULAR, GMM_TILE, GMM_MAX_BATCH = 32, 8, 16, 1, 128, 1024
 GMM_ST_ITER, GMM_ST_CONVERGED, GMM_ST_STATUS, GMM_ST_K, GMM_ST_D, GMM_ST_LOWER, GMM_ST_PREV, GMM_ST_CHANGE, GMM_ST_HEADER = range(9)
 
 # pinn_cluster.hip: limits, status and the 8-byte words of the state headers
@@ -137,6 +137,8 @@ E_RANGE = -4
 # the head of every entry point that reads rows of the results array in place (_device._DevRows.head()):
 # array, leading dimension, rows of the array, columns, their number, gather index or NULL, rows to read
 _ROWS = [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll]
+# what follows it in the pinn_gmm_batch_* entry points: candidates, their component counts (host array), the largest count
+_BATCH = [c_int, ctypes.POINTER(c_int), c_int]
 
 _SIGS = {
     "pinn_abi_version": (c_int, []),
@@ -210,6 +212,13 @@ _SIGS = {
     "pinn_gmm_kmeans": (c_int, _ROWS + [c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_gmm_label_map": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_gmm_posterior": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_gmm_batch_state_stride": (c_size_t, [c_int, c_int]),
+    "pinn_gmm_batch_workspace_bytes": (c_size_t, [c_ll, c_int, c_int, c_int]),
+    "pinn_gmm_batch_seed": (c_int, _ROWS + _BATCH + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_batch_kmeans": (c_int, _ROWS + _BATCH + [c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_batch_mstep_init": (c_int, _ROWS + _BATCH + [c_void_p, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_batch_em": (c_int, _ROWS + _BATCH + [c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gmm_batch_score": (c_int, _ROWS + _BATCH + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_lr_state_bytes": (c_size_t, [c_int, c_int]),
     "pinn_lr_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
     "pinn_lr_scaler": (c_int, _ROWS + [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -299,6 +299,8 @@ class DeviceGMM:
     step hands to its first M-step); `weights_init`, `means_init` and `precisions_init` all three; otherwise the package's
     own k-means (k-means++ seeds from a private generator seeded by `random_state`, then Lloyd iterations), whose result
     `weights_init` / `means_init` may override.  The own initialisation does not reproduce scikit-learn's draw for draw.
+    `n_init` stays 1: several seeds, and several component counts, are fitted together by `selection.select_gmm`, whose
+    criterion="lower_bound" over the seeds of one component count is scikit-learn's n_init rule.
 
     `fit`, `predict_proba`, `predict`, `score_samples`, `score` take X as a [n, D] array, or any array plus `columns`
     (and `row_index`): the device backend then reads the rows in place.  numpy in -> numpy out, device tensor in ->
@@ -310,7 +312,8 @@ class DeviceGMM:
         if covariance_type != "full":
             raise NotImplementedError("covariance_type=%r: only 'full' is implemented" % (covariance_type,))
         if n_init != 1:
-            raise NotImplementedError("n_init > 1 is not implemented")
+            raise NotImplementedError("n_init > 1 is not implemented here: selection.select_gmm(X, (n_components,), seeds, "
+                                      "criterion='lower_bound') fits the seeds in one batch and keeps the best")
         if warm_start:
             raise NotImplementedError("warm_start is not implemented")
         if init_params != "kmeans":
