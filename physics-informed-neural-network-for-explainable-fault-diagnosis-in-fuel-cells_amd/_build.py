@@ -59,7 +59,7 @@ SOURCES = [
     ("pinn_optim.hip", []),
     ("pinn_general.hip", []),
 ]
-HEADERS = ["pinn_mlp_core.h", "pinn_loss.h", "pinn_bf16_core.h", "pinn_x6_core.h", "pinn_wgrad_args.h", "pinn_rows.h", "pinn_lloyd.h", "pinn_ovo.h", "pinn_physics.h",
+HEADERS = ["pinn_mlp_core.h", "pinn_loss.h", "pinn_bf16_core.h", "pinn_x6_core.h", "pinn_wgrad_args.h", "pinn_wgrad_core.h", "pinn_rows.h", "pinn_lloyd.h", "pinn_ovo.h", "pinn_physics.h",
            os.path.join("..", "..", "include", "pinn_hip.h")]
 
 

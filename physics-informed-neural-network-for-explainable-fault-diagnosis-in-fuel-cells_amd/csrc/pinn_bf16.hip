@@ -1,6 +1,7 @@
 // pinn_bf16.hip -- bf16/fp32-mixed variants of the forward, MC-dropout and training kernels
 // (pinn_net_t.precision = PINN_PREC_BF16).  See pinn_bf16_core.h for the layout and policy.
 #include "pinn_bf16_core.h"
+#include "pinn_wgrad_core.h"
 
 namespace pinn {
 
@@ -283,24 +284,12 @@ __global__ __launch_bounds__(kThreads, 2) void train_chain_bf16_kernel(TrainArgs
 
 // =======================================================================================
 // weight gradients from the bf16 stash: v_mfma_f32_32x32x16_bf16, K = the 16 rows of a tile
-// (lane half hh supplies rows 8 hh .. 8 hh + 7 of its feature = 16 contiguous bytes)
+// (lane half hh supplies rows 8 hh .. 8 hh + 7 of its feature = 16 contiguous bytes); slice range, accumulator start and C/D
+// row map from pinn_wgrad_core.h, tiling table and problem list from pinn_wgrad_args.h
 // =======================================================================================
-typedef float f32x16b __attribute__((ext_vector_type(16)));
 #define PINN_MFMA32_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
-struct WgradArgsB {
-  const __bf16* P;   // [T16][OUT][16]
-  const __bf16* Q;   // [T16][IN][16] or nullptr (x rows, IN = 8)
-  const float* x;
-  long long n_rows;
-  int OUT, IN;
-  long long t16;
-  int n_slices;
-  long long slab_stride;
-  float* dW; float* db;
-  const float* s1; float* dvq;
-  const float* s2; const __bf16* R; float* dvr;
-};
+struct WgradArgsB : WgradArgsT<__bf16> {};
 
 template <int TI, int TJ>
 struct WFragB {
@@ -333,13 +322,8 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_bf16_kernel(WgradArgsB a) {
   const int wi = wave / WJ, wj = wave % WJ;
   const int hh = lane >> 5, i = lane & 31;
   const int i0 = wi * TI * 32, j0 = wj * TJ * 32;
-  f32x16b acc[TI][TJ];
-#pragma unroll
-  for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < TJ; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.0f;
+  f32x16 acc[TI][TJ];
+  zero_acc(acc);
   float bsum[TI], vq[TJ], vr[TI];
 #pragma unroll
   for (int ti = 0; ti < TI; ++ti) { bsum[ti] = 0.f; vr[ti] = 0.f; }
@@ -347,10 +331,8 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_bf16_kernel(WgradArgsB a) {
   for (int tj = 0; tj < TJ; ++tj) vq[tj] = 0.f;
 
   const int slice = blockIdx.x;
-  const long long per = (a.t16 + a.n_slices - 1) / a.n_slices;
-  const long long t_begin = slice * per;
-  long long t_end = t_begin + per;
-  if (t_end > a.t16) t_end = a.t16;
+  const SliceRange sr = slice_range(a, slice);
+  const long long t_begin = sr.t_begin, t_end = sr.t_end;
 
   WFragB<TI, TJ> cur, nxt;
   if (t_begin < t_end) wgrad_load_b<TI, TJ, QX>(cur, a, t_begin, i0, j0, hh, i);
@@ -406,7 +388,7 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_bf16_kernel(WgradArgsB a) {
       if (col < a.IN) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = i0 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          const int row = cd_row(r, hh, i0 + ti * 32);
           a.dW[so + (long long)row * a.IN + col] = acc[ti][tj][r];
         }
       }
@@ -431,25 +413,17 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_bf16_kernel(WgradArgsB a) {
   }
 }
 
-template <int TI, int TJ, int WI, int WJ, bool QX>
-static void launch_wgrad_b(const WgradArgsB& a, hipStream_t st) {
-  hipLaunchKernelGGL((wgrad_bf16_kernel<TI, TJ, WI, WJ, QX>), dim3(a.n_slices), dim3(kThreads), 0, st, a);
-}
 static int dispatch_wgrad_b(const WgradArgsB& a, hipStream_t st) {
-  const int to = a.OUT / 32, ti = (a.IN + 31) / 32;
-  if (a.Q == nullptr) {
-    if (to == 8) launch_wgrad_b<2, 1, 4, 1, true>(a, st);
-    else if (to == 4) launch_wgrad_b<1, 1, 4, 1, true>(a, st);
-    else return PINN_E_ARCH;
-    return PINN_OK;
-  }
-  if (to == 8 && ti == 8) launch_wgrad_b<4, 4, 2, 2, false>(a, st);
-  else if (to == 4 && ti == 8) launch_wgrad_b<2, 4, 2, 2, false>(a, st);
-  else if (to == 2 && ti == 4) launch_wgrad_b<1, 2, 2, 2, false>(a, st);
-  else if (to == 4 && ti == 4) launch_wgrad_b<2, 2, 2, 2, false>(a, st);
-  else if (to == 1 && ti == 2) launch_wgrad_b<1, 1, 1, 2, false>(a, st);
-  else return PINN_E_ARCH;
-  return PINN_OK;
+  const int to = a.OUT / 32;
+  if (a.Q == nullptr)
+    return visit_wgrad_tiling_x(to, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((wgrad_bf16_kernel<T::TI, T::TJ, T::WI, T::WJ, true>), dim3(a.n_slices), dim3(kThreads), 0, st, a);
+    }) ? PINN_OK : PINN_E_ARCH;
+  return visit_wgrad_tiling(to, (a.IN + 31) / 32, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((wgrad_bf16_kernel<T::TI, T::TJ, T::WI, T::WJ, false>), dim3(a.n_slices), dim3(kThreads), 0, st, a);
+  }) ? PINN_OK : PINN_E_ARCH;
 }
 
 // chain + weight-gradient launches of one bf16 training step (the fp32 finalize kernel is shared)
@@ -474,25 +448,11 @@ int launch_train_bf16(const pinn_net_t* net, const float* d_params, const float*
     }
   }
   if (phases & PINN_PHASE_WGRAD) {
-    const long long tot = L.total();
-    const long long hs = (long long)b.t16 * H * 16;
-    const __bf16* sh = (const __bf16*)b.stash_h;
-    const __bf16* dh = (const __bf16*)b.dpre_h;
-    WgradArgsB g{};
-    g.x = d_x; g.n_rows = n_rows; g.t16 = b.t16; g.n_slices = b.n_slices; g.slab_stride = tot;
-    g.P = dh; g.Q = nullptr; g.OUT = H; g.IN = 8; g.dW = b.slabs + L.w0(); g.db = b.slabs + L.b0();
-    int rc;
-    if ((rc = dispatch_wgrad_b(g, st))) return rc;
-    for (int l = 1; l < nh; ++l) {
-      g.P = dh + l * hs; g.Q = sh + (l - 1) * hs; g.OUT = H; g.IN = H; g.dW = b.slabs + L.w(l); g.db = b.slabs + L.b(l);
-      if ((rc = dispatch_wgrad_b(g, st))) return rc;
-    }
-    g.P = (const __bf16*)b.dpre_v1; g.Q = sh + (nh - 1) * hs; g.OUT = H / 2; g.IN = H; g.dW = b.slabs + L.wv0(); g.db = b.slabs + L.bv0();
-    g.s1 = b.du; g.dvq = b.slabs + L.wp();
-    if ((rc = dispatch_wgrad_b(g, st))) return rc;
-    g.P = (const __bf16*)b.dpre_v2; g.Q = (const __bf16*)b.stash_v1; g.OUT = H / 4; g.IN = H / 2; g.dW = b.slabs + L.wv1(); g.db = b.slabs + L.bv1();
-    g.s1 = nullptr; g.dvq = nullptr; g.s2 = b.dz; g.R = (const __bf16*)b.stash_v2; g.dvr = b.slabs + L.wv2();
-    if ((rc = dispatch_wgrad_b(g, st))) return rc;
+    // (one after the other on the caller's stream whatever the route, in the common order of for_each_wgrad_problem)
+    const int rc = for_each_wgrad_problem(b, H, nh, 2, PINN_PHASE_WGRAD_HEAD | PINN_PHASE_WGRAD_TAIL, [&](const WgradProblem& w) -> int {
+      return dispatch_wgrad_b(wgrad_args<WgradArgsB>(w, b, d_x, n_rows, L.total()), st);
+    });
+    if (rc) return rc;
   }
   return PINN_OK;
 }

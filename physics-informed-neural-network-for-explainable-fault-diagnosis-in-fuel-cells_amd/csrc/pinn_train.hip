@@ -8,18 +8,17 @@
 //   K6 wgrad_kernel : dW = dpre^T . h_prev as a split-K GEMM over row tiles (K = rows), operands
 //        read straight from the tiled stash as v_mfma_f32_32x32x2_f32 fragments (8 contiguous
 //        floats per lane and tile), fp32 partial slabs per K-slice; bias / vector-head gradients
-//        ride along as per-lane sums.
+//        ride along as per-lane sums.  What the kernels of this family share is in pinn_wgrad_core.h
+//        (device) and pinn_wgrad_args.h (arguments, tiling table, the step's problem list).
 //   grad_finalize_kernel : fixed-order sum of the slabs -> flat gradient (bitwise reproducible,
 //        no float atomics), already divided by the GLOBAL row count (data-parallel shards
 //        all-reduce it with SUM).
 #include <cstdlib>
 #include "pinn_mlp_core.h"
-#include "pinn_wgrad_args.h"
+#include "pinn_wgrad_core.h"
 #include "pinn_adam_update.h"
 
 namespace pinn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kMaxSlices = 256;
 
@@ -192,11 +191,6 @@ __global__ __launch_bounds__(kThreads, 2) void train_chain_kernel(TrainArgs a) {
 // ---------------------------------------------------------------------------------------
 #define PINN_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
-template <int TI, int TJ>
-struct WFrag {
-  f32x4 a[TI][2], b[TJ][2];
-};
-
 template <int TI, int TJ, bool QX>
 __device__ __forceinline__ void wgrad_load(WFrag<TI, TJ>& f, const WgradArgs& a, long long t, int i0, int j0, int hh, int i) {
   const float* pP = a.P + ((t * a.OUT + i0 + i) * 16 + 8 * hh);
@@ -234,12 +228,7 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_kernel(WgradArgs a) {
   const int i0 = blockIdx.y * (TI * 32 * WI) + wi * TI * 32, j0 = wj * TJ * 32;     // blockIdx.y: output block (wide nets' layer 0)
 
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < TJ; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.0f;
+  zero_acc(acc);
   // (bias sums: a slice adds up to a few thousand rows per lane one after the other, where torch sums pairwise -- fp32 over
   //  eight tiles, those partial sums in float64; float64 adds in every tile cost the layer-0 kernel a quarter of its time)
   double bsum[TI];
@@ -251,10 +240,8 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_kernel(WgradArgs a) {
   for (int tj = 0; tj < TJ; ++tj) vq[tj] = 0.f;
 
   const int slice = blockIdx.x;
-  const long long per = (a.t16 + a.n_slices - 1) / a.n_slices;
-  const long long t_begin = slice * per;
-  long long t_end = t_begin + per;
-  if (t_end > a.t16) t_end = a.t16;
+  const SliceRange sr = slice_range(a, slice);
+  const long long t_begin = sr.t_begin, t_end = sr.t_end;
 
   // software pipeline, two tiles deep where the registers allow (< 256 accumulator registers): the fragments and the
   // vector-head operands of tiles t+1 and t+2 are in flight while tile t multiplies (one tile ahead is about one HBM
@@ -353,7 +340,7 @@ __global__ __launch_bounds__(kThreads, 1) void wgrad_kernel(WgradArgs a) {
       if (col < a.IN) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = i0 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          const int row = cd_row(r, hh, i0 + ti * 32);
           a.dW[so + (long long)row * a.IN + col] = acc[ti][tj][r];
         }
       }
@@ -589,27 +576,20 @@ static int row_scale_boost(const DropDev& d, int nh) {
   return c < 0 ? 0 : (c > 12 ? 12 : c);
 }
 
-template <int TI, int TJ, int WI, int WJ, bool QX>
-static void launch_wgrad(const WgradArgs& a, hipStream_t st, int out_blocks = 1) {
-  hipLaunchKernelGGL((wgrad_kernel<TI, TJ, WI, WJ, QX>), dim3(a.n_slices, out_blocks), dim3(kThreads), 0, st, a);
-}
-
-// pick the wave tiling for an [OUT x IN] gradient (tiles of 32x32; IN = 8 is padded to one tile)
+// pick the wave tiling for an [OUT x IN] gradient (visit_wgrad_tiling, pinn_wgrad_args.h) and launch it
 static int dispatch_wgrad(const WgradArgs& a, hipStream_t st) {
-  const int to = a.OUT / 32, ti = (a.IN + 31) / 32;
-  if (a.Q == nullptr) {
-    if (to % 8 == 0) launch_wgrad<2, 1, 4, 1, true>(a, st, to / 8);       // 256 outputs per workgroup
-    else if (to == 4) launch_wgrad<1, 1, 4, 1, true>(a, st);
-    else return PINN_E_ARCH;
-    return PINN_OK;
+  const int to = a.OUT / 32;
+  if (a.Q == nullptr) {      // layer 0: blocks of 256 outputs
+    const int out_blocks = to % 8 == 0 ? to / 8 : 1;
+    return visit_wgrad_tiling_x(to % 8 == 0 ? 8 : to, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((wgrad_kernel<T::TI, T::TJ, T::WI, T::WJ, true>), dim3(a.n_slices, out_blocks), dim3(kThreads), 0, st, a);
+    }) ? PINN_OK : PINN_E_ARCH;
   }
-  if (to == 8 && ti == 8) launch_wgrad<4, 4, 2, 2, false>(a, st);
-  else if (to == 4 && ti == 8) launch_wgrad<2, 4, 2, 2, false>(a, st);
-  else if (to == 2 && ti == 4) launch_wgrad<1, 2, 2, 2, false>(a, st);
-  else if (to == 4 && ti == 4) launch_wgrad<2, 2, 2, 2, false>(a, st);
-  else if (to == 1 && ti == 2) launch_wgrad<1, 1, 1, 2, false>(a, st);
-  else return PINN_E_ARCH;
-  return PINN_OK;
+  return visit_wgrad_tiling(to, (a.IN + 31) / 32, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((wgrad_kernel<T::TI, T::TJ, T::WI, T::WJ, false>), dim3(a.n_slices), dim3(kThreads), 0, st, a);
+  }) ? PINN_OK : PINN_E_ARCH;
 }
 
 // the other families' launchers, and the loss partials their chains write for n_rows rows (one per workgroup of the kernel that
@@ -744,91 +724,43 @@ struct WgradStreams {
   }
 };
 
-// tail = the layers whose d pre-activations the backward chain finishes first (last hidden layer, heads); head = the rest
-static bool in_part(const TrainCall& c, int l) {      // hidden layer l >= 1
-  return c.phases & (l == c.net->n_hidden - 1 ? PINN_PHASE_WGRAD_TAIL : PINN_PHASE_WGRAD_HEAD);
-}
-
 // PINN_PREC_F32X6: the chain kernels (fused nets) / layer kernels (wide nets) left every operand as fp16 fragments
 // (pinn_x6_core.h), the row scales in the meta records
 static int launch_wgrads_packed(const TrainCall& c, WgradStreams& s) {
-  const int H = c.net->hidden, nh = c.net->n_hidden;
-  const ParamLayout L{H, nh};
   const TrainBuffers& b = c.b;
   const bool multi = c.w.route == kRouteMulti;
-  const bool do_tail = c.phases & PINN_PHASE_WGRAD_TAIL, do_head = c.phases & PINN_PHASE_WGRAD_HEAD;
-  int rc;
   WgradPMulti mp{};
-  auto issue = [&](const WgradPArgs& pa, int kind) -> int {
-    if (!multi) return dispatch_wgrad_p(pa, (void*)s.pick());
-    mp.p[mp.n] = pa; mp.kind[mp.n] = kind; ++mp.n;
+  const int rc = for_each_wgrad_problem(b, c.net->hidden, c.net->n_hidden, 4, c.phases, [&](const WgradProblem& w) -> int {
+    WgradPArgs p{};
+    p.meta = b.rowmeta; p.emax = b.emax; p.qboost = b.qboost;
+    p.t16 = b.t16; p.n_slices = b.n_slices; p.slab_stride = ParamLayout{c.net->hidden, c.net->n_hidden}.total(); p.q_log2 = 3;
+    p.P = w.P; p.Q = w.Q; p.OUT = w.OUT; p.IN = w.IN; p.dW = b.slabs + w.w; p.db = b.slabs + w.b;
+    if (w.kind == 0) {
+      // layer 0: dW0 = d pre_0^T x with the rows as a packed group of their own (8 features of 32, stored as x / 16: any
+      // |x| < 256 survives the row scale in fp16); [H][8] of the [H][32] product is written
+      p.Q = (const char*)b.stash_x; p.IN = 32; p.ldW = 8; p.n_cols = 8; p.q_log2 = -4;
+    }
+    if (w.kind == 2) p.dvq = b.slabs + w.v;
+    if (w.kind == 3) { p.s2 = b.dz; p.R = (const float*)w.R; p.dvr = b.slabs + w.v; }      // (fp32 operands)
+    if (!multi) return dispatch_wgrad_p(p, (void*)s.pick());
+    mp.p[mp.n] = p; mp.kind[mp.n] = w.kind; ++mp.n;
     return PINN_OK;
-  };
-  WgradPArgs p{};
-  p.meta = b.rowmeta; p.emax = b.emax; p.qboost = b.qboost;
-  p.t16 = b.t16; p.n_slices = b.n_slices; p.slab_stride = L.total(); p.q_log2 = 3;
-  const long long hb = b.t16 * H * 16 * 4;      // bytes per hidden-layer stash
-  if (do_head) {
-    // layer 0: dW0 = d pre_0^T x with the rows as a packed group of their own (8 features of 32, stored as x / 16: any
-    // |x| < 256 survives the row scale in fp16); [H][8] of the [H][32] product is written
-    p.P = (const char*)b.dpre_h; p.Q = (const char*)b.stash_x; p.OUT = H; p.IN = 32; p.dW = b.slabs + L.w0(); p.db = b.slabs + L.b0();
-    p.ldW = 8; p.n_cols = 8; p.q_log2 = -4;
-    if ((rc = issue(p, 0))) return rc;
-    p.ldW = 0; p.n_cols = 0; p.q_log2 = 3;
-  }
-  for (int l = nh - 1; l >= 1; --l) {
-    if (!in_part(c, l)) continue;
-    p.P = (const char*)b.dpre_h + l * hb; p.Q = (const char*)b.stash_h + (l - 1) * hb; p.OUT = H; p.IN = H; p.dW = b.slabs + L.w(l); p.db = b.slabs + L.b(l);
-    if ((rc = issue(p, 1))) return rc;
-  }
-  if (do_tail) {
-    // variance head layer 0 (+ predict weight: dw_p[j] = sum du * h_last[j])
-    p.P = (const char*)b.dpre_v1; p.Q = (const char*)b.stash_h + (nh - 1) * hb; p.OUT = H / 2; p.IN = H; p.dW = b.slabs + L.wv0(); p.db = b.slabs + L.bv0();
-    p.dvq = b.slabs + L.wp();
-    if ((rc = issue(p, 2))) return rc;
-    // variance head layer 1 (+ final weight: dwv2[i] = sum dz * v2[i], fp32 operands)
-    p.P = (const char*)b.dpre_v2; p.Q = (const char*)b.stash_v1; p.OUT = H / 4; p.IN = H / 2; p.dW = b.slabs + L.wv1(); p.db = b.slabs + L.bv1();
-    p.dvq = nullptr; p.s2 = b.dz; p.R = (const float*)b.stash_v2; p.dvr = b.slabs + L.wv2();
-    if ((rc = issue(p, 3))) return rc;
-  }
+  });
+  if (rc) return rc;
   return multi && mp.n > 0 ? dispatch_wgrad_p_multi(mp, (void*)c.st) : PINN_OK;
 }
 
 // every other precision: fp32 operands in the tiled stash.  Operand split of the kernels: 0 = exact fp32 (wgrad_kernel); 3 = three
 // bf16 parts, six products (PINN_PREC_F32X6_G6); 1 = bf16-mixed (wide nets under PINN_PREC_BF16)
 static int launch_wgrads_fp32_stash(const TrainCall& c, WgradStreams& s) {
-  const int H = c.net->hidden, nh = c.net->n_hidden;
-  const ParamLayout L{H, nh};
-  const TrainBuffers& b = c.b;
-  const float* stash_h = (const float*)b.stash_h;
-  const float* dpre_h = (const float*)b.dpre_h;
-  const long long hs = b.t16 * H * 16;   // floats per hidden-layer stash
   const int ns = c.net->precision == PINN_PREC_F32X6_G6 ? 3 : (c.net->precision == PINN_PREC_BF16 ? 1 : 0);
-  auto wgrad = [&](const WgradArgs& wa) { hipStream_t s_ = s.pick(); return ns ? dispatch_wgrad_x6(wa, ns, (void*)s_) : dispatch_wgrad(wa, s_); };
-  int rc;
-  WgradArgs g{};
-  g.x = c.x; g.n_rows = c.n_rows; g.t16 = b.t16; g.n_slices = b.n_slices; g.slab_stride = L.total();
-  if (c.phases & PINN_PHASE_WGRAD_HEAD) {
+  const long long tot = ParamLayout{c.net->hidden, c.net->n_hidden}.total();
+  return for_each_wgrad_problem(c.b, c.net->hidden, c.net->n_hidden, 4, c.phases, [&](const WgradProblem& w) -> int {
+    const WgradArgs g = wgrad_args<WgradArgs>(w, c.b, c.x, c.n_rows, tot);
+    hipStream_t st = s.pick();
     // layer 0: dW0 = dpre_0 x^T (exact fp32 at every precision)
-    g.P = dpre_h; g.Q = nullptr; g.OUT = H; g.IN = 8; g.dW = b.slabs + L.w0(); g.db = b.slabs + L.b0();
-    if ((rc = dispatch_wgrad(g, s.pick()))) return rc;
-  }
-  for (int l = nh - 1; l >= 1; --l) {
-    if (!in_part(c, l)) continue;
-    g.P = dpre_h + l * hs; g.Q = stash_h + (l - 1) * hs; g.OUT = H; g.IN = H; g.dW = b.slabs + L.w(l); g.db = b.slabs + L.b(l);
-    if ((rc = wgrad(g))) return rc;
-  }
-  if (c.phases & PINN_PHASE_WGRAD_TAIL) {
-    // variance head layer 0 (+ predict weight: dw_p[j] = sum du * h_last[j])
-    g.P = (const float*)b.dpre_v1; g.Q = stash_h + (nh - 1) * hs; g.OUT = H / 2; g.IN = H; g.dW = b.slabs + L.wv0(); g.db = b.slabs + L.bv0();
-    g.s1 = b.du; g.dvq = b.slabs + L.wp();
-    if ((rc = wgrad(g))) return rc;
-    // variance head layer 1 (+ final weight: dwv2[i] = sum dz * v2[i])
-    g.P = (const float*)b.dpre_v2; g.Q = (const float*)b.stash_v1; g.OUT = H / 4; g.IN = H / 2; g.dW = b.slabs + L.wv1(); g.db = b.slabs + L.bv1();
-    g.s1 = nullptr; g.dvq = nullptr; g.s2 = b.dz; g.R = (const float*)b.stash_v2; g.dvr = b.slabs + L.wv2();
-    if ((rc = wgrad(g))) return rc;
-  }
-  return PINN_OK;
+    return ns && w.kind != 0 ? dispatch_wgrad_x6(g, ns, (void*)st) : dispatch_wgrad(g, st);
+  });
 }
 
 // the per-layer weight gradients into the slices' slabs

@@ -6,7 +6,9 @@
 //                     (PINN_PREC_F32X6_G6)
 //     NS = 1:  hi.hi  (bf16-mixed: PINN_PREC_BF16 on the wide nets)
 // PINN_PREC_F32X6 reads the packed fp16 stash instead (wgrad_p_kernel below), on the fused and the wide nets.
-// Same slices / slabs / bias and vector-head sums as wgrad_kernel (pinn_train.hip); layer 0 (IN = 8) stays there.
+// Same slices / slabs / bias and vector-head sums as wgrad_kernel (pinn_train.hip); layer 0 (IN = 8) stays there.  The pieces
+// shared with it are in pinn_wgrad_core.h (slice range, accumulator start, C/D row map, slab store, product order); the
+// tiling table and the argument structs in pinn_wgrad_args.h.
 #include <cstdlib>
 #include "pinn_x6_core.h"
 #ifdef PINN_ABL_NTLOAD
@@ -16,13 +18,10 @@
 #define PINN_WG_LD4(p) (*reinterpret_cast<const f32x4*>(p))
 #define PINN_WG_AUX 0
 #endif
-#include "pinn_wgrad_args.h"
+#include "pinn_wgrad_core.h"
 
 namespace pinn {
 namespace x6 {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define PINN_MFMA32_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
 // 8 fp32 -> NS bf16x8 parts
 template <int NS>
@@ -61,11 +60,7 @@ __device__ __forceinline__ Parts<NS> split8(const f32x4& v0, const f32x4& v1) {
 #define PINN_MFMA32_F16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 
 template <int TI, int TJ>
-struct Raw {
-  f32x4 a[TI][2], b[TJ][2];
-};
-template <int TI, int TJ>
-__device__ __forceinline__ void wgrad_load(Raw<TI, TJ>& f, const WgradArgs& a, long long t, int i0, int j0, int hh, int i) {
+__device__ __forceinline__ void wgrad_load(WFrag<TI, TJ>& f, const WgradArgs& a, long long t, int i0, int j0, int hh, int i) {
   const float* pP = a.P + ((t * a.OUT + i0 + i) * 16 + 8 * hh);
 #pragma unroll
   for (int ti = 0; ti < TI; ++ti) {
@@ -91,12 +86,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_x_kernel(WgradArgs a) {
   const bool row_sums = wj == 0 && blockIdx.z == 0, col_sums = wi == 0 && blockIdx.y == 0;
 
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < TJ; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.0f;
+  zero_acc(acc);
   double bsum[TI];        // (float64: a slice adds thousands of rows one after the other, where torch sums pairwise)
   float vq[TJ], vr[TI];
 #pragma unroll
@@ -105,10 +95,8 @@ __global__ __launch_bounds__(256, 1) void wgrad_x_kernel(WgradArgs a) {
   for (int tj = 0; tj < TJ; ++tj) vq[tj] = 0.f;
 
   const int slice = blockIdx.x;
-  const long long per = (a.t16 + a.n_slices - 1) / a.n_slices;
-  const long long t_begin = slice * per;
-  long long t_end = t_begin + per;
-  if (t_end > a.t16) t_end = a.t16;
+  const SliceRange sr = slice_range(a, slice);
+  const long long t_begin = sr.t_begin, t_end = sr.t_end;
 
   // software pipeline, two tiles deep where the registers allow (< 256 accumulator registers): the fp32 fragments and the
   // vector-head operands of tiles t+1 and t+2 are in flight while tile t is split and multiplied -- one tile ahead is
@@ -118,7 +106,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_x_kernel(WgradArgs a) {
   const bool want_r = row_sums && a.dvr, want_q = col_sums && a.dvq;
   auto load_r = [&](long long t, int ti, int sg) { return PINN_WG_LD4(a.R + ((t * a.OUT + i0 + i) * 16 + 8 * hh) + ti * 512 + sg * 4); };
   auto load_s = [&](const float* sv, long long t, int sg) { return PINN_WG_LD4(sv + t * 16 + 8 * hh + sg * 4); };
-  auto fetch = [&](Raw<TI, TJ>& f, Side& sd, long long t) {
+  auto fetch = [&](WFrag<TI, TJ>& f, Side& sd, long long t) {
     if (t >= t_end) t = t_end - 1;
     wgrad_load<TI, TJ>(f, a, t, i0, j0, hh, i);
     if constexpr (kDeep) {
@@ -133,22 +121,13 @@ __global__ __launch_bounds__(256, 1) void wgrad_x_kernel(WgradArgs a) {
       }
     }
   };
-  auto tile = [&](const Raw<TI, TJ>& cur, const Side& sd, long long t) {
+  auto tile = [&](const WFrag<TI, TJ>& cur, const Side& sd, long long t) {
     Parts<NS> pa[TI], pb[TJ];
 #pragma unroll
     for (int ti = 0; ti < TI; ++ti) pa[ti] = split8<NS>(cur.a[ti][0], cur.a[ti][1]);
 #pragma unroll
     for (int tj = 0; tj < TJ; ++tj) pb[tj] = split8<NS>(cur.b[tj][0], cur.b[tj][1]);
-    // products (sa, sb) with sa + sb < NS, smallest first
-#pragma unroll
-    for (int tot = NS - 1; tot >= 0; --tot)
-#pragma unroll
-      for (int sa = 0; sa <= tot; ++sa)
-#pragma unroll
-        for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-          for (int tj = 0; tj < TJ; ++tj)
-            acc[ti][tj] = PINN_MFMA32_BF16(__builtin_bit_cast(bf16x8, pa[ti].p[sa]), __builtin_bit_cast(bf16x8, pb[tj].p[tot - sa]), acc[ti][tj]);
+    split_products<NS>(acc, pa, pb);
     if (row_sums) {
 #pragma unroll
       for (int ti = 0; ti < TI; ++ti)
@@ -180,7 +159,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_x_kernel(WgradArgs a) {
     }
   };
   if constexpr (kDeep) {
-    Raw<TI, TJ> f0, f1, f2;
+    WFrag<TI, TJ> f0, f1, f2;
     Side d0, d1, d2;
     if (t_begin < t_end) { fetch(f0, d0, t_begin); fetch(f1, d1, t_begin + 1); }
     for (long long t = t_begin; t < t_end; t += 3) {
@@ -190,7 +169,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_x_kernel(WgradArgs a) {
       if (t + 2 < t_end) { fetch(f1, d1, t + 4); tile(f2, d2, t + 2); }
     }
   } else {
-    Raw<TI, TJ> cur, nxt;
+    WFrag<TI, TJ> cur, nxt;
     Side none;
     if (t_begin < t_end) fetch(cur, none, t_begin);
     for (long long t = t_begin; t < t_end; ++t) {
@@ -202,17 +181,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_x_kernel(WgradArgs a) {
 
   // ---- write this slice's slab
   const long long so = (long long)slice * a.slab_stride;
-#pragma unroll
-  for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < TJ; ++tj) {
-      const int col = j0 + tj * 32 + i;          // input feature (C/D layout: column on the lane)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = i0 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-        a.dW[so + (long long)row * a.IN + col] = acc[ti][tj][r];
-      }
-    }
+  store_slab(a, so, acc, i0, j0, hh, i);
   if (row_sums) {
 #pragma unroll
     for (int ti = 0; ti < TI; ++ti) {
@@ -252,21 +221,14 @@ __global__ __launch_bounds__(256, 1) void wgrad_d_kernel(WgradArgs a) {
   const bool row_sums = wj == 0 && blockIdx.z == 0;
 
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < TJ; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.0f;
+  zero_acc(acc);
   double bsum[TI];
 #pragma unroll
   for (int ti = 0; ti < TI; ++ti) bsum[ti] = 0.0;
 
   const int slice = blockIdx.x;
-  const long long per = (a.t16 + a.n_slices - 1) / a.n_slices;
-  const long long t_begin = slice * per;
-  long long t_end = t_begin + per;
-  if (t_end > a.t16) t_end = a.t16;
+  const SliceRange sr = slice_range(a, slice);
+  const long long t_begin = sr.t_begin, t_end = sr.t_end;
 
   // 2 x kFrags DMA instructions per tile: half q (rows 8 hh + 4 q ..) of fragment f, lane-linear 16 B per lane
   auto fetch = [&](long long t, int stage) {
@@ -280,7 +242,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_d_kernel(WgradArgs a) {
       __builtin_amdgcn_global_load_lds((gptr_t)(src + 4), (lptr_t)(st + f * 2048 + 1024), 16, 0, PINN_WG_AUX);
     }
   };
-  auto read = [&](Raw<TI, TJ>& r, int stage) {
+  auto read = [&](WFrag<TI, TJ>& r, int stage) {
     const char* st = ring + stage * kStage + lane * 16;
 #pragma unroll
     for (int ti = 0; ti < TI; ++ti) {
@@ -295,7 +257,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_d_kernel(WgradArgs a) {
   };
   if (t_begin < t_end) {
     auto clampt = [&](long long t) { return t < t_end ? t : t_end - 1; };
-    Raw<TI, TJ> cur, nxt;
+    WFrag<TI, TJ> cur, nxt;
     fetch(t_begin, 0);
     fetch(clampt(t_begin + 1), 1);
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * kFrags) : "memory");       // tile t_begin has landed
@@ -318,32 +280,14 @@ __global__ __launch_bounds__(256, 1) void wgrad_d_kernel(WgradArgs a) {
       for (int ti = 0; ti < TI; ++ti) pa[ti] = split8<NS>(cur.a[ti][0], cur.a[ti][1]);
 #pragma unroll
       for (int tj = 0; tj < TJ; ++tj) pb[tj] = split8<NS>(cur.b[tj][0], cur.b[tj][1]);
-#pragma unroll
-      for (int tot = NS - 1; tot >= 0; --tot)
-#pragma unroll
-        for (int sa = 0; sa <= tot; ++sa)
-#pragma unroll
-          for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < TJ; ++tj)
-              acc[ti][tj] = PINN_MFMA32_BF16(__builtin_bit_cast(bf16x8, pa[ti].p[sa]), __builtin_bit_cast(bf16x8, pb[tj].p[tot - sa]), acc[ti][tj]);
+      split_products<NS>(acc, pa, pb);
       cur = nxt;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the trailing re-fetches must land before the LDS is released
   }
 
   const long long so = (long long)slice * a.slab_stride;
-#pragma unroll
-  for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < TJ; ++tj) {
-      const int col = j0 + tj * 32 + i;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = i0 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-        a.dW[so + (long long)row * a.IN + col] = acc[ti][tj][r];
-      }
-    }
+  store_slab(a, so, acc, i0, j0, hh, i);
   if (row_sums) {
 #pragma unroll
     for (int ti = 0; ti < TI; ++ti) {
@@ -457,12 +401,7 @@ __device__ __forceinline__ void wgrad_p_body(const WgradPArgs& a, const int slic
   const int gP = a.OUT / 32, gQ = a.IN / 32;
 
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < TJ; ++tj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.0f;
+  zero_acc(acc);
   double bsum[TI];
   float vq[TJ], vr[TI];
 #pragma unroll
@@ -634,7 +573,7 @@ __device__ __forceinline__ void wgrad_p_body(const WgradPArgs& a, const int slic
       if (col < ncol) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = i0 + ti * 32 + tr_feature((r & 3) + 8 * (r >> 2) + 4 * hh);      // A's lane = row of the tile
+          const int row = i0 + ti * 32 + tr_feature(cd_row(r, hh));      // A's lane = row of the tile
           a.dW[so + (long long)row * ldw + col] = acc[ti][tj][r] * sw;
         }
       }
@@ -775,12 +714,8 @@ int dispatch_wgrad_x6(const WgradArgs& a, int ns, void* stream) {
   constexpr bool direct = false;
 #endif
   if (!direct && !a.dvq && !a.dvr && to % 8 == 0 && ti % 8 == 0) return launch_d<4, 4, 2, 2>(a, ns, st);   // plain layers: deep prefetch
-  if (to == 8 && ti == 8) launch<4, 4, 2, 2>(a, ns, st);
-  else if (to == 4 && ti == 8) launch<2, 4, 2, 2>(a, ns, st);
-  else if (to == 2 && ti == 4) launch<1, 2, 2, 2>(a, ns, st);
-  else if (to == 4 && ti == 4) launch<2, 2, 2, 2>(a, ns, st);
-  else if (to == 1 && ti == 2) launch<1, 1, 1, 2>(a, ns, st);
-  else if (to % 8 == 0 && ti % 8 == 0) launch<4, 4, 2, 2>(a, ns, st);        // wide nets: blocks of 256 x 256
+  if (visit_wgrad_tiling(to, ti, [&](auto t) { using T = decltype(t); launch<T::TI, T::TJ, T::WI, T::WJ>(a, ns, st); })) return PINN_OK;      // fused nets
+  if (to % 8 == 0 && ti % 8 == 0) launch<4, 4, 2, 2>(a, ns, st);             // wide nets: blocks of 256 x 256
   else if (to % 4 == 0 && ti % 8 == 0) launch<2, 4, 2, 2>(a, ns, st);        //            blocks of 128 x 256
   else return PINN_E_ARCH;
   return PINN_OK;
