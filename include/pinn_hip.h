@@ -1227,6 +1227,50 @@ int pinn_auc_bootstrap(const int* d_group_pos, const int* d_group_neg, long long
                        const long long* groups, unsigned long long seed, long long first, long long n_boot,
                        long long* d_u2, void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- exact Shapley attributions: which input made the model say so -------------------------------------------------
+ * f is a model with D <= PINN_GMM_MAX_FEAT inputs and C <= PINN_GMM_MAX_CLASSES outputs, the background a set of B rows.
+ * The value of a coalition S of inputs at a row x is the interventional one, v(S; x) = (1 / B) sum over b of f(z) with
+ * z_i = x_i for i in S and b_i otherwise, and the attribution of input j is
+ *   phi_j(x) = sum over S without j of |S|! (D - |S| - 1)! / D! (v(S + j) - v(S)),
+ * over all 2^D coalitions: nothing is sampled.  base = v(none), the mean prediction over the background; fx = v(all) = f(x);
+ * sum over j of phi_j = fx - base.  Outputs: d_phi [n][D][C], d_base [C], d_fx [n][C], float64.  Every sum has a fixed order
+ * that depends on B alone: the same call gives the same bytes, and a row's bytes do not depend on the other rows of the call.
+ *
+ * Rows and background are two row heads as above (array, leading dimension, rows of the array, column list, gather list or
+ * NULL, positions), with the same number of columns; they may be the same array.  A row position that reads nothing gets
+ * NaN outputs; a background position that reads nothing makes every output NaN.  Checks as make_rows': PINN_E_ARG for
+ * NULL or misaligned pointers and sizes outside the limits (n_bg >= 1), PINN_E_WORKSPACE for a workspace below
+ * pinn_shap_gmm_workspace_bytes (256-byte aligned), both before any launch.
+ *
+ * pinn_shap_gmm: f = d_y_prob of pinn_gmm_posterior under d_state and d_map [n_comp][n_classes], fused: a workgroup takes
+ * PINN_SHAP_TILE rows and one split of the background, staged through LDS in blocks of PINN_SHAP_BG_BLOCK rows (at most
+ * PINN_SHAP_MAX_SPLIT splits of whole blocks), and walks the coalitions on-chip; neither a hybrid row nor a coalition value is
+ * written.  d_fx is what pinn_gmm_posterior writes for the rows.  n = 0 writes nothing. */
+#define PINN_SHAP_TILE 128
+#define PINN_SHAP_BG_BLOCK 32
+#define PINN_SHAP_MAX_SPLIT 32
+
+size_t pinn_shap_gmm_workspace_bytes(long long n_rows, long long n_background, int n_feat, int n_classes);   /* 0 outside the limits */
+int pinn_shap_gmm(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                  const long long* d_row_index, long long n, const double* d_bg, long long ld_bg, long long n_bg_rows,
+                  const int* cols_bg, int n_feat_bg, const long long* d_bg_index, long long n_bg, int n_comp,
+                  const double* d_state, const double* d_map, int n_classes, double* d_phi, double* d_base, double* d_fx,
+                  void* d_ws, size_t ws_bytes, void* stream);
+
+/* Any model, in two calls with the caller's model between them.  pinn_shap_hybrid writes the hybrid rows of the row
+ * positions row0 .. row0 + n_chunk - 1 as a dense array d_out [n_chunk * 2^D * B][D], float64 (f64 != 0) or float32: row-major
+ * over (row, coalition, background), i.e. hybrid row (r * 2^D + S) * B + b takes column i from row r where bit i of S is
+ * set and from background row b otherwise (NaN where that position reads nothing).  pinn_shap_reduce takes the model's
+ * outputs on those rows, d_f [n_chunk * 2^D * B][C] float64 or float32, and returns d_phi [n_chunk][D][C], d_fx [n_chunk][C]
+ * and, when d_base is not NULL, d_base [C] from the chunk's first row; it sums in float64, background rows in order, then
+ * coalitions in order.  fx is the model's output on the first hybrid row of the full coalition, which is the row itself. */
+int pinn_shap_hybrid(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                     const long long* d_row_index, long long n, const double* d_bg, long long ld_bg, long long n_bg_rows,
+                     const int* cols_bg, int n_feat_bg, const long long* d_bg_index, long long n_bg, long long row0,
+                     long long n_chunk, int f64, void* d_out, void* stream);
+int pinn_shap_reduce(const void* d_f, int f64, long long n_chunk, int n_feat, long long n_bg, int n_classes, double* d_phi,
+                     double* d_base, double* d_fx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

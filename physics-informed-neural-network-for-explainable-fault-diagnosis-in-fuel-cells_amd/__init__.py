@@ -25,7 +25,9 @@ reached from `compare_methods` through `spectral_extras` (comparison); and the R
 `build_kernel_svm_classifier` and `KernelSVMDiagnoser` (ksvm), reached from `compare_methods` through `kernel_extras` (comparison);
 and what script 02's four AUCs leave open, their intervals and paired tests: `auc_components`, `delong_covariance`, `auc_ci`,
 `delong_test`, `compare_aucs`, `bootstrap_auc`, `compare_feature_groups` (rocstat); and the choice of the mixture's size and
-seed, all candidates fitted and scored in one batch: `gmm_sweep`, `select_gmm`, `GMMSweep` (selection).
+seed, all candidates fitted and scored in one batch: `gmm_sweep`, `select_gmm`, `GMMSweep` (selection); and the question after
+a diagnosis, which input made the model say so, as exact Shapley values over all coalitions: `shapley_diagnosis`,
+`shapley_values`, `voltage_predictor`, `DiagnosisExplainer`, `global_importance`, `top_features` (explain).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -65,6 +67,8 @@ _LAZY = {
     "auc_components": "rocstat", "delong_covariance": "rocstat", "auc_ci": "rocstat", "delong_test": "rocstat",
     "compare_aucs": "rocstat", "bootstrap_auc": "rocstat", "compare_feature_groups": "rocstat",
     "gmm_sweep": "selection", "select_gmm": "selection", "GMMSweep": "selection",
+    "shapley_values": "explain", "shapley_diagnosis": "explain", "voltage_predictor": "explain", "DiagnosisExplainer": "explain",
+    "global_importance": "explain", "top_features": "explain", "Shapley": "explain",
 }
 
 

@@ -48,6 +48,8 @@ SOURCES = [
     ("pinn_ksvm.hip", ["-ffp-contract=off"]),
     # ROC inference (DeLong components, 128-bit cross sums, bootstrap): integers only, so no float flag matters
     ("pinn_rocstat.hip", []),
+    # exact Shapley attributions: float64, every operation rounded on its own; the host backend states the same coalition sums
+    ("pinn_shap.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),
@@ -59,7 +61,7 @@ SOURCES = [
     ("pinn_optim.hip", []),
     ("pinn_general.hip", []),
 ]
-HEADERS = ["pinn_mlp_core.h", "pinn_loss.h", "pinn_bf16_core.h", "pinn_x6_core.h", "pinn_wgrad_args.h", "pinn_wgrad_core.h", "pinn_rows.h", "pinn_lloyd.h", "pinn_ovo.h", "pinn_physics.h",
+HEADERS = ["pinn_mlp_core.h", "pinn_loss.h", "pinn_bf16_core.h", "pinn_x6_core.h", "pinn_wgrad_args.h", "pinn_wgrad_core.h", "pinn_rows.h", "pinn_gmm_state.h", "pinn_lloyd.h", "pinn_ovo.h", "pinn_physics.h",
            os.path.join("..", "..", "include", "pinn_hip.h")]
 
 

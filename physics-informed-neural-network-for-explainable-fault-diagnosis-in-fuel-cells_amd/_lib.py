@@ -276,6 +276,10 @@ _SIGS = {
     "pinn_auc_bootstrap_workspace_bytes": (c_size_t, [c_ll, c_int, ctypes.POINTER(c_ll)]),
     "pinn_auc_bootstrap": (c_int, [c_void_p, c_void_p, c_ll, c_ll, c_int, ctypes.POINTER(c_ll), ctypes.c_ulonglong, c_ll, c_ll, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
+    "pinn_shap_gmm_workspace_bytes": (c_size_t, [c_ll, c_ll, c_int, c_int]),
+    "pinn_shap_gmm": (c_int, _ROWS + _ROWS + [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_shap_hybrid": (c_int, _ROWS + _ROWS + [c_ll, c_ll, c_int, c_void_p, c_void_p]),
+    "pinn_shap_reduce": (c_int, [c_void_p, c_int, c_ll, c_int, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -22,6 +22,7 @@
 
 #include "../../include/pinn_hip.h"
 #include "pinn_rows.h"
+#include "pinn_gmm_state.h"
 
 namespace pinn {
 namespace {
@@ -32,49 +33,14 @@ constexpr int kTri = kMaxD * (kMaxD + 1) / 2;
 constexpr int kMaxOut = (kMaxK * (1 + kMaxD + kTri) + kRows - 1) / kRows;      // output sums per thread: 12
 constexpr int kMaxBlocks = 1024;            // workgroups of a row pass = partial sums per output
 constexpr int kFinThreads = 256;
-constexpr int kHdr = 8;                     // 8-byte words of the state header
 
 enum { SRC_ESTEP = 0, SRC_RESP = 1, SRC_LABELS = 2, SRC_NEAREST = 3 };
 enum { OUT_MOMENTS = 0, OUT_CLASS = 1 };
 enum { FIN_MEANS = 0, FIN_INIT = 1, FIN_EM = 2, FIN_KMEANS = 3, FIN_MAP = 4 };
 
-// state block: header words, then weights[K], means[K][D], covariances[K][D][D], precisions_cholesky[K][D][D], logdet[K]
-__host__ __device__ inline size_t st_weights() { return kHdr; }
-__host__ __device__ inline size_t st_means(int K) { return kHdr + (size_t)K; }
-__host__ __device__ inline size_t st_cov(int K, int D) { return st_means(K) + (size_t)K * D; }
-__host__ __device__ inline size_t st_chol(int K, int D) { return st_cov(K, D) + (size_t)K * D * D; }
-__host__ __device__ inline size_t st_logdet(int K, int D) { return st_chol(K, D) + (size_t)K * D * D; }
-__host__ __device__ inline size_t st_words(int K, int D) { return st_logdet(K, D) + (size_t)K; }
-
 __device__ __forceinline__ bool stopped(const double* st) {
   const long long* h = reinterpret_cast<const long long*>(st);
   return h[PINN_GMM_ST_CONVERGED] != 0 || h[PINN_GMM_ST_STATUS] != 0;
-}
-
-// parameters of the state in LDS: means, upper-triangular precisions_cholesky (packed by columns), logdet, log weights
-struct Staged {
-  double* mu;      // [K][D]
-  double* U;       // [K][D (D + 1) / 2]
-  double* ld;      // [K]
-  double* lw;      // [K]
-};
-
-__device__ __forceinline__ void stage_params(const double* __restrict__ st, int K, int D, const Staged& s, bool density) {
-  const int T = D * (D + 1) / 2;
-  for (int e = threadIdx.x; e < K * D; e += blockDim.x) s.mu[e] = st[st_means(K) + e];
-  if (density) {
-    for (int e = threadIdx.x; e < K * T; e += blockDim.x) {
-      const int k = e / T, t = e - k * T;
-      int i, j;
-      untri(t, &i, &j);
-      s.U[e] = st[st_chol(K, D) + ((size_t)k * D + i) * D + j];
-    }
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-      s.ld[k] = st[st_logdet(K, D) + k];
-      s.lw[k] = log(st[st_weights() + k]);
-    }
-  }
-  __syncthreads();
 }
 
 // log(w_k N(x | mu_k, Sigma_k)) for every k into lp[k * stride]; returns log_prob_norm (scipy's logsumexp: max, sum, log)
