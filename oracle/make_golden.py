@@ -94,7 +94,9 @@ def edge_rows(ds, lamH3=197.715, lamO3=200.0):
     for k, tgt in enumerate([lamH3, np.nextafter(np.float32(lamH3), np.float32(1e9)), np.nextafter(np.float32(lamH3), np.float32(0)),
                              lamO3, 230.0, 210.0, 199.99, 200.01]):
         X[k, 0] = float(tgt) - 270e-5
-    # oxygen target clamps: high I*lambda_O2 pushes raw above 15 with the second lambda set
+    # the ends of the current range.  These rows do NOT reach the oxygen target's clamp(1.05, 15) with either recorded set: the second
+    # set's |lambda_O3| = 210 caps raw at 0.9 + 3.9 * 2.1 = 9.09, and its smallest raw is 0.9 + 3.9 * 0.55 = 3.05.  The clamp, the sign 0
+    # and the 1e-8 flow clamp are reached by the parameter sets and idle rows of tests/residual_referee.py instead.
     X[8:12, 0] = [404.0, 380.0, 60.0, 55.0]
     # act_O < 1 penalty rows: starve the air flow
     X[12:20, 7] *= 0.3

@@ -145,11 +145,17 @@ def _within(got, r64, r32, what, rel=1e-5):
 
 
 def _golden_rows(si):
+    """The fixture's edge rows with its parameter set `si` (0, 1), or with one of the sets of tests/residual_referee.py ("A", "B", "D":
+    the oxygen target clamped, so the inclusive clamp mask is 0 on those rows; "C": lambda_O3 = 0, the sign is 0)."""
     g = load_golden("g_resid.npz")
     sx, sy = ScalerFromArrays(g, "sx."), ScalerFromArrays(g, "sy.")
     x = torch.from_numpy(g["x"]).to(_dev())
     u = torch.from_numpy(g["u_eval"]).reshape(-1).to(_dev())
-    lam = torch.tensor(g["s%d.lambdas" % si], dtype=torch.float32).to(_dev())
+    if isinstance(si, str):
+        import residual_referee as rr
+        lam = torch.from_numpy(rr.param_sets()[si].copy()).to(_dev())
+    else:
+        lam = torch.tensor(g["s%d.lambdas" % si], dtype=torch.float32).to(_dev())
     return g, sx, sy, x, u, lam
 
 
@@ -195,10 +201,10 @@ def test_backward_golden_lambda_grads(lib, si):
 
 
 # 2. against a float64 referee, every column and subsets, golden rows and a multi-workgroup synthetic set
-@pytest.mark.parametrize("case", ["golden0", "golden1", "synthetic"])
+@pytest.mark.parametrize("case", ["golden0", "golden1", "synthetic", "goldenA", "goldenB", "goldenD"])
 def test_backward_vs_float64_referee(lib, case):
     if case.startswith("golden"):
-        g, sx, sy, x, u, lam = _golden_rows(int(case[-1]))
+        g, sx, sy, x, u, lam = _golden_rows(int(case[-1]) if case[-1].isdigit() else case[-1])
     else:
         sx, sy, x, u = _synthetic(100003)
         lam = torch.tensor([O.LAMBDA_INIT[k] for k in NAMES], dtype=torch.float32).to(_dev())
@@ -236,6 +242,28 @@ def test_backward_nan_rows_like_torch(lib):
             np.testing.assert_allclose(a[fin], b[fin], rtol=1e-3, atol=1e-3 * (np.abs(b[fin]).max() + 1e-30), err_msg=str((names, what)))
         if "FV" in names or "VCONC" in names:
             assert np.isnan(got[2][:, 5]).any()
+
+
+def test_backward_sign_zero_like_torch(lib):
+    """lambda_O3 = 0 (set C): the threshold |lambda_O3| is 0, every row is past it, and d|x|/dx at 0 is 0 in torch.  Where float32 torch
+    autograd has a gradient and where it has exactly none, so has the kernel."""
+    import residual_referee as rr
+    assert rr.edge_stats("C")["o_sgn"] == 0.0 and rr.edge_stats("C")["o_lin"] == 0
+    g, sx, sy, x, u, lam = _golden_rows("C")
+    aff = _aff(sx, sy)
+    n = x.shape[0]
+    lamv = lam.cpu().numpy()
+    for i, names in enumerate([ALL, COLS["O"], ["FO"], ["TGTO"]]):
+        up = _upstream(names, n, 17 + i)
+        got = res_backward(lib, x, u, aff, lam, up)
+        r32 = referee(x.cpu().numpy(), u.cpu().numpy(), lamv, sx, sy, up, torch.float32)
+        for what, a, b in zip(("glambda", "gu", "gx"), got, r32):
+            assert np.array_equal(np.isnan(a), np.isnan(b)), (names, what, np.argwhere(np.isnan(a) != np.isnan(b))[:5])
+            fin = ~np.isnan(b)
+            np.testing.assert_allclose(a[fin], b[fin], rtol=1e-3, atol=1e-3 * (np.abs(b[fin]).max() + 1e-30), err_msg=str((names, what)))
+        k = NAMES.index("lambda_O3")
+        assert got[0][k] == 0.0 and r32[0][k] == 0.0, (got[0][k], r32[0][k])
+        assert got[0][NAMES.index("lambda_O1")] != 0.0          # (the target itself is live: lambda_O1 + lambda_O2 0 / 100, inside the clamp)
 
 
 # 3. determinism, row windows, shards
