@@ -228,11 +228,11 @@ def _mm_chunked(a, b, k_chunk):
     return acc
 
 
-def bf16_train_step(params, x, y, p_list=None, masks=None, dtype=torch.float64, n_global=None, k_chunk=None, rounding=True):
+def bf16_train_step(params, x, y, p_list=None, masks=None, dtype=torch.float64, n_global=None, k_chunk=None, rounding=True, policy="fused"):
     """One training step (loss sums and every gradient tensor) under the rounding policy of the FUSED bf16/fp32-mixed kernels
     (pinn_net_t.precision = PINN_PREC_BF16, H in {128, 256}), by a manual backward -- NOT the reference's arithmetic.  The wide
-    nets' bf16 scheme (x6::B1 in csrc/pinn_wide.hip) stashes and contracts through the split-operand machinery and needs a
-    statement of its own; it is not restated here.
+    nets' bf16 scheme (x6::B1 in csrc/pinn_wide.hip) rounds at other points: policy="wide" (bf16_wide_train_step below states
+    them) runs the same forward, loss and chain with those points instead of the ones listed here.
 
     bf(.) below is value -> float32 -> bfloat16, round to nearest; everything else is computed in `dtype` (float64: the
     referee; float32: the kernels' own accumulator width).  Rounding points, with where the kernels have them (core =
@@ -267,6 +267,8 @@ def bf16_train_step(params, x, y, p_list=None, masks=None, dtype=torch.float64, 
     Returns (sums, grads, detail): sums = float64 array (sum of 0.5 prec e^2 + 0.5 s, sum |s|, sum e^2) = the kernels'
     loss[0..2]; grads in param_names order; detail = dict(u, logvar [N, 1], terms) with terms[i] = (g [N, out], inp [N, in]
     or None for a bias): gradient tensor i is g^T inp, row by row."""
+    assert policy in ("fused", "wide"), policy
+    wide = policy == "wide"
     nh = (len(params) - 8) // 2
     N = x.shape[0]
     n_global = N if n_global is None else n_global
@@ -274,6 +276,9 @@ def bf16_train_step(params, x, y, p_list=None, masks=None, dtype=torch.float64, 
     x = x.detach().to(dtype)
     y = y.detach().to(dtype).reshape(-1, 1)
     q = (lambda t: t.to(torch.float32).to(torch.bfloat16).to(dtype)) if rounding else (lambda t: t)
+    # what is rounded where it is STORED (the stash, the d pre-activations) or read as rows (x in dW_0): the fused kernels only.
+    # Every matrix product rounds its operands in both policies; on an already rounded value that is the identity.
+    qs = (lambda t: t) if wide else q
     mm = lambda a, b: _mm_chunked(a, b, k_chunk)
     lin = F.linear if k_chunk is None else (lambda h, W, b: mm(h, W.t()) + b)
     drop = masks is not None
@@ -308,28 +313,77 @@ def bf16_train_step(params, x, y, p_list=None, masks=None, dtype=torch.float64, 
         sums = np.array([float((0.5 * prec * e * e + 0.5 * s).double().sum()), float(s.abs().double().sum()),
                          float((e * e).double().sum())])
 
+        def stash_of(a, l):          # what the backward chain and the weight gradients read of a tanh + dropout module's output
+            if not wide:
+                return qs(a)
+            kept = keep[l] != 0 if drop else torch.ones_like(a, dtype=torch.bool)
+            return torch.where(kept & (a == 0), torch.full_like(a, 1.17549435e-38), a)      # stash_value: a kept zero stays "kept"
+
         def dact(d, stash, l):       # d pre-activation of a tanh + dropout module from its stashed output
             a = stash * float(np.float32(1.0) / np.float32(scale[l])) if dtype == torch.float32 else stash / scale[l]
             g = d * (scale[l] * (1.0 - a * a))
+            if wide:
+                return g * (stash != 0).to(g.dtype)      # "kept" is read off the stash; stored unrounded
             return q(g * keep[l] if drop else g)
 
-        # backward chain
-        g2 = q(P[k + 6] * dz * (1.0 - v2 * v2))
-        g1 = dact(mm(g2, q(P[k + 4])), q(v1), nh)
-        dh = P[k] * du + mm(g1, q(P[k + 2]))
+        sh, sv1, sv2 = [stash_of(hs[l], l) for l in range(nh)], stash_of(v1, nh), qs(v2)
+        # backward chain; a product rounds its operands, a stored d pre-activation is rounded in the fused policy only
+        g2 = qs(P[k + 6] * dz * (1.0 - v2 * v2))
+        g1 = dact(mm(q(g2), q(P[k + 4])), sv1, nh)
+        dh = P[k] * du + mm(q(g1), q(P[k + 2]))
         gh = [None] * nh
         for l in range(nh - 1, -1, -1):
-            gh[l] = dact(dh, q(hs[l]), l)
+            gh[l] = dact(dh, sh[l], l)
             if l > 0:
-                dh = mm(gh[l], q(P[2 * l]))
-        # weight gradients: g^T inp over the rows
+                dh = mm(q(gh[l]), q(P[2 * l]))
+        # weight gradients: g^T inp over the rows.  Matrices: both operands rounded (layer 0 -- wide: exact fp32 on the stored g_0 and x;
+        # fused: g_0 is stored rounded and x is rounded); bias sums: the STORED g; vector heads: the stash as it stands
         terms = []
         for l in range(nh):
-            terms += [(gh[l], q(x) if l == 0 else q(hs[l - 1])), (gh[l], None)]
-        terms += [(du, q(hs[-1])), (du, None), (g1, q(hs[-1])), (g1, None), (g2, q(v1)), (g2, None), (dz, q(v2)), (dz, None)]
+            terms += [(gh[0], qs(x)) if l == 0 else (q(gh[l]), q(sh[l - 1])), (gh[l], None)]
+        terms += [(du, sh[-1]), (du, None), (q(g1), q(sh[-1])), (g1, None), (q(g2), q(sv1)), (g2, None), (dz, sv2), (dz, None)]
         ones = x.new_ones(N, 1)
         grads = [mm(g.t(), ones).reshape(-1) if inp is None else mm(g.t(), inp) for g, inp in terms]
     return sums, grads, dict(u=u, logvar=s, terms=terms)
+
+
+def bf16_wide_train_step(params, x, y, p_list=None, masks=None, dtype=torch.float64, n_global=None, k_chunk=None, rounding=True):
+    """bf16_train_step under the rounding policy of the WIDE nets' bf16/fp32-mixed kernels (PINN_PREC_BF16, H in {512, 1024,
+    2048}): layer-by-layer kernels wide_layer_x6_kernel<x6::B1, ..> with an fp32 stash between them, weight gradients on
+    wgrad_d_kernel<.., 1> / wgrad_x_kernel<.., 1>.  Same arguments and return value.  Rounding points, with where the kernels have
+    them (wide = csrc/pinn_wide.hip, core = csrc/pinn_x6_core.h, wg = csrc/pinn_x6_wgrad.hip, train = csrc/pinn_train.hip, args =
+    csrc/pinn_wgrad_args.h, loss = csrc/pinn_loss.h, mlp = csrc/pinn_mlp_core.h):
+
+      forward (= mlp_forward(bf16=True), the fused forward: launch_train_chain_wide, wide:631-645)
+        layer 0 exact fp32, eight fmas (wide_input_kernel, wide:299-305), tanh and dropout a * scale (wide:307; mlp:414-417)
+        every later product bf(h) . bf(W) + b: the bias starts the accumulator (wide:130), the B operand is the fp32 stash rounded
+        where the kernel splits it (B1::split, core:364-367: a round-to-nearest cast, one part; wide:116, 156 with bsc = kActScale =
+        1, wide:98, core:355), the A operand is the first packed copy, bf(w) (csrc/pinn_x6.hip:56); fp32 accumulation, nothing
+        else scaled (kAccScale = 1)
+        predict head and z: dot products of the UNROUNDED stash (head_dot wide:365-371; wide:382-387 and, in training, 438-444)
+      stash: fp32 [T16][F][16], UNROUNDED: h_l and v1 after dropout (wide:326-327, 241-242), v2 (EPI_TANH, wide:246-248).  A kept
+        activation that is exactly 0 is stored as FLT_MIN (stash_value core:462-464; wide:238-239, 323-324), a dropped one as 0
+      loss, du, dz (wide_loss_kernel wide:447 -> loss_row, loss:38-57): as the fused step, 1 / n_global inside du and dz (wide:432)
+      backward (wide:660-672; epilogue EPI_BACKWARD, not packed: wide:196-212)
+        g2 = wv2 dz (1 - v2^2), stored UNROUNDED (wide:480, 483)
+        dv1 = bf(g2) . bf(Wv1) (the transposed copy, wide:662; operand rounded at the split, wide:116, 156 with bsc = 1)
+        g1 = dv1 s (1 - (v1 / s)^2) where the stashed v1 != 0, else 0: the derivative from the UNROUNDED stash (wide:206-207, 1 / s
+        in fp32 wide:197), "kept" read off h != 0 instead of a mask bit (wide:208); stored UNROUNDED (wide:211)
+        dh = wp du + bf(g1) . bf(Wv0): wp du in fp32 starts the accumulator (wide:123-127, 666)
+        per layer l = nh-1 .. 0: gh_l = dh s_l (1 - (h_l / s_l)^2) [h_l != 0], unrounded; then dh = bf(gh_l) . bf(W_l) (wide:669-672)
+      weight gradients (train:755-763, ns = 1; problems args:104-113; kernels chosen in dispatch_wgrad_x6, wg:716-719)
+        dW_l = bf(gh_l)^T bf(h_{l-1}), l >= 1, dWv0 = bf(g1)^T bf(h_last), dWv1 = bf(g2)^T bf(v1): both operands read from the fp32
+        stash and rounded in registers (split8<1>, wg:42-58; wgrad_d_kernel wg:278-283, wgrad_x_kernel wg:125-130), fp32 accumulation
+        db_l, dbv0, dbv1 = sums of the UNROUNDED g in double precision (wg:272-277, 131-135)
+        dW_0 = gh_0^T x in exact fp32 on the unrounded gh_0 and x (train:762 -> wgrad_kernel, train:277; x rows train:210-218);
+        db_0 its unrounded sum (train:278-286)
+        dwp = sum du h_last and dwv2 = sum dz v2 on the UNROUNDED stash, fp32 (wgrad_x_kernel's dvq wg:150-159, dvr wg:136-148;
+        operands args:125-126)
+        dbp = sum du, dbv2 = sum dz with the loss sums (loss:53-54, train:461-462)
+
+    Against the fused policy: the stash and the stored d pre-activations are not rounded, so the tanh derivative, the bias sums and the
+    two vector heads see fp32 values, and layer 0's gradient sees x itself."""
+    return bf16_train_step(params, x, y, p_list, masks, dtype, n_global, k_chunk, rounding, policy="wide")
 
 
 def aleatoric_loss(gt, pred_y, logvar):

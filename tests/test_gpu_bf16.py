@@ -2,9 +2,11 @@
 
 Two checks per kernel: (1) against the oracle run with the SAME rounding policy (bf16 MFMA inputs,
 fp32 everything else) -- tight, only accumulation order differs; (2) against the fp32 oracle (= the
-reference's arithmetic) at the mixed-precision tolerance rtol 2e-2 of SURVEY.md 8(c).  For the fused
-nets' training step (1) is the second half of this file: every gradient tensor against a float64
-run of the kernels' own policy, inside a band derived on the CPU (tests/bf16_policy.py)."""
+reference's arithmetic) at the mixed-precision tolerance rtol 2e-2 of SURVEY.md 8(c).  For the training
+step (1) is the second half of this file: every loss sum and gradient tensor against a float64 run of
+the kernels' own rounding policy -- O.bf16_train_step for the fused nets (H = 128, 256), O.bf16_wide_train_step
+for the wide ones (H = 512, 1024, 2048: layer-by-layer kernels in scheme B1, weight gradients with one bf16
+part per operand) --, inside a band derived on the CPU (tests/bf16_policy.py, test_bf16_policy_host.py)."""
 import ctypes
 
 import numpy as np
@@ -134,7 +136,7 @@ def test_model_surface_bf16_end_to_end():
 
 
 # =======================================================================================
-# The fused kernels against a float64 reference of their OWN rounding policy (O.bf16_train_step), inside a band that
+# The kernels against a float64 reference of their OWN rounding policy (O.bf16_train_step, O.bf16_wide_train_step), inside a band that
 # test_bf16_policy_host.py derives from that reference and float32 restatements alone (tests/bf16_policy.py).  The gates
 # above, against the reference's fp32 arithmetic, state the 2e-2 mixed-precision contract and have to swallow the whole
 # bf16 rounding error; the ones below do not, so a dropped ragged row, a skipped weight-gradient tile or a wrong keep bit
@@ -183,6 +185,41 @@ def test_train_grads_bf16_in_policy_band(lib, name):
     drop = hh.dropout_struct(c.mode, c.pl, seed=B.SEED, stream_id=B.STREAM, row_offset=B.ROW0)
     grads, loss = hh.train_grads(lib, c.H, c.nh, fp, xd, yd, drop, precision=1)
     _assert_in_band("%s (H %d, nh %d, %d rows)" % (name, c.H, c.nh, c.n), c.band, loss, grads, c.H, c.nh)
+
+
+@pytest.mark.parametrize("name", B.WIDE_IDS)
+def test_train_grads_bf16_wide_in_policy_band(lib, name):
+    """The wide nets' bf16-mixed training step (wide_layer_x6_kernel<x6::B1, ..>, wgrad_d_kernel<.., 1>, wgrad_x_kernel<.., 1>): loss
+    sums and all 2 nh + 8 gradient tensors against the float64 reference of the WIDE policy (O.bf16_wide_train_step), inside the same
+    band_t = 3 E_t + 4 * 2^-8 * R_t with E_t from the wide policy's float32 orders.  The cases (bf16_policy.WIDE_CASES): one row; the
+    wave tile (15 / 16 / 17) and the 128-row workgroup tile (127 / 128 / 129); no dropout at H = 1024; three hidden layers; the
+    fan-out route with short and empty slices at H = 1024 and H = 512; 8 x 8 gradient blocks at H = 2048; and the serial route with
+    more workgroup tiles than CUs (a second tile per workgroup)."""
+    import hip_helpers as hh
+    c = B.case(name, _cus())
+    fp, xd, yd = _dev_inputs(c.P, c.x, c.y, c.H, c.nh)
+    drop = hh.dropout_struct(c.mode, c.pl, seed=B.SEED, stream_id=B.STREAM, row_offset=B.ROW0)
+    grads, loss = hh.train_grads(lib, c.H, c.nh, fp, xd, yd, drop, precision=1)
+    _assert_in_band("%s (H %d, nh %d, %d rows)" % (name, c.H, c.nh, c.n), c.band, loss, grads, c.H, c.nh)
+
+
+def test_bf16_wide_injected_masks(lib):
+    """PINN_DROP_BITS through the wide kernels' activate_pair_rt: 129 torch-drawn rows of [8, 512, 512, 1], one p per module.  One row
+    behind a 128-row workgroup tile: the padding rows of the second tile read the last real row's mask words (the local-row clamp of
+    wide_input_kernel and wide_layer_x6_kernel).  Forward at the forward test's gate, the training step inside the wide band."""
+    import hip_helpers as hh
+    P, x, y, pl, masks, band = B.wide_drawn_mask_case()
+    H, nh = 512, 2
+    bits = hh.pack_mask_bits([masks]).to(hh.dev())
+    drop = hh.dropout_struct(2, pl, bits=bits)
+    fp, xd, yd = _dev_inputs(P, x, y, H, nh)
+    u, lv = hh.forward(lib, H, nh, fp, xd, drop, precision=1)
+    with torch.no_grad():
+        ub, lvb = O.mlp_forward(P, x, pl, masks, bf16=True)
+    np.testing.assert_allclose(u.cpu().numpy(), ub.numpy().reshape(-1), rtol=2e-3, atol=2e-3)
+    np.testing.assert_allclose(lv.cpu().numpy(), lvb.numpy().reshape(-1), rtol=2e-3, atol=2e-3)
+    grads, loss = hh.train_grads(lib, H, nh, fp, xd, yd, drop, precision=1)
+    _assert_in_band("wide injected masks, 129 drawn rows", band, loss, grads, H, nh)
 
 
 @pytest.mark.parametrize("which", ["g_net128", "drawn65"])
@@ -236,20 +273,21 @@ def test_forward_and_mc_bf16_above_the_grid_cap(lib):
 
 def test_bf16_repeatable_and_shard_additive(lib):
     """Two identical bf16 training calls are bitwise equal; two row shards with n_global = N and their row offsets sum to the full
-    call's gradient and loss sums within band_t (sharding only reorders the slab sums: no wider band is due)."""
+    call's gradient and loss sums within band_t (sharding only reorders the slab sums: no wider band is due).  A fused net
+    ([8, 128 x 3, 1], 333 rows cut at 130) and a wide one ([8, 512, 512, 1], 333 rows cut at 129: one row behind a workgroup tile)."""
     import hip_helpers as hh
-    c = B.case("mid128")
-    fp, xd, yd = _dev_inputs(c.P, c.x, c.y, c.H, c.nh)
-    mk = lambda off: hh.dropout_struct(1, c.pl, seed=B.SEED, stream_id=B.STREAM, row_offset=B.ROW0 + off)
-    g1, l1 = hh.train_grads(lib, c.H, c.nh, fp, xd, yd, mk(0), precision=1)
-    g2, l2 = hh.train_grads(lib, c.H, c.nh, fp, xd, yd, mk(0), precision=1)
-    assert torch.equal(g1, g2) and torch.equal(l1, l2)
-    cut = 130
-    ga, la = hh.train_grads(lib, c.H, c.nh, fp, xd[:cut].contiguous(), yd[:cut].contiguous(), mk(0), n_global=c.n, precision=1)
-    gb, lb = hh.train_grads(lib, c.H, c.nh, fp, xd[cut:].contiguous(), yd[cut:].contiguous(), mk(cut), n_global=c.n, precision=1)
-    full = (l1.cpu().numpy()[:3], [g.numpy() for g in hh.unflat(g1.cpu(), c.H, c.nh)])
-    _assert_in_band("shards %d + %d against the full call" % (cut, c.n - cut), c.band, la + lb, ga + gb, c.H, c.nh, ref=full)
-    _assert_in_band("shards %d + %d against the reference" % (cut, c.n - cut), c.band, la + lb, ga + gb, c.H, c.nh)
+    for c, cut in ((B.case("mid128"), 130), (B.wide_shard_case(), 129)):
+        fp, xd, yd = _dev_inputs(c.P, c.x, c.y, c.H, c.nh)
+        mk = lambda off: hh.dropout_struct(1, c.pl, seed=B.SEED, stream_id=B.STREAM, row_offset=B.ROW0 + off)
+        g1, l1 = hh.train_grads(lib, c.H, c.nh, fp, xd, yd, mk(0), precision=1)
+        g2, l2 = hh.train_grads(lib, c.H, c.nh, fp, xd, yd, mk(0), precision=1)
+        assert torch.equal(g1, g2) and torch.equal(l1, l2), c.name
+        ga, la = hh.train_grads(lib, c.H, c.nh, fp, xd[:cut].contiguous(), yd[:cut].contiguous(), mk(0), n_global=c.n, precision=1)
+        gb, lb = hh.train_grads(lib, c.H, c.nh, fp, xd[cut:].contiguous(), yd[cut:].contiguous(), mk(cut), n_global=c.n, precision=1)
+        full = (l1.cpu().numpy()[:3], [g.numpy() for g in hh.unflat(g1.cpu(), c.H, c.nh)])
+        tag = "%s: shards %d + %d" % (c.name, cut, c.n - cut)
+        _assert_in_band(tag + " against the full call", c.band, la + lb, ga + gb, c.H, c.nh, ref=full)
+        _assert_in_band(tag + " against the reference", c.band, la + lb, ga + gb, c.H, c.nh)
 
 
 def test_mc_dropout_bf16_row_shards_and_eval_forward(lib):

@@ -20,11 +20,13 @@ of the last workgroup tile all padding.
     multi_deep      32913    kRouteMulti: 32 slices of 64 or 65 tiles (the one-launch kernel, 8x the depth of any other referenced case)
     serial_x3       163857   t16 = 10248 >= kMultiT16: the per-layer wgrad_p_kernel instantiations bench.py times, 256 slices of 40 tiles,
                              slices 0-7 take 41
-    wide512         8209     [8,512,512,1]: grid 64 x 2 x 2, re-numbered over the XCDs with per_xcd = 8, 8 or 9 tiles
+    wide512         8209     [8,512,512,1]: grid 64 x 2 x 2, re-numbered over the XCDs with per_xcd = 8, 8 or 9 tiles.  Also PINN_PREC_F32X6_G6
+                             (wgrad_d_kernel / wgrad_x_kernel with three bf16 parts, blockIdx.y / z > 0): contiguous, 57 slices of 9
+                             tiles, one of 7, 6 empty
     wide1024        2065     [8,1024,1024,1]: t16 = 136, grid 64 x 4 x 4, per_xcd = 8, 2 or 3 tiles
     wide2048        273      [8,2048,2048,1]: t16 = 24, 12 slices of 2 tiles, grid 12 x 8 x 8: NOT a multiple of 8, re-numbering off
     wide512_serial  32913    kRouteSerial for a wide net, where the slice count is 512 / (H / 256)^2 = 128: grid 128 x 2 x 2,
-                             per_xcd = 16, 16 or 17 tiles
+                             per_xcd = 16, 16 or 17 tiles.  Also PINN_PREC_F32X6_G6: contiguous, 121 slices of 17 tiles, one of 7, 6 empty
     wide2048_xcd    401      t16 = 32, 16 slices of 2 tiles, grid 16 x 8 x 8: the re-numbering over 8 x 8 blocks with per_xcd = 2
 
 The three wide rows of the table were drawn up expecting 512 / (H / 256)^2 slices (128, 32, 8).  plan_workspace applies that count on
@@ -89,10 +91,10 @@ CASES = [("fan", FUSED5, 8209, 1, 0),
          ("serial", FUSED5, 32913, 1, 2),
          ("multi_deep", ((X6, 256, 2),), 32913, 1, 2),
          ("serial_x3", ((X6, 256, 2),), 163857, 1, 0),
-         ("wide512", ((X6, 512, 2),), 8209, 1, 0),
+         ("wide512", ((X6, 512, 2), (G6, 512, 2)), 8209, 1, 0),
          ("wide1024", ((X6, 1024, 2),), 2065, 1, 0),
          ("wide2048", ((X6, 2048, 2),), 273, 1, 0),
-         ("wide512_serial", ((X6, 512, 2),), 32913, 1, 0),
+         ("wide512_serial", ((X6, 512, 2), (G6, 512, 2)), 32913, 1, 0),
          ("wide2048_xcd", ((X6, 2048, 2),), 401, 1, 0)]
 CASE_IDS = [c[0] for c in CASES]
 RUNS = [(c[0], p, H, nh) for c in CASES for p, H, nh in c[1]]
@@ -104,7 +106,12 @@ RUNS = [(c[0], p, H, nh) for c in CASES for p, H, nh in c[1]]
 #   * hidden-layer bias gradients of PINN_PREC_F32X6: a plain sum over rows of d pre, whose operand is stored in two fp16 parts (22 bits)
 #     where torch sums 24-bit values; the wide nets scale them once per call, not per row, and lose more;
 #   * var_layers.5.weight of the 128-wide net: 32 elements under the per-element rule, where torch's own error on one element is a
-#     single draw that can land near zero -- the exact-fp32 kernels show the largest ratio of the three families.
+#     single draw that can land near zero -- the exact-fp32 kernels show the largest ratio of the three families;
+#   * layers.layer_0.bias of PINN_PREC_F32X6_G6 on [8,512,512,1] (K = 3): the same one-sided cut of the matrix unit, with twice the
+#     MFMAs per product and two 512-deep backward layers in front of it.  Measured on the device: 2.5e-7 of the tensor's rms at 8209 rows
+#     (fan-out, 64 slices) and at 32 913 rows (serial, 128 slices) alike, 88 - 89 % of the elements err to the same side, 0.96 - 1.04 of
+#     the overall rms in either 256-row block, correlation with the gradient -0.1, projection on a row's or a tile's share below 8e-5
+#     of that share (one row's share: 3e-4 - 1.6e-3 of the tensor); layers.layer_1.bias shows the same signature at 0.69 - 0.90 bands.
 EXCEPTIONS = {
     ("serial-x6-H128", "layers.layer_0.bias"): 1.138,
     ("serial-x6-H128", "layers.layer_1.bias"): 1.048,
@@ -112,12 +119,14 @@ EXCEPTIONS = {
     ("serial-g6-H128", "var_layers.5.weight"): 1.044,
     ("serial-fp32-H128", "var_layers.5.weight"): 1.849,
     ("wide512-x6-H512", "layers.layer_0.bias"): 1.107,
+    ("wide512-g6-H512", "layers.layer_0.bias"): 1.144,
     ("wide1024-x6-H1024", "layers.layer_0.bias"): 1.833,
     ("wide1024-x6-H1024", "layers.layer_1.bias"): 1.972,
     ("wide2048-x6-H2048", "layers.layer_0.bias"): 2.013,
     ("wide2048-x6-H2048", "layers.layer_1.bias"): 2.047,
     ("wide512_serial-x6-H512", "layers.layer_0.bias"): 1.374,
     ("wide512_serial-x6-H512", "layers.layer_1.bias"): 1.032,
+    ("wide512_serial-g6-H512", "layers.layer_0.bias"): 1.420,
     ("wide2048_xcd-x6-H2048", "layers.layer_0.bias"): 2.658,
     ("wide2048_xcd-x6-H2048", "layers.layer_1.bias"): 3.491,
 }
@@ -199,6 +208,10 @@ CLAIMS.update({
     ("wide512_serial", X6, 512): dict(t16=2064, route="serial", slices=128, walk="interleaved", tiles={16: 112, 17: 16}, grid=(128, 2, 2),
                                       per_xcd=16),
     ("wide2048_xcd", X6, 2048): dict(t16=32, route="fan", slices=16, walk="interleaved", tiles={2: 16}, grid=(16, 8, 8), per_xcd=2),
+    # PINN_PREC_F32X6_G6 on a wide net: wgrad_d_kernel<.., 3> / wgrad_x_kernel<.., 3> over blocks of the gradient (blockIdx.y / z > 0), the
+    # contiguous walk with a short last slice and empty ones behind it (no re-numbering: that is wgrad_p_kernel's)
+    ("wide512", G6, 512): dict(t16=520, route="fan", slices=64, walk="contiguous", tiles={9: 57, 7: 1, 0: 6}, grid=(64, 2, 2)),
+    ("wide512_serial", G6, 512): dict(t16=2064, route="serial", slices=128, walk="contiguous", tiles={17: 121, 7: 1, 0: 6}, grid=(128, 2, 2)),
 })
 
 
