@@ -1271,6 +1271,63 @@ int pinn_shap_hybrid(const double* d_arr, long long ld, long long n_arr_rows, co
 int pinn_shap_reduce(const void* d_f, int f64, long long n_chunk, int n_feat, long long n_bg, int n_classes, double* d_phi,
                      double* d_base, double* d_fx, void* stream);
 
+/* ---- temporal diagnosis: a hidden Markov chain over the fault classes, the per-row posteriors as emissions ----------
+ * S <= PINN_HMM_MAX_STATES states.  The rows are a row head as above with S columns (array, leading dimension, rows of the
+ * array, column list, gather list or NULL, positions).  The emission of position t is b_t(s) = column s * inv_prior[s];
+ * a position whose b_t is all zero, or holds a negative or non-finite value, or reads nothing, is missing: b_t = 1.
+ * Emissions are scale-free: a row may be multiplied by any positive constant (the log-likelihood moves by its logarithm).
+ *
+ * d_model, float64 words: [0] iterations done, [1] converged, [3] last log-likelihood, [4] last gain (written by
+ * pinn_hmm_mstep); A(i, j) at PINN_HMM_MODEL_A + 8 i + j (row-stochastic, zeros allowed), p0 at PINN_HMM_MODEL_P0,
+ * inv_prior at PINN_HMM_MODEL_INV_PRIOR (ones for none), the log-likelihood history from PINN_HMM_HEADER on.
+ *
+ * d_seg_start [n_segments] (ascending, the first 0; n_segments = 0: one segment) restarts the chain from p0.  A carry holds
+ * 2 S + 1 words per segment: the filtered distribution [S], the log-likelihood so far, the Viterbi scores [S].  With
+ * d_carry_in the first position of segment s continues from it instead of p0; pinn_hmm_forward_backward reads and writes
+ * the first S + 1 words, pinn_hmm_viterbi the last S.
+ *
+ * The recurrences are scans: an element is a flag, an S x S matrix and a 64-bit exponent; after every product the matrix
+ * is scaled by the exact power of two that brings its largest entry into [0.5, 1).  Reduce-then-scan over tiles of
+ * PINN_HMM_TILE positions (64 threads, PINN_HMM_ROWS_PER_THREAD consecutive positions each): one launch reduces every
+ * tile, a one-workgroup launch scans the tile elements in tile order, a third finishes each tile; n <= PINN_HMM_TILE is one
+ * launch.  No float atomics and a fixed order everywhere: the same call gives the same bytes.
+ *
+ * pinn_hmm_forward_backward: outputs, each skipped when NULL: d_alpha [n][S] filtered, d_gamma [n][S] smoothed, d_loglik
+ * [segments], d_xi [S][S] expected transition counts, d_gamma_sum [S] (sum of gamma over positions with a successor in
+ * their segment), d_carry_out.  Without d_gamma, d_xi and d_gamma_sum no backward launch runs.  With respect_converged != 0
+ * every launch returns at once when word [1] of the model is set.
+ * pinn_hmm_viterbi: max-plus scan of log A(i, j) + log b_t(j) (log 0 = -inf), backpointers = the lowest maximising i, the
+ * path as a suffix composition of the backpointer maps (one 32-bit word per position) from the lowest arg-max of each
+ * segment's last scores.  d_path [n] int64, d_logprob [segments], d_carry_out.
+ * pinn_hmm_mstep: one launch.  A(i, j) <- (xi(i, j) + pseudo(i, j)) / their row total over the j with A(i, j) > 0; a zero
+ * of A stays zero and a row whose total is zero keeps its values.  Appends the sum of d_loglik to the history (while it
+ * has room: max_hist entries), counts the iteration and sets word [1] when |gain| < tol from the second iteration on.
+ * Returns at once when word [1] is already set.  d_xi [S][S], d_pseudo [S][S] or NULL.
+ *
+ * Checks, on the host before any launch: PINN_E_ARG for NULL or misaligned pointers, S outside 1 .. PINN_HMM_MAX_STATES
+ * and negative sizes; PINN_E_WORKSPACE for a workspace below pinn_hmm_workspace_bytes(n, S) (256-byte aligned; 0 outside
+ * the limits); n = 0 (pinn_hmm_mstep: n_segments = 0) returns PINN_OK without a launch. */
+#define PINN_HMM_MAX_STATES 8
+#define PINN_HMM_TILE 1024
+#define PINN_HMM_ROWS_PER_THREAD 16
+#define PINN_HMM_HEADER 96
+#define PINN_HMM_MODEL_A 16
+#define PINN_HMM_MODEL_P0 80
+#define PINN_HMM_MODEL_INV_PRIOR 88
+
+size_t pinn_hmm_workspace_bytes(long long n, int n_states);
+int pinn_hmm_forward_backward(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_states,
+                              const long long* d_row_index, long long n, const double* d_model, const long long* d_seg_start,
+                              long long n_segments, const double* d_carry_in, int respect_converged, double* d_alpha,
+                              double* d_gamma, double* d_loglik, double* d_xi, double* d_gamma_sum, double* d_carry_out,
+                              void* d_ws, size_t ws_bytes, void* stream);
+int pinn_hmm_viterbi(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_states,
+                     const long long* d_row_index, long long n, const double* d_model, const long long* d_seg_start,
+                     long long n_segments, const double* d_carry_in, long long* d_path, double* d_logprob,
+                     double* d_carry_out, void* d_ws, size_t ws_bytes, void* stream);
+int pinn_hmm_mstep(double* d_model, int n_states, const double* d_xi, const double* d_loglik, long long n_segments,
+                   const double* d_pseudo, double tol, int max_hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

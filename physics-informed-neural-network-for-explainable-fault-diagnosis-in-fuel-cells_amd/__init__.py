@@ -27,7 +27,10 @@ and what script 02's four AUCs leave open, their intervals and paired tests: `au
 `delong_test`, `compare_aucs`, `bootstrap_auc`, `compare_feature_groups` (rocstat); and the choice of the mixture's size and
 seed, all candidates fitted and scored in one batch: `gmm_sweep`, `select_gmm`, `GMMSweep` (selection); and the question after
 a diagnosis, which input made the model say so, as exact Shapley values over all coalitions: `shapley_diagnosis`,
-`shapley_values`, `voltage_predictor`, `DiagnosisExplainer`, `global_importance`, `top_features` (explain).
+`shapley_values`, `voltage_predictor`, `DiagnosisExplainer`, `global_importance`, `top_features` (explain); and the time
+axis every per-row diagnosis ignores, a hidden Markov chain over the fault classes with the posteriors as emissions:
+`DeviceHMM` (filter, smoother, Viterbi path, Baum-Welch for the transitions), `TemporalDiagnoser`, `sticky_transitions`,
+`transitions_from_labels`, `scaled_likelihood` (temporal).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -69,6 +72,8 @@ _LAZY = {
     "gmm_sweep": "selection", "select_gmm": "selection", "GMMSweep": "selection",
     "shapley_values": "explain", "shapley_diagnosis": "explain", "voltage_predictor": "explain", "DiagnosisExplainer": "explain",
     "global_importance": "explain", "top_features": "explain", "Shapley": "explain",
+    "DeviceHMM": "temporal", "TemporalDiagnoser": "temporal", "sticky_transitions": "temporal",
+    "transitions_from_labels": "temporal", "scaled_likelihood": "temporal",
 }
 
 

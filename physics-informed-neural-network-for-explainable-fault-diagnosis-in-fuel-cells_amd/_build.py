@@ -50,6 +50,9 @@ SOURCES = [
     ("pinn_rocstat.hip", []),
     # exact Shapley attributions: float64, every operation rounded on its own; the host backend states the same coalition sums
     ("pinn_shap.hip", ["-ffp-contract=off"]),
+    # hidden Markov chain: float64 products and sums of non-negative numbers, scaled by exact powers of two; contraction is
+    # allowed as in the mixture (gates are tolerances derived from the product lengths, the order of every product is fixed)
+    ("pinn_hmm.hip", []),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

@@ -122,6 +122,10 @@ SP_ST_N, SP_ST_M, SP_ST_K, SP_ST_MATVEC, SP_ST_DEGREE, SP_ST_MAXRES, SP_ST_FILT_
 AUC_MAX_SCORES, AUC_TILE, AUC_BOOT_LDS_GROUPS, AUC_DRAW_BOOT, AUC_COUNTS = 8, 256, 12288, 2, 8
 AUC_POS, AUC_NEG, AUC_GROUPS, AUC_U2, AUC_U2B = range(5)
 
+# pinn_hmm.hip: limits, the scan tile and the 8-byte words of the device model
+HMM_MAX_STATES, HMM_TILE, HMM_ROWS_PER_THREAD, HMM_HEADER, HMM_MODEL_A, HMM_MODEL_P0, HMM_MODEL_INV_PRIOR = 8, 1024, 16, 96, 16, 80, 88
+HMM_ITER, HMM_CONVERGED, HMM_PREV, HMM_GAIN = 0, 1, 3, 4
+
 
 class PinnError(RuntimeError):
     pass
@@ -280,6 +284,11 @@ _SIGS = {
     "pinn_shap_gmm": (c_int, _ROWS + _ROWS + [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_shap_hybrid": (c_int, _ROWS + _ROWS + [c_ll, c_ll, c_int, c_void_p, c_void_p]),
     "pinn_shap_reduce": (c_int, [c_void_p, c_int, c_ll, c_int, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_hmm_workspace_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_hmm_forward_backward": (c_int, _ROWS + [c_void_p, c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_hmm_viterbi": (c_int, _ROWS + [c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_hmm_mstep": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p, ctypes.c_double, c_int, c_void_p]),
 }
 
 _lib = None

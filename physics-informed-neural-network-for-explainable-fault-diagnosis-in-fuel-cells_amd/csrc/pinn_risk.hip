@@ -67,23 +67,6 @@ __device__ __forceinline__ double clip_nan(double x, double lo, double hi) {
   return x > hi ? hi : x;
 }
 
-// segment of position j: the last s with seg_start[s] <= j; segment 0 always starts at 0
-__device__ __forceinline__ long long seg_of(const long long* __restrict__ ss, long long ns, long long j) {
-  if (!ss || ns <= 1) return 0;
-  long long lo = 0, hi = ns;
-  while (hi - lo > 1) {
-    const long long mid = (lo + hi) >> 1;
-    if (ss[mid] <= j) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ long long seg_begin(const long long* __restrict__ ss, long long s) { return (ss && s > 0) ? ss[s] : 0; }
-
-__device__ __forceinline__ long long seg_next(const long long* __restrict__ ss, long long ns, long long s, long long n) {
-  return (ss && s + 1 < ns) ? ss[s + 1] : n;
-}
-
 // Exclusive prefix of the threads' aggregates in thread order (identity for thread 0); *total = the workgroup's aggregate.
 __device__ __forceinline__ Op block_exclusive(const Op& mine, Op* s_wave, Op* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

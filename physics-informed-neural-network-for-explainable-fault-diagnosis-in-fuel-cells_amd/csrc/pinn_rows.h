@@ -28,6 +28,24 @@ __device__ __forceinline__ bool load_row(const Rows& a, long long j, double x[kR
   return ok;
 }
 
+// Segments of a series (risk, hmm): ss[ns] ascending start positions, NULL or ns <= 1 for one segment.
+// segment of position j: the last s with seg_start[s] <= j; segment 0 always starts at 0
+__device__ __forceinline__ long long seg_of(const long long* __restrict__ ss, long long ns, long long j) {
+  if (!ss || ns <= 1) return 0;
+  long long lo = 0, hi = ns;
+  while (hi - lo > 1) {
+    const long long mid = (lo + hi) >> 1;
+    if (ss[mid] <= j) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ long long seg_begin(const long long* __restrict__ ss, long long s) { return (ss && s > 0) ? ss[s] : 0; }
+
+__device__ __forceinline__ long long seg_next(const long long* __restrict__ ss, long long ns, long long s, long long n) {
+  return (ss && s + 1 < ns) ? ss[s + 1] : n;
+}
+
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // packed upper triangle, column by column: (i, j), i <= j, sits at j (j + 1) / 2 + i
