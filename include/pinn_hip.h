@@ -1328,6 +1328,55 @@ int pinn_hmm_viterbi(const double* d_arr, long long ld, long long n_arr_rows, co
 int pinn_hmm_mstep(double* d_model, int n_states, const double* d_xi, const double* d_loglik, long long n_segments,
                    const double* d_pseudo, double tol, int max_hist, void* stream);
 
+/* ---- parameter identification: which physics parameter moved, per window, with a covariance -------------------------
+ * A table is a row head as above with four columns (array, leading dimension, rows of the array, cols[4], gather list or
+ * NULL, positions); p = 3 parameters per model.
+ *   PINN_ID_VOLTAGE  columns (i, b, E, v), theta = (r, q, c) = (lambda_1, ln lambda_2, 1 / lambda_3):
+ *                    residual E - b (ln i - q) - i r + 0.5 b log1p(-i c) - v, Jacobian row (-i, b, -0.5 b i / (1 - i c));
+ *                    domain 1 - i c > 0 on every used row, tested as c max_i < 1.
+ *   PINN_ID_THERMAL  columns (It, mc, T_in, T_out), theta = (lambda_T1, lambda_T3, lambda_T5):
+ *                    residual T_out - (theta0 It + theta1 mc + 0.5 T_in + theta2), Jacobian row (-It, -mc, -1).
+ * A position is missing (skipped, not counted) when it reads nothing or one of its four entries is not finite; for the
+ * voltage model also when i <= 0 or b <= 0.
+ *
+ * Window w is the positions [d_win_start[w], d_win_start[w] + d_win_len[w]) of the gathered sequence; windows may overlap.
+ * One workgroup of 256 threads runs the whole Levenberg-Marquardt loop of a window (grid-stride over windows, no other
+ * workgroup involved, no float atomics).  Windows of at most PINN_ID_ONCHIP_ROWS positions keep their rows in registers
+ * over all passes, longer ones (up to PINN_ID_MAX_WINDOW) read them again every pass; either way thread t adds positions
+ * t, t + 256, ... in order, then a wave butterfly, then the four waves in index order: the same call gives the same
+ * bytes and a window's bytes do not depend on the other windows of the call.
+ *
+ * The solver, per window: one row pass per trial point returns sse = r'r, A = J'J, g = J'r, n_used and max i.  With
+ * D = diag(A) and C = D^-1/2 A D^-1/2 the trial step solves (A + mu D) d = -g by a Cholesky factorisation of C + mu I
+ * (mu starts at opts->mu0); the trial theta + d is accepted when it is finite, inside the domain and sse_t < sse, then
+ * mu = max(mu / 10, 1e-15), else mu *= 10.  Before every trial: s2 = sse / (n_used - 3), m = sqrt(g' A^-1 g / s2), which
+ * bounds every component's first-order distance to the stationary point in its standard errors.  Status, in this order:
+ *   6 bad window (negative start or length, length > PINN_ID_MAX_WINDOW, end beyond n)   3 n_used < 4
+ *   4 theta0 not finite or outside the domain, or sums not finite   5 a diagonal entry of A not positive or a pivot of
+ *   C's factorisation <= 2^-40   0 sse == 0, m <= tol, or every |d_k| <= xtol (|theta_k| + xtol)
+ *   1 passes >= max_passes (the first pass counts; max_passes = 0 evaluates at theta0)   2 mu > 1e15.
+ *
+ * d_fit [n_windows][16]: theta [3], the covariance s2 A^-1 packed column by column [6], sse, m, mu, n_used, passes, status,
+ * 0.  Status 3, 4 and 6: NaN but for n_used, passes and status; status 5: theta, sse and mu, the rest NaN.
+ * d_normal (NULL: skipped) [n_windows][12], at the returned theta: A packed [6], g [3], sse, n_used, max i; NaN for status 6.
+ * d_theta0 [3] with theta0_stride 0, [n_windows][3] with 3.  opts NULL: tol 1e-8, xtol 1e-14, mu0 1e-3, max_passes 100.
+ *
+ * Checks, on the host before any launch: PINN_E_ARG for NULL or misaligned pointers, a model or stride outside the above,
+ * negative counts, options that are not finite and positive (max_passes < 0, reserved != 0); n_windows = 0 returns PINN_OK. */
+#define PINN_ID_VOLTAGE 0
+#define PINN_ID_THERMAL 1
+#define PINN_ID_MAX_WINDOW 65536
+#define PINN_ID_ONCHIP_ROWS 4096
+#define PINN_ID_FIT_WORDS 16
+#define PINN_ID_NORMAL_WORDS 12
+
+typedef struct pinn_id_opts { double tol, xtol, mu0; int max_passes; int reserved; } pinn_id_opts_t;
+
+int pinn_id_fit(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int model,
+                const long long* d_row_index, long long n, const long long* d_win_start, const long long* d_win_len,
+                long long n_windows, const double* d_theta0, long long theta0_stride, const pinn_id_opts_t* opts,
+                double* d_fit, double* d_normal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,9 @@ a diagnosis, which input made the model say so, as exact Shapley values over all
 `shapley_values`, `voltage_predictor`, `DiagnosisExplainer`, `global_importance`, `top_features` (explain); and the time
 axis every per-row diagnosis ignores, a hidden Markov chain over the fault classes with the posteriors as emissions:
 `DeviceHMM` (filter, smoother, Viterbi path, Baum-Welch for the transitions), `TemporalDiagnoser`, `sticky_transitions`,
-`transitions_from_labels`, `scaled_likelihood` (temporal).
+`transitions_from_labels`, `scaled_likelihood` (temporal); and which physical quantity of the stack moved, the polarisation
+and thermal parameters identified per window with covariances: `voltage_table`, `thermal_table`, `sliding_windows`,
+`fit_windows`, `fit_baseline`, `drift`, `WindowFit`, `ParameterTracker` (identify).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -74,6 +76,8 @@ _LAZY = {
     "global_importance": "explain", "top_features": "explain", "Shapley": "explain",
     "DeviceHMM": "temporal", "TemporalDiagnoser": "temporal", "sticky_transitions": "temporal",
     "transitions_from_labels": "temporal", "scaled_likelihood": "temporal",
+    "voltage_table": "identify", "thermal_table": "identify", "sliding_windows": "identify", "fit_windows": "identify",
+    "fit_baseline": "identify", "drift": "identify", "WindowFit": "identify", "ParameterTracker": "identify",
 }
 
 

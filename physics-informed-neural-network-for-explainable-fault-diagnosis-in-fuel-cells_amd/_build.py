@@ -53,6 +53,9 @@ SOURCES = [
     # hidden Markov chain: float64 products and sums of non-negative numbers, scaled by exact powers of two; contraction is
     # allowed as in the mixture (gates are tolerances derived from the product lengths, the order of every product is fixed)
     ("pinn_hmm.hip", []),
+    # parameter identification: float64 Levenberg-Marquardt per window, every operation rounded on its own; the host backend states
+    # the same solver, and the on-chip and streaming forms of a row pass must give the same sums
+    ("pinn_identify.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

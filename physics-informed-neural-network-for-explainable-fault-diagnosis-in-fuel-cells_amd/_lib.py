@@ -126,6 +126,14 @@ AUC_POS, AUC_NEG, AUC_GROUPS, AUC_U2, AUC_U2B = range(5)
 HMM_MAX_STATES, HMM_TILE, HMM_ROWS_PER_THREAD, HMM_HEADER, HMM_MODEL_A, HMM_MODEL_P0, HMM_MODEL_INV_PRIOR = 8, 1024, 16, 96, 16, 80, 88
 HMM_ITER, HMM_CONVERGED, HMM_PREV, HMM_GAIN = 0, 1, 3, 4
 
+# pinn_identify.hip: models, limits and the 8-byte words of a fit row and of a normal-equations row
+ID_VOLTAGE, ID_THERMAL, ID_MAX_WINDOW, ID_ONCHIP_ROWS, ID_FIT_WORDS, ID_NORMAL_WORDS = 0, 1, 65536, 4096, 16, 12
+
+
+class IdOpts(ctypes.Structure):
+    """pinn_id_opts_t (pinn_identify.hip)."""
+    _fields_ = [("tol", ctypes.c_double), ("xtol", ctypes.c_double), ("mu0", ctypes.c_double), ("max_passes", c_int), ("reserved", c_int)]
+
 
 class PinnError(RuntimeError):
     pass
@@ -289,6 +297,8 @@ _SIGS = {
                                                   c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_hmm_viterbi": (c_int, _ROWS + [c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_hmm_mstep": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p, ctypes.c_double, c_int, c_void_p]),
+    "pinn_id_fit": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_void_p, c_ll, c_void_p, c_ll,
+                            ctypes.POINTER(IdOpts), c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
