@@ -1377,6 +1377,67 @@ int pinn_id_fit(const double* d_arr, long long ld, long long n_arr_rows, const i
                 long long n_windows, const double* d_theta0, long long theta0_stride, const pinn_id_opts_t* opts,
                 double* d_fit, double* d_normal, void* stream);
 
+/* ---- supply laws: the hydrogen and oxygen excess-ratio models per window, breakpoint included ------------------------
+ * A table is a row head as for pinn_id_fit with two columns (x, y) = (It [A], act): array, leading dimension, rows of the
+ * array, cols[2], gather list or NULL, positions.  The model is y = a + b min(x, c) / 100, theta = (a, b, c) = (l1, l2, l3)
+ * of hydrogen_target / oxygen_target (the oxygen model's clamp and its penalty on act < 1 do not depend on theta and are
+ * not part of the fit; its |l3| means c is reported non-negative whenever the currents are).  A position is missing
+ * (skipped, not counted) when it reads nothing or one of its two entries is not finite.
+ *
+ * Window w is the positions [d_win_start[w], d_win_start[w] + d_win_len[w]) of the gathered sequence; windows may overlap.
+ * max_window bounds the lengths of the call (at most PINN_BP_MAX_WINDOW is used): it sizes the dynamic LDS, rounded up to
+ * a power of two, and a longer window is answered by status 6 from a bounds test, not by a read.
+ *
+ * The objective is only piecewise smooth in c, so the solver enumerates instead of iterating.  Per window, the used rows
+ * sorted by (x, position), m = n_used:
+ *   1 centring and sums: z = x / 100 and y are centred on the window means; running sums of (1, z, y, zz, zy, yy) in
+ *     sorted order.
+ *   2 candidates, only at k with x_(k) < x_(k+1) or k = m:
+ *       knot k: c = x_(k), the two-parameter regression of y on u = min(z, z_k) over all rows; when x_(k) = x_(1) (u has
+ *               one value) or the centred sum of uu is not positive, the constant model.
+ *       free k (2 <= k <= m - 1, x_(k) > x_(1)): a line on the first k rows, the mean d of the rest, c = (d - a) / b;
+ *               admissible only if the left sum of zz is positive, b != 0 and x_(k) <= c <= x_(k+1).
+ *     Each candidate's SSE comes from the sums.  The smallest wins; on equal SSE a knot beats a free candidate, then the
+ *     smaller k.  (For a fixed gap the model is linear in (a, b, d); where the unconstrained optimum of a gap is not
+ *     admissible the constrained one lies on the gap's boundary, which is a knot, or at b = 0, which every knot contains.)
+ *   3 one more pass over the rows at the winning theta: the direct sse, the normal matrix A = J'J of the Jacobian row
+ *     (1, u, (b / 100) [x > c]) with u = min(x, c) / 100; sse_line (the knot at k = m) and sse_const come from the sums.
+ *   4 cov = s2 A^-1, s2 = sse / (m - 3), by the scaled Cholesky factorisation and the 2^-40 pivot rule of pinn_id_fit.
+ *     kind 2: the 2 x 2 block with s2 = sse / (m - 2), the c entries of cov NaN and c = +inf.
+ *   5 c_lo / c_hi: the smallest and largest of the winner's own c (kind 2 and 3: its knot) and of the knot values whose
+ *     SSE from the sums is <= sse_min (1 + q / (m - 3)), each moved outwards to the next current of the window where there
+ *     is one (the profile crosses the threshold somewhere inside that gap; without this step the interval held the true
+ *     c in 76 % of windows at a nominal 95 %, with it in 98 %): an interval to the resolution of the window's own
+ *     currents.  At a knot the covariance is a one-sided linearisation, and `kind` says so.
+ *
+ * One workgroup of 256 threads owns a window (grid-stride over windows, no other workgroup involved, no float atomics):
+ * it compacts the used rows into LDS in position order, sorts them by (x, position) with a bitonic network padded with
+ * +inf keys to the next power of two m_pad, and thread t owns the sorted rows [t R, (t + 1) R), R = max(1, m_pad / 256).
+ * Every sum adds a thread's rows in sorted order, then scans the 256 thread totals: Hillis-Steele over the 64 lanes of a
+ * wave in steps 1, 2, ... 32, then the four waves in index order; a thread's running sums start at its exclusive prefix.
+ * The same call gives the same bytes; a window's bytes depend neither on the other windows of the call nor on whether its
+ * rows are read packed or through a gather list.
+ *
+ * d_fit [n_windows][24]: theta [3], cov packed column by column [6], sse, kind (0 free, 1 knot, 2 line: no row beyond c,
+ * 3 constant), k, n_used, distinct currents, status, sse_line, sse_const, c_lo, c_hi, x_min, x_max, 0, 0, 0.
+ * Status, in this order: 6 bad window (negative start or length, length > max_window or PINN_BP_MAX_WINDOW, end beyond n):
+ * words 0..9 and 15..20 NaN, 10..13 zero; 3 n_used < 4: the same with n_used; 7 fewer than two distinct currents:
+ * a = mean y, b = 0, c, cov, c_lo and c_hi NaN; 5 no candidate with a comparable SSE, a diagonal entry of A not positive
+ * or a pivot <= 2^-40 (the constant model always ends here): theta and sse reported, cov NaN; 0 otherwise.
+ * opts NULL: q = 3.841458820694124, the 95 % point of chi-square with one degree of freedom.
+ *
+ * Checks, on the host before any launch: PINN_E_ARG for NULL or misaligned pointers, ld < 1, a column outside the array,
+ * negative counts, n beyond the rows without a gather list, q not finite and positive, reserved words not 0; n_windows = 0
+ * returns PINN_OK after the options check. */
+#define PINN_BP_MAX_WINDOW 4096
+#define PINN_BP_FIT_WORDS 24
+
+typedef struct pinn_bp_opts { double q; int reserved; int reserved2; } pinn_bp_opts_t;
+
+int pinn_bp_fit(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, const long long* d_row_index,
+                long long n, const long long* d_win_start, const long long* d_win_len, long long n_windows,
+                long long max_window, const pinn_bp_opts_t* opts, double* d_fit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,7 +32,9 @@ axis every per-row diagnosis ignores, a hidden Markov chain over the fault class
 `DeviceHMM` (filter, smoother, Viterbi path, Baum-Welch for the transitions), `TemporalDiagnoser`, `sticky_transitions`,
 `transitions_from_labels`, `scaled_likelihood` (temporal); and which physical quantity of the stack moved, the polarisation
 and thermal parameters identified per window with covariances: `voltage_table`, `thermal_table`, `sliding_windows`,
-`fit_windows`, `fit_baseline`, `drift`, `WindowFit`, `ParameterTracker` (identify).
+`fit_windows`, `fit_baseline`, `drift`, `WindowFit`, `ParameterTracker` (identify); and the same question for the two
+starvation faults, the hydrogen and oxygen excess-ratio laws fitted per window with their breakpoint by exact enumeration:
+`flow_table`, `fit_breakpoints`, `fit_breakpoint_baseline`, `BreakpointFit`, `SupplyTracker`, `supply_law` (supply).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -78,6 +80,8 @@ _LAZY = {
     "transitions_from_labels": "temporal", "scaled_likelihood": "temporal",
     "voltage_table": "identify", "thermal_table": "identify", "sliding_windows": "identify", "fit_windows": "identify",
     "fit_baseline": "identify", "drift": "identify", "WindowFit": "identify", "ParameterTracker": "identify",
+    "flow_table": "supply", "fit_breakpoints": "supply", "fit_breakpoint_baseline": "supply", "BreakpointFit": "supply",
+    "SupplyTracker": "supply", "supply_law": "supply",
 }
 
 

@@ -56,6 +56,9 @@ SOURCES = [
     # parameter identification: float64 Levenberg-Marquardt per window, every operation rounded on its own; the host backend states
     # the same solver, and the on-chip and streaming forms of a row pass must give the same sums
     ("pinn_identify.hip", ["-ffp-contract=off"]),
+    # supply laws: float64 enumeration of a window's breakpoints from running sums, every operation rounded on its own; the host
+    # backend states the same solver
+    ("pinn_breakpoint.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

@@ -135,6 +135,15 @@ class IdOpts(ctypes.Structure):
     _fields_ = [("tol", ctypes.c_double), ("xtol", ctypes.c_double), ("mu0", ctypes.c_double), ("max_passes", c_int), ("reserved", c_int)]
 
 
+# pinn_breakpoint.hip: the longest window and the 8-byte words of a fit row
+BP_MAX_WINDOW, BP_FIT_WORDS = 4096, 24
+
+
+class BpOpts(ctypes.Structure):
+    """pinn_bp_opts_t (pinn_breakpoint.hip)."""
+    _fields_ = [("q", ctypes.c_double), ("reserved", c_int), ("reserved2", c_int)]
+
+
 class PinnError(RuntimeError):
     pass
 
@@ -299,6 +308,8 @@ _SIGS = {
     "pinn_hmm_mstep": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p, ctypes.c_double, c_int, c_void_p]),
     "pinn_id_fit": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll, c_void_p, c_void_p, c_ll, c_void_p, c_ll,
                             ctypes.POINTER(IdOpts), c_void_p, c_void_p, c_void_p]),
+    "pinn_bp_fit": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_void_p, c_ll, c_void_p, c_void_p, c_ll, c_ll,
+                            ctypes.POINTER(BpOpts), c_void_p, c_void_p]),
 }
 
 _lib = None
