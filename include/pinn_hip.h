@@ -1438,6 +1438,103 @@ int pinn_bp_fit(const double* d_arr, long long ld, long long n_arr_rows, const i
                 long long n, const long long* d_win_start, const long long* d_win_len, long long n_windows,
                 long long max_window, const pinn_bp_opts_t* opts, double* d_fit, void* stream);
 
+/* ---- uncertainty calibration and conformal bands: are the voltage network's standard deviations honest? -------------
+ * Predictive law, per row: y ~ N(y_pred, v), v = a ale^2 + b epi^2 + c computed as ((a ale) ale + (b epi) epi) + c, with the
+ * variance model var_model = (a, b, c), finite and non-negative; s = sqrt(v), r = y_true - y_pred, z = r / s.
+ * The rows are a row head as above with the four columns cols = (y_true, y_pred, ale, epi): array, leading dimension, rows
+ * of the array, cols[4], n_cols = 4, gather list or NULL, positions.
+ *
+ * Valid rows.  A position is valid when its gather index lies inside the array, its label maps to a group, y_true and
+ * y_pred are finite, and v is finite and > 0.  Every other position is skipped and counted (n_skipped).
+ * Groups.  label_col >= 0: the row's label x is used when 0 <= x < n_labels (n_labels <= PINN_UNC_MAX_LABELS; a NaN fails),
+ * truncated to an integer, and label_table[label] (host array) is the group 0 .. n_groups - 1 or -1 for "skip";
+ * n_groups <= PINN_UNC_MAX_GROUPS.  label_col = -1: every row is in group 0, no label is read, n_groups must be 1.
+ * Arithmetic.  float64, every operation rounded on its own.  z, |z| and every comparison use +, *, sqrt, / and <= only: z
+ * and everything counted from it are the bits a float64 numpy restatement gives.  log, erfc and exp enter the nll and crps
+ * terms and the per-row Phi only.
+ *
+ * pinn_unc_score: one row pass and a one-workgroup launch that adds the workgroups' partials in index order.
+ *   z_level [n_levels] (n_levels <= PINN_UNC_MAX_LEVELS, each >= 0) and z_edge [n_bins - 1] (strictly ascending, n_bins <=
+ *   PINN_UNC_MAX_BINS) are host arrays of z-values, not probabilities.
+ *   d_sums [n_groups][PINN_UNC_SUMS]: sums over the group's valid rows of 1, r, r^2, s, v (= s^2), z, z^2, nll, crps with
+ *     nll = 0.5 (log 2 pi + log v + z^2),  Phi = 0.5 erfc(-z / sqrt 2),  phi = exp(-0.5 z^2) / sqrt(2 pi),
+ *     crps = s (z (2 Phi - 1) + 2 phi - 1 / sqrt pi), the closed form for a Gaussian.
+ *   d_n [n_groups], d_hits [n_groups][n_levels] = #{|z| <= z_level[l]}, d_pit [n_groups][n_bins] (a row's bin is the number
+ *   of edges <= z), d_n_skipped [1]: int64.  Per-row outputs [n], each skipped when NULL: d_z, d_phi, d_crps, d_nll (NaN on
+ *   a row that is not valid).
+ *   Order of a float sum: workgroup b of row_blocks(n, PINN_UNC_TILE, PINN_UNC_MAX_BLOCKS) takes the tiles b, b + blocks,
+ *   ...; a wave adds the 64 rows of a step by a shuffle tree and the steps in row order, then the four waves and the
+ *   workgroups in index order.  Counts use integer atomics in LDS.  No float atomics.
+ *
+ * pinn_unc_quantiles: exact order statistics of a score per group, n_quantiles <= PINN_UNC_MAX_QUANTILES levels in (0, 1],
+ *   n_groups * n_quantiles <= PINN_UNC_MAX_TARGETS.  kind: PINN_UNC_ABS_Z (|z|), PINN_UNC_Z (z), PINN_UNC_COLUMN (the value
+ *   of column score_col; valid = inside the array, label mapped, value finite; the four columns are not read).
+ *   Keys: the bits of the double (-0 taken as +0), all flipped for a negative value, the sign bit set otherwise: unsigned
+ *   order = numeric order.  The result is the k-th smallest score (1-based) of the group's n_g valid rows, with k computed on
+ *   the device in float64:  conformal != 0: k = ceil((n_g + 1) level), k > n_g gives +inf;  conformal = 0: k = ceil(n_g level)
+ *   clipped to [1, n_g].  An empty group gives NaN and rank 0.
+ *   d_q [n_groups][n_quantiles], d_rank [n_groups][n_quantiles] (k), d_n [n_groups], d_n_skipped [1].
+ *   Method: eight passes over the rows read in place, the key's bytes from the top; scores are computed on the fly and
+ *   never stored.  A pass counts, per target, the next byte of the rows that carry the target's prefix: 32-bit integer atomics
+ *   on a [targets][256] histogram in LDS, merged by 64-bit integer atomics into the workspace.  Targets that still share
+ *   group and prefix share one histogram.  After each pass a one-workgroup launch moves every target's prefix and remaining
+ *   rank on in a device header and clears the histograms; the first also counts n_g.  A target whose new prefix at most
+ *   PINN_UNC_COLLECT keys carry stops counting: the next pass appends those keys to a list in the workspace (an integer
+ *   atomic hands out the places; their order is arbitrary), and a launch of one workgroup per target picks the key with
+ *   fewer than k keys below it and at least k at or below it, by counting, so neither ties nor the order matter.  Passes
+ *   in which no target is left return at once.  No host synchronisation between passes and no workgroup waits on
+ *   another.  n <= 2^40.
+ *
+ * pinn_unc_update: the online band, one launch of one workgroup per chunk of n <= PINN_UNC_MAX_CHUNK positions (one group).
+ *   d_state: 8-byte words; [0] fill and [1] next position of the ring (int64), [2] alpha_t, [3] q_t (float64), [4] valid and
+ *   [5] missed rows so far (int64), [6..7] zero, then the ring of the last `window` scores |z| from word
+ *   PINN_UNC_STATE_HEADER on; pinn_unc_state_bytes(window) bytes, window <= PINN_UNC_MAX_WINDOW (0 outside).
+ *   1 every position gets lo / hi = y_pred -+ q_t s, z and a flag (1: |z| <= q_t is false, 0: inside, -1 and NaNs: not valid),
+ *     with q_t as at the start of the chunk; each output is skipped when NULL (d_flag is int32).
+ *   2 learn != 0: the valid rows' scores enter the ring in row order (of more than `window` the last `window` remain).
+ *   3 alpha <- clip(alpha + gamma ((1 - level) - misses / valid), alpha_min, alpha_max); skipped when valid = 0.
+ *   4 q <- the k-th smallest of the m ring entries, k = max(1, ceil((m + 1) (1 - alpha))) in float64, +inf when k > m.
+ *   The ring image is sorted by a bitonic network in LDS (non-negative doubles order as their bits).  learn = 0 leaves
+ *   every byte of the state as it is.  0 < level < 1, gamma >= 0 and finite, 0 <= alpha_min <= alpha_max <= 1.
+ *
+ * Checks, on the host before any launch: PINN_E_ARG for NULL or misaligned pointers and sizes outside the limits (edges
+ * that do not ascend, a label table entry outside -1 .. n_groups - 1, n_cols != 4); PINN_E_WORKSPACE for a workspace below
+ * pinn_unc_workspace_bytes(n, n_groups, n_quantiles) (256-byte aligned, enough for either entry point; pinn_unc_score asks
+ * for n_quantiles = 1; 0 outside the limits); n = 0 returns PINN_OK without a launch. */
+#define PINN_UNC_TILE 2048
+#define PINN_UNC_MAX_BLOCKS 1024
+#define PINN_UNC_SUMS 9
+#define PINN_UNC_MAX_GROUPS 16
+#define PINN_UNC_MAX_LABELS 64
+#define PINN_UNC_MAX_LEVELS 16
+#define PINN_UNC_MAX_BINS 64
+#define PINN_UNC_MAX_QUANTILES 8
+#define PINN_UNC_MAX_TARGETS 64
+#define PINN_UNC_COLLECT 256
+#define PINN_UNC_MAX_WINDOW 4096
+#define PINN_UNC_MAX_CHUNK 2048
+#define PINN_UNC_STATE_HEADER 8
+#define PINN_UNC_ABS_Z 0
+#define PINN_UNC_Z 1
+#define PINN_UNC_COLUMN 2
+
+size_t pinn_unc_workspace_bytes(long long n, int n_groups, int n_quantiles);
+size_t pinn_unc_state_bytes(int window);
+int pinn_unc_score(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_cols,
+                   const long long* d_row_index, long long n, int label_col, const int* label_table, int n_labels,
+                   int n_groups, const double* var_model, const double* z_level, int n_levels, const double* z_edge,
+                   int n_bins, double* d_sums, long long* d_n, long long* d_hits, long long* d_pit, long long* d_n_skipped,
+                   double* d_z, double* d_phi, double* d_crps, double* d_nll, void* d_ws, size_t ws_bytes, void* stream);
+int pinn_unc_quantiles(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_cols,
+                       const long long* d_row_index, long long n, int label_col, const int* label_table, int n_labels,
+                       int n_groups, const double* var_model, int kind, int score_col, const double* levels, int n_quantiles,
+                       int conformal, double* d_q, long long* d_rank, long long* d_n, long long* d_n_skipped, void* d_ws,
+                       size_t ws_bytes, void* stream);
+int pinn_unc_update(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_cols,
+                    const long long* d_row_index, long long n, const double* var_model, double level, double gamma,
+                    double alpha_min, double alpha_max, int window, int learn, void* d_state, double* d_lo, double* d_hi,
+                    double* d_z, int* d_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,10 @@ axis every per-row diagnosis ignores, a hidden Markov chain over the fault class
 and thermal parameters identified per window with covariances: `voltage_table`, `thermal_table`, `sliding_windows`,
 `fit_windows`, `fit_baseline`, `drift`, `WindowFit`, `ParameterTracker` (identify); and the same question for the two
 starvation faults, the hydrogen and oxygen excess-ratio laws fitted per window with their breakpoint by exact enumeration:
-`flow_table`, `fit_breakpoints`, `fit_breakpoint_baseline`, `BreakpointFit`, `SupplyTracker`, `supply_law` (supply).
+`flow_table`, `fit_breakpoints`, `fit_breakpoint_baseline`, `BreakpointFit`, `SupplyTracker`, `supply_law` (supply); and
+whether the voltage network's own standard deviations are honest, reliability scores, exact conformal quantiles and an online
+band: `score_uncertainty`, `conformal_quantiles`, `conformal_band`, `UncertaintyMonitor`, `UncertaintyReport`, `Quantiles`
+(uncertainty).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -82,6 +85,8 @@ _LAZY = {
     "fit_baseline": "identify", "drift": "identify", "WindowFit": "identify", "ParameterTracker": "identify",
     "flow_table": "supply", "fit_breakpoints": "supply", "fit_breakpoint_baseline": "supply", "BreakpointFit": "supply",
     "SupplyTracker": "supply", "supply_law": "supply",
+    "score_uncertainty": "uncertainty", "conformal_quantiles": "uncertainty", "conformal_band": "uncertainty",
+    "UncertaintyMonitor": "uncertainty", "UncertaintyReport": "uncertainty", "Quantiles": "uncertainty",
 }
 
 

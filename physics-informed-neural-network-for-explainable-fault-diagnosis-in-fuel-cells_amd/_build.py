@@ -59,6 +59,9 @@ SOURCES = [
     # supply laws: float64 enumeration of a window's breakpoints from running sums, every operation rounded on its own; the host
     # backend states the same solver
     ("pinn_breakpoint.hip", ["-ffp-contract=off"]),
+    # uncertainty calibration: float64, every operation rounded on its own; z and everything counted from it are the host
+    # backend's to the bit
+    ("pinn_uncertainty.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

@@ -144,6 +144,14 @@ class BpOpts(ctypes.Structure):
     _fields_ = [("q", ctypes.c_double), ("reserved", c_int), ("reserved2", c_int)]
 
 
+# pinn_uncertainty.hip: the row tile and the limit of partial sums (they fix the order of every float sum), the limits,
+# the 8-byte words of the monitor's state header and the score kinds
+UNC_TILE, UNC_MAX_BLOCKS, UNC_SUMS, UNC_MAX_GROUPS, UNC_MAX_LABELS, UNC_MAX_LEVELS, UNC_MAX_BINS = 2048, 1024, 9, 16, 64, 16, 64
+UNC_MAX_QUANTILES, UNC_MAX_TARGETS, UNC_MAX_WINDOW, UNC_MAX_CHUNK, UNC_STATE_HEADER = 8, 64, 4096, 2048, 8
+UNC_ABS_Z, UNC_Z, UNC_COLUMN = 0, 1, 2
+UNC_COLLECT = 256                       # the select gathers a target's keys once at most this many carry its prefix
+
+
 class PinnError(RuntimeError):
     pass
 
@@ -160,6 +168,9 @@ E_RANGE = -4
 _ROWS = [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll]
 # what follows it in the pinn_gmm_batch_* entry points: candidates, their component counts (host array), the largest count
 _BATCH = [c_int, ctypes.POINTER(c_int), c_int]
+# what follows it in pinn_unc_score / pinn_unc_quantiles: label column, label table (host array), labels, groups
+_UNC_GROUPS = [c_int, ctypes.POINTER(c_int), c_int, c_int]
+_c_dp = ctypes.POINTER(ctypes.c_double)    # a host array of float64
 
 _SIGS = {
     "pinn_abi_version": (c_int, []),
@@ -310,6 +321,14 @@ _SIGS = {
                             ctypes.POINTER(IdOpts), c_void_p, c_void_p, c_void_p]),
     "pinn_bp_fit": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_void_p, c_ll, c_void_p, c_void_p, c_ll, c_ll,
                             ctypes.POINTER(BpOpts), c_void_p, c_void_p]),
+    "pinn_unc_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
+    "pinn_unc_state_bytes": (c_size_t, [c_int]),
+    "pinn_unc_score": (c_int, _ROWS + _UNC_GROUPS + [_c_dp, _c_dp, c_int, _c_dp, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_unc_quantiles": (c_int, _ROWS + _UNC_GROUPS + [_c_dp, c_int, c_int, _c_dp, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                         c_void_p, c_size_t, c_void_p]),
+    "pinn_unc_update": (c_int, _ROWS + [_c_dp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
