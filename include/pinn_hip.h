@@ -686,6 +686,66 @@ int pinn_lr_roc(const double* d_score_sorted, const long long* d_pos_sorted, lon
                 long long* d_counts, long long* d_fps, long long* d_tps, double* d_thresholds, double* d_fpr, double* d_tpr,
                 void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- batches of logistic regressions: feature selection over column subsets ------------------------------------
+ * n_batch <= PINN_LR_MAX_BATCH candidates are standardised, fitted and scored together.  They share the array and the
+ * row set (d_arr, ld, n_arr_rows, d_row_index, n: the row head above without its column list), d_y, n_classes, tol, l2,
+ * fit_intercept and balanced.  Candidate c reads n_feat[c] columns (1..max_feat), cols[c * max_feat + i], i < n_feat[c].
+ * Both lists are given twice: as host arrays, which are checked before any launch, and as device copies d_n_feat, d_cols of
+ * the same layout, which the kernels read.  A kernel that meets a column outside [0, ld) in the device copy reads nothing
+ * for that candidate's rows, as a gather index outside the array reads nothing.
+ *
+ * The state block of candidate c starts c * pinn_lr_batch_state_stride(n_classes, max_feat) bytes into d_state and has
+ * exactly the single-model layout for (n_classes, n_feat[c]): it is a valid d_state of pinn_lr_newton and, from its mean,
+ * scale and accepted point, of pinn_lr_posterior's model block.  The caller zeroes the blocks and writes the starting point
+ * and MAXITER into each, as for the single model.
+ *
+ * The row passes run on a grid of (row blocks, candidates), the judgements with one workgroup per candidate, and both are
+ * the single model's device code with the same tile-to-workgroup map, the same row_blocks(n, 128, 1024) partials per sum and
+ * the same order of every sum: a candidate's bytes are those of the single-model calls and do not depend on what else is in
+ * the batch.  A candidate whose header says stopped (CONVERGED, STATUS, or ITER >= MAXITER) returns at once in both kernels
+ * while the others go on.  No entry point synchronises with the host.
+ *
+ * The workspace holds, per candidate, the totals, row_blocks(n, 128, 1024) partials per sum and as many class-count partials:
+ * it grows with the rows, so that 4096 candidates over 1.3e3 rows stay within a few MiB.
+ *
+ * n_batch outside 1..PINN_LR_MAX_BATCH, an n_feat[c] outside 1..max_feat, a column outside [0, ld), (n_classes, max_feat)
+ * outside the limits of the single model, NULL or misaligned pointers: PINN_E_ARG; a workspace below
+ * pinn_lr_batch_workspace_bytes(n, n_batch, n_classes, max_feat): PINN_E_WORKSPACE; both before any launch. */
+#define PINN_LR_MAX_BATCH 4096
+
+size_t pinn_lr_batch_state_stride(int n_classes, int max_feat);             /* bytes; 0 for sizes outside the limits */
+size_t pinn_lr_batch_workspace_bytes(long long n_rows, int n_batch, int n_classes, int max_feat);   /* likewise */
+
+/* pinn_lr_scaler per candidate, four launches for the whole batch: mean, var, scale, class counts, class weights, SWSUM,
+ * NSEEN, C, D of every state block. */
+int pinn_lr_batch_scaler(const double* d_arr, long long ld, long long n_arr_rows, const long long* d_row_index, long long n,
+                         const long long* d_y, int n_classes, int n_batch, const int* n_feat, const int* cols, int max_feat,
+                         const int* d_n_feat, const int* d_cols, int balanced, double* d_state, void* d_ws, size_t ws_bytes,
+                         void* stream);
+
+/* pinn_lr_newton per candidate: n_passes times (row pass, judgement), two launches each for the whole batch. */
+int pinn_lr_batch_newton(const double* d_arr, long long ld, long long n_arr_rows, const long long* d_row_index, long long n,
+                         const long long* d_y, int n_classes, int n_batch, const int* n_feat, const int* cols, int max_feat,
+                         const int* d_n_feat, const int* d_cols, int n_passes, double tol, double l2, int fit_intercept,
+                         double* d_state, void* d_ws, size_t ws_bytes, void* stream);
+
+/* Scores of a row set (which need not be the one fitted on, with its own d_y) under every candidate's accepted point, two
+ * launches: d_loss_sum [n_batch] the sum of -log p[y] (unweighted; rows of a tile, tiles of a workgroup, workgroups, each in
+ * index order), d_hits [n_batch] the rows whose first-maximum class equals y, and d_p_fault (may be NULL) [n_batch][n] =
+ * 1 - p[normal_class], the bytes that pinn_lr_posterior writes for the same model.  A row that reads nothing or whose class is
+ * outside [0, n_classes) adds nothing to either sum; the former gets a NaN p_fault. */
+int pinn_lr_batch_score(const double* d_arr, long long ld, long long n_arr_rows, const long long* d_row_index, long long n,
+                        const long long* d_y, int n_classes, int n_batch, const int* n_feat, const int* cols, int max_feat,
+                        const int* d_n_feat, const int* d_cols, const double* d_state, int normal_class, double* d_loss_sum,
+                        long long* d_hits, double* d_p_fault, void* d_ws, size_t ws_bytes, void* stream);
+
+/* The integers of pinn_lr_roc for n_batch rows of scores, one launch: d_score_sorted [n_batch][n], each row sorted
+ * descending, d_pos_sorted [n_batch][n] the flags gathered with them, d_counts [n_batch][PINN_LR_ROC_COUNTS] with positives,
+ * negatives, distinct scores and U2 at PINN_LR_ROC_POS, _N, _M and _U2 (the other words are 0).  Equal scores form one
+ * group, as in pinn_lr_roc, so U2 is its U2 exactly. */
+int pinn_lr_batch_auc(const double* d_score_sorted, const long long* d_pos_sorted, long long n, int n_batch, long long* d_counts,
+                      void* stream);
+
 /* ---- clustering baselines of the method comparison: reference script 05 (cited as 05:<line>) -------------------------
  * k-means and Ward agglomerative clustering with nearest-centre assignment, float64 throughout, every operation rounded on
  * its own.  Rows are read in place as for the mixture above (column list, optional gather list, leading dimension; an index

@@ -25,7 +25,9 @@ reached from `compare_methods` through `spectral_extras` (comparison); and the R
 `build_kernel_svm_classifier` and `KernelSVMDiagnoser` (ksvm), reached from `compare_methods` through `kernel_extras` (comparison);
 and what script 02's four AUCs leave open, their intervals and paired tests: `auc_components`, `delong_covariance`, `auc_ci`,
 `delong_test`, `compare_aucs`, `bootstrap_auc`, `compare_feature_groups` (rocstat); and the choice of the mixture's size and
-seed, all candidates fitted and scored in one batch: `gmm_sweep`, `select_gmm`, `GMMSweep` (selection); and the question after
+seed, all candidates fitted and scored in one batch: `gmm_sweep`, `select_gmm`, `GMMSweep` (selection); and the choice of script 02's feature group, every column subset of
+a pool fitted and scored in one batch: `feature_subsets`, `feature_sweep`, `select_features`, `forward_select`,
+`FeatureSweep`, `ForwardPath` (featsel); and the question after
 a diagnosis, which input made the model say so, as exact Shapley values over all coalitions: `shapley_diagnosis`,
 `shapley_values`, `voltage_predictor`, `DiagnosisExplainer`, `global_importance`, `top_features` (explain); and the time
 axis every per-row diagnosis ignores, a hidden Markov chain over the fault classes with the posteriors as emissions:
@@ -77,6 +79,8 @@ _LAZY = {
     "auc_components": "rocstat", "delong_covariance": "rocstat", "auc_ci": "rocstat", "delong_test": "rocstat",
     "compare_aucs": "rocstat", "bootstrap_auc": "rocstat", "compare_feature_groups": "rocstat",
     "gmm_sweep": "selection", "select_gmm": "selection", "GMMSweep": "selection",
+    "feature_subsets": "featsel", "feature_sweep": "featsel", "select_features": "featsel", "forward_select": "featsel",
+    "FeatureSweep": "featsel", "ForwardPath": "featsel",
     "shapley_values": "explain", "shapley_diagnosis": "explain", "voltage_predictor": "explain", "DiagnosisExplainer": "explain",
     "global_importance": "explain", "top_features": "explain", "Shapley": "explain",
     "DeviceHMM": "temporal", "TemporalDiagnoser": "temporal", "sticky_transitions": "temporal",

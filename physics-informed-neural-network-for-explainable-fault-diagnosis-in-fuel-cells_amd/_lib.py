@@ -84,6 +84,7 @@ WARD_ST_N, WARD_ST_D, WARD_ST_MERGES, WARD_ST_CHAIN, WARD_ST_FIRST = range(3, 8)
 
 # pinn_lr.hip: limits, status and the 8-byte words of the state header and of the ROC counts
 LR_MAX_CLASSES, LR_MAX_FEAT, LR_MAX_HESS, LR_SINGULAR, LR_NAN, LR_STALLED, LR_TILE = 13, 8, 1365, 1, 2, 3, 128
+LR_MAX_BATCH = 4096
 (LR_ST_ITER, LR_ST_CONVERGED, LR_ST_STATUS, LR_ST_C, LR_ST_D, LR_ST_F, LR_ST_STEP, LR_ST_DD, LR_ST_PASSES, LR_ST_GMAX, LR_ST_SWSUM,
  LR_ST_PHASE, LR_ST_NSEEN, LR_ST_MAXITER) = range(14)
 LR_ST_HEADER = 16
@@ -168,6 +169,11 @@ E_RANGE = -4
 _ROWS = [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_void_p, c_ll]
 # what follows it in the pinn_gmm_batch_* entry points: candidates, their component counts (host array), the largest count
 _BATCH = [c_int, ctypes.POINTER(c_int), c_int]
+# the head of the pinn_lr_batch_* entry points: array, leading dimension, rows of the array, gather index or NULL, rows to
+# read, class indices, classes; candidates, their feature counts and column lists (host arrays), the largest count, and the
+# device copies of both lists
+_LR_BATCH = [c_void_p, c_ll, c_ll, c_void_p, c_ll, c_void_p, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
+             c_void_p, c_void_p]
 # what follows it in pinn_unc_score / pinn_unc_quantiles: label column, label table (host array), labels, groups
 _UNC_GROUPS = [c_int, ctypes.POINTER(c_int), c_int, c_int]
 _c_dp = ctypes.POINTER(ctypes.c_double)    # a host array of float64
@@ -260,6 +266,12 @@ _SIGS = {
     "pinn_lr_roc_workspace_bytes": (c_size_t, [c_ll]),
     "pinn_lr_roc": (c_int, [c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_size_t, c_void_p]),
+    "pinn_lr_batch_state_stride": (c_size_t, [c_int, c_int]),
+    "pinn_lr_batch_workspace_bytes": (c_size_t, [c_ll, c_int, c_int, c_int]),
+    "pinn_lr_batch_scaler": (c_int, _LR_BATCH + [c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_lr_batch_newton": (c_int, _LR_BATCH + [c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_lr_batch_score": (c_int, _LR_BATCH + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_lr_batch_auc": (c_int, [c_void_p, c_void_p, c_ll, c_int, c_void_p, c_void_p]),
     "pinn_km_state_bytes": (c_size_t, [c_ll, c_int, c_int]),
     "pinn_km_workspace_bytes": (c_size_t, [c_ll, c_int, c_int]),
     "pinn_km_lloyd": (c_int, _ROWS + [c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -5,6 +5,10 @@
 //   pinn_lr_newton     damped Newton iterations, two launches each, no host synchronisation between them
 //   pinn_lr_posterior  decision_function, predict_proba, predict and p_fault per row, one launch
 //   pinn_lr_roc        boundaries of the sorted scores, fps / tps, drop_intermediate, fpr / tpr and the integer area
+//   pinn_lr_batch_*    scaler, Newton iterations, validation scores and the integer area for a batch of models over column
+//                      subsets of one array: grids of (row blocks, candidates) and one workgroup per candidate around the
+//                      single model's bodies (lr_stats_body, lr_rows_body, lr_final_body, post_scores), so that a
+//                      candidate's bytes are the single model's
 //
 // The row pass follows pinn_gmm.hip: a workgroup takes tiles of 128 rows, one thread per row standardises its row and
 // writes (z, 1), the class probabilities, the sample weight and the loss term into LDS; then every thread owns up to 12 of
@@ -86,8 +90,9 @@ __device__ __forceinline__ double softmax_inplace(double* s, int C) {
 }
 
 // ---- the row pass.  part: [gridDim.x][n_sums]
-__global__ __launch_bounds__(kRows) void lr_rows_kernel(Rows a, const double* __restrict__ st, const long long* __restrict__ y_in,
-                                                        int force, double* __restrict__ part) {
+// (bx of gx: the workgroup's place among those of its model, which is blockIdx.x of gridDim.x in both launch forms)
+__device__ __forceinline__ void lr_rows_body(const Rows& a, const double* __restrict__ st, const long long* __restrict__ y_in, int force,
+                                             double* __restrict__ part, unsigned bx, unsigned gx) {
   __shared__ double s_p[kRows * kMaxC];          // probabilities, row stride C | 1
   __shared__ double s_u[kRows * (kMaxD + 1)];    // (z, 1), row stride (D + 1) | 1
   __shared__ double s_w[kRows], s_l[kRows];
@@ -122,7 +127,7 @@ __global__ __launch_bounds__(kRows) void lr_rows_kernel(Rows a, const double* __
   }
 
   const long long tiles = (a.n + kRows - 1) / kRows;
-  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+  for (long long tile = bx; tile < tiles; tile += gx) {
     const long long j = tile * kRows + t;
     double x[kMaxD];
     bool ok = false;
@@ -173,13 +178,17 @@ __global__ __launch_bounds__(kRows) void lr_rows_kernel(Rows a, const double* __
   }
 #pragma unroll
   for (int q = 0; q < kMaxOut; ++q)
-    if (oc[q] != -2) part[(size_t)blockIdx.x * n_sums + t + q * kRows] = acc[q];
+    if (oc[q] != -2) part[(size_t)bx * n_sums + t + q * kRows] = acc[q];
+}
+
+__global__ __launch_bounds__(kRows) void lr_rows_kernel(Rows a, const double* __restrict__ st, const long long* __restrict__ y_in,
+                                                        int force, double* __restrict__ part) {
+  lr_rows_body(a, st, y_in, force, part, blockIdx.x, gridDim.x);
 }
 
 // ---- sums of the partials in index order, then the step.  One workgroup.  tot: [n_sums] (kept in the workspace).
-__global__ __launch_bounds__(kFinThreads) void lr_final_kernel(double* __restrict__ st, int C, int D, int mode, int n_part, long long n,
-                                                               double tol, double l2, int fit_intercept,
-                                                               const double* __restrict__ part, double* __restrict__ tot) {
+__device__ __forceinline__ void lr_final_body(double* __restrict__ st, int C, int D, int mode, int n_part, long long n, double tol, double l2,
+                                              int fit_intercept, const double* __restrict__ part, double* __restrict__ tot) {
   __shared__ double A[kMaxP * kMaxP];
   __shared__ double g[kMaxP], dirv[kMaxP];
   __shared__ int s_flag;
@@ -325,9 +334,15 @@ __global__ __launch_bounds__(kFinThreads) void lr_final_kernel(double* __restric
   }
 }
 
+__global__ __launch_bounds__(kFinThreads) void lr_final_kernel(double* __restrict__ st, int C, int D, int mode, int n_part, long long n,
+                                                               double tol, double l2, int fit_intercept,
+                                                               const double* __restrict__ part, double* __restrict__ tot) {
+  lr_final_body(st, C, D, mode, n_part, n, tol, l2, fit_intercept, part, tot);
+}
+
 // ---- scaler: sums of x (pass 0) or of (x - mean)^2 (pass 1) per feature, class counts.  part: [grid][D], cnt: [grid][C]
-__global__ __launch_bounds__(kRows) void lr_stats_kernel(Rows a, const double* __restrict__ st, const long long* __restrict__ y_in, int pass,
-                                                         double* __restrict__ part, long long* __restrict__ cnt) {
+__device__ __forceinline__ void lr_stats_body(const Rows& a, const double* __restrict__ st, const long long* __restrict__ y_in, int pass,
+                                              double* __restrict__ part, long long* __restrict__ cnt, unsigned bx, unsigned gx) {
   __shared__ double s_x[kRows * (kMaxD + 1)];
   __shared__ int s_y[kRows];
   const int C = a.K, D = a.D, Dp = D | 1, t = threadIdx.x;
@@ -335,7 +350,7 @@ __global__ __launch_bounds__(kRows) void lr_stats_kernel(Rows a, const double* _
   double acc = 0.0;
   long long count = 0;
   const long long tiles = (a.n + kRows - 1) / kRows;
-  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+  for (long long tile = bx; tile < tiles; tile += gx) {
     const long long j = tile * kRows + t;
     double x[kMaxD];
     bool ok = false;
@@ -360,12 +375,17 @@ __global__ __launch_bounds__(kRows) void lr_stats_kernel(Rows a, const double* _
     }
     __syncthreads();
   }
-  if (t < D) part[(size_t)blockIdx.x * D + t] = acc;
-  else if (t - kMaxD >= 0 && t - kMaxD < C) cnt[(size_t)blockIdx.x * C + (t - kMaxD)] = count;
+  if (t < D) part[(size_t)bx * D + t] = acc;
+  else if (t - kMaxD >= 0 && t - kMaxD < C) cnt[(size_t)bx * C + (t - kMaxD)] = count;
 }
 
-__global__ __launch_bounds__(64) void lr_stats_final_kernel(double* __restrict__ st, int C, int D, int pass, int balanced, int n_part,
-                                                            const double* __restrict__ part, const long long* __restrict__ cnt) {
+__global__ __launch_bounds__(kRows) void lr_stats_kernel(Rows a, const double* __restrict__ st, const long long* __restrict__ y_in, int pass,
+                                                         double* __restrict__ part, long long* __restrict__ cnt) {
+  lr_stats_body(a, st, y_in, pass, part, cnt, blockIdx.x, gridDim.x);
+}
+
+__device__ __forceinline__ void lr_stats_final_body(double* __restrict__ st, int C, int D, int pass, int balanced, int n_part,
+                                                    const double* __restrict__ part, const long long* __restrict__ cnt) {
   __shared__ long long s_cnt[kMaxC];
   long long* hdr = reinterpret_cast<long long*>(st);
   const int t = threadIdx.x;
@@ -407,6 +427,30 @@ __global__ __launch_bounds__(64) void lr_stats_final_kernel(double* __restrict__
   }
 }
 
+__global__ __launch_bounds__(64) void lr_stats_final_kernel(double* __restrict__ st, int C, int D, int pass, int balanced, int n_part,
+                                                            const double* __restrict__ part, const long long* __restrict__ cnt) {
+  lr_stats_final_body(st, C, D, pass, balanced, n_part, part, cnt);
+}
+
+// The posterior's scores of a row into p[0..C): R parameter rows W [R][D + 1] (coefficients, then the intercept), R = 1 for
+// two classes (scores (-d, d)); NaN for a row that read nothing.  Shared with the batched score.
+__device__ __forceinline__ void post_scores(const double x[kMaxD], bool ok, int C, int D, int R, const double* mean, const double* scale,
+                                            const double* W, double* p) {
+  double u[kMaxD];
+  if (ok) {
+    row_scores(x, D, R, mean, scale, W, D + 1, true, u, p, 1);
+    if (R == 1) { p[1] = p[0]; p[0] = -p[1]; }
+  } else {
+    for (int c = 0; c < C; ++c) p[c] = quiet_nan();
+  }
+}
+
+__device__ __forceinline__ int first_max(const double* p, int C) {
+  int best = 0;
+  for (int c = 1; c < C; ++c) best = p[c] > p[best] ? c : best;
+  return best;
+}
+
 // ---- posterior of given rows: one thread per row, every output optional.
 // model: mean [D], scale [D], W [R][D], b [R]; R = 1 for two classes (scikit-learn's coef_ [1, D]: scores (-d, d)), else C.
 __global__ __launch_bounds__(kRows) void lr_posterior_kernel(Rows a, const double* __restrict__ model, int normal, double* __restrict__ dec_out,
@@ -423,21 +467,15 @@ __global__ __launch_bounds__(kRows) void lr_posterior_kernel(Rows a, const doubl
   __syncthreads();
   const long long j = (long long)blockIdx.x * kRows + t;
   if (j >= a.n) return;
-  double x[kMaxD], u[kMaxD];
+  double x[kMaxD];
   const bool ok = load_row(a, j, x);
   double* p = s_p + t * Cp;
-  if (ok) {
-    row_scores(x, D, R, s_mean, s_scale, s_W, D + 1, true, u, p, 1);
-    if (R == 1) { p[1] = p[0]; p[0] = -p[1]; }
-  } else {
-    for (int c = 0; c < C; ++c) p[c] = quiet_nan();
-  }
+  post_scores(x, ok, C, D, R, s_mean, s_scale, s_W, p);
   if (dec_out) {
     if (R == 1) dec_out[j] = p[1];
     else for (int c = 0; c < C; ++c) dec_out[j * C + c] = p[c];
   }
-  int best = 0;
-  for (int c = 1; c < C; ++c) best = p[c] > p[best] ? c : best;       // the first maximum
+  const int best = first_max(p, C);
   if (pred_out) pred_out[j] = ok ? best : -1;
   if (proba_out || pf_out) {
     if (ok) softmax_inplace(p, C);
@@ -568,6 +606,192 @@ __global__ __launch_bounds__(kTile) void roc_emit2_kernel(const long long* __res
     if (o_thr) o_thr[0] = INFINITY;
     if (o_fpr) o_fpr[0] = 0.0;
     if (o_tpr) o_tpr[0] = 0.0;
+  }
+}
+
+// ---- batches of models over column subsets (feature selection).  Candidate c: n_feat[c] columns cols[c][0..n_feat[c]) of
+// the shared array, state block c * stride words into the states, its own totals, partials and class-count partials in
+// the workspace.  Every kernel below places a candidate's workgroups as the single launch places them (blockIdx.x of
+// gridDim.x) and calls the single model's body: the bytes of a candidate are those of the single-model calls.
+struct Batch {
+  const int* n_feat;          // device, [n_batch]
+  const int* cols;            // device, [n_batch][max_feat]
+  int max_feat;
+  size_t stride;              // words of a state block
+  size_t tot_w, part_w, cnt_w;   // words of a candidate's totals, partials and count partials
+};
+
+__device__ __forceinline__ int batch_feat(const Batch& b, int c) {
+  const int D = b.n_feat[c];
+  return D >= 1 && D <= b.max_feat ? D : 1;
+}
+
+// The rows of candidate c.  A column outside [0, ld) reads nothing for any row, as a gather index outside the array does.
+__device__ __forceinline__ Rows batch_rows(const Rows& base, const Batch& b, int c) {
+  Rows a = base;
+  const int D = batch_feat(b, c);
+  bool ok = D == b.n_feat[c];
+  a.D = D;
+#pragma unroll
+  for (int i = 0; i < kMaxD; ++i) {
+    int col = i < D ? b.cols[(size_t)c * b.max_feat + i] : 0;
+    if (col < 0 || col >= base.ld) { ok = false; col = 0; }
+    a.col[i] = col;
+  }
+  if (!ok) a.n_arr = 0;
+  return a;
+}
+
+__global__ __launch_bounds__(kRows) void lr_batch_stats_kernel(Rows base, Batch b, const double* __restrict__ st_all,
+                                                               const long long* __restrict__ y_in, int pass, double* __restrict__ part_all,
+                                                               long long* __restrict__ cnt_all) {
+  const int c = blockIdx.y;
+  const Rows a = batch_rows(base, b, c);
+  lr_stats_body(a, st_all + c * b.stride, y_in, pass, part_all + c * b.part_w, cnt_all + c * b.cnt_w, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(64) void lr_batch_stats_final_kernel(Batch b, double* __restrict__ st_all, int C, int pass, int balanced, int n_part,
+                                                                  const double* __restrict__ part_all, const long long* __restrict__ cnt_all) {
+  const int c = blockIdx.x;
+  lr_stats_final_body(st_all + c * b.stride, C, batch_feat(b, c), pass, balanced, n_part, part_all + c * b.part_w, cnt_all + c * b.cnt_w);
+}
+
+__global__ __launch_bounds__(kRows) void lr_batch_rows_kernel(Rows base, Batch b, const double* __restrict__ st_all,
+                                                              const long long* __restrict__ y_in, double* __restrict__ part_all) {
+  const int c = blockIdx.y;
+  const double* st = st_all + c * b.stride;
+  if (stopped(st)) return;                                    // before the candidate's columns are even read
+  const Rows a = batch_rows(base, b, c);
+  lr_rows_body(a, st, y_in, 0, part_all + c * b.part_w, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(kFinThreads) void lr_batch_final_kernel(Batch b, double* __restrict__ st_all, int C, int n_part, long long n,
+                                                                     double tol, double l2, int fit_intercept,
+                                                                     const double* __restrict__ part_all, double* __restrict__ tot_all) {
+  const int c = blockIdx.x;
+  lr_final_body(st_all + c * b.stride, C, batch_feat(b, c), FIN_NEWTON, n_part, n, tol, l2, fit_intercept, part_all + c * b.part_w,
+                tot_all + c * b.tot_w);
+}
+
+// Score of a second row set under every candidate's accepted point: the posterior's arithmetic per row (its model block is
+// the state's mean, scale and accepted point; for two classes the row of class 1), then -log p[y], the hit and p_fault.
+// A workgroup adds the terms of a tile in row order and its tiles in order; loss partials [gridDim.x], then hit partials.
+__global__ __launch_bounds__(kRows) void lr_batch_score_kernel(Rows base, Batch b, const double* __restrict__ st_all,
+                                                               const long long* __restrict__ y_in, int normal, double* __restrict__ pf_out,
+                                                               double* __restrict__ part_all) {
+  __shared__ double s_p[kRows * kMaxC];
+  __shared__ double s_mean[kMaxD], s_scale[kMaxD], s_W[kMaxC * (kMaxD + 1)];
+  __shared__ double s_l[kRows];
+  __shared__ int s_h[kRows];
+  const int c = blockIdx.y, t = threadIdx.x;
+  const double* st = st_all + c * b.stride;
+  const Rows a = batch_rows(base, b, c);
+  const int C = a.K, D = a.D, Cp = C | 1, R = C == 2 ? 1 : C;
+  if (t < D) { s_mean[t] = st[st_mean(C, D) + t]; s_scale[t] = st[st_scale(C, D) + t]; }
+  for (int e = t; e < R * (D + 1); e += kRows) s_W[e] = st[st_prev(C, D) + (R == 1 ? D + 1 : 0) + e];
+  __syncthreads();
+  double loss = 0.0;
+  long long hits = 0;
+  const long long tiles = (a.n + kRows - 1) / kRows;
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long long j = tile * kRows + t;
+    double term = 0.0;
+    int hit = 0;
+    if (j < a.n) {
+      double x[kMaxD];
+      const bool ok = load_row(a, j, x);
+      const long long cls = y_in[j];
+      double* p = s_p + t * Cp;
+      post_scores(x, ok, C, D, R, s_mean, s_scale, s_W, p);
+      const int best = first_max(p, C);
+      if (ok) softmax_inplace(p, C);
+      if (pf_out) pf_out[(size_t)c * a.n + j] = 1.0 - p[normal];
+      if (ok && cls >= 0 && cls < C) {                        // a class outside [0, C) adds nothing
+        term = -log(p[cls]);
+        hit = best == cls;
+      }
+    }
+    s_l[t] = term;
+    s_h[t] = hit;
+    __syncthreads();
+    if (t == 0) {
+      for (int rr = 0; rr < kRows; ++rr) loss += s_l[rr];
+    } else if (t == 64) {
+      for (int rr = 0; rr < kRows; ++rr) hits += s_h[rr];
+    }
+    __syncthreads();
+  }
+  double* part = part_all + c * b.part_w;
+  if (t == 0) part[blockIdx.x] = loss;
+  else if (t == 64) reinterpret_cast<long long*>(part)[gridDim.x + blockIdx.x] = hits;
+}
+
+__global__ __launch_bounds__(64) void lr_batch_score_final_kernel(Batch b, int n_part, const double* __restrict__ part_all,
+                                                                  double* __restrict__ loss_out, long long* __restrict__ hits_out) {
+  const int c = blockIdx.x, t = threadIdx.x;
+  const double* part = part_all + c * b.part_w;
+  if (t == 0) {
+    double s = 0.0;
+    for (int k = 0; k < n_part; ++k) s += part[k];
+    loss_out[c] = s;
+  } else if (t == 1) {
+    long long s = 0;
+    for (int k = 0; k < n_part; ++k) s += reinterpret_cast<const long long*>(part)[n_part + k];
+    hits_out[c] = s;
+  }
+}
+
+// The integers of pinn_lr_roc for n_batch rows of sorted scores, one workgroup per row walking its tiles in order.  Carried
+// from tile to tile: the positives so far and the last boundary (index and positives through it).  A boundary adds
+// dfps (tps_prev + tps), which needs the boundary before it: the one compacted just before it in this tile, or the carried one.
+__global__ __launch_bounds__(kTile) void roc_batch_kernel(const double* __restrict__ score_all, const long long* __restrict__ pos_all, long long n,
+                                                          long long* __restrict__ counts_all) {
+  __shared__ long long sa[kTile], sb[kTile];
+  __shared__ int s_bidx[kTile];
+  const int t = threadIdx.x;
+  const double* score = score_all + (size_t)blockIdx.x * n;
+  const long long* pos = pos_all + (size_t)blockIdx.x * n;
+  long long carry_tp = 0, last_idx = -1, last_tp = 0, area = 0, m = 0;
+  for (long long base = 0; base < n; base += kTile) {
+    const long long i = base + t;
+    const bool bd = i < n && roc_boundary(score, i, n);
+    sa[t] = i < n ? (pos[i] != 0) : 0;
+    sb[t] = bd;
+    __syncthreads();
+    block_scan2(sa, sb, t);
+    if (bd) s_bidx[sb[t] - 1] = t;
+    __syncthreads();
+    if (bd) {
+      const long long k = sb[t] - 1, tp = carry_tp + sa[t], fp = 1 + i - tp;
+      long long tp0 = last_tp, fp0 = last_idx + 1 - last_tp;
+      if (k > 0) {
+        const int q = s_bidx[k - 1];
+        tp0 = carry_tp + sa[q];
+        fp0 = 1 + base + q - tp0;
+      }
+      area += (fp - fp0) * (tp0 + tp);
+      m += 1;
+    }
+    const long long nb = sb[kTile - 1];
+    if (nb > 0) {
+      const int q = s_bidx[nb - 1];
+      last_idx = base + q;
+      last_tp = carry_tp + sa[q];
+    }
+    carry_tp += sa[kTile - 1];
+    __syncthreads();
+  }
+  sa[t] = area; sb[t] = m;
+  __syncthreads();
+  block_scan2(sa, sb, t);
+  if (t == kTile - 1) {
+    long long* cnt = counts_all + (size_t)blockIdx.x * PINN_LR_ROC_COUNTS;
+    cnt[PINN_LR_ROC_POS] = carry_tp;
+    cnt[PINN_LR_ROC_N] = n - carry_tp;
+    cnt[PINN_LR_ROC_M] = sb[t];
+    cnt[PINN_LR_ROC_KEPT] = 0;
+    cnt[PINN_LR_ROC_U2] = sa[t];
+    for (int k = PINN_LR_ROC_U2 + 1; k < PINN_LR_ROC_COUNTS; ++k) cnt[k] = 0;
   }
 }
 
@@ -720,5 +944,132 @@ extern "C" int pinn_lr_roc(const double* d_score_sorted, const long long* d_pos_
   hipLaunchKernelGGL(roc_tiles2_kernel, grid, block, 0, st, fps, tps, d_counts + PINN_LR_ROC_M, drop_intermediate, keep, tile_c, tile_d);
   hipLaunchKernelGGL(roc_scan_tiles_kernel, dim3(1), block, 0, st, tile_c, tile_d, nt, d_counts + PINN_LR_ROC_KEPT, d_counts + PINN_LR_ROC_U2);
   hipLaunchKernelGGL(roc_emit2_kernel, grid, block, 0, st, fps, tps, thr, keep, tile_c, n, d_counts, d_fps, d_tps, d_thresholds, d_fpr, d_tpr);
+  return launch_status();
+}
+
+// ---- batches of models over column subsets
+namespace pinn {
+namespace {
+
+inline size_t batch_sums(int C, int max_feat) { return 1 + (size_t)n_par(C, max_feat) + n_hess(C, max_feat); }
+inline size_t words256(size_t words) { return align256(words * 8) / 8; }
+
+struct BatchWs {
+  double *tot, *part;
+  long long* cnt;
+};
+
+// Everything the batch entry points check before a launch; fills the rows head (without columns), the batch and the workspace.
+inline int make_batch(const double* d_arr, long long ld, long long n_arr_rows, const long long* d_row_index, long long n, int n_classes,
+                      int n_batch, const int* n_feat, const int* cols, int max_feat, const int* d_n_feat, const int* d_cols,
+                      const void* d_state, void* d_ws, size_t ws_bytes, Rows* a, Batch* b, BatchWs* w, int* nb_out) {
+  if (n_batch < 1 || n_batch > PINN_LR_MAX_BATCH || !in_limits(n_classes, max_feat)) return PINN_E_ARG;
+  if (!n_feat || !cols || !d_n_feat || !d_cols || !d_state || !d_ws || misaligned8(d_state) || misaligned8(d_ws)) return PINN_E_ARG;
+  if (((unsigned long long)d_n_feat & 3) || ((unsigned long long)d_cols & 3)) return PINN_E_ARG;
+  const int col0 = 0;
+  const int rc = make_rows(d_arr, ld, n_arr_rows, &col0, 1, n_classes, d_row_index, n, a);
+  if (rc != PINN_OK) return rc;
+  if (n < 1) return PINN_E_ARG;
+  for (int c = 0; c < n_batch; ++c) {
+    if (n_feat[c] < 1 || n_feat[c] > max_feat) return PINN_E_ARG;
+    for (int i = 0; i < n_feat[c]; ++i) {
+      const int col = cols[(size_t)c * max_feat + i];
+      if (col < 0 || col >= ld) return PINN_E_ARG;
+    }
+  }
+  if (ws_bytes < pinn_lr_batch_workspace_bytes(n, n_batch, n_classes, max_feat)) return PINN_E_WORKSPACE;
+  const int nb = row_blocks(n, kRows, kMaxBlocks);
+  const size_t ns = batch_sums(n_classes, max_feat);
+  b->n_feat = d_n_feat; b->cols = d_cols; b->max_feat = max_feat;
+  b->stride = pinn_lr_batch_state_stride(n_classes, max_feat) / 8;
+  b->tot_w = words256(ns); b->part_w = words256((size_t)nb * ns); b->cnt_w = words256((size_t)nb * kMaxC);
+  w->tot = static_cast<double*>(d_ws);
+  w->part = w->tot + (size_t)n_batch * b->tot_w;
+  w->cnt = reinterpret_cast<long long*>(w->part + (size_t)n_batch * b->part_w);
+  *nb_out = nb;
+  return PINN_OK;
+}
+
+}  // namespace
+}  // namespace pinn
+
+extern "C" size_t pinn_lr_batch_state_stride(int n_classes, int max_feat) {
+  if (!pinn::in_limits(n_classes, max_feat)) return 0;
+  return pinn::align256(pinn::st_words(n_classes, max_feat) * sizeof(double));
+}
+
+extern "C" size_t pinn_lr_batch_workspace_bytes(long long n_rows, int n_batch, int n_classes, int max_feat) {
+  using namespace pinn;
+  if (n_rows < 0 || n_batch < 1 || n_batch > PINN_LR_MAX_BATCH || !in_limits(n_classes, max_feat)) return 0;
+  const size_t nb = (size_t)row_blocks(n_rows, kRows, kMaxBlocks), ns = batch_sums(n_classes, max_feat);
+  return (size_t)n_batch * 8 * (words256(ns) + words256(nb * ns) + words256(nb * kMaxC));
+}
+
+#define LR_BATCH_CHECKS(state_ptr)                                                                                        \
+  Rows a;                                                                                                                 \
+  Batch b;                                                                                                                \
+  BatchWs w;                                                                                                              \
+  int nb = 0;                                                                                                             \
+  {                                                                                                                       \
+    const int rc_ = make_batch(d_arr, ld, n_arr_rows, d_row_index, n, n_classes, n_batch, n_feat, cols, max_feat, d_n_feat, d_cols, \
+                               state_ptr, d_ws, ws_bytes, &a, &b, &w, &nb);                                               \
+    if (rc_ != PINN_OK) return rc_;                                                                                       \
+  }                                                                                                                       \
+  if (!d_y || misaligned8(d_y)) return PINN_E_ARG;                                                                        \
+  hipStream_t st = (hipStream_t)stream;                                                                                   \
+  clear_error()
+
+extern "C" int pinn_lr_batch_scaler(const double* d_arr, long long ld, long long n_arr_rows, const long long* d_row_index, long long n,
+                                    const long long* d_y, int n_classes, int n_batch, const int* n_feat, const int* cols, int max_feat,
+                                    const int* d_n_feat, const int* d_cols, int balanced, double* d_state, void* d_ws, size_t ws_bytes,
+                                    void* stream) {
+  using namespace pinn;
+  LR_BATCH_CHECKS(d_state);
+  const dim3 grid((unsigned)nb, (unsigned)n_batch);
+  for (int pass = 0; pass < 2; ++pass) {
+    hipLaunchKernelGGL(lr_batch_stats_kernel, grid, dim3(kRows), 0, st, a, b, d_state, d_y, pass, w.part, w.cnt);
+    hipLaunchKernelGGL(lr_batch_stats_final_kernel, dim3((unsigned)n_batch), dim3(64), 0, st, b, d_state, n_classes, pass, balanced, nb, w.part,
+                       w.cnt);
+  }
+  return launch_status();
+}
+
+extern "C" int pinn_lr_batch_newton(const double* d_arr, long long ld, long long n_arr_rows, const long long* d_row_index, long long n,
+                                    const long long* d_y, int n_classes, int n_batch, const int* n_feat, const int* cols, int max_feat,
+                                    const int* d_n_feat, const int* d_cols, int n_passes, double tol, double l2, int fit_intercept,
+                                    double* d_state, void* d_ws, size_t ws_bytes, void* stream) {
+  using namespace pinn;
+  LR_BATCH_CHECKS(d_state);
+  if (n_passes < 0 || n_passes > 100000 || !(tol >= 0.0) || !(l2 > 0.0) || !(l2 < INFINITY)) return PINN_E_ARG;
+  const dim3 grid((unsigned)nb, (unsigned)n_batch);
+  for (int it = 0; it < n_passes; ++it) {
+    hipLaunchKernelGGL(lr_batch_rows_kernel, grid, dim3(kRows), 0, st, a, b, d_state, d_y, w.part);
+    hipLaunchKernelGGL(lr_batch_final_kernel, dim3((unsigned)n_batch), dim3(kFinThreads), 0, st, b, d_state, n_classes, nb, n, tol, l2,
+                       fit_intercept, w.part, w.tot);
+  }
+  return launch_status();
+}
+
+extern "C" int pinn_lr_batch_score(const double* d_arr, long long ld, long long n_arr_rows, const long long* d_row_index, long long n,
+                                   const long long* d_y, int n_classes, int n_batch, const int* n_feat, const int* cols, int max_feat,
+                                   const int* d_n_feat, const int* d_cols, const double* d_state, int normal_class, double* d_loss_sum,
+                                   long long* d_hits, double* d_p_fault, void* d_ws, size_t ws_bytes, void* stream) {
+  using namespace pinn;
+  LR_BATCH_CHECKS(d_state);
+  if (!d_loss_sum || !d_hits || misaligned8(d_loss_sum) || misaligned8(d_hits) || misaligned8(d_p_fault)) return PINN_E_ARG;
+  if (normal_class < 0 || normal_class >= n_classes) return PINN_E_ARG;
+  hipLaunchKernelGGL(lr_batch_score_kernel, dim3((unsigned)nb, (unsigned)n_batch), dim3(kRows), 0, st, a, b, d_state, d_y, normal_class,
+                     d_p_fault, w.part);
+  hipLaunchKernelGGL(lr_batch_score_final_kernel, dim3((unsigned)n_batch), dim3(64), 0, st, b, nb, w.part, d_loss_sum, d_hits);
+  return launch_status();
+}
+
+extern "C" int pinn_lr_batch_auc(const double* d_score_sorted, const long long* d_pos_sorted, long long n, int n_batch, long long* d_counts,
+                                 void* stream) {
+  using namespace pinn;
+  if (n < 1 || n_batch < 1 || n_batch > PINN_LR_MAX_BATCH || !d_score_sorted || !d_pos_sorted || !d_counts) return PINN_E_ARG;
+  if (misaligned8(d_score_sorted) || misaligned8(d_pos_sorted) || misaligned8(d_counts)) return PINN_E_ARG;
+  clear_error();
+  hipLaunchKernelGGL(roc_batch_kernel, dim3((unsigned)n_batch), dim3(kTile), 0, (hipStream_t)stream, d_score_sorted, d_pos_sorted, n, d_counts);
   return launch_status();
 }
