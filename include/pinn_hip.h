@@ -1595,6 +1595,105 @@ int pinn_unc_update(const double* d_arr, long long ld, long long n_arr_rows, con
                     double alpha_min, double alpha_max, int window, int learn, void* d_state, double* d_lo, double* d_hi,
                     double* d_z, int* d_flag, void* stream);
 
+/* ---- conformal fault sets and unknown-fault rejection (csrc/pinn_faultsets.hip; faultsets.py states the statistics) ----
+ * Scores.  float64, every operation rounded on its own, sums in ascending class or component order, p = a row of y_prob:
+ *   PINN_FS_LAC     s_c = 1 - p_c
+ *   PINN_FS_MARGIN  s_c = max_{k != c} p_k - p_c (n_classes = 1: -p_c)
+ *   PINN_FS_APS     s_c = sum_{k : p_k > p_c or (p_k == p_c and k < c)} p_k + u p_c, u = 1 unless randomized; then u =
+ *                   ((w0 << 21) | (w1 >> 11)) 2^-53 from the Philox4x32-10 block of the counter (row_lo, row_hi, draw_kind, 0)
+ *                   under the key seed, row = first + position (draw_kind: PINN_FS_DRAW_CAL or PINN_FS_DRAW_TEST)
+ *   PINN_FS_DENSITY (pinn_fs_gmm only) s_c = -(logsumexp_{k : logm_kc > -inf}(lp_k + logm_kc) - logpi_c), lp_k as the mixture's
+ *                   E-step forms it, the logsumexp as max, sum in ascending k, log; +inf when logpi_c = -inf.  d_logmap holds
+ *                   log m [n_comp][n_classes] then log pi [n_classes], computed by the caller.  s_any = -log_prob_norm.
+ * A row is missing when an entry of p is non-finite or negative, when all are zero, or when a score is NaN (density kind: when
+ * a feature is non-finite or the gather index lies outside the array): count -1, mask 0, size 0, novel 0, missing 1, no tally.
+ *
+ * Calibration state (d_state), 8-byte words: a header of PINN_FS_HEADER words, then the ascending tables as float64, class
+ * after class and the pooled table (class index n_classes) last, each starting on a multiple of PINN_FS_LINE entries.
+ * Header (int64): [0] magic, [1] n_classes, [2] kind, [3] seed, [4] randomized, [5] rows skipped, [6] status (1: a class holds
+ * more than PINN_FS_MAX_CAL rows; the tables are then not written), [16 + c] n_c, [40 + c] first entry of table c.
+ * pinn_fs_state_bytes(n_cal, n_classes): bytes for n_cal calibration rows in all (0 outside the limits: n_cal < 0 or
+ * > n_classes PINN_FS_MAX_CAL, n_classes outside 1 .. PINN_FS_MAX_CLASSES).
+ *
+ * pinn_fs_build: d_scores [n][n_classes] and d_class [n] in, the state out.  Row i contributes d_scores[i][d_class[i]] + 0 to
+ *   table d_class[i] (and d_any[i] + 0 to the pooled table when d_any is given); a row whose class lies outside the range or
+ *   whose score (or d_any[i]) is NaN is skipped and counted.  Counting, placing (an integer atomic hands out the places)
+ *   and a merge sort of every table by ranks (ceil(log2 n) passes between the state and the workspace, each element's place
+ *   is its own rank plus a binary search in the sibling run) all run inside the library; a sorted multiset of non-NaN doubles
+ *   with one zero has one byte image, so the order of placing does not matter.
+ *
+ * pinn_fs_rank: one thread per row of d_y_prob [n][n_classes], tiles of PINN_FS_TILE rows, at most PINN_FS_MAX_BLOCKS
+ *   workgroups striding over the tiles.  n_cal [n_classes + 1] (host) are the table sizes as the header has them, kmin
+ *   [n_classes][n_levels] (host) the integer thresholds: class c is in the set at level l iff count_c >= kmin[c][l], count_c =
+ *   n_c - #{t in T_c : t < s_c}.  Outputs, each skipped when NULL: d_count int32 [n][n_classes], d_mask uint16 [n][n_levels]
+ *   (bit c), d_size uint8 [n][n_levels], d_novel uint8 [n][n_levels] (size 0 and not missing), d_missing uint8 [n], d_scores
+ *   [n][n_classes] (NaN on a missing row).  With d_y [n] the tallies are added to d_tally (PINN_FS_TALLY_WORDS int64 words,
+ *   zeroed by the caller; integer atomics in LDS, then to global memory): n [16], covered [16][8], size_hist [8][17] and
+ *   singleton_correct [8] over rows with 0 <= y < n_classes, outside_n and outside_novel [8] over the others.  d_state = NULL
+ *   (with n_levels = 0 and no output but d_scores and d_missing) computes scores only.
+ *   Where the tables are searched (the integers do not depend on it): PINN_FS_REGIME_LDS all tables staged in LDS (their
+ *   padded entries <= PINN_FS_LDS_ENTRIES); PINN_FS_REGIME_SAMPLED every PINN_FS_LINE-th entry in LDS (<= PINN_FS_LDS_ENTRIES
+ *   of them), searched on-chip, then one 128-byte line read and counted; PINN_FS_REGIME_GLOBAL binary search in global
+ *   memory.  PINN_FS_REGIME_AUTO takes LDS from PINN_FS_STAGE_MIN_ROWS rows on when the padded entries are at most
+ *   PINN_FS_AUTO_LDS_ENTRIES, and GLOBAL otherwise: as measured on an MI355X, where SAMPLED lost at every shape
+ *   and stays a forced regime.  A forced regime that does not fit is PINN_E_ARG.
+ *
+ * pinn_fs_gmm: the same from rows read in place under a mixture (d_gmm_state, d_map [n_comp][n_classes] as
+ *   pinn_gmm_posterior takes them), tiles of PINN_FS_GMM_TILE rows; also d_y_prob, d_y_pred, d_log_prob_norm with
+ *   pinn_gmm_posterior's bytes, d_any_score [n] (s_any) and d_any_count int32 [n] (density kind), each skipped when NULL.
+ *
+ * Checks, on the host before any launch: PINN_E_ARG for NULL or misaligned pointers, n_classes, n_levels, kind, regime, a
+ * negative kmin or n_cal, n_cal beyond the cap; PINN_E_WORKSPACE for a workspace below pinn_fs_workspace_bytes(n, n_classes)
+ * (256-byte aligned; 0 outside the limits).  n = 0 returns PINN_OK without a launch. */
+#define PINN_FS_MAX_CLASSES 16
+#define PINN_FS_MAX_LEVELS 8
+#define PINN_FS_MAX_CAL (1 << 20)
+#define PINN_FS_TILE 256
+#define PINN_FS_GMM_TILE 64
+#define PINN_FS_MAX_BLOCKS 1024
+#define PINN_FS_LINE 16
+#define PINN_FS_HEADER 64
+#define PINN_FS_LDS_ENTRIES 7680       /* what a forced regime may stage (60 KiB); pinn_fs_gmm: PINN_FS_GMM_LDS_ENTRIES */
+#define PINN_FS_GMM_LDS_ENTRIES 3072
+#define PINN_FS_AUTO_LDS_ENTRIES 1536  /* what PINN_FS_REGIME_AUTO stages: measured faster at 1360 entries, slower at 7648 */
+#define PINN_FS_STAGE_MIN_ROWS (1 << 20) /* and from this many rows on: below it the regimes measure alike */
+#define PINN_FS_LAC 0
+#define PINN_FS_MARGIN 1
+#define PINN_FS_APS 2
+#define PINN_FS_DENSITY 3
+#define PINN_FS_DRAW_CAL 3             /* Philox draw kinds (0 and 1 are the isolation forest's, 2 the ROC bootstrap's) */
+#define PINN_FS_DRAW_TEST 4
+#define PINN_FS_REGIME_AUTO 0
+#define PINN_FS_REGIME_LDS 1
+#define PINN_FS_REGIME_SAMPLED 2
+#define PINN_FS_REGIME_GLOBAL 3
+#define PINN_FS_MAGIC 0x46534554
+#define PINN_FS_H_NCAL 16
+#define PINN_FS_H_OFFSET 40
+#define PINN_FS_T_N 0
+#define PINN_FS_T_COVERED 16
+#define PINN_FS_T_HIST 144
+#define PINN_FS_T_SINGLE 280
+#define PINN_FS_T_OUT_N 288
+#define PINN_FS_T_OUT_NOVEL 289
+#define PINN_FS_TALLY_WORDS 304
+
+size_t pinn_fs_state_bytes(long long n_cal, int n_classes);
+size_t pinn_fs_workspace_bytes(long long n, int n_classes);
+int pinn_fs_build(const double* d_scores, const double* d_any, const long long* d_class, long long n, int n_classes, int kind,
+                  unsigned long long seed, int randomized, void* d_state, void* d_ws, size_t ws_bytes, void* stream);
+int pinn_fs_rank(const double* d_y_prob, long long n, int n_classes, const void* d_state, const long long* n_cal,
+                 const long long* kmin, int n_levels, int kind, int randomized, unsigned long long seed, int draw_kind,
+                 long long first, int regime, const long long* d_y, int* d_count, unsigned short* d_mask, unsigned char* d_size,
+                 unsigned char* d_novel, unsigned char* d_missing, double* d_scores, long long* d_tally, void* stream);
+int pinn_fs_gmm(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                const long long* d_row_index, long long n, int n_comp, const double* d_gmm_state, const double* d_map,
+                int n_classes, const double* d_logmap, const void* d_state, const long long* n_cal, const long long* kmin,
+                int n_levels, int kind, int randomized, unsigned long long seed, int draw_kind, long long first, int regime,
+                const long long* d_y, int* d_count, unsigned short* d_mask, unsigned char* d_size, unsigned char* d_novel,
+                unsigned char* d_missing, double* d_scores, long long* d_tally, double* d_y_prob, long long* d_y_pred,
+                double* d_log_prob_norm, double* d_any_score, int* d_any_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

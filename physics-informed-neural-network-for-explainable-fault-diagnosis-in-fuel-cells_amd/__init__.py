@@ -39,7 +39,9 @@ starvation faults, the hydrogen and oxygen excess-ratio laws fitted per window w
 `flow_table`, `fit_breakpoints`, `fit_breakpoint_baseline`, `BreakpointFit`, `SupplyTracker`, `supply_law` (supply); and
 whether the voltage network's own standard deviations are honest, reliability scores, exact conformal quantiles and an online
 band: `score_uncertainty`, `conformal_quantiles`, `conformal_band`, `UncertaintyMonitor`, `UncertaintyReport`, `Quantiles`
-(uncertainty).
+(uncertainty); and how sure the diagnosis itself is and whether it is none of the trained faults, conformal fault sets with
+class-conditional coverage and unknown-fault rejection: `calibrate`, `calibrate_gmm`, `p_values`, `prediction_sets`,
+`evaluate_sets`, `GMMSetDiagnoser`, `SetCalibration`, `FaultSets`, `SetReport` (faultsets).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -91,6 +93,9 @@ _LAZY = {
     "SupplyTracker": "supply", "supply_law": "supply",
     "score_uncertainty": "uncertainty", "conformal_quantiles": "uncertainty", "conformal_band": "uncertainty",
     "UncertaintyMonitor": "uncertainty", "UncertaintyReport": "uncertainty", "Quantiles": "uncertainty",
+    "calibrate": "faultsets", "calibrate_gmm": "faultsets", "p_values": "faultsets", "prediction_sets": "faultsets",
+    "evaluate_sets": "faultsets", "GMMSetDiagnoser": "faultsets", "SetCalibration": "faultsets", "FaultSets": "faultsets",
+    "SetReport": "faultsets", "PValues": "faultsets",
 }
 
 

@@ -62,6 +62,8 @@ SOURCES = [
     # uncertainty calibration: float64, every operation rounded on its own; z and everything counted from it are the host
     # backend's to the bit
     ("pinn_uncertainty.hip", ["-ffp-contract=off"]),
+    # conformal fault sets: float64 scores, every operation rounded on its own, so that counts and masks are the host backend's to the bit
+    ("pinn_faultsets.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

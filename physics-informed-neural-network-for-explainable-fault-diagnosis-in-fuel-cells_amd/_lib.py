@@ -152,6 +152,15 @@ UNC_MAX_QUANTILES, UNC_MAX_TARGETS, UNC_MAX_WINDOW, UNC_MAX_CHUNK, UNC_STATE_HEA
 UNC_ABS_Z, UNC_Z, UNC_COLUMN = 0, 1, 2
 UNC_COLLECT = 256                       # the select gathers a target's keys once at most this many carry its prefix
 
+# pinn_faultsets.hip: limits, row tiles, the on-chip table budgets and the row count below which nothing is staged, score kinds,
+# Philox draw kinds, table regimes, and the 8-byte words of the state header and of the tallies
+FS_MAX_CLASSES, FS_MAX_LEVELS, FS_MAX_CAL, FS_TILE, FS_GMM_TILE, FS_MAX_BLOCKS, FS_LINE, FS_HEADER = 16, 8, 1 << 20, 256, 64, 1024, 16, 64
+FS_LDS_ENTRIES, FS_GMM_LDS_ENTRIES, FS_AUTO_LDS_ENTRIES, FS_STAGE_MIN_ROWS = 7680, 3072, 1536, 1 << 20
+FS_LAC, FS_MARGIN, FS_APS, FS_DENSITY, FS_DRAW_CAL, FS_DRAW_TEST = 0, 1, 2, 3, 3, 4
+FS_REGIME_AUTO, FS_REGIME_LDS, FS_REGIME_SAMPLED, FS_REGIME_GLOBAL = range(4)
+FS_MAGIC, FS_H_NCAL, FS_H_OFFSET = 0x46534554, 16, 40
+FS_T_N, FS_T_COVERED, FS_T_HIST, FS_T_SINGLE, FS_T_OUT_N, FS_T_OUT_NOVEL, FS_TALLY_WORDS = 0, 16, 144, 280, 288, 289, 304
+
 
 class PinnError(RuntimeError):
     pass
@@ -177,6 +186,11 @@ _LR_BATCH = [c_void_p, c_ll, c_ll, c_void_p, c_ll, c_void_p, c_int, c_int, ctype
 # what follows it in pinn_unc_score / pinn_unc_quantiles: label column, label table (host array), labels, groups
 _UNC_GROUPS = [c_int, ctypes.POINTER(c_int), c_int, c_int]
 _c_dp = ctypes.POINTER(ctypes.c_double)    # a host array of float64
+_c_llp = ctypes.POINTER(c_ll)              # a host array of int64
+# what pinn_fs_rank and pinn_fs_gmm share from the calibration state on: state, table sizes and thresholds (host arrays), levels,
+# kind, randomized, seed, draw kind, first row, regime; classes or NULL; count, mask, size, novel, missing, scores, tallies
+_FS_RANK = [c_void_p, _c_llp, _c_llp, c_int, c_int, c_int, ctypes.c_ulonglong, c_int, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+            c_void_p, c_void_p, c_void_p, c_void_p]
 
 _SIGS = {
     "pinn_abi_version": (c_int, []),
@@ -341,6 +355,11 @@ _SIGS = {
                                                          c_void_p, c_size_t, c_void_p]),
     "pinn_unc_update": (c_int, _ROWS + [_c_dp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_int, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_fs_state_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_fs_workspace_bytes": (c_size_t, [c_ll, c_int]),
+    "pinn_fs_build": (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, ctypes.c_ulonglong, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_fs_rank": (c_int, [c_void_p, c_ll, c_int] + _FS_RANK + [c_void_p]),
+    "pinn_fs_gmm": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_int, c_void_p] + _FS_RANK + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -43,35 +43,6 @@ __device__ __forceinline__ bool stopped(const double* st) {
   return h[PINN_GMM_ST_CONVERGED] != 0 || h[PINN_GMM_ST_STATUS] != 0;
 }
 
-// log(w_k N(x | mu_k, Sigma_k)) for every k into lp[k * stride]; returns log_prob_norm (scipy's logsumexp: max, sum, log)
-__device__ __forceinline__ double estep_row(const double x[kMaxD], int K, int D, const Staged& s, double* lp, int stride) {
-  const double c = (double)D * 1.8378770664093453;          // D log(2 pi)
-  double m = -INFINITY;
-  for (int k = 0; k < K; ++k) {
-    double d[kMaxD];
-#pragma unroll
-    for (int i = 0; i < kMaxD; ++i) d[i] = i < D ? x[i] - s.mu[k * D + i] : 0.0;
-    const double* U = s.U + k * (D * (D + 1) / 2);
-    double q = 0.0;
-#pragma unroll
-    for (int j = 0; j < kMaxD; ++j) {
-      if (j < D) {
-        double y = 0.0;
-#pragma unroll
-        for (int i = 0; i <= j; ++i) y += d[i] * U[tri(i, j)];
-        q += y * y;
-      }
-    }
-    const double v = (-0.5 * (c + q) + s.ld[k]) + s.lw[k];
-    lp[k * stride] = v;
-    m = v > m ? v : m;
-  }
-  if (m == -INFINITY) return m;                             // every density underflowed: nothing to normalise
-  double sum = 0.0;
-  for (int k = 0; k < K; ++k) sum += exp(lp[k * stride] - m);
-  return log(sum) + m;
-}
-
 // ---- the row pass: K x F sums per workgroup.  F = n_f columns; OUT_MOMENTS: (1, d_i, d_i d_j i <= j) cut to n_f, OUT_CLASS:
 // one column per class.  part: [gridDim.x][K * n_f]; part_l: [gridDim.x] sums of log_prob_norm (SRC_ESTEP) or of the
 // squared distance to the nearest centre (SRC_NEAREST).

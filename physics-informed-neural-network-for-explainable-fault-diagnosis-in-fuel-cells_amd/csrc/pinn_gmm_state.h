@@ -1,5 +1,6 @@
 // The mixture's device state block as the kernels that read it see it (pinn_gmm.hip fits and evaluates it, pinn_shap.hip
-// explains its posterior): the word offsets of include/pinn_hip.h's layout and the parameters staged in LDS.
+// explains its posterior, pinn_faultsets.hip ranks its rows): the word offsets of include/pinn_hip.h's layout, the parameters
+// staged in LDS, and the per-row E-step that pinn_gmm.hip and pinn_faultsets.hip share to the byte.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -43,6 +44,36 @@ __device__ __forceinline__ void stage_params(const double* __restrict__ st, int 
     }
   }
   __syncthreads();
+}
+
+// log(w_k N(x | mu_k, Sigma_k)) for every k into lp[k * stride]; returns log_prob_norm (scipy's logsumexp: max, sum, log)
+__device__ __forceinline__ double estep_row(const double x[kRowsMaxD], int K, int D, const Staged& s, double* lp, int stride) {
+#pragma clang fp contract(fast)                             // as pinn_gmm.hip is built, also where the including file is not
+  const double c = (double)D * 1.8378770664093453;          // D log(2 pi)
+  double m = -INFINITY;
+  for (int k = 0; k < K; ++k) {
+    double d[kRowsMaxD];
+#pragma unroll
+    for (int i = 0; i < kRowsMaxD; ++i) d[i] = i < D ? x[i] - s.mu[k * D + i] : 0.0;
+    const double* U = s.U + k * (D * (D + 1) / 2);
+    double q = 0.0;
+#pragma unroll
+    for (int j = 0; j < kRowsMaxD; ++j) {
+      if (j < D) {
+        double y = 0.0;
+#pragma unroll
+        for (int i = 0; i <= j; ++i) y += d[i] * U[tri(i, j)];
+        q += y * y;
+      }
+    }
+    const double v = (-0.5 * (c + q) + s.ld[k]) + s.lw[k];
+    lp[k * stride] = v;
+    m = v > m ? v : m;
+  }
+  if (m == -INFINITY) return m;                             // every density underflowed: nothing to normalise
+  double sum = 0.0;
+  for (int k = 0; k < K; ++k) sum += exp(lp[k * stride] - m);
+  return log(sum) + m;
 }
 
 }  // namespace
