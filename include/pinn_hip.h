@@ -382,6 +382,39 @@ int pinn_gnet_backward2(const pinn_gnet_t* net, const float* d_params, const flo
                         const pinn_dropout_t* drop, const float* d_gu, const float* d_glv, const float* d_vx,
                         float* d_grads, float* d_gx, float* d_ggu, float* d_gglv, void* d_work, size_t work_bytes, void* stream);
 
+/* ---- deep ensembles: n_members equal networks in the launches of one (pinn_general.hip) ---------------------------
+ * n_members copies of one pinn_gnet_t, 1 <= n_members <= 32 (PINN_E_ARG otherwise), on the same rows d_x (and targets d_y): every
+ * kernel of the pinn_gnet_* forward and training step takes the member from its launch grid, so a call is as many launches as
+ * one network's.  d_params, d_grads, d_m, d_v: [n_members, pinn_gnet_param_count(net)] contiguous (the count is a multiple of 4
+ * floats, so every member starts 16-byte aligned); d_u, d_logvar: [n_members, n_rows]; d_loss: double [n_members][4].
+ * Member m of a call is bit for bit the pinn_gnet_* call on member m's slices with drop->seed + m (64-bit wrap) for the seed and
+ * everything else of `drop` as given: a member's chunks, weight-gradient slices and fixed-order sums are those of the single
+ * network at this n_rows, whatever n_members is.  drop: NULL / PINN_DROP_NONE or PINN_DROP_PHILOX; PINN_DROP_BITS and a
+ * non-NULL d_step_counter are PINN_E_ARG.  No floating-point atomics.
+ * Checks as pinn_gnet_*: NULL or misaligned pointers PINN_E_ARG, a workspace (16-byte aligned) below
+ * pinn_gens_workspace_bytes(net, n_members, n_rows) PINN_E_WORKSPACE, a bad net PINN_E_ARCH, all before any launch;
+ * n_rows == 0 returns PINN_OK and does nothing. */
+size_t pinn_gens_workspace_bytes(const pinn_gnet_t* net, int n_members, long long n_rows);   /* 0: unsupported net, bad argument */
+/* what fixes the order of a member's training sums at n_rows rows: the rows of a chunk and the weight-gradient slices of a chunk */
+int pinn_gens_train_plan(const pinn_gnet_t* net, long long n_rows, long long* chunk_rows, int* slices);
+/* as pinn_gnet_forward, per member */
+int pinn_gens_forward(const pinn_gnet_t* net, int n_members, const float* d_params, const float* d_x, long long n_rows,
+                      const pinn_dropout_t* drop, float* d_u, float* d_logvar, void* d_work, size_t work_bytes, void* stream);
+/* as pinn_gnet_train_grads, per member: each member's gradient divided by n_global and its four raw loss sums */
+int pinn_gens_train_grads(const pinn_gnet_t* net, int n_members, const float* d_params, const float* d_x, const float* d_y,
+                          long long n_rows, long long n_global, const pinn_dropout_t* drop, float* d_grads, double* d_loss,
+                          void* d_work, size_t work_bytes, void* stream);
+/* pinn_gens_train_grads + one pinn_adam_step over all n_members * pinn_gnet_param_count elements (Adam is elementwise) */
+int pinn_gens_train_step(const pinn_gnet_t* net, int n_members, float* d_params, const float* d_x, const float* d_y,
+                         long long n_rows, long long n_global, const pinn_dropout_t* drop, float* d_grads, double* d_loss,
+                         void* d_work, size_t work_bytes, float* d_m, float* d_v, float lr, int step, void* stream);
+/* The ensemble as a mixture, per row, members in index order, sums in double, each output rounded once to float32:
+ *   pred_mean = mean_m u_m;  e_u = sqrt(max(mean_m u_m^2 - pred_mean^2, 0)) (population form; exactly 0 for equal members);
+ *   rule 0: a_u = sqrt(exp(mean_m logvar_m)) (get_MC_samples' form);  rule 1: a_u = sqrt(mean_m exp(logvar_m)) (mixture variance).
+ * d_u, d_logvar [n_members, n_rows]; outputs [n_rows].  Any other rule: PINN_E_ARG. */
+int pinn_gens_combine(const float* d_u, const float* d_logvar, int n_members, long long n_rows, int rule, float* d_pred_mean,
+                      float* d_a_u, float* d_e_u, void* stream);
+
 /* ---- results assembly: create_comprehensive_results_array_v2 (01:1877-2010) -----------------------------------
  * Fills d_out = float64 [n_rows, 22] row-major (the `comprehensive_results` layout scripts 02-05 read):
  *   0-7 inputs and 8 target, de-normalised like sklearn's inverse_transform on float32 (aff->x_*, aff->y_*; 01:1916-1917);

@@ -41,7 +41,8 @@ whether the voltage network's own standard deviations are honest, reliability sc
 band: `score_uncertainty`, `conformal_quantiles`, `conformal_band`, `UncertaintyMonitor`, `UncertaintyReport`, `Quantiles`
 (uncertainty); and how sure the diagnosis itself is and whether it is none of the trained faults, conformal fault sets with
 class-conditional coverage and unknown-fault rejection: `calibrate`, `calibrate_gmm`, `p_values`, `prediction_sets`,
-`evaluate_sets`, `GMMSetDiagnoser`, `SetCalibration`, `FaultSets`, `SetReport` (faultsets).
+`evaluate_sets`, `GMMSetDiagnoser`, `SetCalibration`, `FaultSets`, `SetReport` (faultsets); and a second source of the
+epistemic column beside MC-dropout, E networks trained and evaluated in the launches of one: `DeepEnsemble` (ensemble).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -96,6 +97,7 @@ _LAZY = {
     "calibrate": "faultsets", "calibrate_gmm": "faultsets", "p_values": "faultsets", "prediction_sets": "faultsets",
     "evaluate_sets": "faultsets", "GMMSetDiagnoser": "faultsets", "SetCalibration": "faultsets", "FaultSets": "faultsets",
     "SetReport": "faultsets", "PValues": "faultsets",
+    "DeepEnsemble": "ensemble",
 }
 
 

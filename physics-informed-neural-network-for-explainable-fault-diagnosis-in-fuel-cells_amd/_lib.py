@@ -244,6 +244,15 @@ _SIGS = {
     "pinn_gnet_backward2_workspace_bytes": (c_size_t, [ctypes.POINTER(GNet), c_ll]),
     "pinn_gnet_backward2": (c_int, [ctypes.POINTER(GNet), c_void_p, c_void_p, c_ll, ctypes.POINTER(Dropout), c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gens_workspace_bytes": (c_size_t, [ctypes.POINTER(GNet), c_int, c_ll]),
+    "pinn_gens_train_plan": (c_int, [ctypes.POINTER(GNet), c_ll, ctypes.POINTER(c_ll), ctypes.POINTER(c_int)]),
+    "pinn_gens_forward": (c_int, [ctypes.POINTER(GNet), c_int, c_void_p, c_void_p, c_ll, ctypes.POINTER(Dropout), c_void_p, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
+    "pinn_gens_train_grads": (c_int, [ctypes.POINTER(GNet), c_int, c_void_p, c_void_p, c_void_p, c_ll, c_ll, ctypes.POINTER(Dropout),
+                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pinn_gens_train_step": (c_int, [ctypes.POINTER(GNet), c_int, c_void_p, c_void_p, c_void_p, c_ll, c_ll, ctypes.POINTER(Dropout),
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_float, c_int, c_void_p]),
+    "pinn_gens_combine": (c_int, [c_void_p, c_void_p, c_int, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pinn_results_assemble": (c_int, [c_void_p, c_void_p, ctypes.POINTER(Affine), ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_void_p]),
     "pinn_rf_stats_workspace_bytes": (c_size_t, []),

@@ -15,6 +15,8 @@
 //   reduce / finalize      fixed-order slab sums -> the flat gradient (state_dict layout); loss sums in fp64
 //   gemm_kernel<., 2>, head2_kernel, vec_grad2_kernel   the double backward (pinn_gnet_backward2): see the section below
 //   mc_moments_kernel      MC-dropout: (pass, row) pairs are virtual rows; per row, in pass order, the Welford moments of pinn_mc_dropout
+//   pack, gemm<., 1>, heads, vec_grad, reduce, finalize take a member index from the launch grid (struct Members): E equal networks in
+//   the launches of one, member m bit for bit the single call (pinn_gens_*); combine_kernel reads the members as a mixture
 //
 // Widths are padded to 32 inside the workspace only (zero weights, zero activations); the flat parameter buffer holds exactly the
 // reference's tensors.  Determinism: no floating-point atomics; every output element's K order is fixed by the layer alone (the
@@ -218,17 +220,32 @@ static int convert(const Shape& s, const pinn_dropout_t* in, Drop* d) {
 // ---------------------------------------------------------------------------------------
 // weight packing: zero-padded forward [mp][kp] and transposed [kp][mp] copies of the GEMM matrices
 // ---------------------------------------------------------------------------------------
+// ---------------------------------------------------------------------------------------
+// the member dimension (pinn_gens_*): one launch of pack, gemm<., 1>, heads, vec_grad, reduce and finalize serves every member of an
+// ensemble of n equal networks.  The member index comes from the launch grid, and member m's buffers lie m strides behind member 0's:
+//   work  the workspace (4-byte words): n copies of the regions of one network's Layout -- packed weights, activations, keep words,
+//         d pre-activations, du / dz, slabs, acc, loss partials.  A member's Layout is the single network's, so its chunks, slices and
+//         fixed-order sums are too
+//   par   the flat parameters and the flat gradient [n][pinn_gnet_param_count]
+//   out   the per-row outputs u, logvar [n][n_rows]
+// The input rows and the targets are shared.  Member m draws the Philox stream of seed + m.  One member (every pinn_gnet_* call):
+// index 0, strides unused.  The double backward (NS = 2), dx_kernel and the MC-dropout kernels have no member dimension.
+// ---------------------------------------------------------------------------------------
+struct Members { int n; long long work, par, out; };
+
 struct PackJob { long long src, dst; int out, in, mp, kp, transposed; };
-struct PackArgs { const float* params; float* pack; PackJob job[2 * kMaxMat]; int n_jobs; };
+struct PackArgs { const float* params; float* pack; PackJob job[2 * kMaxMat]; int n_jobs; Members mem; };
 
 __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
   const PackJob j = a.job[blockIdx.y];
+  const float* __restrict__ params = a.params + (long long)blockIdx.z * a.mem.par;
+  float* __restrict__ pack = a.pack + (long long)blockIdx.z * a.mem.work;
   const long long n = (long long)j.mp * j.kp;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
     int o, i;
     if (j.transposed) { i = (int)(e / j.mp); o = (int)(e - (long long)i * j.mp); }
     else { o = (int)(e / j.kp); i = (int)(e - (long long)o * j.kp); }
-    a.pack[j.dst + e] = (o < j.out && i < j.in) ? a.params[j.src + (long long)o * j.in + i] : 0.0f;
+    pack[j.dst + e] = (o < j.out && i < j.in) ? params[j.src + (long long)o * j.in + i] : 0.0f;
   }
 }
 
@@ -262,6 +279,9 @@ struct GemmArgs {
   long long slice_rows; float* slab; long long slab_stride; long long reg; int out_real, in_real;
   // the second stream (NS = 2; same strides and extents as the first): WGRAD q; the tangent input / BWD q; their outputs; the kept tangent
   const float* A2; const float* B2; float* out2; const float* stash2;
+  // members (NS = 1): FWD / BWD take the member from the grid's z; WGRAD, whose z counts slices, from its x = member * tiles_x + tile.
+  // A, out, keep, stash, du, keep_in and slab are workspace, bias and wp parameters, B workspace unless it is the shared input rows
+  Members mem; int b_shared; unsigned tiles_x;
 };
 
 // one 64 x 32 operand tile: K-contiguous source (row m, 4 consecutive k per float4)
@@ -322,15 +342,17 @@ __device__ __forceinline__ void row_ctx(const GemmArgs& a, long long n, long lon
 // features): bit 16 i + 4 kq + r keeps feature 32 P + 16 i + 4 kq + r.  Every pass over a row -- forward, MC-dropout, the first- and
 // the second-order backward's recomputing forwards -- takes its masks from here, so they cannot disagree about them.
 // on = the module drops in this pass.  Philox: lane quarter kq draws its own 8 bits (counter = global row, key word = module, P, kq;
-// stream + pass) and the four quarters of a row are OR-ed by two shuffles, so all 64 lanes of the wave must call.
-__device__ __forceinline__ unsigned keep_word(const GemmArgs& a, bool on, long long lrow, int pass, bool valid, int P, int kq) {
+// stream + pass) and the four quarters of a row are OR-ed by two shuffles, so all 64 lanes of the wave must call.  Member mem of an
+// ensemble draws with seed + mem (64-bit wrap): the stream of the single call with that seed.
+__device__ __forceinline__ unsigned keep_word(const GemmArgs& a, int mem, bool on, long long lrow, int pass, bool valid, int P, int kq) {
   const unsigned thr = a.module >= 0 ? a.drop.thr[a.module] : 0u;
   unsigned mine = 0;
   if (on && a.drop.mode == PINN_DROP_PHILOX) {
     const unsigned long long g = (unsigned long long)(a.drop.row_offset + lrow);
+    const unsigned long long seed = (((unsigned long long)a.drop.seed_hi << 32) | a.drop.seed_lo) + (unsigned long long)mem;
     unsigned o[4];
     philox4x32_10((unsigned)g, (unsigned)(g >> 32), ((unsigned)a.module << 16) | ((unsigned)P << 2) | (unsigned)kq,
-                  a.drop.stream + (unsigned)pass, a.drop.seed_lo, a.drop.seed_hi, o);
+                  a.drop.stream + (unsigned)pass, (unsigned)seed, (unsigned)(seed >> 32), o);
 #pragma unroll
     for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -344,7 +366,9 @@ __device__ __forceinline__ unsigned keep_word(const GemmArgs& a, bool on, long l
   mine |= __shfl_xor(mine, 32, 64);
   unsigned word = 0xFFFFFFFFu;
   if (on && a.drop.mode == PINN_DROP_PHILOX) word = mine;
-  if (on && a.drop.mode == PINN_DROP_BITS && valid)
+  // (a wave whose 32 features lie past the layer's padded width stores nothing; its word would be the next module's or, for the last
+  // module of the last row, the word past the end of the masks)
+  if (on && a.drop.mode == PINN_DROP_BITS && valid && 32LL * P < a.M)
     word = a.drop.bits[((long long)pass * a.n_rows + lrow) * a.drop.words + a.keep_off + P];
   return word;
 }
@@ -376,7 +400,16 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
   __shared__ __attribute__((aligned(16))) float Bs[NB][64 * kLd];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, li = lane & 15;
   const int wm = wave & 1, wn = wave >> 1;
-  const long long m0 = (long long)blockIdx.y * 64, n0 = (long long)blockIdx.x * 64;
+  unsigned bx = blockIdx.x;
+  int mem = 0;
+  if (NS == 1) {
+    if (MODE == kWgrad) { mem = (int)(bx / a.tiles_x); bx -= (unsigned)mem * a.tiles_x; }
+    else mem = (int)blockIdx.z;
+  }
+  const long long wo = mem * a.mem.work, po = mem * a.mem.par;
+  const float* __restrict__ A = a.A + wo;
+  const float* __restrict__ B = a.B + (a.b_shared ? 0 : wo);
+  const long long m0 = (long long)blockIdx.y * 64, n0 = (long long)bx * 64;
   long long kbeg = 0, kend = a.K, span = 0;
   if (MODE == kWgrad) {
     kbeg = (long long)blockIdx.z * a.slice_rows;
@@ -401,16 +434,16 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const long long m = m0 + 32 * wm + 16 * i + 4 * kq + r;
-          acc[0][i][j][r] = m < a.bias_n ? a.bias[m] : 0.0f;
+          acc[0][i][j][r] = m < a.bias_n ? a.bias[po + m] : 0.0f;
         }
       }
       if (MODE == kBwd && a.wp) {       // the predict head joins the stream of the first-order chain
         const long long n = n0 + 32 * wn + 16 * j + li;
-        const float du = a.du[n];
+        const float du = a.du[wo + n];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const long long m = m0 + 32 * wm + 16 * i + 4 * kq + r;
-          acc[NB - 1][i][j][r] = (m < a.wp_n ? a.wp[m] : 0.0f) * du;
+          acc[NB - 1][i][j][r] = (m < a.wp_n ? a.wp[po + m] : 0.0f) * du;
         }
       }
     }
@@ -421,7 +454,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
   auto load_b = [&](f32x4 (&r)[2], const float* __restrict__ p, long long k0) {
     if (MODE == kWgrad) {
       const bool s2 = second(k0);
-      load_mc(r, s2 ? a.B2 : a.B, a.ldb, n0, s2 ? k0 - span : k0, a.b_mv, a.b_kv, tid, a.in_real, s2 ? 0.0f : 1.0f);
+      load_mc(r, s2 ? a.B2 : B, a.ldb, n0, s2 ? k0 - span : k0, a.b_mv, a.b_kv, tid, a.in_real, s2 ? 0.0f : 1.0f);
     } else if (MODE == kFwd && a.map_rows) {
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
@@ -437,14 +470,14 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
   };
   auto load_a = [&](f32x4 (&r)[2], long long k0) {
     const bool s2 = second(k0);
-    if (MODE == kWgrad) load_mc(r, s2 ? a.A2 : a.A, a.lda, m0, s2 ? k0 - span : k0, a.a_mv, a.a_kv, tid, -1);
-    else load_kc(r, a.A, a.lda, m0, k0, a.a_mv, a.a_kv, tid);
+    if (MODE == kWgrad) load_mc(r, s2 ? a.A2 : A, a.lda, m0, s2 ? k0 - span : k0, a.a_mv, a.a_kv, tid, -1);
+    else load_kc(r, A, a.lda, m0, k0, a.a_mv, a.a_kv, tid);
   };
   f32x4 ra[2], rb[NB][2];
   if (kbeg < kend) {
     load_a(ra, kbeg);
 #pragma unroll
-    for (int s = 0; s < NB; ++s) load_b(rb[s], s ? a.B2 : a.B, kbeg);
+    for (int s = 0; s < NB; ++s) load_b(rb[s], s ? a.B2 : B, kbeg);
   }
   for (long long k = kbeg; k < kend; k += kBK) {
     __syncthreads();
@@ -457,7 +490,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
     if (k + kBK < kend) {      // spelled out twice: one lambda around the pair costs the single-stream forward 8 VGPRs and 2 % at thin layers
       load_a(ra, k + kBK);
 #pragma unroll
-      for (int s = 0; s < NB; ++s) load_b(rb[s], s ? a.B2 : a.B, k + kBK);
+      for (int s = 0; s < NB; ++s) load_b(rb[s], s ? a.B2 : B, k + kBK);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -483,7 +516,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
   // acc[s][i][j][r] = C_s[m = m0 + 32 wm + 16 i + 4 kq + r][n = n0 + 32 wn + 16 j + li]
   const long long mw = m0 + 32 * wm;          // first feature of this wave's 32-feature group
   if (MODE == kWgrad) {
-    float* dst = a.slab + (long long)blockIdx.z * a.slab_stride + a.reg;
+    float* dst = a.slab + wo + (long long)blockIdx.z * a.slab_stride + a.reg;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -505,7 +538,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
       row_ctx<NS>(a, n, lrow, pass);
       const bool on = a.module >= 0 && a.drop.mode != PINN_DROP_NONE && pass >= 0;
       const float scale = on ? a.drop.scale[a.module] : 1.0f;
-      const unsigned word = keep_word(a, on, lrow, pass, valid, P, kq);
+      const unsigned word = keep_word(a, mem, on, lrow, pass, valid, P, kq);
       if (mw < a.M) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -517,19 +550,19 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
             v[r] = kept ? t * scale : 0.0f;
             if (NS == 2) vd[r] = (kept && valid) ? acc[NB - 1][i][j][r] * (scale * (1.0f - t * t)) : 0.0f;
           }
-          *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = v;
+          *reinterpret_cast<f32x4*>(a.out + wo + n * a.ldo + mw + 16 * i + 4 * kq) = v;
           if (NS == 2) *reinterpret_cast<f32x4*>(a.out2 + n * a.ldo + mw + 16 * i + 4 * kq) = vd;
         }
-        if (a.keep && a.module >= 0 && kq == 0) a.keep[n * a.drop.words + a.keep_off + P] = word;
+        if (a.keep && a.module >= 0 && kq == 0) a.keep[wo + n * a.drop.words + a.keep_off + P] = word;
       }
     } else {      // kBwd
       if (mw < a.M) {
         const bool on = a.drop.mode != PINN_DROP_NONE && a.stash_module >= 0;
         const float scale = on ? a.drop.scale[a.stash_module] : 1.0f, inv_scale = 1.0f / scale;
-        const unsigned word = a.stash_module >= 0 ? a.keep_in[n * a.drop.words + a.keep_off + P] : 0xFFFFFFFFu;
+        const unsigned word = a.stash_module >= 0 ? a.keep_in[wo + n * a.drop.words + a.keep_off + P] : 0xFFFFFFFFu;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-          const f32x4 h = *reinterpret_cast<const f32x4*>(a.stash + n * a.ld_stash + mw + 16 * i + 4 * kq);
+          const f32x4 h = *reinterpret_cast<const f32x4*>(a.stash + wo + n * a.ld_stash + mw + 16 * i + 4 * kq);
           f32x4 hd, vp, vq;
           if (NS == 2) hd = *reinterpret_cast<const f32x4*>(a.stash2 + n * a.ld_stash + mw + 16 * i + 4 * kq);
 #pragma unroll
@@ -543,7 +576,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
             if (NS == 2) vp[r] = kept ? gp : 0.0f;
           }
           if (NS == 2) *reinterpret_cast<f32x4*>(a.out + n * a.ldo + mw + 16 * i + 4 * kq) = vp;
-          *reinterpret_cast<f32x4*>((NS == 2 ? a.out2 : a.out) + n * a.ldo + mw + 16 * i + 4 * kq) = vq;
+          *reinterpret_cast<f32x4*>((NS == 2 ? a.out2 : a.out + wo) + n * a.ldo + mw + 16 * i + 4 * kq) = vq;
         }
       }
     }
@@ -563,6 +596,8 @@ struct HeadArgs {
   const float* y; long long n_global;             // TRAIN
   const float* gu; const float* glv;              // GRAD: dL/du, dL/dlogvar at row0 + r (glv NULL: zero)
   float* du; float* dz; float* dpre_v2; long long ld_dpre; int wd; double* loss_part;
+  Members mem;                                    // member = the grid's y: h, v2, du, dz, dpre_v2, loss_part are workspace, the four
+                                                  // head tensors parameters, u and lv outputs; y is shared (kHeadGrad: one member)
 };
 
 __device__ __forceinline__ float sum16(float s) {
@@ -578,17 +613,20 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
   __shared__ double red[16][kLossSums];
   const int tid = threadIdx.x, g = tid & 15, rr = tid >> 4;
   const long long r = (long long)blockIdx.x * 16 + rr;      // chunk row (every one is allocated)
-  const float* hrow = a.h + r * a.ldh;
-  const float* vrow = a.v2 + r * a.ldv;
+  const long long wo = (long long)blockIdx.y * a.mem.work, po = (long long)blockIdx.y * a.mem.par;
+  const float* hrow = a.h + wo + r * a.ldh;
+  const float* vrow = a.v2 + wo + r * a.ldv;
+  const float* wp = a.wp + po;
+  const float* wv2 = a.wv2 + po;
   float su = 0.f, sz = 0.f;
-  for (int f = g; f < a.hk; f += 16) su = fmaf(a.wp[f], hrow[f], su);
-  for (int f = g; f < a.hv2; f += 16) sz = fmaf(a.wv2[f], vrow[f], sz);
-  const float u = sum16(su) + a.bp[0];
-  const float z = sum16(sz) + a.bv2[0];
+  for (int f = g; f < a.hk; f += 16) su = fmaf(wp[f], hrow[f], su);
+  for (int f = g; f < a.hv2; f += 16) sz = fmaf(wv2[f], vrow[f], sz);
+  const float u = sum16(su) + a.bp[po];
+  const float z = sum16(sz) + a.bv2[po];
   const bool valid = r < a.n_valid;
   if (HM == kHeadFwd || HM == kHeadMC) {
     if (valid && g == 0) {
-      const long long o = HM == kHeadFwd ? a.row0 + r : r;
+      const long long o = (HM == kHeadFwd ? a.row0 + r : r) + (long long)blockIdx.y * a.mem.out;
       a.u[o] = u;
       a.lv[o] = logvar_of(z);
     }
@@ -607,7 +645,7 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
     float* drow = a.dpre_v2 + r * a.ld_dpre;
     for (int f = g; f < a.wd; f += 16) {
       const float v = vrow[f];
-      drow[f] = f < a.hv2 ? a.wv2[f] * dz * (1.0f - v * v) : 0.0f;
+      drow[f] = f < a.hv2 ? wv2[f] * dz * (1.0f - v * v) : 0.0f;
     }
     return;
   }
@@ -617,8 +655,8 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
   LossSums row;          // this row's terms alone
   loss_row(u, z, a.y[valid ? a.row0 + r : a.row0], inv_n, valid, true, du, dz, row);
   if (g == 0) {
-    a.du[r] = du;
-    a.dz[r] = dz;
+    a.du[wo + r] = du;
+    a.dz[wo + r] = dz;
     red[rr][kLossNll] = (double)row.nll;
     red[rr][kLossAbs] = (double)row.abs;
     red[rr][kLossMse] = (double)row.mse;
@@ -626,16 +664,16 @@ __global__ __launch_bounds__(256) void heads_kernel(HeadArgs a) {
     red[rr][kLossDz] = (double)dz;
   }
   // d pre_v2 = w_v2[f] * dz * (1 - v2^2) (zero in the padding and on invalid rows)
-  float* drow = a.dpre_v2 + r * a.ld_dpre;
+  float* drow = a.dpre_v2 + wo + r * a.ld_dpre;
   for (int f = g; f < a.wd; f += 16) {
     const float v = vrow[f];
-    drow[f] = f < a.hv2 ? a.wv2[f] * dz * (1.0f - v * v) : 0.0f;
+    drow[f] = f < a.hv2 ? wv2[f] * dz * (1.0f - v * v) : 0.0f;
   }
   __syncthreads();
   if (tid < kLossSums) {
     double s = 0.0;
     for (int q = 0; q < 16; ++q) s += red[q][tid];
-    a.loss_part[((a.row0 / 16) + blockIdx.x) * kLossTerms + tid] = s;
+    (a.loss_part + wo / 2)[((a.row0 / 16) + blockIdx.x) * kLossTerms + tid] = s;      // the stride is whole 256-byte blocks
   }
 }
 
@@ -648,21 +686,27 @@ struct VecArgs {
   const float* du; const float* dz;
   long long K, slice_rows;
   float* slab; long long slab_stride, reg_p, reg_v2;
+  Members mem;          // member = the grid's z; every pointer is workspace
 };
 __global__ __launch_bounds__(256) void vec_grad_kernel(VecArgs a) {
   const int c = blockIdx.y * 256 + threadIdx.x;
   const long long r0 = (long long)blockIdx.x * a.slice_rows;
   long long r1 = r0 + a.slice_rows;
   if (r1 > a.K) r1 = a.K;
-  float* dst = a.slab + (long long)blockIdx.x * a.slab_stride;
+  const long long wo = (long long)blockIdx.z * a.mem.work;
+  const float* __restrict__ h = a.h + wo;
+  const float* __restrict__ v2 = a.v2 + wo;
+  const float* __restrict__ du = a.du + wo;
+  const float* __restrict__ dz = a.dz + wo;
+  float* dst = a.slab + wo + (long long)blockIdx.x * a.slab_stride;
   if (c <= a.hk) {
     float s = 0.f;
-    for (long long r = r0; r < r1; ++r) s = fmaf(a.du[r], c < a.hk ? a.h[r * a.ldh + c] : 1.0f, s);
+    for (long long r = r0; r < r1; ++r) s = fmaf(du[r], c < a.hk ? h[r * a.ldh + c] : 1.0f, s);
     dst[a.reg_p + c] = s;
   } else if (c - (a.hk + 1) <= a.hv2) {
     const int j = c - (a.hk + 1);
     float s = 0.f;
-    for (long long r = r0; r < r1; ++r) s = fmaf(a.dz[r], j < a.hv2 ? a.v2[r * a.ldv + j] : 1.0f, s);
+    for (long long r = r0; r < r1; ++r) s = fmaf(dz[r], j < a.hv2 ? v2[r * a.ldv + j] : 1.0f, s);
     dst[a.reg_v2 + j] = s;
   }
 }
@@ -690,9 +734,11 @@ __global__ __launch_bounds__(256) void dx_kernel(const float* __restrict__ w0, i
   }
 }
 
-// acc (+)= sum_s slab[s], slices in order, fp64 within the chunk
+// acc (+)= sum_s slab[s], slices in order, fp64 within the chunk.  Member = the grid's y (slabs and acc are workspace)
 __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ slabs, int slices, long long total, float* __restrict__ acc,
-                                                     int first) {
+                                                     int first, long long mem_work) {
+  slabs += (long long)blockIdx.y * mem_work;
+  acc += (long long)blockIdx.y * mem_work;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
     double s = 0.0;
     for (int q = 0; q < slices; ++q) s += (double)slabs[(long long)q * total + e];
@@ -705,34 +751,38 @@ struct FinArgs {
   const float* acc; float* grads; long long total;
   int n_mat; long long woff[kMaxMat], boff[kMaxMat], reg[kMaxMat]; int out[kMaxMat], in[kMaxMat];
   const double* loss_part; long long n_parts; double* loss;
+  Members mem;          // member = the grid's y: acc and loss_part are workspace, grads a parameter-shaped buffer, loss [n][kLossOut]
 };
 __global__ __launch_bounds__(256) void finalize_kernel(FinArgs a) {
+  const long long wo = (long long)blockIdx.y * a.mem.work;
+  const float* __restrict__ acc = a.acc + wo;
+  float* __restrict__ grads = a.grads + (long long)blockIdx.y * a.mem.par;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < a.total; e += (long long)gridDim.x * 256) {
     float v = 0.0f;
     for (int t = 0; t < a.n_mat; ++t) {
       const long long nw = (long long)a.out[t] * a.in[t];
       if (e >= a.woff[t] && e < a.woff[t] + nw) {
         const long long q = e - a.woff[t], o = q / a.in[t], i = q - o * a.in[t];
-        v = a.acc[a.reg[t] + o * (a.in[t] + 1) + i];
+        v = acc[a.reg[t] + o * (a.in[t] + 1) + i];
       } else if (e >= a.boff[t] && e < a.boff[t] + a.out[t]) {
         const long long o = e - a.boff[t];
-        v = a.acc[a.reg[t] + o * (a.in[t] + 1) + a.in[t]];
+        v = acc[a.reg[t] + o * (a.in[t] + 1) + a.in[t]];
       }
     }
-    a.grads[e] = v;
+    grads[e] = v;
   }
   if (blockIdx.x == 0 && a.loss_part) {
     __shared__ double red[256];
     for (int q = 0; q < kLossOut; ++q) {
       double s = 0.0;
-      for (long long b = threadIdx.x; b < a.n_parts; b += 256) s += a.loss_part[b * kLossTerms + q];
+      for (long long b = threadIdx.x; b < a.n_parts; b += 256) s += (a.loss_part + wo / 2)[b * kLossTerms + q];
       red[threadIdx.x] = s;
       __syncthreads();
       for (int w = 128; w > 0; w >>= 1) {
         if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
       }
-      if (threadIdx.x == 0) a.loss[q] = red[0];
+      if (threadIdx.x == 0) a.loss[(long long)blockIdx.y * kLossOut + q] = red[0];
       __syncthreads();
     }
   }
@@ -763,15 +813,39 @@ __global__ __launch_bounds__(256) void mc_final_kernel(const float* __restrict__
   mc_finish(st[2 * n_rows + r], st[3 * n_rows + r], n_passes, o1[r], o2[r]);
 }
 
+// deep-ensemble combine (pinn_gens_combine): one thread per row, members in index order, sums in double, each result rounded once.
+// Every double operation is rounded on its own: with a fused multiply-add the variance of one member, or of equal members, would be
+// the rounding error of u^2 instead of exactly 0
+__global__ __launch_bounds__(256) void combine_kernel(const float* __restrict__ u, const float* __restrict__ lv, int n_members,
+                                                      long long n_rows, int rule, float* __restrict__ pred_mean, float* __restrict__ a_u,
+                                                      float* __restrict__ e_u) {
+#pragma clang fp contract(off)
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n_rows) return;
+  double su = 0.0, suu = 0.0, sl = 0.0;
+  for (int m = 0; m < n_members; ++m) {
+    const double um = (double)u[(long long)m * n_rows + r], lm = (double)lv[(long long)m * n_rows + r];
+    su += um;
+    suu += um * um;
+    sl += rule ? exp(lm) : lm;
+  }
+  const double mean = su / n_members;
+  double var = suu / n_members - mean * mean;
+  if (!(var > 0.0)) var = 0.0;
+  pred_mean[r] = (float)mean;
+  e_u[r] = (float)sqrt(var);
+  a_u[r] = (float)sqrt(rule ? sl / n_members : exp(sl / n_members));
+}
+
 // ---------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 static int last_error() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? PINN_OK : (int)e; }
 
-static int launch_pack(const Shape& s, const float* params, float* pack, hipStream_t st) {
+static int launch_pack(const Shape& s, const Members& mb, const float* params, float* pack, hipStream_t st) {
   PackArgs pa{};
-  pa.params = params; pa.pack = pack;
+  pa.params = params; pa.pack = pack; pa.mem = mb;
   int nj = 0;
   long long mx = 0;
   for (int t = 0; t < s.n_mat; ++t) {
@@ -784,7 +858,7 @@ static int launch_pack(const Shape& s, const float* params, float* pack, hipStre
   pa.n_jobs = nj;
   long long gx = (mx + 255) / 256;
   if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(pack_kernel, dim3((unsigned)gx, nj), dim3(256), 0, st, pa);
+  hipLaunchKernelGGL(pack_kernel, dim3((unsigned)gx, nj, mb.n), dim3(256), 0, st, pa);
   return last_error();
 }
 
@@ -817,8 +891,8 @@ static ChunkIO train_io(const Shape& s, float* const* act, float* const* tan, un
   return io;
 }
 
-static void forward_layers(const Shape& s, const float* params, const float* pack, const Drop& d, const ChunkIO& io, long long row0,
-                           long long nv, long long rows, long long n_rows, bool mc, hipStream_t st) {
+static void forward_layers(const Shape& s, const Members& mb, const float* params, const float* pack, const Drop& d, const ChunkIO& io,
+                           long long row0, long long nv, long long rows, long long n_rows, bool mc, hipStream_t st) {
   for (int step = 0; step < s.k + 2; ++step) {
     const int t = step < s.k ? step : (step == s.k ? s.mat_v0() : s.mat_v1());
     GemmArgs g{};
@@ -836,13 +910,15 @@ static void forward_layers(const Shape& s, const float* params, const float* pac
     g.keep = io.keep;
     g.keep_off = g.module >= 0 ? s.word_off[g.module] : 0;
     g.stash_module = -1;
-    launch_gemm<kFwd>(g, io.out2[t] != nullptr, dim3((unsigned)(rows / 64), (unsigned)((s.mp[t] + 63) / 64)), st);
+    g.mem = mb; g.b_shared = t == 0;        // matrix 0 reads the input rows
+    launch_gemm<kFwd>(g, io.out2[t] != nullptr, dim3((unsigned)(rows / 64), (unsigned)((s.mp[t] + 63) / 64), mb.n), st);
   }
 }
 
-static HeadArgs head_args(const Shape& s, const float* params, const float* h, long long ldh, const float* v2, long long ldv,
-                          long long nv, long long row0) {
+static HeadArgs head_args(const Shape& s, const Members& mb, const float* params, const float* h, long long ldh, const float* v2,
+                          long long ldv, long long nv, long long row0) {
   HeadArgs h2{};
+  h2.mem = mb;
   h2.h = h; h2.ldh = ldh; h2.hk = s.hk;
   h2.v2 = v2; h2.ldv = ldv; h2.hv2 = s.hv2;
   h2.wp = params + s.woff[s.mat_pred()]; h2.bp = params + s.boff[s.mat_pred()];
@@ -852,15 +928,17 @@ static HeadArgs head_args(const Shape& s, const float* params, const float* h, l
 }
 
 // forward (n_passes == 0) or MC-dropout (1 eval pass + n_passes stochastic passes as virtual rows)
-static int run_infer(const Shape& s, const float* d_params, const float* d_x, long long n_rows, const Drop& d, int n_passes,
+// n_members > 1 (forward only): o0, o1 [n_members][n_rows] from parameters [n_members][total], the workspace n_members Layouts
+static int run_infer(const Shape& s, int n_members, const float* d_params, const float* d_x, long long n_rows, const Drop& d, int n_passes,
                      float* o0, float* o1, float* o2, void* d_work, size_t work_bytes, hipStream_t st) {
   const bool mc = n_passes > 0;
   const Layout L = infer_layout(s, n_rows, n_passes);
   if (!d_work || !al16(d_work)) return PINN_E_ARG;
-  if (work_bytes < L.end) return PINN_E_WORKSPACE;
+  if (work_bytes < L.end * (size_t)n_members) return PINN_E_WORKSPACE;
+  const Members mb = {n_members, (long long)(L.end / 4), s.total, n_rows};
   char* base = (char*)d_work;
   const float* pack = (const float*)(base + L.pack);
-  int rc = launch_pack(s, d_params, (float*)(base + L.pack), st);
+  int rc = launch_pack(s, mb, d_params, (float*)(base + L.pack), st);
   if (rc) return rc;
   float* buf[3] = {(float*)(base + L.act[0][0]), (float*)(base + L.act[0][1]), (float*)(base + L.act[0][2])};
   ChunkIO io{};
@@ -879,15 +957,15 @@ static int run_infer(const Shape& s, const float* d_params, const float* d_x, lo
   const long long total = mc ? n_rows * ((long long)n_passes + 1) : n_rows;
   for (long long v0 = 0; v0 < total; v0 += L.rows) {
     const long long nv = total - v0 < L.rows ? total - v0 : L.rows;
-    forward_layers(s, d_params, pack, d, io, v0, nv, L.rows, n_rows, mc, st);
-    HeadArgs h = head_args(s, d_params, buf[c], s.max_wp, buf[2], s.max_wp, nv, v0);
+    forward_layers(s, mb, d_params, pack, d, io, v0, nv, L.rows, n_rows, mc, st);
+    HeadArgs h = head_args(s, mb, d_params, buf[c], s.max_wp, buf[2], s.max_wp, nv, v0);
     if (mc) {
       h.u = ub; h.lv = lvb;
       hipLaunchKernelGGL(heads_kernel<kHeadMC>, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, h);
       hipLaunchKernelGGL(mc_moments_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, ub, lvb, v0, nv, n_rows, state);
     } else {
       h.u = o0; h.lv = o1;
-      hipLaunchKernelGGL(heads_kernel<kHeadFwd>, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, h);
+      hipLaunchKernelGGL(heads_kernel<kHeadFwd>, dim3((unsigned)(L.rows / 16), mb.n), dim3(256), 0, st, h);
     }
     rc = last_error();
     if (rc) return rc;
@@ -897,7 +975,7 @@ static int run_infer(const Shape& s, const float* d_params, const float* d_x, lo
 }
 
 // weight gradient of matrix t, per slice.  Double backward: dpre = p with x_in = a, dpre2 = q with x_in2 = ad (same strides)
-static void wgrad(const Shape& s, int t, const Layout& L, const float* dpre, long long ld_dpre, const float* x_in, long long ld_in,
+static void wgrad(const Shape& s, const Members& mb, int t, const Layout& L, const float* dpre, long long ld_dpre, const float* x_in, long long ld_in,
                   long long nv, float* slabs, hipStream_t st, const float* dpre2 = nullptr, const float* x_in2 = nullptr) {
   GemmArgs g{};
   g.A = dpre; g.A2 = dpre2; g.lda = ld_dpre; g.a_mv = s.mp[t]; g.a_kv = nv;
@@ -907,13 +985,15 @@ static void wgrad(const Shape& s, int t, const Layout& L, const float* dpre, lon
   g.slice_rows = L.slice_rows; g.slab = slabs; g.slab_stride = s.gtotal; g.reg = s.reg[t];
   g.out_real = s.out[t]; g.in_real = s.in[t];
   g.module = -1; g.stash_module = -1;
-  const dim3 grid((unsigned)((s.in[t] + 1 + 63) / 64), (unsigned)((s.out[t] + 63) / 64), (unsigned)L.slices);
+  g.mem = mb; g.b_shared = t == 0;          // matrix 0's input is the input rows
+  g.tiles_x = (unsigned)((s.in[t] + 1 + 63) / 64);
+  const dim3 grid(g.tiles_x * (unsigned)mb.n, (unsigned)((s.out[t] + 63) / 64), (unsigned)L.slices);
   launch_gemm<kWgrad>(g, dpre2 != nullptr, grid, st);
 }
 
 // d pre-activation of the layer feeding matrix t: (W_t^T dpre_t (+ w_p du)) * tanh' * mask.  Double backward: (dpre, dpre2) = (p, q) of
 // matrix t, (dpre_in, dpre_in2) = (p, q) of that layer, from its kept activation and tangent (stash, stash2); w_p du joins the q stream
-static void bwd(const Shape& s, int t, const Layout& L, const float* pack, const Drop& d, const float* dpre, float* dpre_in,
+static void bwd(const Shape& s, const Members& mb, int t, const Layout& L, const float* pack, const Drop& d, const float* dpre, float* dpre_in,
                 const float* stash, long long ld_stash, int module, const unsigned* keep, const float* wp, const float* du, long long nv,
                 hipStream_t st, const float* dpre2 = nullptr, float* dpre_in2 = nullptr, const float* stash2 = nullptr) {
   GemmArgs g{};
@@ -927,26 +1007,27 @@ static void bwd(const Shape& s, int t, const Layout& L, const float* pack, const
   g.stash = stash; g.stash2 = stash2; g.ld_stash = ld_stash; g.stash_module = module;
   g.keep_in = keep; g.keep_off = s.word_off[module];
   g.wp = wp; g.du = du; g.wp_n = wp ? s.hk : 0;
-  launch_gemm<kBwd>(g, dpre2 != nullptr, dim3((unsigned)(L.rows / 64), (unsigned)((s.kp[t] + 63) / 64)), st);
+  g.mem = mb;
+  launch_gemm<kBwd>(g, dpre2 != nullptr, dim3((unsigned)(L.rows / 64), (unsigned)((s.kp[t] + 63) / 64), mb.n), st);
 }
 
 // acc (+)= the chunk's slab sums
-static void launch_reduce(const Shape& s, const Layout& L, const float* slabs, float* acc, bool first, hipStream_t st) {
+static void launch_reduce(const Shape& s, const Members& mb, const Layout& L, const float* slabs, float* acc, bool first, hipStream_t st) {
   long long gx = (s.gtotal + 255) / 256;
   if (gx > 4096) gx = 4096;
-  hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)gx), dim3(256), 0, st, slabs, L.slices, s.gtotal, acc, first ? 1 : 0);
+  hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)gx, mb.n), dim3(256), 0, st, slabs, L.slices, s.gtotal, acc, first ? 1 : 0, mb.work);
 }
 
 // acc -> the flat gradient; loss_part != NULL: also the loss sums of its n_parts partials
-static void launch_finalize(const Shape& s, const float* acc, float* grads, const double* loss_part, long long n_parts, double* loss,
+static void launch_finalize(const Shape& s, const Members& mb, const float* acc, float* grads, const double* loss_part, long long n_parts, double* loss,
                             hipStream_t st) {
   FinArgs f{};
   f.acc = acc; f.grads = grads; f.total = s.total; f.n_mat = s.n_mat;
   for (int t = 0; t < s.n_mat; ++t) { f.woff[t] = s.woff[t]; f.boff[t] = s.boff[t]; f.reg[t] = s.reg[t]; f.out[t] = s.out[t]; f.in[t] = s.in[t]; }
-  f.loss_part = loss_part; f.n_parts = n_parts; f.loss = loss;
+  f.loss_part = loss_part; f.n_parts = n_parts; f.loss = loss; f.mem = mb;
   long long gx = (s.total + 255) / 256;
   if (gx > 4096) gx = 4096;
-  hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)gx), dim3(256), 0, st, f);
+  hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)gx, mb.n), dim3(256), 0, st, f);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1065,7 +1146,7 @@ struct ChunkBufs {
 };
 
 // heads of a chunk: du, dz (, pz) per row and the d pre-activation(s) below the variance head's second tanh, in dp[0] (, dq[0])
-static void launch_heads(const Shape& s, const Layout& L, const float* params, const GradCall& c, const ChunkBufs& w, long long nv,
+static void launch_heads(const Shape& s, const Members& mb, const Layout& L, const float* params, const GradCall& c, const ChunkBufs& w, long long nv,
                          long long row0, hipStream_t st) {
   const int v1m = s.mat_v1();
   const dim3 grid((unsigned)(L.rows / 16)), blk(256);
@@ -1080,16 +1161,16 @@ static void launch_heads(const Shape& s, const Layout& L, const float* params, c
     hipLaunchKernelGGL(head2_kernel, grid, blk, 0, st, h);
     return;
   }
-  HeadArgs h = head_args(s, params, w.act[s.k - 1], s.mp[s.k - 1], w.act[v1m], s.mp[v1m], nv, row0);
+  HeadArgs h = head_args(s, mb, params, w.act[s.k - 1], s.mp[s.k - 1], w.act[v1m], s.mp[v1m], nv, row0);
   h.y = c.y; h.n_global = c.n_global; h.gu = c.gu; h.glv = c.glv;
   h.du = w.du; h.dz = w.dz; h.dpre_v2 = w.dp[0]; h.ld_dpre = s.max_wp; h.wd = s.mp[v1m];
   h.loss_part = w.loss_part;
   if (c.gu) hipLaunchKernelGGL(heads_kernel<kHeadGrad>, grid, blk, 0, st, h);
-  else hipLaunchKernelGGL(heads_kernel<kHeadTrain>, grid, blk, 0, st, h);
+  else hipLaunchKernelGGL(heads_kernel<kHeadTrain>, dim3(grid.x, mb.n), blk, 0, st, h);
 }
 
 // the two one-row tensors (predict, last variance layer) of a chunk, per slice
-static void launch_vec_grad(const Shape& s, const Layout& L, const ChunkBufs& w, bool paired, hipStream_t st) {
+static void launch_vec_grad(const Shape& s, const Members& mb, const Layout& L, const ChunkBufs& w, bool paired, hipStream_t st) {
   const int v1m = s.mat_v1(), cols = s.hk + 1 + s.hv2 + 1;
   const dim3 grid((unsigned)L.slices, (unsigned)((cols + 255) / 256)), blk(256);
   if (paired) {
@@ -1105,13 +1186,15 @@ static void launch_vec_grad(const Shape& s, const Layout& L, const ChunkBufs& w,
     va.v2 = w.act[v1m]; va.ldv = s.mp[v1m]; va.hv2 = s.hv2;
     va.du = w.du; va.dz = w.dz; va.K = L.rows; va.slice_rows = L.slice_rows;
     va.slab = w.slabs; va.slab_stride = s.gtotal; va.reg_p = s.reg[s.mat_pred()]; va.reg_v2 = s.reg[s.mat_v2()];
-    hipLaunchKernelGGL(vec_grad_kernel, grid, blk, 0, st, va);
+    va.mem = mb;
+    hipLaunchKernelGGL(vec_grad_kernel, dim3(grid.x, grid.y, mb.n), blk, 0, st, va);
   }
 }
 
 // recomputing forward + backward of every chunk, fixed-order slab sums -> c.grads.  With one stream tan[..], dq[..] and vx are NULL, and
 // the optional arguments of train_io / wgrad / bwd select the single-stream kernels
-static int run_grads(const Shape& s, const float* d_params, const float* d_x, long long n_rows, const pinn_dropout_t* drop,
+// n_members > 1 (one stream, the loss upstream): parameters, c.grads [n_members][total], c.loss [n_members][4], the workspace n_members Layouts
+static int run_grads(const Shape& s, int n_members, const float* d_params, const float* d_x, long long n_rows, const pinn_dropout_t* drop,
                      const GradCall& c, void* d_work, size_t work_bytes, hipStream_t st) {
   Drop d;
   int rc = convert(s, drop, &d);
@@ -1120,10 +1203,11 @@ static int run_grads(const Shape& s, const float* d_params, const float* d_x, lo
   const bool two = c.vx != nullptr;
   const Layout L = train_layout(s, n_rows, two ? 2 : 1);
   if (!d_work || !al16(d_work)) return PINN_E_ARG;
-  if (work_bytes < L.end) return PINN_E_WORKSPACE;
+  if (work_bytes < L.end * (size_t)n_members) return PINN_E_WORKSPACE;
+  const Members mb = {n_members, (long long)(L.end / 4), s.total, n_rows};
   char* base = (char*)d_work;
   const float* pack = (const float*)(base + L.pack);
-  rc = launch_pack(s, d_params, (float*)(base + L.pack), st);
+  rc = launch_pack(s, mb, d_params, (float*)(base + L.pack), st);
   if (rc) return rc;
   auto f32 = [&](size_t off, bool have = true) { return have ? (float*)(base + off) : nullptr; };
   ChunkBufs w{};
@@ -1145,26 +1229,26 @@ static int run_grads(const Shape& s, const float* d_params, const float* d_x, lo
     const long long nv = n_rows - row0 < L.rows ? n_rows - row0 : L.rows;
     const float* x = d_x + row0 * 8;
     const float* vx = c.vx ? c.vx + row0 * 8 : nullptr;
-    forward_layers(s, d_params, pack, d, io, row0, nv, L.rows, n_rows, false, st);      // primal (and tangent)
-    launch_heads(s, L, d_params, c, w, nv, row0, st);
+    forward_layers(s, mb, d_params, pack, d, io, row0, nv, L.rows, n_rows, false, st);      // primal (and tangent)
+    launch_heads(s, mb, L, d_params, c, w, nv, row0, st);
     if (want_back) {
       // variance head layer 1, then layer 0 (+ the predict head; on the q stream of two), then the hidden layers top-down
-      if (want_w) wgrad(s, v1m, L, dp[0], s.max_wp, act[v0m], s.mp[v0m], nv, w.slabs, st, dq[0], tan[v0m]);
-      bwd(s, v1m, L, pack, d, dp[0], dp[1], act[v0m], s.mp[v0m], s.k, w.keep, nullptr, nullptr, nv, st, dq[0], dq[1], tan[v0m]);
+      if (want_w) wgrad(s, mb, v1m, L, dp[0], s.max_wp, act[v0m], s.mp[v0m], nv, w.slabs, st, dq[0], tan[v0m]);
+      bwd(s, mb, v1m, L, pack, d, dp[0], dp[1], act[v0m], s.mp[v0m], s.k, w.keep, nullptr, nullptr, nv, st, dq[0], dq[1], tan[v0m]);
       if (want_w) {
-        wgrad(s, v0m, L, dp[1], s.max_wp, act[s.k - 1], s.mp[s.k - 1], nv, w.slabs, st, dq[1], tan[s.k - 1]);
-        launch_vec_grad(s, L, w, two, st);
+        wgrad(s, mb, v0m, L, dp[1], s.max_wp, act[s.k - 1], s.mp[s.k - 1], nv, w.slabs, st, dq[1], tan[s.k - 1]);
+        launch_vec_grad(s, mb, L, w, two, st);
       }
-      bwd(s, v0m, L, pack, d, dp[1], dp[0], act[s.k - 1], s.mp[s.k - 1], s.k - 1, w.keep, d_params + s.woff[s.mat_pred()], w.du, nv, st,
+      bwd(s, mb, v0m, L, pack, d, dp[1], dp[0], act[s.k - 1], s.mp[s.k - 1], s.k - 1, w.keep, d_params + s.woff[s.mat_pred()], w.du, nv, st,
           dq[1], dq[0], tan[s.k - 1]);
       int cur = 0;
       for (int l = s.k - 1; l >= 0; --l) {
         if (want_w) {
-          if (l == 0) wgrad(s, 0, L, dp[cur], s.max_wp, x, 8, nv, w.slabs, st, dq[cur], vx);
-          else wgrad(s, l, L, dp[cur], s.max_wp, act[l - 1], s.mp[l - 1], nv, w.slabs, st, dq[cur], tan[l - 1]);
+          if (l == 0) wgrad(s, mb, 0, L, dp[cur], s.max_wp, x, 8, nv, w.slabs, st, dq[cur], vx);
+          else wgrad(s, mb, l, L, dp[cur], s.max_wp, act[l - 1], s.mp[l - 1], nv, w.slabs, st, dq[cur], tan[l - 1]);
         }
         if (l > 0) {
-          bwd(s, l, L, pack, d, dp[cur], dp[cur ^ 1], act[l - 1], s.mp[l - 1], l - 1, w.keep, nullptr, nullptr, nv, st, dq[cur], dq[cur ^ 1],
+          bwd(s, mb, l, L, pack, d, dp[cur], dp[cur ^ 1], act[l - 1], s.mp[l - 1], l - 1, w.keep, nullptr, nullptr, nv, st, dq[cur], dq[cur ^ 1],
               tan[l - 1]);
           cur ^= 1;
         }
@@ -1172,12 +1256,12 @@ static int run_grads(const Shape& s, const float* d_params, const float* d_x, lo
       if (c.gx)        // dp[cur] is now d pre-activation of hidden layer 0 (two streams: p_0, dS/dx = W_0^T p_0)
         hipLaunchKernelGGL(dx_kernel, dim3((unsigned)(L.rows / 16)), dim3(256), 0, st, d_params + s.woff[0], s.w[0], (const float*)dp[cur],
                            (long long)s.max_wp, nv, row0, c.gx);
-      if (want_w) launch_reduce(s, L, w.slabs, w.acc, ch == 0, st);
+      if (want_w) launch_reduce(s, mb, L, w.slabs, w.acc, ch == 0, st);
     }
     rc = last_error();
     if (rc) return rc;
   }
-  if (want_w) launch_finalize(s, w.acc, c.grads, c.gu ? nullptr : w.loss_part, w.loss_part ? nch * (L.rows / 16) : 0, c.loss, st);
+  if (want_w) launch_finalize(s, mb, w.acc, c.grads, c.gu ? nullptr : w.loss_part, w.loss_part ? nch * (L.rows / 16) : 0, c.loss, st);
   return last_error();
 }
 
@@ -1211,7 +1295,7 @@ extern "C" int pinn_gnet_forward(const pinn_gnet_t* net, const float* d_params, 
   rc = convert(s, drop, &d);
   if (rc) return rc;
   (void)hipGetLastError();
-  return run_infer(s, d_params, d_x, n_rows, d, 0, d_u, d_logvar, nullptr, d_work, work_bytes, (hipStream_t)stream);
+  return run_infer(s, 1, d_params, d_x, n_rows, d, 0, d_u, d_logvar, nullptr, d_work, work_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pinn_gnet_mc_dropout(const pinn_gnet_t* net, const float* d_params, const float* d_x, long long n_rows, const pinn_dropout_t* drop,
@@ -1228,7 +1312,7 @@ extern "C" int pinn_gnet_mc_dropout(const pinn_gnet_t* net, const float* d_param
   rc = convert(s, drop, &d);
   if (rc) return rc;
   (void)hipGetLastError();
-  return run_infer(s, d_params, d_x, n_rows, d, n_passes, d_pred_mean, d_a_u, d_e_u, d_work, work_bytes, (hipStream_t)stream);
+  return run_infer(s, 1, d_params, d_x, n_rows, d, n_passes, d_pred_mean, d_a_u, d_e_u, d_work, work_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pinn_gnet_train_grads(const pinn_gnet_t* net, const float* d_params, const float* d_x, const float* d_y, long long n_rows,
@@ -1243,7 +1327,7 @@ extern "C" int pinn_gnet_train_grads(const pinn_gnet_t* net, const float* d_para
   if (!d_x || !al16(d_x) || !d_y) return PINN_E_ARG;
   GradCall c{};
   c.y = d_y; c.n_global = n_global; c.grads = d_grads; c.loss = d_loss;
-  return run_grads(s, d_params, d_x, n_rows, drop, c, d_work, work_bytes, (hipStream_t)stream);
+  return run_grads(s, 1, d_params, d_x, n_rows, drop, c, d_work, work_bytes, (hipStream_t)stream);
 }
 
 extern "C" int pinn_gnet_train_step(const pinn_gnet_t* net, float* d_params, const float* d_x, const float* d_y, long long n_rows,
@@ -1267,7 +1351,7 @@ extern "C" int pinn_gnet_backward(const pinn_gnet_t* net, const float* d_params,
   if (!d_x || !al16(d_x) || !d_gu || (d_gx && !al16(d_gx))) return PINN_E_ARG;
   GradCall c{};
   c.n_global = n_rows; c.gu = d_gu; c.glv = d_glv; c.grads = d_grads; c.gx = d_gx;
-  return run_grads(s, d_params, d_x, n_rows, drop, c, d_work, work_bytes, (hipStream_t)stream);
+  return run_grads(s, 1, d_params, d_x, n_rows, drop, c, d_work, work_bytes, (hipStream_t)stream);
 }
 
 extern "C" size_t pinn_gnet_backward2_workspace_bytes(const pinn_gnet_t* net, long long n_rows) {
@@ -1292,5 +1376,83 @@ extern "C" int pinn_gnet_backward2(const pinn_gnet_t* net, const float* d_params
   if (!d_x || !al16(d_x) || !d_gu || !d_vx || !al16(d_vx) || (d_gx && !al16(d_gx))) return PINN_E_ARG;
   GradCall c{};
   c.gu = d_gu; c.glv = d_glv; c.vx = d_vx; c.ggu = d_ggu; c.gglv = d_gglv; c.grads = d_grads; c.gx = d_gx;
-  return run_grads(s, d_params, d_x, n_rows, drop, c, d_work, work_bytes, (hipStream_t)stream);
+  return run_grads(s, 1, d_params, d_x, n_rows, drop, c, d_work, work_bytes, (hipStream_t)stream);
+}
+
+// ---- deep ensembles: n_members equal networks in the launches of one (the member dimension above) ------------------------------
+constexpr int kMaxMembers = 32;
+
+// the dropout modes a batched call takes: eval (NULL or PINN_DROP_NONE) and Philox; convert() rejects the rest of a bad struct
+static bool gens_drop_ok(const pinn_dropout_t* drop) { return !drop || drop->mode != PINN_DROP_BITS; }
+
+extern "C" size_t pinn_gens_workspace_bytes(const pinn_gnet_t* net, int n_members, long long n_rows) {
+  Shape s;
+  if (make_shape(net, &s) || n_members < 1 || n_members > kMaxMembers || n_rows < 0) return 0;
+  const size_t a = train_layout(s, n_rows, 1).end, b = infer_layout(s, n_rows, 0).end;
+  return (a > b ? a : b) * (size_t)n_members;
+}
+
+extern "C" int pinn_gens_train_plan(const pinn_gnet_t* net, long long n_rows, long long* chunk_rows, int* slices) {
+  Shape s;
+  const int rc = make_shape(net, &s);
+  if (rc) return rc;
+  if (n_rows < 0 || !chunk_rows || !slices) return PINN_E_ARG;
+  const Layout L = train_layout(s, n_rows, 1);
+  *chunk_rows = L.rows;
+  *slices = L.slices;
+  return PINN_OK;
+}
+
+extern "C" int pinn_gens_forward(const pinn_gnet_t* net, int n_members, const float* d_params, const float* d_x, long long n_rows,
+                                 const pinn_dropout_t* drop, float* d_u, float* d_logvar, void* d_work, size_t work_bytes, void* stream) {
+  Shape s;
+  int rc = make_shape(net, &s);
+  if (rc) return rc;
+  if (n_members < 1 || n_members > kMaxMembers || n_rows < 0 || !d_params || !al16(d_params) || !gens_drop_ok(drop)) return PINN_E_ARG;
+  Drop d;
+  rc = convert(s, drop, &d);
+  if (rc) return rc;
+  if (n_rows == 0) return PINN_OK;
+  if (!d_x || !al16(d_x) || !d_u || !d_logvar) return PINN_E_ARG;
+  (void)hipGetLastError();
+  return run_infer(s, n_members, d_params, d_x, n_rows, d, 0, d_u, d_logvar, nullptr, d_work, work_bytes, (hipStream_t)stream);
+}
+
+extern "C" int pinn_gens_train_grads(const pinn_gnet_t* net, int n_members, const float* d_params, const float* d_x, const float* d_y,
+                                     long long n_rows, long long n_global, const pinn_dropout_t* drop, float* d_grads, double* d_loss,
+                                     void* d_work, size_t work_bytes, void* stream) {
+  Shape s;
+  int rc = make_shape(net, &s);
+  if (rc) return rc;
+  if (n_members < 1 || n_members > kMaxMembers || n_rows < 0 || n_global < 1 || n_global < n_rows || !d_params || !al16(d_params) ||
+      !d_grads || !al16(d_grads) || !d_loss || !gens_drop_ok(drop))
+    return PINN_E_ARG;
+  Drop d;
+  rc = convert(s, drop, &d);          // (run_grads converts again: a bad struct is refused before the n_rows == 0 return as well)
+  if (rc) return rc;
+  if (n_rows == 0) return PINN_OK;
+  if (!d_x || !al16(d_x) || !d_y) return PINN_E_ARG;
+  GradCall c{};
+  c.y = d_y; c.n_global = n_global; c.grads = d_grads; c.loss = d_loss;
+  return run_grads(s, n_members, d_params, d_x, n_rows, drop, c, d_work, work_bytes, (hipStream_t)stream);
+}
+
+extern "C" int pinn_gens_train_step(const pinn_gnet_t* net, int n_members, float* d_params, const float* d_x, const float* d_y,
+                                    long long n_rows, long long n_global, const pinn_dropout_t* drop, float* d_grads, double* d_loss,
+                                    void* d_work, size_t work_bytes, float* d_m, float* d_v, float lr, int step, void* stream) {
+  if (!d_m || !d_v || step < 1) return PINN_E_ARG;
+  int rc = pinn_gens_train_grads(net, n_members, d_params, d_x, d_y, n_rows, n_global, drop, d_grads, d_loss, d_work, work_bytes, stream);
+  if (rc || n_rows == 0) return rc;          // no rows: no gradient was written, so there is no step to take
+  return pinn_adam_step(d_params, d_grads, d_m, d_v, (long long)n_members * pinn_gnet_param_count(net), lr, step, stream);
+}
+
+extern "C" int pinn_gens_combine(const float* d_u, const float* d_logvar, int n_members, long long n_rows, int rule, float* d_pred_mean,
+                                 float* d_a_u, float* d_e_u, void* stream) {
+  if (n_members < 1 || n_members > kMaxMembers || n_rows < 0 || rule < 0 || rule > 1) return PINN_E_ARG;
+  if (n_rows == 0) return PINN_OK;
+  if (!d_u || !d_logvar || !d_pred_mean || !d_a_u || !d_e_u) return PINN_E_ARG;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_u, d_logvar, n_members,
+                     n_rows, rule, d_pred_mean, d_a_u, d_e_u);
+  return last_error();
 }

@@ -69,11 +69,13 @@ def create_fault_labels(n_samples, data_info, verbose=False):
     return fault_labels
 
 
-def create_comprehensive_results_array_v2(model, dataset, mc_times=2000, dropout=0.2, device_output=False):
+def create_comprehensive_results_array_v2(model, dataset, mc_times=2000, dropout=0.2, device_output=False, ensemble=None):
     """01:1877-2010.  Accepts the 7- or 9-tuple dataset (01:1900-1903); returns float64 [N, 22]:
     0-7 inputs, 8 y_true, 9 y_pred, 10 ale (smoothed), 11 epi (smoothed), 12 y_true - y_pred,
     13 f_V, 14 f_T, 15 f_H2, 16 f_O2, 17 label, 18 V_phys*5, 19 T_phys, 20 ratio_H, 21 ratio_O.
-    device_output=True (not in the reference) returns the device tensor, so that pinn_amd.risk continues without a host copy."""
+    device_output=True (not in the reference) returns the device tensor, so that pinn_amd.risk continues without a host copy.
+    ensemble (not in the reference): a pinn_amd.DeepEnsemble; columns 9, 10 and 11 (and so 12) then come from its predict() instead
+    of MC-dropout (mc_times and dropout are unused); the residual columns stay `model`'s."""
     if len(dataset) == 9:
         x_train, y_train, x_val, y_val, x_test, y_test, scaler_X, scaler_Y, data_info = dataset
     else:
@@ -82,7 +84,10 @@ def create_comprehensive_results_array_v2(model, dataset, mc_times=2000, dropout
     n_samples = len(x_test)
     smooth_window = 200                                                   # 01:1972
     # MC-dropout with the reference's dropout-rate override / restore (01:1449-1473); outputs stay on the device
-    pred_mean, a_u, e_u = get_MC_samples(model, x_test, scaler_X, mc_times=mc_times, dropout=dropout, device_outputs=True)
+    if ensemble is None:
+        pred_mean, a_u, e_u = get_MC_samples(model, x_test, scaler_X, mc_times=mc_times, dropout=dropout, device_outputs=True)
+    else:
+        pred_mean, a_u, e_u = ensemble.predict(x_test, device_output=True)
 
     # min_y / scale_y as 01:1925-1930 rebuilds them from the target scaler, in float64
     lo_y, hi_y = float(scaler_Y.feature_range[0]), float(scaler_Y.feature_range[1])
