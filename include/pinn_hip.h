@@ -1727,6 +1727,80 @@ int pinn_fs_gmm(const double* d_arr, long long ld, long long n_arr_rows, const i
                 unsigned char* d_missing, double* d_scores, long long* d_tally, double* d_y_prob, long long* d_y_pred,
                 double* d_log_prob_norm, double* d_any_score, int* d_any_count, void* stream);
 
+/* ---- pinn_cp_*: penalised change-point segmentation of the rows (csrc/pinn_changepoint.hip; changepoint.py) ---------------
+ * Where the statistics of up to PINN_CP_MAX_FEAT columns change, by exact optimal partitioning.  The rows are a row head as
+ * above; `seg_starts` (host) and `d_seg_starts` (its device copy) hold n_segments strictly ascending start positions, the
+ * first 0, the last below n (n_segments = 0, both NULL: one segment); n_segments <= PINN_CP_MAX_SEGMENTS and
+ * n + n_segments < 2^31.  Segments are independent problems.  `mu`, `sigma` (host, [n_feat], both or neither): z = (x - mu) / sigma.
+ *
+ * The problem.  For a segment of m rows a partition 0 = tau_0 < ... < tau_k < tau_{k+1} = m with every piece at least
+ * min_len and at most max_len long (max_len = 0: no upper limit) minimises sum_i C(tau_i, tau_{i+1}) + beta k.  With S, Q
+ * the prefix sums of c and c^2 per column, c = z - z(first row of the segment), len = t - s, inv = 1 / len:
+ *   SS_d(s, t) = max(Q_d(t) - Q_d(s) - (S_d(t) - S_d(s))^2 * inv, 0)
+ *   PINN_CP_MEAN     C = sum_d SS_d                                                 min_len >= 1
+ *   PINN_CP_MEANVAR  C = sum_d [len log v_d + SS_d / v_d], v_d = max(SS_d * inv, var_floor)       min_len >= 2
+ * summed over d ascending from 0.  F(0) = -beta, F(t) = min over admissible s of (F(s) + C(s, t)) + beta, +inf without an
+ * admissible s; ties go to the smallest s; last[t] is the arg-min and the change points are the walk of `last` from m.
+ *
+ * Prefix sums: tiles of PINN_CP_TILE positions counted from the segment's first row; inside a tile the sum runs row by row
+ * from 0.0; the tile totals are summed tile by tile from 0.0 into exclusive offsets; S = offset + sum inside the tile.  A
+ * row that reads nothing or holds a non-finite z flags its segment: status PINN_CP_BAD_ROW, F = NaN, no change point.
+ *
+ * The solver: one workgroup per (segment, penalty), steps in blocks of block_steps (0: PINN_CP_BLOCK, at most that).  A
+ * candidate s joins the list in the block that holds step s + min_len.  Candidates known before a block are evaluated for
+ * all its steps in parallel, the triangular part inside the block is finished by one wave.  After a block that ends at
+ * t1 a candidate leaves the list when s < t1 + 1 - max_len, or, with prune != 0, when F(s) + C(s, t*) > F(t*) at
+ * t* = t1 + 1 - min_len >= s + min_len (PELT's test at the last step that already permits leaving: s is not needed from
+ * step t* + min_len = t1 + 1 on).  Pruning never changes F or the change points.  `evals` counts the (s, t) pairs that
+ * entered a minimum (the one test per candidate and block is not counted).  A launch stops after the block at which the
+ * sum of list length x steps reaches launch_evals (0: PINN_CP_LAUNCH_EVALS) and the next queued launch continues from
+ * the workspace; a finished pair returns at once.  No workgroup waits on another, no float atomics; a pair's bytes do not
+ * depend on what else is in the call.
+ *
+ * Outputs per (segment, penalty), at [segment * n_pen + penalty]: d_F = F(m), d_n_cp, d_evals, d_status (bits below),
+ * d_cp [.. * cp_cap] ascending change points as positions of the call (segment start + tau); more than cp_cap sets
+ * PINN_CP_OVERFLOW and keeps the first cp_cap.  PINN_CP_INFEASIBLE: no admissible partition (F = +inf).
+ * pinn_cp_window: the same for one segment of n <= PINN_CP_MAX_WINDOW rows in a single launch of one workgroup, prefix sums
+ * included; position j reads row (ring_start + j) mod n_arr_rows of the array (a ring of rows; ring_start = 0: the rows as they stand).
+ *
+ * Checks, on the host before any launch: PINN_E_ARG for NULL or misaligned pointers, n_feat outside 1 .. PINN_CP_MAX_FEAT,
+ * n_pen outside 1 .. PINN_CP_MAX_PEN, a kind other than the two, min_len below the kind's minimum, max_len != 0 below
+ * min_len, block_steps outside 0 .. PINN_CP_BLOCK, a non-finite or negative penalty, var_floor, launch_evals or cp_cap,
+ * sigma not finite and positive, seg_starts that do not ascend strictly from 0 inside n; PINN_E_WORKSPACE for a workspace
+ * below pinn_cp_workspace_bytes (256-byte aligned; 0 outside the limits); n = 0 returns PINN_OK without a launch. */
+#define PINN_CP_MAX_FEAT 8
+#define PINN_CP_MAX_PEN 16
+#define PINN_CP_MAX_SEGMENTS 65535
+#define PINN_CP_MAX_WINDOW 4096
+#define PINN_CP_TILE 256
+#define PINN_CP_BLOCK 64
+#define PINN_CP_LAUNCH_EVALS (1LL << 24)
+#define PINN_CP_MEAN 0
+#define PINN_CP_MEANVAR 1
+#define PINN_CP_BAD_ROW 1
+#define PINN_CP_OVERFLOW 2
+#define PINN_CP_INFEASIBLE 4
+
+typedef struct {
+  int kind, min_len;
+  long long max_len;
+  int prune, block_steps;
+  double var_floor;
+  long long launch_evals;
+} pinn_cp_opts_t;
+
+size_t pinn_cp_workspace_bytes(long long n, int n_feat, long long n_segments, int n_pen);
+int pinn_cp_segment(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat,
+                    const long long* d_row_index, long long n, const double* mu, const double* sigma,
+                    const long long* seg_starts, const long long* d_seg_starts, long long n_segments,
+                    const pinn_cp_opts_t* opts, const double* penalties, int n_pen, double* d_F, long long* d_n_cp,
+                    long long* d_cp, long long cp_cap, long long* d_evals, long long* d_status, void* d_ws, size_t ws_bytes,
+                    void* stream);
+int pinn_cp_window(const double* d_arr, long long ld, long long n_arr_rows, const int* cols, int n_feat, long long ring_start,
+                   long long n, const double* mu, const double* sigma, const pinn_cp_opts_t* opts, const double* penalties,
+                   int n_pen, double* d_F, long long* d_n_cp, long long* d_cp, long long cp_cap, long long* d_evals,
+                   long long* d_status, void* d_ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

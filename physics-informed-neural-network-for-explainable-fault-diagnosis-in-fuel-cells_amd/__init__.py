@@ -42,7 +42,10 @@ band: `score_uncertainty`, `conformal_quantiles`, `conformal_band`, `Uncertainty
 (uncertainty); and how sure the diagnosis itself is and whether it is none of the trained faults, conformal fault sets with
 class-conditional coverage and unknown-fault rejection: `calibrate`, `calibrate_gmm`, `p_values`, `prediction_sets`,
 `evaluate_sets`, `GMMSetDiagnoser`, `SetCalibration`, `FaultSets`, `SetReport` (faultsets); and a second source of the
-epistemic column beside MC-dropout, E networks trained and evaluated in the launches of one: `DeepEnsemble` (ensemble).
+epistemic column beside MC-dropout, E networks trained and evaluated in the launches of one: `DeepEnsemble` (ensemble); and
+where the regimes of a recording begin when nobody typed the boundaries, exact penalised change-point segmentation of the
+residual columns: `segment`, `penalty_path`, `select_penalty`, `segment_table`, `labels_from_segments`, `diagnose_segments`,
+`ChangeMonitor` (changepoint).
 Submodules are imported lazily so that `pinn_amd.synth` (numpy only) works without torch/HIP.
 """
 import importlib
@@ -98,6 +101,9 @@ _LAZY = {
     "evaluate_sets": "faultsets", "GMMSetDiagnoser": "faultsets", "SetCalibration": "faultsets", "FaultSets": "faultsets",
     "SetReport": "faultsets", "PValues": "faultsets",
     "DeepEnsemble": "ensemble",
+    "segment": "changepoint", "default_penalty": "changepoint", "penalty_path": "changepoint", "select_penalty": "changepoint",
+    "segment_table": "changepoint", "labels_from_segments": "changepoint", "diagnose_segments": "changepoint",
+    "ChangeMonitor": "changepoint", "Segmentation": "changepoint", "PenaltyPath": "changepoint",
 }
 
 

@@ -64,6 +64,9 @@ SOURCES = [
     ("pinn_uncertainty.hip", ["-ffp-contract=off"]),
     # conformal fault sets: float64 scores, every operation rounded on its own, so that counts and masks are the host backend's to the bit
     ("pinn_faultsets.hip", ["-ffp-contract=off"]),
+    # change-point segmentation: float64 prefix sums and segment costs, every operation rounded on its own; the host backend states
+    # the same sums in the same order, so F and the change points of the "mean" cost are its to the bit
+    ("pinn_changepoint.hip", ["-ffp-contract=off"]),
     ("pinn_mlp.hip", []),
     ("pinn_train.hip", []),
     ("pinn_bf16.hip", []),

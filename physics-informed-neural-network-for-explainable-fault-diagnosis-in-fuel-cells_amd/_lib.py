@@ -161,6 +161,16 @@ FS_REGIME_AUTO, FS_REGIME_LDS, FS_REGIME_SAMPLED, FS_REGIME_GLOBAL = range(4)
 FS_MAGIC, FS_H_NCAL, FS_H_OFFSET = 0x46534554, 16, 40
 FS_T_N, FS_T_COVERED, FS_T_HIST, FS_T_SINGLE, FS_T_OUT_N, FS_T_OUT_NOVEL, FS_TALLY_WORDS = 0, 16, 144, 280, 288, 289, 304
 
+# pinn_changepoint.hip: limits, the prefix tile, the solver's step block, the default cap of a launch, cost kinds and status bits
+CP_MAX_FEAT, CP_MAX_PEN, CP_MAX_SEGMENTS, CP_MAX_WINDOW, CP_TILE, CP_BLOCK, CP_LAUNCH_EVALS = 8, 16, 65535, 4096, 256, 64, 1 << 24
+CP_MEAN, CP_MEANVAR, CP_BAD_ROW, CP_OVERFLOW, CP_INFEASIBLE = 0, 1, 1, 2, 4
+
+
+class CpOpts(ctypes.Structure):
+    """pinn_cp_opts_t (pinn_changepoint.hip)."""
+    _fields_ = [("kind", c_int), ("min_len", c_int), ("max_len", c_ll), ("prune", c_int), ("block_steps", c_int),
+                ("var_floor", ctypes.c_double), ("launch_evals", c_ll)]
+
 
 class PinnError(RuntimeError):
     pass
@@ -191,6 +201,10 @@ _c_llp = ctypes.POINTER(c_ll)              # a host array of int64
 # kind, randomized, seed, draw kind, first row, regime; classes or NULL; count, mask, size, novel, missing, scores, tallies
 _FS_RANK = [c_void_p, _c_llp, _c_llp, c_int, c_int, c_int, ctypes.c_ulonglong, c_int, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
             c_void_p, c_void_p, c_void_p, c_void_p]
+
+# what pinn_cp_segment and pinn_cp_window share from the options on: options, penalties (host array), their number; F, change
+# point counts, change points, their capacity, evaluations, status; workspace and its size
+_CP_TAIL = [ctypes.POINTER(CpOpts), _c_dp, c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_size_t]
 
 _SIGS = {
     "pinn_abi_version": (c_int, []),
@@ -369,6 +383,9 @@ _SIGS = {
     "pinn_fs_build": (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, ctypes.c_ulonglong, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pinn_fs_rank": (c_int, [c_void_p, c_ll, c_int] + _FS_RANK + [c_void_p]),
     "pinn_fs_gmm": (c_int, _ROWS + [c_int, c_void_p, c_void_p, c_int, c_void_p] + _FS_RANK + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pinn_cp_workspace_bytes": (c_size_t, [c_ll, c_int, c_ll, c_int]),
+    "pinn_cp_segment": (c_int, _ROWS + [_c_dp, _c_dp, _c_llp, c_void_p, c_ll] + _CP_TAIL + [c_void_p]),
+    "pinn_cp_window": (c_int, [c_void_p, c_ll, c_ll, ctypes.POINTER(c_int), c_int, c_ll, c_ll, _c_dp, _c_dp] + _CP_TAIL + [c_void_p]),
 }
 
 _lib = None
